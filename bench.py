@@ -7,6 +7,9 @@ A step = dec(x, level) followed by rec(y).  N>1: the same volume sharded on the 
 periodic halo exchange per level through torch.distributed (RCCL).  `--ndim 4` runs BASELINE config 5's transform
 (256x256x256x32, t-sharded for N>1); `--wname db6 --level 4` config 4's.
 
+A plain run sets up, warms up, times exactly --steps steps and prints the headline line; `--full` adds every other figure and check
+(HIP-event median, roofline, round-trip error, pitched layout, sustained run, other configurations, CPU baseline) after that timed region.
+
 Launch: `python bench.py --gpus N` starts its own N ranks (one child `torch.distributed.run` process, spawned before
 anything touches the GPU) unless it is already running under a launcher (WORLD_SIZE set).
 
@@ -27,6 +30,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec (6.3 TB/s is the measured copy ceiling)
 TRAFFIC_PROFILE = "r04_traffic.json"   # committed rocprofv3 --pmc figures of the headline command (fallback when the live passes cannot run)
 KERNEL_NAMES = {0: "fused_analysis", 1: "fused_synthesis", 2: "axis_analysis", 3: "axis_synthesis"}
+DUMP_BYTES = 48 << 20   # --dump-outputs: bytes of all files of the job together (2/3 coefficients, 1/3 reconstruction)
+DUMP_SEED = 20240607    # --dump-outputs: positions of the sampled elements (the same for every build, so files compare element for element)
 
 
 def parse_args():
@@ -47,11 +52,17 @@ def parse_args():
     ap.add_argument("--packed-only", action="store_true", help="skip the secondary pass with pitched coefficients (profiling runs: "
                     "both passes launch the same kernels, which a kernel-stats average would mix)")
     ap.add_argument("--no-others", action="store_true", help="skip the `sustained` run and the `other_configs` (cfg2 / cfg4 / cfg5) that "
-                    "the default N=1 line carries after the headline's timed region")
+                    "the --full N=1 line carries after the headline's timed region")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not start the rocprofv3 --pmc child passes that measure "
                     "roofline.traffic of the headline configuration (the committed profile's figure is reported instead)")
     ap.add_argument("--zchunk", type=int, default=0)
     ap.add_argument("--target-blocks", type=int, default=0)
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure and check everything else: HIP-event median, "
+                    "per-kernel roofline (with the live traffic passes), round-trip error, pitched coefficients, sustained run, other "
+                    "configurations, one rank's share, CPU baseline.  Without it a run times the headline steps and prints their line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs (coefficients, reconstruction) "
+                    "as DIR/<name>.npy, float32; an output larger than its share of %d MiB is a sample at fixed seeded positions"
+                    % (DUMP_BYTES >> 20))
     a = ap.parse_args()
     if a.size is None:
         a.size = {2: [4096, 4096], 3: [512, 512, 512], 4: [256, 256, 256, 32]}[a.ndim]
@@ -356,6 +367,18 @@ def live_traffic(extra_args):
         shutil.rmtree(tmp, ignore_errors=True)
 
 
+def dump_outputs(torch, out_dir, arrays):
+    """--dump-outputs: every (name, tensor, n) as out_dir/<name>.npy in float32 -- the whole tensor when it has at most n elements, else
+    the n elements at sorted positions drawn from DUMP_SEED (they depend on the shape only, so two builds' files compare element for element)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t, n in arrays:
+        if t.numel() > n:
+            idx = torch.randint(t.numel(), (n,), generator=torch.Generator().manual_seed(DUMP_SEED)).to(t.device).sort().values
+            t = t[torch.unravel_index(idx, t.shape)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().contiguous().cpu().numpy())
+
+
 def main():
     a = parse_args()
     world = int(os.environ.get("WORLD_SIZE", "0") or 0)
@@ -426,7 +449,8 @@ def main():
         r_holder = {}
 
         def step():
-            yl = eng.dec(x, level)
+            r_holder.pop("y", None)                               # (freed before dec allocates, as when it was a local: only the
+            r_holder["y"] = yl = eng.dec(x, level)                #  last step's coefficients outlive the step, for --dump-outputs)
             r_holder["r"] = eng.rec(yl)
 
     def fence():
@@ -457,7 +481,40 @@ def main():
         tt = torch.tensor([dt], device=red_dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
+    ms_per_step = dt / a.steps * 1e3
+    value = V / (dt / a.steps) / 1e6
 
+    if a.dump_outputs:                                            # what the caller holds after the last timed step
+        if sharded:
+            y_out, r_out = r_holder["y"], r_holder["r"]
+        else:                                                     # the bands of the coefficient buffer (pitched: without the padding)
+            y_out, r_out = lay["y"].view(nbands, -1)[:, :V].unflatten(1, kshape), r
+        n = DUMP_BYTES // 4 // world
+        sfx = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(torch, a.dump_outputs, [("coefficients" + sfx, y_out, n * 2 // 3), ("reconstruction" + sfx, r_out, n // 3)])
+        del y_out, r_out                                          # (--full frees the coefficient buffer before its pitched pass)
+
+    shape = "x".join(str(n) for n in sizes)
+    cube = f"{sizes[0]}^3" if d == 3 and len(set(sizes)) == 1 else shape
+    out = {"metric": f"Mvoxels/s fwd+inv NDWT ({cube} fp32, {level} lvl {a.wname})", "value": round(value, 1), "unit": "Mvoxels/s",
+           "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4),
+           "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": f"{d}D fp32 {shape} {a.wname} {level} levels, dec+rec, pres_l2_norm, reference dilation (stride 1)",
+                      "sharding": "none" if not sharded else f"outer-axis slabs x{world}; per level: analysis halo fetch (1 band) and synthesis "
+                                                             f"scatter-add (1 band) via RCCL send/recv; exchange "
+                                                             f"{'overlapped with the interior planes' if eng.overlap else 'then one launch per level'}"
+                                                             f" (overlap={eng.overlap_mode}, tune: {eng.tuned})",
+                      "path": "per-axis" if a.generic else plan.describe(),
+                      "coefficient_layout": ("pitched local slabs owned by the sharded driver" if sharded else
+                                             "packed (reference)" if a.band_pitch == "packed" else "pitched bands (ndwt_band_pitch)")}}
+    if not a.full:                                                # a plain run: the headline line and nothing else
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything below measures or checks beside the headline ----
     # ---- per-step HIP events (median of >= 20 iterations), a pass of its own: torch's current stream is the launch stream ----
     import statistics
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
@@ -490,8 +547,6 @@ def main():
         rt_err = float(torch.linalg.vector_norm((r - x).double()) / torch.linalg.vector_norm(x.double()))
 
     esize = 4
-    ms_per_step = dt / a.steps * 1e3
-    value = V / (dt / a.steps) / 1e6
     v_local = V // world
     step_bytes = 2 * level * (1 + (1 << d)) * V * esize          # whole job, BASELINE.md section 3
     # dominant kernel = the kind with the largest total time; its algorithmic bytes per launch
@@ -577,21 +632,7 @@ def main():
         except Exception:
             pass
 
-    shape = "x".join(str(n) for n in sizes)
-    cube = f"{sizes[0]}^3" if d == 3 and len(set(sizes)) == 1 else shape
-    out = {"metric": f"Mvoxels/s fwd+inv NDWT ({cube} fp32, {level} lvl {a.wname})", "value": round(value, 1), "unit": "Mvoxels/s",
-           "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 4),
-           "median_ms_per_step_hip_events": round(median_ms, 4),
-           "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": {"workload": f"{d}D fp32 {shape} {a.wname} {level} levels, dec+rec, pres_l2_norm, reference dilation (stride 1)",
-                      "sharding": "none" if not sharded else f"outer-axis slabs x{world}; per level: analysis halo fetch (1 band) and synthesis "
-                                                             f"scatter-add (1 band) via RCCL send/recv; exchange "
-                                                             f"{'overlapped with the interior planes' if eng.overlap else 'then one launch per level'}"
-                                                             f" (overlap={eng.overlap_mode}, tune: {eng.tuned})",
-                      "path": "per-axis" if a.generic else plan.describe(),
-                      "coefficient_layout": ("pitched local slabs owned by the sharded driver" if sharded else
-                                             "packed (reference)" if a.band_pitch == "packed" else "pitched bands (ndwt_band_pitch)")},
-           "roofline": roofline, "roundtrip_rel_l2": rt_err}
+    out.update({"median_ms_per_step_hip_events": round(median_ms, 4), "roofline": roofline, "roundtrip_rel_l2": rt_err})
     if pitched is not None:
         out["pitched_coefficients"] = pitched
     # ---- after the headline: a sustained run of the same step and the other single-GPU BASELINE configurations ----

@@ -1,15 +1,15 @@
 """What the reference itself holds for the hot path, pinned (the reference stores no golden vectors).
 
-  * the tap table -- the literal db1..db10 lists of Functions/wave_filters.m:19-160 -- parsed as text where the reference
-    checkout is present (build container; skipped on the GPU box) and compared, to the last bit in fp64, with
+  * the tap table -- the literal db1..db10 lists of Functions/wave_filters.m:19-160, stored verbatim as decimal strings in
+    tests/golden/wave_filters_low_d.json -- converted by float() and compared, to the last bit in fp64, with
     oracle/db_taps.py (spectral factorisation, tools/derive_daubechies.py) and with what the C ABI returns;
   * the db1 closed forms the reference ships as signal-domain code: harr_nddwt_2D.m (tests/test_oracle.py) and the
     4-D one, harr_nddwt_4D.m:262-281,555-579 (multi-level band bookkeeping of :173,:228), against all three oracle
     restatements.  tests/test_gpu_parity.py compares the HIP path with the same closed form.
 Parity with MATLAB output stays "unpinned" by the rules (no fixtures exist); these are the pins that do exist.
 """
+import json
 import os
-import re
 
 import numpy as np
 import pytest
@@ -17,27 +17,24 @@ import pytest
 import ndwt_oracle as orc
 from db_taps import DB_H
 
-REF_FILTERS = "/root/reference/Functions/wave_filters.m"
+REF_FILTERS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wave_filters_low_d.json")
 
 
-def parse_wave_filters_m(path):
-    """{K: [h0, h1, ...]} from the `case {'dbK'} low_d = [ ... ];` blocks, literals converted by float()"""
-    txt = open(path).read()
+def load_low_d_literals(path):
+    """{K: [h0, h1, ...]} from the stored `low_d = [ ... ]` literals of each `case {'dbK'}`, converted by float()"""
     out = {}
-    for m in re.finditer(r"case\s*\{'db(\d+)'\}\s*low_d\s*=\s*\[(.*?)\];", txt, re.S):
-        K, body = int(m.group(1)), m.group(2)
-        body = body.replace("...", " ")
-        if "sqrt" in body:                                    # db1: [1/sqrt(2),1/sqrt(2)]
-            assert K == 1 and body.replace(" ", "") == "1/sqrt(2),1/sqrt(2)"
+    for name, lits in json.load(open(path)).items():
+        K = int(name[2:])
+        if any("sqrt" in v for v in lits):                    # db1: [1/sqrt(2),1/sqrt(2)]
+            assert K == 1 and lits == ["1/sqrt(2)", "1/sqrt(2)"]
             out[K] = [1 / np.sqrt(2.0)] * 2
             continue
-        out[K] = [float(v) for v in re.split(r"[,\s]+", body.strip()) if v]
+        out[K] = [float(v) for v in lits]
     return out
 
 
-@pytest.mark.skipif(not os.path.exists(REF_FILTERS), reason="reference checkout not present (GPU box)")
 def test_tap_table_equals_reference_literals_to_the_bit():
-    ref = parse_wave_filters_m(REF_FILTERS)
+    ref = load_low_d_literals(REF_FILTERS)
     assert sorted(ref) == list(range(1, 11))
     for K in range(1, 11):
         h_ref = np.array(ref[K], dtype=np.float64)
@@ -53,10 +50,9 @@ def test_tap_table_equals_reference_literals_to_the_bit():
         assert np.array_equal(lo_d, h_ref[::-1]) and np.array_equal(hi_d, hi[::-1])
 
 
-@pytest.mark.skipif(not os.path.exists(REF_FILTERS), reason="reference checkout not present (GPU box)")
 def test_c_abi_wave_filters_equals_reference_literals_to_the_bit():
     import ndwt_amd as ndwt                                   # loads libndwt_hip.so; ndwt_wave_filters needs no GPU
-    ref = parse_wave_filters_m(REF_FILTERS)
+    ref = load_low_d_literals(REF_FILTERS)
     for K in range(1, 11):
         h_ref = np.array(ref[K], dtype=np.float64)
         hi = h_ref[::-1].copy()

@@ -15,7 +15,7 @@ for c in $cfgs; do
     cfg4) args="--ndim 3 --size 512 512 512 --wname db6 --level 4 --steps 20";;
     cfg5) args="--ndim 4 --size 256 256 256 32 --wname db4 --level 3 --steps 5";;
   esac
-  common="--warmup 3 --no-cpu-baseline --packed-only --no-others --no-live-traffic"
+  common="--full --warmup 3 --no-cpu-baseline --packed-only --no-others --no-live-traffic"
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_$c -- python bench.py $args $common > $out/${c}_bench.json 2> $out/stats_$c.log || { echo "stats pass of $c failed"; tail -5 $out/stats_$c.log; exit 1; }
   f=$(ls $out/stats_$c/*/*kernel_stats.csv | head -1)
   grep -E '^"Name"|ndwt::' $f > $out/${c}_kernel_stats.csv
