@@ -79,6 +79,24 @@ int ndwt_plan_create(ndwt_plan** plan, int ndim, const int64_t* dims, const char
  * when the local length is shorter than the filter. */
 int ndwt_plan_create_slab(ndwt_plan** plan, int ndim, const int64_t* dims_local, int64_t global_outer, const char* const* wnames,
                           int dtype, int complexity, int pres_l2_norm, int dilation, int max_level, int device);
+/* Plan for ONE SLAB of a volume sharded on axis `shard_axis` (counted from the fastest axis, 0 = x): ndim - 1 is the outermost axis
+ * (exactly ndwt_plan_create_slab, global_len = global_outer), 2 with ndim == 4 shards a (3-D + time) volume on z and keeps t whole on
+ * every rank; anything else is NDWT_ERR_UNSUPPORTED.  dims_local[shard_axis] = the local planes, global_len = the length of the sharded
+ * axis of the whole volume: the reference's filter-length check (nd_dwt_3D.m:277-286, "Third Dimension of Data is shorter ...")
+ * applies to it, the local slab may be thinner than the filter.
+ * Layouts of a z-slab (a "plane" = one (ny, nx) plane of one frame; memory order t, z, y, x as always):
+ *   input with halo of ndwt_analysis_level_slab         (nt, ab + n + aa, ny, nx)
+ *   halo buffers of ndwt_analysis_level_slab_split      (nt, ab, ny, nx) and (nt, aa, ny, nx)
+ *   every band of ndwt_synthesis_level_slab             (nt, sb + n + sa, ny, nx)
+ *   output of ndwt_synthesis_level_slab_ext             (nt, sa + n + sb, ny, nx)
+ * with ab, aa, sb, sa = ndwt_slab_halo (from the z filter).  A level is nd_dwt_4D.m's dec / rec: the periodic t pass over the z-extended
+ * frames, then the fused 3-D kernel with the halo on z batched over the frames (reverse order in the synthesis); plans the fused kernels do
+ * not take (fp64 long filters, dilated levels, a z filter shorter than another axis' ...) run the per-axis passes with the halo on z.
+ * The split form assembles the slab and its two halo buffers in a plan-owned scratch (one ndwt_slab_segments_strided launch) first.
+ * ndwt_synthesis_level_slab_ext needs the fused kernels with the z filter the longest, at tap stride 1; the run-of-planes forms
+ * (_part, _runs) return NDWT_ERR_UNSUPPORTED for z-slabs. */
+int ndwt_plan_create_slab_axis(ndwt_plan** plan, int ndim, const int64_t* dims_local, int shard_axis, int64_t global_len,
+                               const char* const* wnames, int dtype, int complexity, int pres_l2_norm, int dilation, int max_level, int device);
 /* A plan owns scratch (the approximation ping-pong between levels, temporaries): use it from ONE host thread and ONE stream
  * at a time.  Calls on different streams must be ordered by the caller (an event), or use one plan per stream. */
 int ndwt_plan_destroy(ndwt_plan* plan);
@@ -185,7 +203,8 @@ int ndwt_rec_split_host(ndwt_plan* plan, const void* y_re, const void* y_im, voi
  * halo_before = (L/2)*stride and halo_after = (L/2-1)*stride planes around the local slab.
  * ndwt_slab_halo() reports those four numbers. */
 /* 1 when the plan offers the slab forms that read a slab in place (split-halo analysis, runs of the zero-extended synthesis:
- * a 3-D plan on the fused kernels whose outer-axis filter is its longest), else 0 */
+ * a 3-D plan on the fused kernels whose outer-axis filter is its longest; z-slab plans: the zero-extended synthesis, i.e. the fused
+ * kernels with the z filter the longest), else 0 */
 int ndwt_plan_slab_fast(const ndwt_plan* plan);
 int ndwt_slab_halo(const ndwt_plan* plan, int stride, int64_t* ana_before, int64_t* ana_after,
                    int64_t* syn_before, int64_t* syn_after);
@@ -229,6 +248,11 @@ int ndwt_synthesis_level_slab_runs(ndwt_plan* plan, const void* const* in_local,
 #define NDWT_SEG_COPY 0
 #define NDWT_SEG_ADD 1
 int ndwt_slab_segments(ndwt_plan* plan, int op, int nseg, void* const* dst, const void* const* src, const int64_t* count, void* stream);
+/* The strided form: `nrep` repetitions of every run in ONE launch, repetition r of run i at dst[i] + r * dst_stride[i] and
+ * src[i] + r * src_stride[i] (scalars, like count) -- the planes of a z-slab are one run per frame (nt runs per halo).  Repetitions of a
+ * run must not overlap in dst (dst_stride[i] >= count[i] when nrep > 1).  The pointers may lie on another device with peer access. */
+int ndwt_slab_segments_strided(ndwt_plan* plan, int op, int nseg, void* const* dst, const void* const* src, const int64_t* count, int64_t nrep,
+                               const int64_t* dst_stride, const int64_t* src_stride, void* stream);
 
 /* ---- single-process multi-device plan (hard part 5; section 8b `devices[]`) ---------------------------
  * The reference's host is ONE process calling one gateway (nd_dwt_3D.m:161,225): this is the multi-GPU path that fits behind
@@ -249,6 +273,14 @@ typedef struct ndwt_mplan ndwt_mplan;
 enum { NDWT_EXCHANGE_SCATTER = 0, NDWT_EXCHANGE_GATHER = 1 };
 int ndwt_mplan_create(ndwt_mplan** plan, int ndim, const int64_t* dims, const char* const* wnames, int dtype, int complexity,
                       int pres_l2_norm, int dilation, int max_level, const int* devices, int ndev);
+/* The same with the sharded axis chosen (ndwt_plan_create_slab_axis): ndim - 1 = ndwt_mplan_create, 2 with ndim == 4 = z-slabs, t whole
+ * on every slab.  ndwt_mplan_slab then reports first plane and planes along z; the slab buffers of ndwt_mdec / ndwt_mrec are
+ * (nt, nz_i, ny, nx), band-planar ((bands, nt, nz_i, ny, nx)); the host forms take the whole-volume arrays as before.  Planes move between
+ * slabs with ndwt_slab_segments_strided where the devices are the same or have peer access, else one peer copy per frame.  The exchange
+ * schemes and barriers are those of t-slabs (scatter where the slab plans offer the zero-extended synthesis); the overlapped schedule is
+ * not offered (exchange, then compute). */
+int ndwt_mplan_create_axis(ndwt_mplan** plan, int ndim, const int64_t* dims, const char* const* wnames, int dtype, int complexity,
+                           int pres_l2_norm, int dilation, int max_level, const int* devices, int ndev, int shard_axis);
 int ndwt_mplan_destroy(ndwt_mplan* plan);
 int ndwt_mplan_num_slabs(const ndwt_mplan* plan);
 int ndwt_mplan_slab(const ndwt_mplan* plan, int idx, int* device, int64_t* first_plane, int64_t* planes);

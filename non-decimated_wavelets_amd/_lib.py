@@ -30,7 +30,8 @@ EXPORTS = [
     "ndwt_mrec_host", "ndwt_mplan_last_error", "ndwt_mdec", "ndwt_mrec", "ndwt_mplan_set_exchange", "ndwt_mplan_describe", "ndwt_plan_slab_fast", "ndwt_dec_pitched", "ndwt_rec_pitched", "ndwt_shrink_pitched", "ndwt_band_pitch", "ndwt_slab_segments",
     "ndwt_plan_release_staging", "ndwt_mplan_set_overlap", "ndwt_mplan_last_enqueue_us", "ndwt_mplan_set_threads", "ndwt_comm_unique_id", "ndwt_comm_create", "ndwt_comm_destroy", "ndwt_comm_exchange",
     "ndwt_comm_last_error", "ndwt_coef_create", "ndwt_coef_release", "ndwt_coef_info", "ndwt_coef_dec_host", "ndwt_coef_rec_host",
-    "ndwt_coef_shrink", "ndwt_coef_get_host", "ndwt_coef_put_host",
+    "ndwt_coef_shrink", "ndwt_coef_get_host", "ndwt_coef_put_host", "ndwt_plan_create_slab_axis", "ndwt_slab_segments_strided",
+    "ndwt_mplan_create_axis",
 ]
 
 
@@ -75,6 +76,9 @@ def lib() -> ctypes.CDLL:
                                    ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ndwt_plan_create_slab.argtypes = [c_void_pp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.POINTER(ctypes.c_char_p),
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.ndwt_plan_create_slab_axis.argtypes = [c_void_pp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int64,
+                                             ctypes.POINTER(ctypes.c_char_p), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int]
     L.ndwt_plan_destroy.argtypes = [ctypes.c_void_p]
     L.ndwt_plan_set_path.argtypes = [ctypes.c_void_p, ctypes.c_int]
     L.ndwt_plan_set_tuning.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
@@ -116,6 +120,7 @@ def lib() -> ctypes.CDLL:
                                                                                                     ctypes.c_void_p]
     L.ndwt_mplan_create.argtypes = [c_void_pp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_char_p), ctypes.c_int,
                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.c_int]
+    L.ndwt_mplan_create_axis.argtypes = L.ndwt_mplan_create.argtypes + [ctypes.c_int]
     L.ndwt_mplan_destroy.argtypes = [ctypes.c_void_p]
     L.ndwt_mplan_num_slabs.argtypes = [ctypes.c_void_p]
     L.ndwt_mplan_slab.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int64),
@@ -149,6 +154,8 @@ def lib() -> ctypes.CDLL:
     L.ndwt_coef_put_host.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, c_void_pp]
     L.ndwt_slab_segments.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_void_pp, c_void_pp, ctypes.POINTER(ctypes.c_int64),
                                      ctypes.c_void_p]
+    L.ndwt_slab_segments_strided.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_void_pp, c_void_pp, ctypes.POINTER(ctypes.c_int64),
+                                             ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), ctypes.c_void_p]
     L.ndwt_last_error.restype = ctypes.c_char_p
     L.ndwt_version.restype = ctypes.c_char_p
     _lib = L

@@ -33,9 +33,11 @@ class Plan:
     """Thin RAII wrapper over ndwt_plan (include/ndwt.h)."""
 
     def __init__(self, dims, wnames, dtype, complex_interleaved=False, pres_l2_norm=False, dilation="reference",
-                 max_level=1, device=0, global_outer=None):
-        """global_outer: length of the outermost axis of the WHOLE volume when `dims` describe one slab of it (multi-GPU):
-        the reference's filter-length check then applies to the whole axis, a slab may be thinner than the filter"""
+                 max_level=1, device=0, global_outer=None, shard_axis=None):
+        """global_outer: length of the sharded axis of the WHOLE volume when `dims` describe one slab of it (multi-GPU):
+        the reference's filter-length check then applies to the whole axis, a slab may be thinner than the filter.
+        shard_axis: the sharded axis, counted from the fastest (0 = x); None = the outermost (ndwt_plan_create_slab), 2 of a 4-D
+        volume = z-slabs (ndwt_plan_create_slab_axis)"""
         self.dims = [int(d) for d in dims]
         self.ndim = len(self.dims)
         self.wnames = list(wnames)
@@ -48,7 +50,12 @@ class Plan:
         dt = L.NDWT_F32 if dtype in (torch.float32, np.float32, "single") else L.NDWT_F64
         dil = {"reference": L.NDWT_DILATION_REFERENCE, "atrous": L.NDWT_DILATION_ATROUS}[dilation]
         cplx = L.NDWT_COMPLEX_INTERLEAVED if complex_interleaved else L.NDWT_REAL
-        if global_outer is None:
+        self.shard_axis = self.ndim - 1 if shard_axis is None else int(shard_axis)
+        if shard_axis is not None:
+            L.check(L.lib().ndwt_plan_create_slab_axis(ctypes.byref(self._h), self.ndim, dims_c, self.shard_axis,
+                                                       int(global_outer if global_outer is not None else self.dims[self.shard_axis]),
+                                                       names_c, dt, cplx, int(bool(pres_l2_norm)), dil, self.max_level, self.device))
+        elif global_outer is None:
             L.check(L.lib().ndwt_plan_create(ctypes.byref(self._h), self.ndim, dims_c, names_c, dt, cplx,
                                              int(bool(pres_l2_norm)), dil, self.max_level, self.device))
         else:
@@ -141,6 +148,14 @@ class Plan:
         n = len(dsts)
         L.check(L.lib().ndwt_slab_segments(self._h, 1 if add else 0, n, (ctypes.c_void_p * n)(*dsts), (ctypes.c_void_p * n)(*srcs),
                                            (ctypes.c_int64 * n)(*counts), ctypes.c_void_p(stream)))
+
+    def slab_segments_strided(self, add, dsts, srcs, counts, nrep, dst_strides, src_strides, stream=0):
+        """up to 8 runs, each repeated `nrep` times (repetition r at r * stride, per run and side), copied or added in one launch
+        (include/ndwt.h: ndwt_slab_segments_strided); counts and strides in scalars"""
+        n = len(dsts)
+        L.check(L.lib().ndwt_slab_segments_strided(self._h, 1 if add else 0, n, (ctypes.c_void_p * n)(*dsts), (ctypes.c_void_p * n)(*srcs),
+                                                   (ctypes.c_int64 * n)(*counts), int(nrep), (ctypes.c_int64 * n)(*dst_strides),
+                                                   (ctypes.c_int64 * n)(*src_strides), ctypes.c_void_p(stream)))
 
     def release_staging(self):
         L.check(L.lib().ndwt_plan_release_staging(self._h))
@@ -246,9 +261,12 @@ class MultiPlan:
     sharded in slabs on its outermost axis (a device listed twice holds two slabs).  Host arrays in kernel order
     ((bands,) nd, ..., n1, contiguous) in and out -- the path behind the MATLAB gateway, where the host is one process."""
 
-    def __init__(self, dims, wnames, dtype, devices, complex_interleaved=False, pres_l2_norm=False, dilation="reference", max_level=3):
+    def __init__(self, dims, wnames, dtype, devices, complex_interleaved=False, pres_l2_norm=False, dilation="reference", max_level=3,
+                 shard_axis=None):
+        """shard_axis: None = the outermost axis; 2 of a 4-D volume = z-slabs (t whole on every slab; slab tensors (nt, nz_i, ny, nx))"""
         self.dims = [int(d) for d in dims]
         self.ndim = len(self.dims)
+        self.shard_axis = self.ndim - 1 if shard_axis is None else int(shard_axis)
         self.np_dtype = np.float32 if dtype in (torch.float32, np.float32, "single") else np.float64
         self.complex = bool(complex_interleaved)
         self.max_level = int(max_level)
@@ -258,9 +276,14 @@ class MultiPlan:
         devs = (ctypes.c_int * len(devices))(*[int(d) for d in devices])
         dt = L.NDWT_F32 if self.np_dtype == np.float32 else L.NDWT_F64
         dil = {"reference": L.NDWT_DILATION_REFERENCE, "atrous": L.NDWT_DILATION_ATROUS}[dilation]
-        L.mcheck(L.lib().ndwt_mplan_create(ctypes.byref(self._h), self.ndim, dims_c, names_c, dt,
-                                           L.NDWT_COMPLEX_INTERLEAVED if self.complex else L.NDWT_REAL, int(bool(pres_l2_norm)), dil,
-                                           self.max_level, devs, len(devices)))
+        if shard_axis is None:
+            L.mcheck(L.lib().ndwt_mplan_create(ctypes.byref(self._h), self.ndim, dims_c, names_c, dt,
+                                               L.NDWT_COMPLEX_INTERLEAVED if self.complex else L.NDWT_REAL, int(bool(pres_l2_norm)), dil,
+                                               self.max_level, devs, len(devices)))
+        else:
+            L.mcheck(L.lib().ndwt_mplan_create_axis(ctypes.byref(self._h), self.ndim, dims_c, names_c, dt,
+                                                    L.NDWT_COMPLEX_INTERLEAVED if self.complex else L.NDWT_REAL, int(bool(pres_l2_norm)), dil,
+                                                    self.max_level, devs, len(devices), self.shard_axis))
 
     def __del__(self):
         try:
@@ -328,13 +351,16 @@ class MultiPlan:
         if len(tensors) != len(sl):
             raise ValueError(f"{len(sl)} slab tensors expected")
         for t, (dev, _, n) in zip(tensors, sl):
-            shape = ((bands,) if bands else ()) + (n,) + tuple(reversed(self.dims[:-1]))
+            local = list(self.dims)
+            local[self.shard_axis] = n
+            shape = ((bands,) if bands else ()) + tuple(reversed(local))
             if not (t.is_cuda and t.device.index == dev and t.dtype == tdt and t.is_contiguous() and tuple(t.shape) == shape):
                 raise ValueError(f"slab tensor: contiguous {tdt} of shape {shape} on cuda:{dev} expected")
         return (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
     def dec_device(self, x_slabs, level):
-        """device-resident form: x_slabs[i] = torch tensor (n_i, ..., n1) on slab i's device -> list of (bands, n_i, ..., n1) tensors.
+        """device-resident form: x_slabs[i] = torch tensor (n_i, ..., n1) on slab i's device -> list of (bands, n_i, ..., n1) tensors
+        (z-slabs: (nt, nz_i, ny, nx) -> (bands, nt, nz_i, ny, nx)).
         Ordered against torch by host synchronisation: every slab device is synchronised before the call; returns when the result is."""
         xs = self._slab_tensors(x_slabs, 0)
         nbt = num_bands(self.ndim, level)

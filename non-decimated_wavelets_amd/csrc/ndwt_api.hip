@@ -11,6 +11,7 @@
 #include <climits>
 #include <cstring>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/ndwt.h"
@@ -105,6 +106,9 @@ struct ndwt_plan {
     size_t stage_bytes[2];             // kept across calls (ndwt_plan_release_staging frees them)
     int live_coefs;                    // ndwt_coef handles bound to this plan
     int thin_slab;                     // slab plan whose outer axis is shorter than its filter: slab entry points only
+    int shard;                         // slab plans: the sharded axis (ndim-1, or 2 for a 4-D volume sharded on z); halos live on it
+    void* zin;                         // z-slabs, split-halo analysis: the slab assembled with its halo planes (lazily allocated)
+    size_t zin_bytes;
     std::vector<hipEvent_t>* ev_pool;  // profiling events, reused
 };
 
@@ -262,15 +266,27 @@ template <typename T> struct GenericCtx {
     T* tmp;                  // 2*(ndim-1) volumes of vol_tmp scalars
     long long vol_tmp;
     hipStream_t s;
+    long long n_in;          // slab mode: planes of the sharded axis p->shard with its halo (the local planes: dims_cur[p->shard])
 };
 
+// dims a pass on `axis` sees in slab mode: the sharded axis carries its halo planes until its own pass trims them (analysis: the
+// passes of the axes above it run on the haloed slab; synthesis: the passes of the axes below it do).  Outer-axis slabs: every pass
+// sees the local planes (the outer pass is the first of the analysis and the last of the synthesis).
+template <typename T> static const long long* generic_dims(const GenericCtx<T>& c, int axis, bool synthesis, long long* buf) {
+    if (!c.slab || c.p->shard == c.p->ndim - 1) return c.dims_cur;
+    for (int k = 0; k < c.p->ndim; ++k) buf[k] = c.dims_cur[k];
+    if (synthesis ? axis < c.p->shard : axis > c.p->shard) buf[c.p->shard] = c.n_in;
+    return buf;
+}
+
 template <typename T> static int generic_analysis(GenericCtx<T>& c, int axis, const T* src, int prefix, T* const* out) {
-    const bool top = axis == c.p->ndim - 1;
-    const bool wrap = !(c.slab && top);
-    if (axis == 0) return axis_pass<T>(c.p, false, 0, c.dims_cur, c.stride, wrap, src, nullptr, out[prefix], out[prefix | 1], c.s);
+    const bool wrap = !(c.slab && axis == c.p->shard);
+    long long dbuf[NDWT_MAX_DIMS];
+    const long long* dims = generic_dims(c, axis, false, dbuf);
+    if (axis == 0) return axis_pass<T>(c.p, false, 0, dims, c.stride, wrap, src, nullptr, out[prefix], out[prefix | 1], c.s);
     T* lo = c.tmp + (long long)(2 * (axis - 1)) * c.vol_tmp;
     T* hi = lo + c.vol_tmp;
-    int rc = axis_pass<T>(c.p, false, axis, c.dims_cur, c.stride, wrap, src, nullptr, lo, hi, c.s);
+    int rc = axis_pass<T>(c.p, false, axis, dims, c.stride, wrap, src, nullptr, lo, hi, c.s);
     if (rc) return rc;
     rc = generic_analysis(c, axis - 1, lo, prefix, out);
     if (rc) return rc;
@@ -278,16 +294,17 @@ template <typename T> static int generic_analysis(GenericCtx<T>& c, int axis, co
 }
 
 template <typename T> static int generic_synthesis(GenericCtx<T>& c, int axis, int prefix, const T* const* in, T* dst) {
-    const bool top = axis == c.p->ndim - 1;
-    const bool wrap = !(c.slab && top);
-    if (axis == 0) return axis_pass<T>(c.p, true, 0, c.dims_cur, c.stride, wrap, in[prefix], in[prefix | 1], dst, nullptr, c.s);
+    const bool wrap = !(c.slab && axis == c.p->shard);
+    long long dbuf[NDWT_MAX_DIMS];
+    const long long* dims = generic_dims(c, axis, true, dbuf);
+    if (axis == 0) return axis_pass<T>(c.p, true, 0, dims, c.stride, wrap, in[prefix], in[prefix | 1], dst, nullptr, c.s);
     T* a = c.tmp + (long long)(2 * (axis - 1)) * c.vol_tmp;
     T* d = a + c.vol_tmp;
     int rc = generic_synthesis(c, axis - 1, prefix, in, a);
     if (rc) return rc;
     rc = generic_synthesis(c, axis - 1, prefix | (1 << axis), in, d);
     if (rc) return rc;
-    return axis_pass<T>(c.p, true, axis, c.dims_cur, c.stride, wrap, a, d, dst, nullptr, c.s);
+    return axis_pass<T>(c.p, true, axis, dims, c.stride, wrap, a, d, dst, nullptr, c.s);
 }
 
 // ------------------------------------------------------------------------------------ fused levels
@@ -635,8 +652,91 @@ static int fused2_run(const ndwt_plan* p, bool inverse, int Lp, const T* const* 
 
 // ------------------------------------------------------------------------------------------ levels
 // analysis of one level: in (vol scalars, + halo planes on the outer axis in slab mode) -> 2^d bands
+// A 4-D slab sharded on z (p->shard == 2): the input / every synthesis input carries the z halo of every frame, (nt, nz + L_z - 1, ny, nx).
+// The plan's fused path (nd_dwt_4D.m dec / rec: the t filter pair, then the 3-D level of both t-bands) keeps t whole: a periodic t pass
+// over the z-extended frames, then the fused 3-D kernel with the halo on z (z_mode 0), batched over the frames with per-frame strides.
+// Plans the fused kernels do not take (or whose z filter is not the longest: the kernel marches exactly Lp - 1 halo planes) run the
+// per-axis passes, the slab treatment on z.
+static bool zslab_fused(const ndwt_plan* p, long long stride, int* Lp, int dir) {
+    return fused3_eligible(p, stride, Lp, dir) && p->filt[2].len == *Lp;
+}
+
+template <typename T> static int generic_level(ndwt_plan* p, bool synthesis, const T* const* in, T* const* out, long long stride, hipStream_t s);
+
+template <typename T>
+static int analysis_level_z(ndwt_plan* p, const T* in, T* const* out, long long stride, hipStream_t s) {
+    const long long n_in = p->dims[2] + (long long)(p->filt[2].len - 1) * stride;
+    const long long vol3 = p->comp * p->dims[0] * p->dims[1] * p->dims[2], vol3_in = vol3 / p->dims[2] * n_in;
+    const long long vol_in = vol3_in * p->dims[3];
+    int Lp = 0;
+    if (!zslab_fused(p, stride, &Lp, 0)) {
+        const T* ins[1] = {in};
+        return generic_level<T>(p, false, ins, out, stride, s);
+    }
+    const long long skew = 256 / (long long)sizeof(T);
+    int rc = ensure_tmp(p, (size_t)(2 * vol_in + skew) * sizeof(T));
+    if (rc) return rc;
+    T* lo = (T*)p->tmp;
+    T* hi = lo + vol_in + skew;
+    long long dims_in[NDWT_MAX_DIMS] = {p->dims[0], p->dims[1], n_in, p->dims[3]};
+    rc = axis_pass<T>(p, false, 3, dims_in, stride, true, in, nullptr, lo, hi, s);
+    if (rc) return rc;
+    const T* ins_lo[8] = {lo};
+    const T* ins_hi[8] = {hi};
+    rc = fused3_run<T>(p, false, Lp, ins_lo, out, p->dims[2], p->dims[3], vol3_in, vol3, 0, s);
+    if (rc) return rc;
+    return fused3_run<T>(p, false, Lp, ins_hi, out + 8, p->dims[2], p->dims[3], vol3_in, vol3, 0, s);
+}
+
+template <typename T>
+static int synthesis_level_z(ndwt_plan* p, const T* const* in, T* out, long long stride, hipStream_t s) {
+    const long long n_in = p->dims[2] + (long long)(p->filt[2].len - 1) * stride;
+    const long long vol3 = p->comp * p->dims[0] * p->dims[1] * p->dims[2], vol3_in = vol3 / p->dims[2] * n_in;
+    int Lp = 0;
+    if (!zslab_fused(p, stride, &Lp, 1)) {
+        T* outs[1] = {out};
+        return generic_level<T>(p, true, in, outs, stride, s);
+    }
+    const long long skew = 256 / (long long)sizeof(T);
+    int rc = ensure_tmp(p, (size_t)(2 * p->vol + skew) * sizeof(T));
+    if (rc) return rc;
+    T* a = (T*)p->tmp;
+    T* dd = a + p->vol + skew;
+    T* outs_a[8] = {a};
+    T* outs_d[8] = {dd};
+    rc = fused3_run<T>(p, true, Lp, in, outs_a, p->dims[2], p->dims[3], vol3_in, vol3, 0, s, 0, LLONG_MIN, 0, 0xFE);
+    if (rc) return rc;
+    rc = fused3_run<T>(p, true, Lp, in + 8, outs_d, p->dims[2], p->dims[3], vol3_in, vol3, 0, s, 0, LLONG_MIN, 0, 0xFF);
+    if (rc) return rc;
+    return axis_pass<T>(p, true, 3, p->dims, stride, true, a, dd, out, nullptr, s);
+}
+
+// per-axis passes of one slab level, halo on the sharded axis p->shard (z-slabs; outer-axis slabs keep the code below)
+template <typename T> static int generic_level(ndwt_plan* p, bool synthesis, const T* const* in, T* const* out, long long stride, hipStream_t s) {
+    const int d = p->ndim;
+    GenericCtx<T> c;
+    c.p = p; c.stride = stride; c.slab = true; c.s = s;
+    for (int k = 0; k < d; ++k) c.dims_cur[k] = p->dims[k];
+    c.n_in = p->dims[p->shard] + (long long)(p->filt[p->shard].len - 1) * stride;
+    c.vol_cur = p->vol;
+    c.vol_tmp = p->vol / p->dims[p->shard] * c.n_in;
+    int rc = ensure_tmp(p, (size_t)(2 * (d - 1)) * (size_t)c.vol_tmp * sizeof(T));
+    if (rc) return rc;
+    c.tmp = (T*)p->tmp;
+    if (!synthesis) return generic_analysis<T>(c, d - 1, in[0], 0, out);
+    T* a = c.tmp + (long long)(2 * (d - 2)) * c.vol_tmp;
+    T* dd = a + c.vol_tmp;
+    rc = generic_synthesis<T>(c, d - 2, 0, in, a);
+    if (rc) return rc;
+    rc = generic_synthesis<T>(c, d - 2, 1 << (d - 1), in, dd);
+    if (rc) return rc;
+    long long dbuf[NDWT_MAX_DIMS];
+    return axis_pass<T>(p, true, d - 1, generic_dims(c, d - 1, true, dbuf), stride, d - 1 != p->shard, a, dd, out[0], nullptr, s);
+}
+
 template <typename T>
 static int analysis_level(ndwt_plan* p, const T* in, T* const* out, long long stride, bool slab, hipStream_t s) {
+    if (slab && p->shard != p->ndim - 1) return analysis_level_z<T>(p, in, out, stride, s);
     const int d = p->ndim;
     const AxisFilter& ftop = p->filt[d - 1];
     const long long n_top = p->dims[d - 1];
@@ -711,6 +811,7 @@ static int analysis_level(ndwt_plan* p, const T* in, T* const* out, long long st
 
 template <typename T>
 static int synthesis_level(ndwt_plan* p, const T* const* in, T* out, long long stride, bool slab, hipStream_t s) {
+    if (slab && p->shard != p->ndim - 1) return synthesis_level_z<T>(p, in, out, stride, s);
     const int d = p->ndim;
     const AxisFilter& ftop = p->filt[d - 1];
     const long long n_top = p->dims[d - 1];
@@ -1144,6 +1245,65 @@ __global__ __launch_bounds__(256) void segments_kernel(const SegArgs a) {
         else d[i] = s[i];
     }
 }
+// ---- the strided form (include/ndwt.h: ndwt_slab_segments_strided): nrep repetitions of every run, repetition q at q * stride in
+// both buffers -- the planes of a z-slab are one run per frame.  blockIdx.y = run, blockIdx.z = repetition; 16-byte accesses over
+// the whole 16-byte groups of a run whose two sides are 16-byte aligned in every repetition, scalars for the tail and elsewhere.
+struct SegStridedArgs {
+    void* dst[NDWT_MAX_SEGMENTS];
+    const void* src[NDWT_MAX_SEGMENTS];
+    long long count[NDWT_MAX_SEGMENTS];      // scalars
+    long long dst_stride[NDWT_MAX_SEGMENTS], src_stride[NDWT_MAX_SEGMENTS];
+    int vec[NDWT_MAX_SEGMENTS];
+    long long nrep;
+};
+template <typename T, typename V, bool ADD>
+__global__ __launch_bounds__(256) void segments_strided_kernel(const SegStridedArgs a) {
+    constexpr int PER = (int)(sizeof(V) / sizeof(T));
+    const int r = blockIdx.y;
+    const long long n = a.count[r];
+    const long long nv = a.vec[r] ? n / PER : 0;
+    const long long t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
+    for (long long q = blockIdx.z; q < a.nrep; q += gridDim.z) {
+        T* __restrict__ d = (T*)a.dst[r] + q * a.dst_stride[r];
+        const T* __restrict__ s = (const T*)a.src[r] + q * a.src_stride[r];
+        for (long long i = t0; i < nv; i += step) {
+            if constexpr (ADD) ((V*)d)[i] = ((V*)d)[i] + ((const V*)s)[i];
+            else ((V*)d)[i] = ((const V*)s)[i];
+        }
+        for (long long i = nv * PER + t0; i < n; i += step) {
+            if constexpr (ADD) d[i] = d[i] + s[i];
+            else d[i] = s[i];
+        }
+    }
+}
+template <typename T> int segments_strided_launch(int op, int nseg, void* const* dst, const void* const* src, const int64_t* count,
+                                                  long long nrep, const int64_t* dst_stride, const int64_t* src_stride, hipStream_t st) {
+    typedef typename std::conditional<sizeof(T) == 4, typename VecT<T>::v4, typename VecT<T>::v2>::type V;
+    constexpr int per = 16 / (int)sizeof(T);
+    SegStridedArgs a;
+    memset(&a, 0, sizeof a);
+    long long most = 1;
+    for (int i = 0; i < nseg; ++i) {
+        a.dst[i] = dst[i];
+        a.src[i] = src[i];
+        a.count[i] = count[i];
+        a.dst_stride[i] = dst_stride[i];
+        a.src_stride[i] = src_stride[i];
+        a.vec[i] = (uintptr_t)dst[i] % 16 == 0 && (uintptr_t)src[i] % 16 == 0 && (nrep == 1 || (dst_stride[i] % per == 0 && src_stride[i] % per == 0));
+        const long long w = a.vec[i] ? (count[i] + per - 1) / per : count[i];
+        if (w > most) most = w;
+    }
+    a.nrep = nrep;
+    const long long bz = nrep < 65535 ? nrep : 65535;
+    long long bx = (most + 255) / 256;
+    if (bx > 2048) bx = 2048;
+    if (bx * bz > 16384) bx = 16384 / bz > 1 ? 16384 / bz : 1;   // the repetitions fill the chip; the loops cover the rest
+    const dim3 grid((unsigned)bx, (unsigned)nseg, (unsigned)bz);
+    if (op) hipLaunchKernelGGL((segments_strided_kernel<T, V, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((segments_strided_kernel<T, V, false>), grid, dim3(256), 0, st, a);
+    return (int)hipGetLastError();
+}
+
 template <typename T> int segments_launch(int op, int nseg, void* const* dst, const void* const* src, const int64_t* count, hipStream_t st) {
     typedef typename VecT<T>::v4 V4;
     constexpr int per = 16 / (int)sizeof(T);
@@ -1172,6 +1332,59 @@ template <typename T> int segments_launch(int op, int nseg, void* const* dst, co
 }
 }  // namespace
 
+// z-slab, split-halo analysis: the t pass reads whole z-extended frames, so the two halo buffers (nt, ab, ny, nx) / (nt, aa, ny, nx) and
+// the local slab are assembled into one (nt, ab + n + aa, ny, nx) scratch -- one strided segment launch (3 runs x nt frames) -- and the
+// level runs on it
+template <typename T>
+static int slab_split_z_impl(ndwt_plan* p, const void* in, const void* hb, const void* ha, void* const* out, long long stride, hipStream_t s) {
+    const long long ab = (long long)(p->filt[2].len / 2 - 1) * stride, aa = (long long)(p->filt[2].len / 2) * stride, n = p->dims[2];
+    const long long P = p->comp * p->dims[0] * p->dims[1], nin = ab + n + aa;
+    const size_t bytes = (size_t)(P * nin * p->dims[3]) * sizeof(T);
+    if (bytes > p->zin_bytes) {
+        if (p->zin) {
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(hipFree(p->zin));
+            p->zin = nullptr;
+            p->zin_bytes = 0;
+        }
+        hipError_t e = hipMalloc(&p->zin, bytes);
+        if (e != hipSuccess) return fail(NDWT_ERR_ALLOC, "hipMalloc(%zu bytes) for the z-extended slab failed: %s", bytes, hipGetErrorString(e));
+        p->zin_bytes = bytes;
+    }
+    T* z = (T*)p->zin;
+    void* dst[3];
+    const void* src[3];
+    int64_t cnt[3], dstr[3], sstr[3];
+    int k = 0;
+    if (ab) { dst[k] = z; src[k] = hb; cnt[k] = ab * P; dstr[k] = nin * P; sstr[k] = ab * P; ++k; }
+    dst[k] = z + ab * P; src[k] = in; cnt[k] = n * P; dstr[k] = nin * P; sstr[k] = n * P; ++k;
+    dst[k] = z + (ab + n) * P; src[k] = ha; cnt[k] = aa * P; dstr[k] = nin * P; sstr[k] = aa * P; ++k;
+    const int rc = segments_strided_launch<T>(NDWT_SEG_COPY, k, dst, src, cnt, p->dims[3], dstr, sstr, s);
+    if (rc != 0) return fail(NDWT_ERR_HIP, "segment kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return analysis_level_z<T>(p, z, (T* const*)out, stride, s);
+}
+
+// z-slab, zero-extended synthesis (scatter scheme): the 3-D part of both t-bands on the zero-extended z axis of every frame (z_mode 3,
+// the frames as batch items, each tested against the same [0, n)), then the periodic t pass: (nt, n + L - 1, ny, nx)
+template <typename T> static int slab_ext_z_impl(ndwt_plan* p, int Lp, const void* const* in, void* out, hipStream_t s) {
+    const long long n = p->dims[2], next = n + Lp - 1;
+    const long long vol3 = p->comp * p->dims[0] * p->dims[1] * n, vol3_ext = vol3 / n * next, vol_ext = vol3_ext * p->dims[3];
+    const long long skew = 256 / (long long)sizeof(T);
+    int rc = ensure_tmp(p, (size_t)(2 * vol_ext + skew) * sizeof(T));
+    if (rc) return rc;
+    T* a = (T*)p->tmp;
+    T* dd = a + vol_ext + skew;
+    const T* const* inT = (const T* const*)in;
+    T* outs_a[8] = {a};
+    T* outs_d[8] = {dd};
+    rc = fused3_run<T>(p, true, Lp, inT, outs_a, next, p->dims[3], vol3, vol3_ext, 3, s, 0, n, 0);
+    if (rc) return rc;
+    rc = fused3_run<T>(p, true, Lp, inT + 8, outs_d, next, p->dims[3], vol3, vol3_ext, 3, s, 0, n, 0);
+    if (rc) return rc;
+    long long dims_ext[NDWT_MAX_DIMS] = {p->dims[0], p->dims[1], next, p->dims[3]};
+    return axis_pass<T>(p, true, 3, dims_ext, 1, true, a, dd, (T*)out, nullptr, s);
+}
+
 extern "C" {
 
 int ndwt_wave_filters(const char* wname, double* lo_d, double* hi_d, int* len) {
@@ -1198,7 +1411,7 @@ int ndwt_level_from_bands(int ndim, int64_t bands) {
 static bool den3_eligible(const ndwt_plan* p, int* Lp_out);
 static int den3_taps(ndwt_plan* p, int Lp);
 static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, long long global_outer, const char* const* wnames, int dtype,
-                            int complexity, int pres_l2_norm, int dilation, int max_level, int device) {
+                            int complexity, int pres_l2_norm, int dilation, int max_level, int device, int shard = -1) {
     if (!plan) return fail(NDWT_ERR_INVALID_ARG, "null plan pointer");
     *plan = nullptr;
     if (ndim < 1 || ndim > NDWT_MAX_DIMS) return fail(NDWT_ERR_INVALID_ARG, "ndim must be 1..4");
@@ -1223,6 +1436,7 @@ static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, lon
     p->prof = new std::vector<ProfRec>();
     p->ev_pool = new std::vector<hipEvent_t>();
     p->fused_level1 = 1;
+    p->shard = shard >= 0 ? shard : ndim - 1;
     p->fp64_fused = 1;   // measured: 256^3 fp64 db4 L3 2.5 ms fused (LDS analysis + lane-shift synthesis) vs 4.1 ms per-axis
     static const char* ordn[4] = {"First", "Second", "Third", "Fourth"};
     p->vol = p->comp;
@@ -1234,8 +1448,8 @@ static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, lon
         p->order[a] = K;
         p->filt[a] = make_axis_filter(K, p->l2 != 0);
         // nd_dwt_3D.m:277-286; for a slab plan the check is on the whole sharded axis, not on the local planes
-        const long long axis_len = (a == ndim - 1 && global_outer > 0) ? global_outer : dims[a];
-        if (a == ndim - 1 && global_outer > 0 && p->filt[a].len > dims[a]) p->thin_slab = 1;
+        const long long axis_len = (a == p->shard && global_outer > 0) ? global_outer : dims[a];
+        if (a == p->shard && global_outer > 0 && p->filt[a].len > dims[a]) p->thin_slab = 1;
         if (p->filt[a].len > axis_len) {
             delete p->prof;
             delete p->ev_pool;
@@ -1330,6 +1544,21 @@ int ndwt_plan_create_slab(ndwt_plan** plan, int ndim, const int64_t* dims_local,
     return plan_create_impl(plan, ndim, dims_local, global_outer, wnames, dtype, complexity, pres_l2_norm, dilation, max_level, device);
 }
 
+int ndwt_plan_create_slab_axis(ndwt_plan** plan, int ndim, const int64_t* dims_local, int shard_axis, int64_t global_len,
+                               const char* const* wnames, int dtype, int complexity, int pres_l2_norm, int dilation, int max_level, int device) {
+    if (plan) *plan = nullptr;
+    if (ndim < 1 || ndim > NDWT_MAX_DIMS || !dims_local) return fail(NDWT_ERR_INVALID_ARG, "ndim must be 1..4, dims non-null");
+    if (shard_axis == ndim - 1)
+        return ndwt_plan_create_slab(plan, ndim, dims_local, global_len, wnames, dtype, complexity, pres_l2_norm, dilation, max_level, device);
+    if (!(ndim == 4 && shard_axis == 2))
+        return fail(NDWT_ERR_UNSUPPORTED, "shard_axis %d of a %d-D volume: slab plans shard the outermost axis (%d), or z (2) of a 4-D volume",
+                    shard_axis, ndim, ndim - 1);
+    if (global_len < dims_local[shard_axis])
+        return fail(NDWT_ERR_INVALID_ARG, "global_len (%lld) is shorter than the local slab (%lld)", (long long)global_len,
+                    (long long)dims_local[shard_axis]);
+    return plan_create_impl(plan, ndim, dims_local, global_len, wnames, dtype, complexity, pres_l2_norm, dilation, max_level, device, shard_axis);
+}
+
 int ndwt_plan_destroy(ndwt_plan* p) {
     if (!p) return NDWT_OK;
     if (p->live_coefs > 0)                                // (a handle points back at its plan: release the handles first)
@@ -1338,6 +1567,7 @@ int ndwt_plan_destroy(ndwt_plan* p) {
     for (int i = 0; i < 2; ++i)
         if (p->approx_base[i]) (void)hipFree(p->approx_base[i]);
     if (p->tmp) (void)hipFree(p->tmp);
+    if (p->zin) (void)hipFree(p->zin);
     if (p->coef) (void)hipFree(p->coef);
     if (p->taps_den) (void)hipFree(p->taps_den);
     if (p->den_a1) (void)hipFree(p->den_a1);
@@ -1917,12 +2147,13 @@ int ndwt_rec_split_host(ndwt_plan* p, const void* y_re, const void* y_im, void* 
 
 int ndwt_plan_slab_fast(const ndwt_plan* p) {
     int Lp = 0;
+    if (p && p->shard != p->ndim - 1) return zslab_fused(p, 1, &Lp, -1) ? 1 : 0;   // z-slab: the zero-extended synthesis exists
     return p && p->ndim == 3 && fused3_eligible(p, 1, &Lp) && p->filt[2].len == Lp ? 1 : 0;
 }
 
 int ndwt_slab_halo(const ndwt_plan* p, int stride, int64_t* ab, int64_t* aa, int64_t* sb, int64_t* sa) {
     if (!p || stride < 1) return fail(NDWT_ERR_INVALID_ARG, "bad plan/stride");
-    const int L = p->filt[p->ndim - 1].len;
+    const int L = p->filt[p->shard].len;
     if (ab) *ab = (int64_t)(L / 2 - 1) * stride;
     if (aa) *aa = (int64_t)(L / 2) * stride;
     if (sb) *sb = (int64_t)(L / 2) * stride;
@@ -1949,6 +2180,13 @@ int ndwt_synthesis_level_slab(ndwt_plan* p, const void* const* in, void* out, in
 int ndwt_analysis_level_slab_split(ndwt_plan* p, const void* in_local, const void* halo_before, const void* halo_after,
                                    void* const* out, int stride, void* stream) {
     int Lp = 0;
+    if (p && p->shard != p->ndim - 1) {                  // z-slab: assembled with its halo planes, then the level (any plan kind)
+        if (stride < 1) return fail(NDWT_ERR_INVALID_ARG, "bad stride");
+        if (!in_local || !out || (p->filt[2].len > 2 && !halo_before) || !halo_after) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
+        HIP_TRY(hipSetDevice(p->device));
+        return p->dtype == NDWT_F32 ? slab_split_z_impl<float>(p, in_local, halo_before, halo_after, out, stride, (hipStream_t)stream)
+                                    : slab_split_z_impl<double>(p, in_local, halo_before, halo_after, out, stride, (hipStream_t)stream);
+    }
     int rc = slab_fast_ok(p, stride, &Lp);
     if (rc) return rc;
     if (!in_local || !out || (Lp > 2 && !halo_before) || !halo_after) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
@@ -1960,6 +2198,14 @@ int ndwt_analysis_level_slab_split(ndwt_plan* p, const void* in_local, const voi
 
 int ndwt_synthesis_level_slab_ext(ndwt_plan* p, const void* const* in_local, void* out_ext, int stride, void* stream) {
     int Lp = 0;
+    if (p && p->shard != p->ndim - 1) {                  // z-sharded 4-D: the fused kernels with the z filter the longest, tap stride 1
+        if (stride != 1 || !zslab_fused(p, 1, &Lp, 1))
+            return fail(NDWT_ERR_UNSUPPORTED, "the zero-extended z-slab synthesis needs a plan on the fused 3-D kernels whose z filter is the longest (stride 1)");
+        if (!in_local || !out_ext) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
+        HIP_TRY(hipSetDevice(p->device));
+        return p->dtype == NDWT_F32 ? slab_ext_z_impl<float>(p, Lp, in_local, out_ext, (hipStream_t)stream)
+                                    : slab_ext_z_impl<double>(p, Lp, in_local, out_ext, (hipStream_t)stream);
+    }
     if (p && p->ndim == 4) {                             // t-sharded 4-D: 3-D part per frame, zero-extended t-axis pass
         if (stride != 1 || !fused3_eligible(p, 1, &Lp))
             return fail(NDWT_ERR_UNSUPPORTED, "the zero-extended 4-D slab synthesis needs a plan on the fused 3-D kernels (stride 1)");
@@ -2045,6 +2291,28 @@ int ndwt_slab_segments(ndwt_plan* p, int op, int nseg, void* const* dst, const v
     HIP_TRY(hipSetDevice(p->device));
     const int rc = p->dtype == NDWT_F32 ? segments_launch<float>(op, nseg, dst, src, count, (hipStream_t)stream)
                                         : segments_launch<double>(op, nseg, dst, src, count, (hipStream_t)stream);
+    if (rc != 0) return fail(NDWT_ERR_HIP, "segment kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return NDWT_OK;
+}
+
+int ndwt_slab_segments_strided(ndwt_plan* p, int op, int nseg, void* const* dst, const void* const* src, const int64_t* count, int64_t nrep,
+                               const int64_t* dst_stride, const int64_t* src_stride, void* stream) {
+    if (!p) return fail(NDWT_ERR_INVALID_ARG, "null plan");
+    if (op != NDWT_SEG_COPY && op != NDWT_SEG_ADD) return fail(NDWT_ERR_INVALID_ARG, "op must be NDWT_SEG_COPY or NDWT_SEG_ADD");
+    if (nseg < 0 || nseg > NDWT_MAX_SEGMENTS) return fail(NDWT_ERR_INVALID_ARG, "at most %d runs per call", NDWT_MAX_SEGMENTS);
+    if (nrep < 0) return fail(NDWT_ERR_INVALID_ARG, "negative repetition count");
+    if (nseg == 0 || nrep == 0) return NDWT_OK;
+    if (!dst || !src || !count || !dst_stride || !src_stride) return fail(NDWT_ERR_INVALID_ARG, "null argument");
+    for (int i = 0; i < nseg; ++i) {
+        if (!dst[i] || !src[i] || count[i] < 0 || dst_stride[i] < 0 || src_stride[i] < 0)
+            return fail(NDWT_ERR_INVALID_ARG, "run %d: null pointer, negative count or negative stride", i);
+        if (nrep > 1 && dst_stride[i] < count[i])      // the repetitions of a run are written concurrently: they must not overlap
+            return fail(NDWT_ERR_INVALID_ARG, "run %d: destination stride %lld is shorter than the run (%lld)", i, (long long)dst_stride[i],
+                        (long long)count[i]);
+    }
+    HIP_TRY(hipSetDevice(p->device));
+    const int rc = p->dtype == NDWT_F32 ? segments_strided_launch<float>(op, nseg, dst, src, count, nrep, dst_stride, src_stride, (hipStream_t)stream)
+                                        : segments_strided_launch<double>(op, nseg, dst, src, count, nrep, dst_stride, src_stride, (hipStream_t)stream);
     if (rc != 0) return fail(NDWT_ERR_HIP, "segment kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     return NDWT_OK;
 }

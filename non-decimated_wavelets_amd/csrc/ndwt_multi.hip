@@ -97,7 +97,9 @@ struct Team {
 struct ndwt_mplan {
     int ndim, dtype, complexity, max_level, nb;
     long long dims[NDWT_MAX_DIMS];
-    size_t plane_bytes;            // bytes of one plane of the outer axis (one band)
+    int shard;                     // the sharded axis: ndim - 1 (outermost), or 2 of a 4-D volume (z; t whole on every slab)
+    long long nrep;                // frames: runs of planes per plane index of the sharded axis (1 for the outermost axis)
+    size_t plane_bytes;            // bytes of one plane of the sharded axis (one band; z-slabs: of one frame)
     long long halo_max;            // planes of margin in the approximation buffers
     int L_outer;
     int dilation;
@@ -109,6 +111,7 @@ struct ndwt_mplan {
     double last_enqueue_us;        // host time the last ndwt_mdec / ndwt_mrec spent queueing work (before it waited for the devices)
     int threads;                   // 1: one host thread per slab queues its work (default with more than one slab); 0: the caller queues everything
     Team* team;
+    std::vector<std::pair<int, int>> peer;   // (a, b): kernels on device a may read device b's memory (peer access enabled)
     std::vector<std::vector<int>> nbr;   // nbr[i]: the slabs (i itself included) that own a plane within halo_max of slab i: the only slabs whose
                                          // buffers slab i ever reads or whose copies ever read slab i's (the relation is symmetric)
 };
@@ -229,6 +232,8 @@ template <class F> static int phase(ndwt_mplan* mp, F&& fn) {
 
 static long long stride_of(const ndwt_mplan* mp, int lev) { return mp->dilation == NDWT_DILATION_ATROUS ? (1LL << (lev - 1)) : 1LL; }
 
+static long long axis_len(const ndwt_mplan* mp) { return mp->dims[mp->shard]; }
+
 static Slab* owner_of(ndwt_mplan* mp, long long gp) {
     for (auto& s : mp->slabs)
         if (gp >= s.z0 && gp < s.z0 + s.n) return &s;
@@ -247,7 +252,7 @@ static int copy_run(ndwt_mplan* mp, Slab& to, char* dst, const Slab& from, const
 // plane_ptr(slab, local plane) gives the source address; wait_parity >= 0: wait for the source slab's ready[wait_parity] first.
 template <class SrcFn>
 static int copy_planes(ndwt_mplan* mp, Slab& to, char* dst, long long g, long long count, SrcFn plane_ptr, int wait_parity, hipStream_t st = nullptr) {
-    const long long N = mp->dims[mp->ndim - 1];
+    const long long N = axis_len(mp);
     long long done = 0;
     while (done < count) {
         const long long gp = ((g + done) % N + N) % N;
@@ -335,7 +340,9 @@ static int mcheck(const ndwt_mplan* mp, int level) {
 // ------------------------------------------------------------------------------------------------ analysis
 // x[i]: the slab of the signal on slab i's device (n_i planes); y[i]: its coefficient slab, band b at b * n_i planes.  Queues the
 // whole transform on the slabs' streams; the caller synchronises.
+static int mdec_core_z(ndwt_mplan* mp, const void* const* x, void* const* y, int level);
 static int mdec_core(ndwt_mplan* mp, const void* const* x, void* const* y, int level) {
+    if (mp->shard != mp->ndim - 1) return mdec_core_z(mp, x, y, level);
     const size_t pb = mp->plane_bytes;
     const long long H = mp->halo_max;
     const int nb = mp->nb;
@@ -414,7 +421,7 @@ static int mdec_core(ndwt_mplan* mp, const void* const* x, void* const* y, int l
 // dst_of(slab) = where that slab's n planes of this level's result live.
 template <class DstFn>
 static int scatter_margin(ndwt_mplan* mp, Slab& from, const char* buf, long long g, long long count, DstFn dst_of) {
-    const long long N = mp->dims[mp->ndim - 1];
+    const long long N = axis_len(mp);
     long long done = 0;
     while (done < count) {
         const long long gp = ((g + done) % N + N) % N;
@@ -437,7 +444,9 @@ static int scatter_margin(ndwt_mplan* mp, Slab& from, const char* buf, long long
     return NDWT_OK;
 }
 
+static int mrec_core_z(ndwt_mplan* mp, const void* const* y, void* const* x, int level);
 static int mrec_core(ndwt_mplan* mp, const void* const* y, void* const* x, int level) {
+    if (mp->shard != mp->ndim - 1) return mrec_core_z(mp, y, x, level);
     const size_t pb = mp->plane_bytes;
     const long long H = mp->halo_max;
     const int nb = mp->nb;
@@ -472,7 +481,7 @@ static int mrec_core(ndwt_mplan* mp, const void* const* y, void* const* x, int l
             // "before" margins first, behind the destination's own launch: the same fixed order of summation as without overlap.
             // Every DESTINATION slab queues what arrives at it (its own streams only): the producers' margins events were recorded in the
             // phase above.  The record of its ready[wr] (level barrier) closes the phase.
-            const long long N = mp->dims[mp->ndim - 1];
+            const long long N = axis_len(mp);
             MRET(phase(mp, [&](size_t ti) -> int {
                 Slab& t = mp->slabs[ti];
                 MHIP(hipSetDevice(t.device));
@@ -558,15 +567,179 @@ static int mrec_core(ndwt_mplan* mp, const void* const* y, void* const* x, int l
     return NDWT_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ z-slabs
+// A 4-D volume sharded on z: every slab holds all nt frames of its planes, (nt, n, ny, nx) per band.  A plane index of the sharded axis is
+// nrep = nt runs of plane_bytes, frame q of a slab's array at q * n planes.  Moving planes between slabs is one strided segment launch per
+// run of planes (ndwt_slab_segments_strided on the destination's device: it reads the source in place where the devices are the same or
+// have peer access), else one peer copy per frame.  The levels run the z-slab entry points (split-halo analysis, zero-extended or gathered
+// synthesis); the overlapped schedule is not offered.
+static bool direct_access(const ndwt_mplan* mp, int to_dev, int from_dev) {
+    if (to_dev == from_dev) return true;
+    for (auto& pr : mp->peer)
+        if (pr.first == to_dev && pr.second == from_dev) return true;
+    return false;
+}
+
+// `planes` planes of every frame: dst (dst_fp planes per frame) = / += src (src_fp planes per frame), on `to`'s stream st
+static int copy_frames(ndwt_mplan* mp, Slab& to, char* dst, long long dst_fp, const Slab& from, const char* src, long long src_fp,
+                       long long planes, int op, hipStream_t st) {
+    const size_t pb = mp->plane_bytes;
+    if (planes <= 0) return NDWT_OK;
+    if (direct_access(mp, to.device, from.device)) {
+        const long long spp = (long long)(pb / (mp->dtype == NDWT_F32 ? 4 : 8));   // scalars per plane
+        void* d[1] = {dst};
+        const void* sr[1] = {src};
+        const int64_t cnt = planes * spp, ds = dst_fp * spp, ss = src_fp * spp;
+        MTRY(ndwt_slab_segments_strided(to.plan, op, 1, d, sr, &cnt, mp->nrep, &ds, &ss, st));
+        return NDWT_OK;
+    }
+    if (op != NDWT_SEG_COPY) return mfail(NDWT_ERR_UNSUPPORTED, "internal: adds across devices without peer access are staged");
+    for (long long q = 0; q < mp->nrep; ++q)
+        MHIP(hipMemcpyPeerAsync(dst + (size_t)(q * dst_fp) * pb, to.device, src + (size_t)(q * src_fp) * pb, from.device, (size_t)planes * pb, st));
+    return NDWT_OK;
+}
+
+// `count` planes starting at GLOBAL plane g (periodic) into dst (dst_fp planes per frame) on slab `to`; plane_ptr(slab, local plane) =
+// the source address in frame 0 of that slab's array (n planes per frame)
+template <class SrcFn>
+static int copy_planes_z(ndwt_mplan* mp, Slab& to, char* dst, long long dst_fp, long long g, long long count, SrcFn plane_ptr) {
+    const long long N = axis_len(mp);
+    long long done = 0;
+    while (done < count) {
+        const long long gp = ((g + done) % N + N) % N;
+        Slab* src = owner_of(mp, gp);
+        if (!src) return mfail(NDWT_ERR_INVALID_ARG, "plane %lld has no owner", gp);
+        long long run = src->z0 + src->n - gp;
+        if (run > count - done) run = count - done;
+        MRET(copy_frames(mp, to, dst + (size_t)done * mp->plane_bytes, dst_fp, *src, plane_ptr(*src, gp - src->z0), src->n, run, NDWT_SEG_COPY, to.stream));
+        done += run;
+    }
+    return NDWT_OK;
+}
+
+static int mdec_core_z(ndwt_mplan* mp, const void* const* x, void* const* y, int level) {
+    const size_t pb = mp->plane_bytes;
+    const long long R = mp->nrep;
+    const int nb = mp->nb;
+    for (int lev = 1; lev <= level; ++lev) {
+        const long long st = stride_of(mp, lev);
+        const long long ab = (long long)(mp->L_outer / 2 - 1) * st, aa = (long long)(mp->L_outer / 2) * st;
+        const int rd = ((lev - 1) & 1) ^ 1, wr = (lev - 1) & 1;
+        auto input = [&](Slab& o) -> const char* { return lev == 1 ? (const char*)x[&o - &mp->slabs[0]] : o.approx[rd]; };
+        auto body = [&](size_t i) -> int {
+            Slab& s = mp->slabs[i];
+            MHIP(hipSetDevice(s.device));
+            void* outs[16];
+            outs[0] = lev == level ? y[i] : (void*)s.approx[wr];
+            for (int b = 1; b < nb; ++b) outs[b] = (char*)y[i] + (size_t)((1 + (nb - 1) * (level - lev) + (b - 1)) * R * s.n) * pb;
+            // the halo planes of every frame from their owners' inputs of this level (producers: waited for at the end of level lev - 1)
+            auto src = [&](Slab& o, long long lp) -> const char* { return input(o) + (size_t)lp * pb; };
+            MRET(copy_planes_z(mp, s, s.hb, ab, s.z0 - ab, ab, src));
+            MRET(copy_planes_z(mp, s, s.ha, aa, s.z0 + s.n, aa, src));
+            MTRY(ndwt_analysis_level_slab_split(s.plan, input(s), ab ? s.hb : nullptr, s.ha, outs, (int)st, s.stream));
+            return barrier_record(mp, i, wr);
+        };
+        MRET(phase(mp, body));
+        MRET(phase(mp, [&](size_t i) { return barrier_wait(mp, i, wr); }));
+    }
+    return NDWT_OK;
+}
+
+static int mrec_core_z(ndwt_mplan* mp, const void* const* y, void* const* x, int level) {
+    const size_t pb = mp->plane_bytes;
+    const long long R = mp->nrep, N = axis_len(mp);
+    const int nb = mp->nb;
+    const long long smax = mp->dilation == NDWT_DILATION_ATROUS ? (1LL << (mp->max_level - 1)) : 1LL;
+    for (int ind = 1; ind <= level; ++ind) {
+        const int lev = level - ind + 1;
+        const long long st = stride_of(mp, lev);
+        const long long sb = (long long)(mp->L_outer / 2) * st, sa = (long long)(mp->L_outer / 2 - 1) * st;
+        const int rd = ind & 1, wr = rd ^ 1;
+        const bool scatter = mp->exchange == NDWT_EXCHANGE_SCATTER && mp->fast && st == 1;
+        auto band_ptr = [&](size_t i, Slab& o, int b) -> const char* {
+            if (b == 0) return ind == 1 ? (const char*)y[i] : o.approx[rd];
+            return (const char*)y[i] + (size_t)((1 + (long long)(nb - 1) * (level - lev) + (b - 1)) * R * o.n) * pb;
+        };
+        auto dst_of = [&](Slab& o) -> char* { return lev == 1 ? (char*)x[&o - &mp->slabs[0]] : o.approx[wr]; };
+        for (auto& s : mp->slabs)
+            MRET(lazy_alloc(s, &s.gather, (size_t)((long long)nb * R * (s.n + (long long)(mp->L_outer - 1) * smax)) * pb));
+        if (scatter) {
+            // zero-extended synthesis into the slab's scratch, (nt, sa + n + sb) planes: its own n planes are copied to where the result
+            // lives, the sa planes before and the sb planes after them are partial sums added by their owners, producers in slab order,
+            // "before" margins first (a fixed order of summation)
+            const long long margin = sa + sb;                 // planes of the zero-extended result beyond the slab's own
+            size_t i = 0;
+            for (auto& s : mp->slabs) {
+                MHIP(hipSetDevice(s.device));
+                const void* ins[16];
+                for (int b = 0; b < nb; ++b) ins[b] = band_ptr(i, s, b);
+                MTRY(ndwt_synthesis_level_slab_ext(s.plan, ins, s.gather, 1, s.stream));
+                MRET(copy_frames(mp, s, dst_of(s), s.n, s, s.gather + (size_t)sa * pb, s.n + margin, s.n, NDWT_SEG_COPY, s.stream));
+                MHIP(hipEventRecord(s.margins, s.stream));
+                ++i;
+            }
+            for (auto& from : mp->slabs) {
+                for (int side = 0; side < 2; ++side) {
+                    const long long count = side == 0 ? sa : sb;
+                    const long long g = side == 0 ? from.z0 - sa : from.z0 + from.n;
+                    const char* buf = from.gather + (size_t)(side == 0 ? 0 : sa + from.n) * pb;
+                    long long done = 0;
+                    while (done < count) {
+                        const long long gp = ((g + done) % N + N) % N;
+                        Slab* to = owner_of(mp, gp);
+                        if (!to) return mfail(NDWT_ERR_INVALID_ARG, "plane %lld has no owner", gp);
+                        long long run = to->z0 + to->n - gp;
+                        if (run > count - done) run = count - done;
+                        MHIP(hipSetDevice(to->device));
+                        if (to != &from) MHIP(hipStreamWaitEvent(to->stream, from.margins, 0));
+                        char* dst = dst_of(*to) + (size_t)(gp - to->z0) * pb;
+                        const char* src = buf + (size_t)done * pb;
+                        if (direct_access(mp, to->device, from.device)) {
+                            MRET(copy_frames(mp, *to, dst, to->n, from, src, from.n + margin, run, NDWT_SEG_ADD, to->stream));
+                        } else {                          // staged: the frames' runs into the receive buffer, then added from there
+                            MRET(copy_frames(mp, *to, to->recv, run, from, src, from.n + margin, run, NDWT_SEG_COPY, to->stream));
+                            MRET(copy_frames(mp, *to, dst, to->n, *to, to->recv, run, run, NDWT_SEG_ADD, to->stream));
+                        }
+                        done += run;
+                    }
+                }
+            }
+        } else {
+            for (auto& s : mp->slabs) {
+                MHIP(hipSetDevice(s.device));
+                const long long nh = s.n + sb + sa;
+                const void* ins[16];
+                for (int b = 0; b < nb; ++b) {
+                    char* dst = s.gather + (size_t)((long long)b * R * nh) * pb;
+                    ins[b] = dst;
+                    auto src = [&, b](Slab& o, long long lp) -> const char* { return band_ptr(&o - &mp->slabs[0], o, b) + (size_t)lp * pb; };
+                    MRET(copy_planes_z(mp, s, dst, nh, s.z0 - sb, nh, src));   // all producers were waited for at the end of the previous level
+                }
+                MTRY(ndwt_synthesis_level_slab(s.plan, ins, dst_of(s), (int)st, s.stream));
+            }
+        }
+        MRET(level_barrier(mp, wr));
+    }
+    return NDWT_OK;
+}
+
 extern "C" {
 
 int ndwt_mplan_create(ndwt_mplan** out, int ndim, const int64_t* dims, const char* const* wnames, int dtype, int complexity,
                       int pres_l2_norm, int dilation, int max_level, const int* devices, int ndev) {
+    return ndwt_mplan_create_axis(out, ndim, dims, wnames, dtype, complexity, pres_l2_norm, dilation, max_level, devices, ndev, ndim - 1);
+}
+
+int ndwt_mplan_create_axis(ndwt_mplan** out, int ndim, const int64_t* dims, const char* const* wnames, int dtype, int complexity,
+                           int pres_l2_norm, int dilation, int max_level, const int* devices, int ndev, int shard_axis) {
     if (!out) return mfail(NDWT_ERR_INVALID_ARG, "null plan pointer");
     *out = nullptr;
     if (ndim < 2 || ndim > NDWT_MAX_DIMS || !dims || !wnames || !devices || ndev < 1)
         return mfail(NDWT_ERR_INVALID_ARG, "multi-device plans shard the outermost of 2..4 axes over ndev >= 1 devices");
-    const long long N = dims[ndim - 1];
+    if (shard_axis != ndim - 1 && !(ndim == 4 && shard_axis == 2))
+        return mfail(NDWT_ERR_UNSUPPORTED, "shard_axis %d of a %d-D volume: multi-device plans shard the outermost axis (%d), or z (2) of a 4-D volume",
+                     shard_axis, ndim, ndim - 1);
+    const long long N = dims[shard_axis];
     if (ndev > N) return mfail(NDWT_ERR_INVALID_ARG, "more slabs (%d) than planes (%lld)", ndev, N);
     if (max_level < 1) return mfail(NDWT_ERR_INVALID_ARG, "max_level must be >= 1");
     ndwt_mplan* mp = new ndwt_mplan();
@@ -577,12 +750,16 @@ int ndwt_mplan_create(ndwt_mplan** out, int ndim, const int64_t* dims, const cha
     mp->threads = 1;
     mp->team = nullptr;
     for (int a = 0; a < ndim; ++a) mp->dims[a] = dims[a];
+    mp->shard = shard_axis;
+    mp->nrep = 1;
+    for (int a = shard_axis + 1; a < ndim; ++a) mp->nrep *= dims[a];
     size_t pb = (dtype == NDWT_F32 ? 4 : 8) * (complexity == NDWT_COMPLEX_INTERLEAVED ? 2 : 1);
-    for (int a = 0; a + 1 < ndim; ++a) pb *= (size_t)dims[a];
+    for (int a = 0; a < shard_axis; ++a) pb *= (size_t)dims[a];
     mp->plane_bytes = pb;
+    const size_t R = (size_t)mp->nrep;
     double lo[NDWT_MAX_TAPS], hi[NDWT_MAX_TAPS];
     int L = 0;
-    if (ndwt_wave_filters(wnames[ndim - 1], lo, hi, &L) != NDWT_OK) { delete mp; return mfail(NDWT_ERR_UNKNOWN_WAVELET, "Unknown Wavelet Name"); }
+    if (ndwt_wave_filters(wnames[shard_axis], lo, hi, &L) != NDWT_OK) { delete mp; return mfail(NDWT_ERR_UNKNOWN_WAVELET, "Unknown Wavelet Name"); }
     mp->L_outer = L;
     const long long smax = dilation == NDWT_DILATION_ATROUS ? (1LL << (max_level - 1)) : 1LL;
     mp->halo_max = (long long)(L / 2) * smax;
@@ -609,8 +786,8 @@ int ndwt_mplan_create(ndwt_mplan** out, int ndim, const int64_t* dims, const cha
     int rc = NDWT_OK;
     mp->fast = 1;
     for (auto& s : mp->slabs) {
-        ld[ndim - 1] = s.n;
-        if ((rc = ndwt_plan_create_slab(&s.plan, ndim, ld.data(), N, wnames, dtype, complexity, pres_l2_norm, dilation, 1, s.device)) != NDWT_OK) break;
+        ld[shard_axis] = s.n;
+        if ((rc = ndwt_plan_create_slab_axis(&s.plan, ndim, ld.data(), shard_axis, N, wnames, dtype, complexity, pres_l2_norm, dilation, 1, s.device)) != NDWT_OK) break;
         if (!ndwt_plan_slab_fast(s.plan)) mp->fast = 0;
         hipError_t e = hipSetDevice(s.device);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking);
@@ -618,11 +795,12 @@ int ndwt_mplan_create(ndwt_mplan** out, int ndim, const int64_t* dims, const cha
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s.copied, hipEventDisableTiming);
         for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipEventCreateWithFlags(&s.ready[k], hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s.margins, hipEventDisableTiming);
-        for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMalloc((void**)&s.approx[k], (size_t)(s.n + 2 * mp->halo_max) * pb);
+        // (R = frames of a z-slab: every buffer holds R runs of its planes; 1 for slabs of the outermost axis)
+        for (int k = 0; k < 2 && e == hipSuccess; ++k) e = hipMalloc((void**)&s.approx[k], R * (size_t)(s.n + 2 * mp->halo_max) * pb);
         for (char** p : {&s.hb, &s.ha, &s.ma})
-            if (e == hipSuccess) e = hipMalloc((void**)p, (size_t)mp->halo_max * pb);
+            if (e == hipSuccess) e = hipMalloc((void**)p, R * (size_t)mp->halo_max * pb);
         for (char** p : {&s.mb, &s.recv})               // mb: both margins of the overlapped synthesis (two runs); recv: a region per sender
-            if (e == hipSuccess) e = hipMalloc((void**)p, (size_t)(2 * mp->halo_max) * pb);
+            if (e == hipSuccess) e = hipMalloc((void**)p, R * (size_t)(2 * mp->halo_max) * pb);
         if (e != hipSuccess) { rc = mfail(NDWT_ERR_ALLOC, "device %d: %s", s.device, hipGetErrorString(e)); break; }
         for (auto& o : mp->slabs)                        // peer access where the runtime offers it (same-device pairs need none)
             if (o.device != s.device) {
@@ -631,6 +809,7 @@ int ndwt_mplan_create(ndwt_mplan** out, int ndim, const int64_t* dims, const cha
                 if (pe == hipSuccess && can) {
                     pe = hipDeviceEnablePeerAccess(o.device, 0);
                     if (pe == hipErrorPeerAccessAlreadyEnabled) pe = hipSuccess;
+                    if (pe == hipSuccess) mp->peer.emplace_back(s.device, o.device);
                 }
                 (void)hipGetLastError();
                 if (pe != hipSuccess || !can) {           // the copies still work (staged by the runtime), slower: say so
@@ -705,9 +884,11 @@ double ndwt_mplan_last_enqueue_us(const ndwt_mplan* mp) { return mp ? mp->last_e
 int ndwt_mplan_describe(const ndwt_mplan* mp, char* buf, int buflen) {
     if (!mp || !buf || buflen < 1) return mfail(NDWT_ERR_INVALID_ARG, "bad arguments");
     const bool scatter = mp->exchange == NDWT_EXCHANGE_SCATTER && mp->fast && mp->dilation == NDWT_DILATION_REFERENCE;
-    snprintf(buf, (size_t)buflen, "%d slabs; analysis: halo planes of the approximation band%s; synthesis: %s; %s; %s", (int)mp->slabs.size(),
-             mp->fast ? ", slabs read in place" : "", scatter ? "scatter-add of one band of partial sums" : "gather of the halo planes of all bands",
-             (mp->overlap && mp->fast) ? "exchange overlapped with the planes that do not wait for it (where every slab is thick enough)" : "exchange, then compute",
+    const bool z = mp->shard != mp->ndim - 1;
+    snprintf(buf, (size_t)buflen, "%d slabs of axis %d (%s); analysis: halo planes of the approximation band%s; synthesis: %s; %s; %s", (int)mp->slabs.size(),
+             mp->shard, z ? "z, t whole on every slab" : "outermost", (mp->fast && !z) ? ", slabs read in place" : "",
+             scatter ? "scatter-add of one band of partial sums" : "gather of the halo planes of all bands",
+             (mp->overlap && mp->fast && !z) ? "exchange overlapped with the planes that do not wait for it (where every slab is thick enough)" : "exchange, then compute",
              mp->notes.empty() ? "peer access between all devices" : mp->notes.c_str());
     return NDWT_OK;
 }
@@ -750,8 +931,8 @@ int ndwt_mrec(ndwt_mplan* mp, const void* const* y_slabs, void* const* x_slabs, 
 static int host_buffers(ndwt_mplan* mp, std::vector<void*>& xs, std::vector<void*>& ys) {
     const long long nbt = (long long)ndwt_num_bands(mp->ndim, mp->max_level);
     for (auto& s : mp->slabs) {
-        MRET(lazy_alloc(s, &s.xbuf, (size_t)s.n * mp->plane_bytes));
-        MRET(lazy_alloc(s, &s.coef, (size_t)(nbt * s.n) * mp->plane_bytes));
+        MRET(lazy_alloc(s, &s.xbuf, (size_t)(mp->nrep * s.n) * mp->plane_bytes));
+        MRET(lazy_alloc(s, &s.coef, (size_t)(nbt * mp->nrep * s.n) * mp->plane_bytes));
         xs.push_back(s.xbuf);
         ys.push_back(s.coef);
     }
@@ -763,7 +944,7 @@ int ndwt_mdec_host(ndwt_mplan* mp, const void* x_host, void* y_host, int level) 
     if (rc) return rc;
     if (!x_host || !y_host) return mfail(NDWT_ERR_INVALID_ARG, "null data pointer");
     const size_t pb = mp->plane_bytes;
-    const long long N = mp->dims[mp->ndim - 1];
+    const long long N = axis_len(mp);
     const long long nbt = (long long)ndwt_num_bands(mp->ndim, level);
     std::vector<void*> xs, ys;
     MRET(host_buffers(mp, xs, ys));
@@ -773,7 +954,11 @@ int ndwt_mdec_host(ndwt_mplan* mp, const void* x_host, void* y_host, int level) 
     rc = phase(mp, [&](size_t i) -> int {
         Slab& s = mp->slabs[i];
         MHIP(hipSetDevice(s.device));
-        MHIP(hipMemcpyAsync(s.xbuf, (const char*)x_host + (size_t)s.z0 * pb, (size_t)s.n * pb, hipMemcpyHostToDevice, s.stream));
+        if (mp->nrep > 1)                                 // z-slab: a run of n planes from every frame of the volume (rows of N planes)
+            MHIP(hipMemcpy2DAsync(s.xbuf, (size_t)s.n * pb, (const char*)x_host + (size_t)s.z0 * pb, (size_t)N * pb, (size_t)s.n * pb,
+                                  (size_t)mp->nrep, hipMemcpyHostToDevice, s.stream));
+        else
+            MHIP(hipMemcpyAsync(s.xbuf, (const char*)x_host + (size_t)s.z0 * pb, (size_t)s.n * pb, hipMemcpyHostToDevice, s.stream));
         return NDWT_OK;
     });
     if (rc == NDWT_OK) rc = level_barrier(mp, 1);         // every slab of x is in place before a neighbour reads its halo planes
@@ -782,8 +967,12 @@ int ndwt_mdec_host(ndwt_mplan* mp, const void* x_host, void* y_host, int level) 
         rc = phase(mp, [&](size_t i) -> int {
             Slab& s = mp->slabs[i];
             MHIP(hipSetDevice(s.device));
-            for (long long b = 0; b < nbt; ++b)
-                MHIP(hipMemcpyAsync((char*)y_host + (size_t)(b * N + s.z0) * pb, s.coef + (size_t)(b * s.n) * pb, (size_t)s.n * pb, hipMemcpyDeviceToHost, s.stream));
+            if (mp->nrep > 1)                             // (bands x frames) rows: band b, frame q is row b * nt + q on both sides
+                MHIP(hipMemcpy2DAsync((char*)y_host + (size_t)s.z0 * pb, (size_t)N * pb, s.coef, (size_t)s.n * pb, (size_t)s.n * pb,
+                                      (size_t)(nbt * mp->nrep), hipMemcpyDeviceToHost, s.stream));
+            else
+                for (long long b = 0; b < nbt; ++b)
+                    MHIP(hipMemcpyAsync((char*)y_host + (size_t)(b * N + s.z0) * pb, s.coef + (size_t)(b * s.n) * pb, (size_t)s.n * pb, hipMemcpyDeviceToHost, s.stream));
             return NDWT_OK;
         });
     team_end(mp);
@@ -796,7 +985,7 @@ int ndwt_mrec_host(ndwt_mplan* mp, const void* y_host, void* x_host, int level) 
     if (rc) return rc;
     if (!x_host || !y_host) return mfail(NDWT_ERR_INVALID_ARG, "null data pointer");
     const size_t pb = mp->plane_bytes;
-    const long long N = mp->dims[mp->ndim - 1];
+    const long long N = axis_len(mp);
     const long long nbt = (long long)ndwt_num_bands(mp->ndim, level);
     std::vector<void*> xs, ys;
     MRET(host_buffers(mp, xs, ys));
@@ -804,8 +993,12 @@ int ndwt_mrec_host(ndwt_mplan* mp, const void* y_host, void* x_host, int level) 
     rc = phase(mp, [&](size_t i) -> int {
         Slab& s = mp->slabs[i];
         MHIP(hipSetDevice(s.device));
-        for (long long b = 0; b < nbt; ++b)
-            MHIP(hipMemcpyAsync(s.coef + (size_t)(b * s.n) * pb, (const char*)y_host + (size_t)(b * N + s.z0) * pb, (size_t)s.n * pb, hipMemcpyHostToDevice, s.stream));
+        if (mp->nrep > 1)
+            MHIP(hipMemcpy2DAsync(s.coef, (size_t)s.n * pb, (const char*)y_host + (size_t)s.z0 * pb, (size_t)N * pb, (size_t)s.n * pb,
+                                  (size_t)(nbt * mp->nrep), hipMemcpyHostToDevice, s.stream));
+        else
+            for (long long b = 0; b < nbt; ++b)
+                MHIP(hipMemcpyAsync(s.coef + (size_t)(b * s.n) * pb, (const char*)y_host + (size_t)(b * N + s.z0) * pb, (size_t)s.n * pb, hipMemcpyHostToDevice, s.stream));
         return NDWT_OK;
     });
     if (rc == NDWT_OK) rc = level_barrier(mp, 1);
@@ -814,7 +1007,11 @@ int ndwt_mrec_host(ndwt_mplan* mp, const void* y_host, void* x_host, int level) 
         rc = phase(mp, [&](size_t i) -> int {
             Slab& s = mp->slabs[i];
             MHIP(hipSetDevice(s.device));
-            MHIP(hipMemcpyAsync((char*)x_host + (size_t)s.z0 * pb, s.xbuf, (size_t)s.n * pb, hipMemcpyDeviceToHost, s.stream));
+            if (mp->nrep > 1)
+                MHIP(hipMemcpy2DAsync((char*)x_host + (size_t)s.z0 * pb, (size_t)N * pb, s.xbuf, (size_t)s.n * pb, (size_t)s.n * pb,
+                                      (size_t)mp->nrep, hipMemcpyDeviceToHost, s.stream));
+            else
+                MHIP(hipMemcpyAsync((char*)x_host + (size_t)s.z0 * pb, s.xbuf, (size_t)s.n * pb, hipMemcpyDeviceToHost, s.stream));
             return NDWT_OK;
         });
     team_end(mp);

@@ -37,19 +37,28 @@ def partition(n: int, world: int):
 class HipSlabEngine:
     """Local compute of one slab on one GPU through include/ndwt.h (slab entry points)."""
 
-    def __init__(self, wnames, local_dims, dtype, pres_l2_norm, dilation, device, global_outer=None):
+    def __init__(self, wnames, local_dims, dtype, pres_l2_norm, dilation, device, global_outer=None, shard_axis=None):
         from .api import Plan
         # a slab plan: the filter-length check of the reference applies to the whole sharded axis (global_outer), the local
         # slab may be thinner than the filter (cfg5: 4 frames per rank, 8 taps)
         idx = device.index if device.index is not None else torch.cuda.current_device()
+        zslab = shard_axis is not None and shard_axis != len(local_dims) - 1
+        ax = shard_axis if zslab else len(local_dims) - 1
         self.plan = Plan(local_dims, wnames, dtype, False, pres_l2_norm, dilation, max_level=1, device=idx,
-                         global_outer=global_outer if global_outer is not None else local_dims[-1])
+                         global_outer=global_outer if global_outer is not None else local_dims[ax], shard_axis=ax if zslab else None)
         self.device = torch.device("cuda", idx)
         self._parts = None
         self.dtype = dtype
         self.local_dims = list(local_dims)
         # split-halo analysis + zero-extended synthesis entry points (fused 3-D kernels only)
         lens = [len(L.wave_filters(w)[0]) for w in wnames]
+        if zslab:
+            # z-slabs (4-D, t whole): the split-halo analysis takes every plan (the library assembles the slab with its halo planes);
+            # the zero-extended synthesis needs the fused kernels with the z filter the longest; no run-of-planes pieces
+            self.supports_split = True
+            self.supports_overlap = False
+            self.supports_scatter = dilation == "reference" and bool(L.lib().ndwt_plan_slab_fast(self.plan._h))
+            return
         # copy-free analysis (separate halo buffers), run-of-planes pieces: fused 3-D plans only
         self.supports_split = (dilation == "reference" and len(local_dims) == 3 and self.plan.describe() == "fused3d"
                                and lens[2] == max(lens))
@@ -72,6 +81,16 @@ class HipSlabEngine:
             part = pairs[i:i + 8]
             self.plan.slab_segments(add, [d.data_ptr() for d, _ in part], [s.data_ptr() for _, s in part],
                                     [d.numel() * scal for d, _ in part], self._stream())
+
+    def segments_strided(self, add, items):
+        """items: (dst, src, nrep, run, dst_stride, src_stride) with the counts in elements -- runs repeated nrep times at their strides
+        (the planes of a z-slab: one run per frame), up to 8 runs of equal nrep per launch"""
+        scal = 2 if items[0][0].is_complex() else 1
+        for i in range(0, len(items), 8):
+            part = items[i:i + 8]
+            self.plan.slab_segments_strided(add, [it[0].data_ptr() for it in part], [it[1].data_ptr() for it in part],
+                                            [it[3] * scal for it in part], part[0][2], [it[4] * scal for it in part],
+                                            [it[5] * scal for it in part], self._stream())
 
     def analysis(self, in_with_halo, outs, stride):
         self.plan.analysis_level_slab(in_with_halo.data_ptr(), [o.data_ptr() for o in outs], stride, self._stream())
@@ -216,6 +235,26 @@ def _pitched_bands(nbands, band_shape, like):
     return flat.as_strided((nbands,) + tuple(band_shape), (pitch,) + tuple(strides))
 
 
+def _reps(t):
+    """(nrep, run, rep_stride) in elements when the view t is nrep equal contiguous runs at a constant distance (a range of planes of
+    the sharded axis of a z-slab: one run per frame), else None"""
+    run, k = 1, t.dim()
+    while k > 0 and (t.shape[k - 1] == 1 or t.stride(k - 1) == run):
+        run *= int(t.shape[k - 1])
+        k -= 1
+    nrep, rs = 1, run
+    for i in range(k - 1, -1, -1):
+        if t.shape[i] == 1:
+            continue
+        if nrep == 1:
+            nrep, rs = int(t.shape[i]), int(t.stride(i))
+        elif t.stride(i) == rs * nrep:
+            nrep *= int(t.shape[i])
+        else:
+            return None
+    return nrep, run, rs
+
+
 def _bands_in_place(y):
     """True when every band of y is contiguous (packed or pitched): the engines take band pointers"""
     return y.dim() >= 2 and y[0].is_contiguous() and (y.shape[0] == 1 or y.stride(0) >= y[0].numel())
@@ -223,8 +262,13 @@ def _bands_in_place(y):
 
 class ShardedNdDwt:
     def __init__(self, wname, sizes, pres_l2_norm=False, precision="double", dilation="reference", group=None, device=None,
-                 engine=None, synthesis_scheme="auto", overlap="auto", band_pitch="auto", two_streams=False, transport="torch", _self_p2p=False):
-        """band_pitch: layout of the coefficient slab dec() returns on the GPU -- 'auto' (default): the bands of one allocation, each
+                 engine=None, synthesis_scheme="auto", overlap="auto", band_pitch="auto", two_streams=False, transport="torch", _self_p2p=False,
+                 shard_axis=None):
+        """shard_axis: index into `sizes` of the sharded axis -- None (default): the outermost; 2 of a 4-D volume ([n1, n2, n3, n4] =
+        x, y, z, t): z-slabs, t whole on every rank.  x_local is then (nt, nz_local, ny, nx) (the sharded axis is dim 1 of x_local and
+        dim 2 of the coefficient slab), and the halo of a level is nt runs of z planes -- for cfg5 (256^3 x 32, db4, 8 ranks) 56 MiB per
+        level and rank against 448 MiB for t-slabs, and the rank count is bounded by nz instead of nt.
+        band_pitch: layout of the coefficient slab dec() returns on the GPU -- 'auto' (default): the bands of one allocation, each
         contiguous, prod(local shape) + 256 bytes apart (a strided view: index it like any tensor; .contiguous() packs it; rec()
         takes either) -- the layout the synthesis kernels read 10 % faster; 'packed': a contiguous tensor, for
         callers that hand the result to collectives, .view(-1) or raw pointers."""
@@ -241,7 +285,11 @@ class ShardedNdDwt:
         self.group = group
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(group) if dist.is_initialized() else 0
-        self.n_outer = self.sizes[-1]
+        self.shard_axis = self.d - 1 if shard_axis is None else int(shard_axis)
+        if self.shard_axis != self.d - 1 and not (self.d == 4 and self.shard_axis == 2):
+            raise ValueError(f"shard_axis {shard_axis} of a {self.d}-D volume: the outermost axis ({self.d - 1}) or z (2) of a 4-D volume")
+        self.ax = self.d - 1 - self.shard_axis                     # dim of the sharded axis in x_local (kernel order); 0 = outermost
+        self.n_outer = self.sizes[self.shard_axis]                 # (length of the sharded axis)
         self.parts = partition(self.n_outer, self.world)
         self.z0, self.z1 = self.parts[self.rank]
         self.n_local = self.z1 - self.z0
@@ -251,9 +299,11 @@ class ShardedNdDwt:
         self.dilation = dilation
         self.device = device if device is not None else torch.device("cpu")
         self.inner_shape = tuple(reversed(self.sizes[:-1]))          # kernel order of the unsharded axes
-        local_dims = self.sizes[:-1] + [self.n_local]
+        local_dims = list(self.sizes)
+        local_dims[self.shard_axis] = self.n_local
         self.engine = engine if engine is not None else HipSlabEngine(self.wname, local_dims, self.dtype, pres_l2_norm,
-                                                                     dilation, self.device, global_outer=self.n_outer)
+                                                                     dilation, self.device, global_outer=self.n_outer,
+                                                                     shard_axis=self.shard_axis if self.ax else None)
         self.plan = getattr(self.engine, "plan", None)
         if synthesis_scheme == "auto":
             synthesis_scheme = "scatter" if getattr(self.engine, "supports_scatter", False) else "gather"
@@ -265,7 +315,7 @@ class ShardedNdDwt:
         # staged through host copies.  RCCL ("nccl") sends the device buffers as they are.
         self._host_stage = bool(self.device.type == "cuda" and dist.is_initialized() and dist.get_backend(group) == "gloo")
         # overlap of the exchange with the planes that do not depend on it needs the run-of-planes entry points
-        self.can_overlap = bool(self.scheme == "scatter" and hasattr(self.engine, "analysis_run")
+        self.can_overlap = bool(self.scheme == "scatter" and not self.ax and hasattr(self.engine, "analysis_run")
                                 and hasattr(self.engine, "synthesis_part") and getattr(self.engine, "supports_overlap", True))
         # overlap: True / False, or "auto" = overlapped until tune() has measured both schedules on this machine.  The pieces cost
         # (a slab level cut into interior + ends pays the (L-1)-plane march prologue twice more: cfg3's 64-plane slab 0.86 -> 0.97 ms per
@@ -364,7 +414,7 @@ class ShardedNdDwt:
                 local.append((dst, src))
                 continue
             if p == self.rank:
-                buf = src if src.is_contiguous() else src.contiguous()
+                buf = src if src.is_contiguous() else self._pack(src, ("send", q, side, k0))
                 if self._host_stage:
                     buf = buf.cpu()
                 keep.append(buf)
@@ -375,7 +425,10 @@ class ShardedNdDwt:
                 else:
                     buf = torch.empty(dst.shape, dtype=dst.dtype, device="cpu" if self._host_stage else dst.device)
                     ops.append((False, buf, p) if direct else dist.P2POp(dist.irecv, buf, self._global_rank(p), self.group))
-                    post.append(lambda dst=dst, buf=buf: dst.copy_(buf))
+                    if self.ax and buf.device == dst.device:
+                        post.append(lambda dst=dst, buf=buf: self._apply(False, [(dst, buf)]))   # z-slabs: frames placed by the engine
+                    else:
+                        post.append(lambda dst=dst, buf=buf: dst.copy_(buf))
         self._apply(False, local)
         if direct:
             self._comm.exchange(ops)                      # in stream order on the current stream: nothing to wait for afterwards
@@ -397,23 +450,28 @@ class ShardedNdDwt:
         ops, adds_local, adds_recv, keep = [], [], [], []
         direct = self.transport == "rccl"
         parts = (part_before, part_after)
+        ax = self.ax
         # rank q PRODUCES partial planes for the global planes around its slab; the owner p ADDS them
         for q, side, p, k0, l0, n in self._plan_exchange(before, after):
             if q == self.rank:
-                part = parts[side].narrow(0, k0, n)                 # contiguous view
+                part = parts[side].narrow(ax, k0, n)                # contiguous view (outer-axis slabs; z-slabs: one run per frame)
                 if p == self.rank and not self._self_p2p:
                     adds_local.append((l0, n, part))
                     continue
+                if not part.is_contiguous():
+                    part = self._pack(part, ("scatter_send", p, side, k0))
                 if self._host_stage:
                     part = part.cpu()
                     keep.append(part)
                 ops.append((True, part, p) if direct else dist.P2POp(dist.isend, part, self._global_rank(p), self.group))
             if p == self.rank:
                 ref = parts[side]
+                shape = list(ref.shape)
+                shape[ax] = n
                 if self._host_stage:
-                    buf = torch.empty([n] + list(ref.shape[1:]), dtype=ref.dtype, device="cpu")
+                    buf = torch.empty(shape, dtype=ref.dtype, device="cpu")
                 else:
-                    buf = self._buf(("scatter_recv", q, side, k0), [n] + list(ref.shape[1:]), ref)
+                    buf = self._buf(("scatter_recv", q, side, k0), shape, ref)
                 ops.append((False, buf, q) if direct else dist.P2POp(dist.irecv, buf, self._global_rank(q), self.group))
                 adds_recv.append((l0, n, buf))
         if direct:
@@ -426,11 +484,13 @@ class ShardedNdDwt:
         works, adds, _keep = pending
         for w in works:
             w.wait()
-        self._apply(True, [(own.narrow(0, l0, n), buf if buf.device == own.device else buf.to(own.device)) for l0, n, buf in adds])
+        self._apply(True, [(own.narrow(self.ax, l0, n), buf if buf.device == own.device else buf.to(own.device)) for l0, n, buf in adds])
 
     def _apply(self, add, pairs):
         """dst = src / dst += src for every pair; engines with a multi-run kernel take all contiguous pairs in one launch"""
         if not pairs:
+            return
+        if self.ax and self._apply_strided(add, pairs):
             return
         seg = getattr(self.engine, "segments", None)
         if seg is not None and pairs[0][0].is_cuda and all(d.is_contiguous() and s.is_contiguous() and d.dtype == s.dtype for d, s in pairs):
@@ -452,6 +512,45 @@ class ShardedNdDwt:
                 d.add_(s)
             else:
                 d.copy_(s)
+
+    def _apply_strided(self, add, pairs):
+        """z-slabs on the GPU: every pair is nrep runs at constant distances (one per frame) -- the engine's strided segment kernel, one
+        launch per batch of up to 8 runs with equal nrep whose destinations are disjoint (the addends of one plane one after the other).
+        False when the engine has no such kernel or a pair has another layout (then the caller copies)."""
+        seg = getattr(self.engine, "segments_strided", None)
+        if seg is None or not all(d.is_cuda and s.is_cuda and d.device == s.device and d.dtype == s.dtype for d, s in pairs):
+            return False
+        def fit(a, b):                   # a contiguous block read as the runs of the other side
+            return (b[0], b[1], b[1]) if a[0] == 1 and b[0] > 1 and a[1] == b[0] * b[1] else a
+        items = []
+        for d, s_ in pairs:
+            ld, ls = _reps(d), _reps(s_)
+            if ld is None or ls is None:
+                return False
+            ld, ls = fit(ld, ls), fit(ls, ld)
+            if ld[:2] != ls[:2]:
+                return False
+            items.append((d, s_, ld[0], ld[1], ld[2], ls[2]))
+        batch, spans = [], []
+        for it in items:
+            lo = it[0].data_ptr()
+            hi = lo + it[3] * it[0].element_size()
+            if batch and (it[2] != batch[0][2] or any(lo < h and l < hi for l, h in spans)):
+                seg(add, batch)
+                batch, spans = [], []
+            batch.append(it)
+            spans.append((lo, hi))
+        seg(add, batch)
+        return True
+
+    def _pack(self, src, key):
+        """a contiguous copy of the view src, to be sent: z-slabs on the GPU through the engine's strided segment kernel into a buffer of
+        the driver (RCCL sends contiguous buffers), else torch's copy"""
+        if self.ax and src.is_cuda and getattr(self.engine, "segments_strided", None) is not None:
+            buf = self._buf(key, src.shape, src)
+            if self._apply_strided(False, [(buf, src)]):
+                return buf
+        return src.contiguous()
 
     def _one_stream(self):
         """The driver's scratch buffers (halo margins, partial sums, receive buffers) are reused across calls and every hazard on
@@ -493,7 +592,7 @@ class ShardedNdDwt:
         decision from the same numbers).  Collective: every rank of the group calls it with its own slab and the same level.
         Returns the record it stores in self.tuned."""
         import time
-        if not self.can_overlap:
+        if not self.can_overlap and not self.ax:
             self.tuned = {"schedule": "one_piece", "reason": "engine has no run-of-planes entry points"}
             return self.tuned
         distributed = dist.is_initialized() and self.world > 1
@@ -505,12 +604,15 @@ class ShardedNdDwt:
             if distributed:
                 dist.barrier(self.group)
 
-        modes = [("one_piece", False, False, "torch"), ("overlap", True, False, "torch")] + ([("overlap_two_streams", True, True, "torch")] if cuda else [])
+        # (z-slabs: no run-of-planes pieces -- the one-piece schedule over both transports)
+        ov = self.can_overlap
+        modes = [("one_piece", False, False, "torch")] + ([("overlap", True, False, "torch")] if ov else []) + \
+            ([("overlap_two_streams", True, True, "torch")] if cuda and ov else [])
         note = None
         if cuda and dist.is_initialized() and not self._host_stage and (self.world > 1 or self._self_p2p):
             try:                                          # the exchange as RCCL calls on the transform's own stream (collective: all ranks or none)
                 self._open_direct()
-                modes += [("rccl_one_piece", False, False, "rccl"), ("rccl_overlap_two_streams", True, True, "rccl")]
+                modes += [("rccl_one_piece", False, False, "rccl")] + ([("rccl_overlap_two_streams", True, True, "rccl")] if ov else [])
             except RuntimeError as exc:
                 note = str(exc)[:200]
         ms = []
@@ -549,6 +651,8 @@ class ShardedNdDwt:
         The approximation band of every level lives in a scratch buffer [halo_before | slab | halo_after] whose margins
         receive the neighbours' planes in place, so no haloed copy is assembled (the first level copies x once; engines
         with the split-halo entry point read x and the two received halo buffers from where they are)."""
+        if self.ax:
+            return self._dec_z(x_local, level)
         nb, nbt = self.nb, self.nb + (self.nb - 1) * (level - 1)
         self._one_stream()
         x_local = x_local.to(self.dtype).contiguous()
@@ -619,6 +723,8 @@ class ShardedNdDwt:
 
     def rec(self, y):
         """(bands, n_local, ..., n1) -> (n_local, ..., n1)"""
+        if self.ax:
+            return self._rec_z(y)
         nb = self.nb
         self._one_stream()
         level = 1 + (y.shape[0] - nb) // (nb - 1)
@@ -676,4 +782,60 @@ class ShardedNdDwt:
                 out = torch.empty_like(prev) if lev == 1 else self._buf(("syn_out", lev & 1), prev.shape, prev)
                 self.engine.synthesis([full[b] for b in range(nb)], out, s)
                 prev = out
+        return prev.contiguous()
+
+    # ------------------------------------------------------------------------------ z-slabs (4-D, t whole on every rank)
+    def _dec_z(self, x_local, level):
+        """x_local: (nt, nz_local, ny, nx) -> (bands, nt, nz_local, ny, nx).  Per level: the halo planes of every frame of the
+        approximation band are fetched into two (nt, ab / aa, ny, nx) buffers, then the split-halo analysis of the slab."""
+        nb, nbt = self.nb, self.nb + (self.nb - 1) * (level - 1)
+        self._one_stream()
+        x_local = x_local.to(self.dtype).contiguous()
+        y = (_pitched_bands(nbt, tuple(x_local.shape), x_local) if x_local.is_cuda and self.band_pitch == "auto"
+             else x_local.new_empty((nbt,) + tuple(x_local.shape)))
+        nt, plane = x_local.shape[0], tuple(x_local.shape[2:])
+        cur = x_local
+        for lev in range(1, level + 1):
+            s = self._stride(lev)
+            ab, aa, _, _ = self.engine.halo(s)
+            hb, ha, pending = self._start_fetch_halo(cur, 1, ab, aa, self._buf(("halo_b", lev & 1), (nt, ab) + plane, x_local),
+                                                     self._buf(("halo_a", lev & 1), (nt, aa) + plane, x_local))
+            self._finish_exchange(pending)
+            a_out = y[0] if lev == level else self._buf(("ana_plain", lev & 1), tuple(x_local.shape), x_local)
+            outs = [a_out] + [y[1 + (nb - 1) * (level - lev) + (b - 1)] for b in range(1, nb)]
+            self.engine.analysis_split(cur, hb, ha, outs, s)
+            cur = a_out
+        return y
+
+    def _rec_z(self, y):
+        """(bands, nt, nz_local, ny, nx) -> (nt, nz_local, ny, nx).  Scatter: the zero-extended synthesis (nt, sa + n + sb, ny, nx),
+        its own planes copied out, the partial sums of every frame sent to their owners and added.  Gather: the halo planes of all
+        bands assembled around the slab, (nt, sb + n + sa, ny, nx) per band, then the slab synthesis."""
+        nb = self.nb
+        self._one_stream()
+        level = 1 + (y.shape[0] - nb) // (nb - 1)
+        y = y.to(self.dtype)
+        if not _bands_in_place(y):
+            y = y.contiguous()
+        prev = y[0]
+        n, nt, plane = self.n_local, prev.shape[0], tuple(prev.shape[2:])
+        for ind in range(1, level + 1):
+            lev = level - ind + 1
+            s = self._stride(lev)
+            _, _, sb, sa = self.engine.halo(s)
+            ins = [prev] + [y[1 + (nb - 1) * (level - lev) + (b - 1)] for b in range(1, nb)]
+            own = prev.new_empty(prev.shape) if lev == 1 else self._buf(("syn_out", lev & 1), prev.shape, prev)
+            if self.scheme == "scatter":
+                ext = self._buf(("syn_ext",), (nt, sa + n + sb) + plane, prev)
+                self.engine.synthesis_ext(ins, ext, s)
+                self._apply(False, [(own, ext.narrow(1, sa, n))])
+                pending = self._start_scatter(ext.narrow(1, 0, sa), ext.narrow(1, sa + n, sb), sa, sb)
+                self._finish_scatter(pending, own)
+            else:
+                full = self._buf(("syn_full",), (nb, nt, sb + n + sa) + plane, prev)
+                self._apply(False, [(full[b, :, sb:sb + n], ins[b]) for b in range(nb)])
+                _, _, pending = self._start_fetch_halo(full[:, :, sb:sb + n], 2, sb, sa, full[:, :, :sb], full[:, :, sb + n:])
+                self._finish_exchange(pending)
+                self.engine.synthesis([full[b] for b in range(nb)], own, s)
+            prev = own
         return prev.contiguous()
