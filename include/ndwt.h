@@ -325,6 +325,16 @@ const char* ndwt_comm_last_error(void);
 const char* ndwt_last_error(void); /* thread-local message of the last failing call */
 const char* ndwt_version(void);
 
+/* ---- launch trace (tests / diagnostics) -------------------------------------------------------------- */
+/* Off by default.  While on, every kernel launch of this library (worker threads of ndwt_mplan_* included) appends one record
+ * "<kernel type> grid=(x,y,z) block=(x,y,z)" to a process-global log; the kernel type is the compiler's spelling, which leaves out
+ * trailing template arguments equal to their defaults.  Host-side only: it changes no result and no launch.
+ * ndwt_trace_enable: on != 0 clears the log and starts recording, 0 stops; returns the previous state.
+ * ndwt_trace_get: copies the newline-separated records (NUL-terminated, truncated to buflen - 1 bytes) and returns the buffer
+ * length the whole log needs, terminator included. */
+int ndwt_trace_enable(int on);
+int ndwt_trace_get(char* buf, int buflen);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,7 +31,7 @@ EXPORTS = [
     "ndwt_plan_release_staging", "ndwt_mplan_set_overlap", "ndwt_mplan_last_enqueue_us", "ndwt_mplan_set_threads", "ndwt_comm_unique_id", "ndwt_comm_create", "ndwt_comm_destroy", "ndwt_comm_exchange",
     "ndwt_comm_last_error", "ndwt_coef_create", "ndwt_coef_release", "ndwt_coef_info", "ndwt_coef_dec_host", "ndwt_coef_rec_host",
     "ndwt_coef_shrink", "ndwt_coef_get_host", "ndwt_coef_put_host", "ndwt_plan_create_slab_axis", "ndwt_slab_segments_strided",
-    "ndwt_mplan_create_axis",
+    "ndwt_mplan_create_axis", "ndwt_trace_enable", "ndwt_trace_get",
 ]
 
 
@@ -136,6 +136,8 @@ def lib() -> ctypes.CDLL:
     L.ndwt_mplan_last_enqueue_us.argtypes = [ctypes.c_void_p]
     L.ndwt_mplan_last_enqueue_us.restype = ctypes.c_double
     L.ndwt_mplan_describe.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int]
+    L.ndwt_trace_enable.argtypes = [ctypes.c_int]
+    L.ndwt_trace_get.argtypes = [ctypes.c_char_p, ctypes.c_int]
     L.ndwt_plan_slab_fast.argtypes = [ctypes.c_void_p]
     L.ndwt_plan_release_staging.argtypes = [ctypes.c_void_p]
     L.ndwt_comm_unique_id.argtypes = [ctypes.c_void_p]

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <climits>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -19,6 +20,7 @@
 #include "ndwt_filters.h"
 #include "ndwt_fused.h"
 #include "ndwt_geom.h"
+#include "ndwt_trace.h"
 
 using namespace ndwt;
 
@@ -40,6 +42,30 @@ static int fail(int code, const char* fmt, ...) {
         hipError_t e_ = (expr);                                                                    \
         if (e_ != hipSuccess) return fail(NDWT_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
+
+// ------------------------------------------------------------------------------------ launch trace
+namespace ndwt {
+std::atomic<int> g_trace_on{0};
+static std::mutex g_trace_mu;
+static std::string g_trace_log;
+static constexpr size_t kTraceCap = 8u << 20;            // records past 8 MB are dropped (a test turns the trace on around a few calls)
+
+void trace_append(const std::string& kernel, dim3 grid, dim3 block) {
+    char geo[96];
+    snprintf(geo, sizeof geo, " grid=(%u,%u,%u) block=(%u,%u,%u)\n", grid.x, grid.y, grid.z, block.x, block.y, block.z);
+    std::lock_guard<std::mutex> lk(g_trace_mu);
+    if (!g_trace_on.load(std::memory_order_relaxed) || g_trace_log.size() + kernel.size() + strlen(geo) > kTraceCap) return;
+    g_trace_log += kernel;
+    g_trace_log += geo;
+}
+
+void trace_append_pretty(const char* pretty, dim3 grid, dim3 block) {
+    const char* b = strstr(pretty, "[K = ");
+    const char* e = pretty + strlen(pretty);
+    if (!b || e == pretty || e[-1] != ']') { trace_append(pretty, grid, block); return; }
+    trace_append(std::string(b + 5, e - 1), grid, block);
+}
+}  // namespace ndwt
 
 // ------------------------------------------------------------------------------------ axis kernels
 template <typename T>
@@ -246,6 +272,7 @@ static int axis_pass(const ndwt_plan* p, bool synthesis, int axis, const long lo
     const long long cap = 256LL * 64;   // grid-stride beyond 64 blocks per CU
     if (nb > cap) nb = cap;
     prof_begin(p, synthesis ? NDWT_KERNEL_AXIS_SYNTHESIS : NDWT_KERNEL_AXIS_ANALYSIS, s);
+    trace_plain(dim3((unsigned)nb), dim3(256), synthesis ? "axis_synthesis_kernel" : "axis_analysis_kernel", trace_scalar<T>());
     if (synthesis)
         hipLaunchKernelGGL(axis_synthesis_kernel<T>, dim3((unsigned)nb), dim3(256), 0, s, in0, in1, out0, tp, a);
     else
@@ -1158,6 +1185,7 @@ template <typename T> static int shrink_run(ndwt_plan* p, T* d, long long n, dou
     if (blocks > cap) blocks = cap;
     if (blocks < 1) blocks = 1;
     const dim3 g((unsigned)blocks), b(256);
+    trace_plain(g, b, "shrink_kernel", trace_scalar<T>(), (int)p->comp, vec);
     if (p->comp == 2) {
         if (vec) hipLaunchKernelGGL((shrink_kernel<T, 2, true>), g, b, 0, s, d, n, (T)thr, mode);
         else hipLaunchKernelGGL((shrink_kernel<T, 2, false>), g, b, 0, s, d, n, (T)thr, mode);
@@ -1299,6 +1327,7 @@ template <typename T> int segments_strided_launch(int op, int nseg, void* const*
     if (bx > 2048) bx = 2048;
     if (bx * bz > 16384) bx = 16384 / bz > 1 ? 16384 / bz : 1;   // the repetitions fill the chip; the loops cover the rest
     const dim3 grid((unsigned)bx, (unsigned)nseg, (unsigned)bz);
+    trace_plain(grid, dim3(256), "segments_strided_kernel", trace_scalar<T>(), (int)sizeof(V), op != 0);
     if (op) hipLaunchKernelGGL((segments_strided_kernel<T, V, true>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((segments_strided_kernel<T, V, false>), grid, dim3(256), 0, st, a);
     return (int)hipGetLastError();
@@ -1320,6 +1349,7 @@ template <typename T> int segments_launch(int op, int nseg, void* const* dst, co
     if (bx < 1) bx = 1;
     if (bx > 2048) bx = 2048;
     const dim3 grid((unsigned)bx, (unsigned)nseg);
+    trace_plain(grid, dim3(256), "segments_kernel", vec ? 16 : (int)sizeof(T), op != 0);
     if (sizeof(T) == 4) {
         if (vec) { if (op) hipLaunchKernelGGL((segments_kernel<V4, true>), grid, dim3(256), 0, st, a); else hipLaunchKernelGGL((segments_kernel<V4, false>), grid, dim3(256), 0, st, a); }
         else { if (op) hipLaunchKernelGGL((segments_kernel<T, true>), grid, dim3(256), 0, st, a); else hipLaunchKernelGGL((segments_kernel<T, false>), grid, dim3(256), 0, st, a); }
@@ -2318,5 +2348,24 @@ int ndwt_slab_segments_strided(ndwt_plan* p, int op, int nseg, void* const* dst,
 }
 
 const char* ndwt_version(void) { return "ndwt-hip 0.1 (gfx950)"; }
+
+int ndwt_trace_enable(int on) {
+    std::lock_guard<std::mutex> lk(g_trace_mu);
+    const int was = g_trace_on.load(std::memory_order_relaxed);
+    if (on) g_trace_log.clear();
+    g_trace_on.store(on ? 1 : 0, std::memory_order_relaxed);
+    return was;
+}
+
+int ndwt_trace_get(char* buf, int buflen) {
+    std::lock_guard<std::mutex> lk(g_trace_mu);
+    const size_t need = g_trace_log.size() + 1;
+    if (buf && buflen > 0) {
+        const size_t n = need <= (size_t)buflen ? need - 1 : (size_t)buflen - 1;
+        memcpy(buf, g_trace_log.data(), n);
+        buf[n] = 0;
+    }
+    return need > (size_t)INT_MAX ? INT_MAX : (int)need;
+}
 
 }  // extern "C"

@@ -4,6 +4,7 @@ namespace ndwt {
 template <int LL, int NLEV> static int go(const Fused2CArgs<float>& a, const void* taps_dev, hipStream_t s) {
     typedef Fwd2C<float, LL, NLEV, 2> K;
     if (a.ntx != (a.n1 + K::WX - 1) / K::WX || a.ychunk < 1 || (long long)a.nyc * a.ychunk < a.n2) return -2;
+    trace_kernel<K>(dim3(a.ntx * a.nyc), dim3(K::NT));
     hipLaunchKernelGGL(fused3_kernel<K>, dim3(a.ntx * a.nyc), dim3(K::NT), 0, s, a, (const typename K::Taps*)taps_dev);
     return (int)hipGetLastError();
 }

@@ -1,6 +1,7 @@
 // ndwt_fused_kernels.h -- __global__ wrappers + launch switch for the fused kernels (HIP only).
 #pragma once
 #include "ndwt_fused.h"
+#include "ndwt_trace.h"
 
 namespace ndwt {
 
@@ -35,12 +36,14 @@ template <class K> int launch_fused3(const typename K::Args& a, const FusedTapsD
         (long long)a.nzc * a.zchunk < a.n3 || (long long)(a.nzc - 1) * a.zchunk >= a.n3)
         return -2;
     const int nblocks = a.ntx * a.nty * a.nzc * a.nbatch;
+    trace_kernel<K>(dim3(nblocks), dim3(K::NT));
     hipLaunchKernelGGL(fused3_kernel<K>, dim3(nblocks), dim3(K::NT), 0, s, a, (const typename K::Taps*)taps_dev);
     return (int)hipGetLastError();
 }
 
 template <class K> int launch_fused2(const typename K::Args& a, const void* taps_dev, hipStream_t s) {
     const int nblocks = a.ntx * a.nyc * a.nbatch;
+    trace_kernel<K>(dim3(nblocks), dim3(K::NT));
     hipLaunchKernelGGL(fused3_kernel<K>, dim3(nblocks), dim3(K::NT), 0, s, a, (const typename K::Taps*)taps_dev);
     return (int)hipGetLastError();
 }

@@ -18,6 +18,7 @@ static int launch_march_L(const MarchArgs<T>& a, const double* lo, const double*
     const long long iblocks = (a.ngroups * a.outer + K::NT - 1) / K::NT;
     const long long nblocks = iblocks * a.nchunks;
     if (nblocks <= 0 || nblocks > 0x7fffffffLL) return -2;
+    trace_kernel<K>(dim3((unsigned)nblocks), dim3(K::NT));
     hipLaunchKernelGGL(march_kernel<K>, dim3((unsigned)nblocks), dim3(K::NT), 0, s, a, tp);
     return (int)hipGetLastError();
 }
@@ -52,6 +53,8 @@ static int launch_axisx_L(const AxisXArgs<T>& a0, bool vec4, const double* lo, c
     a.nseg = (a.row + K::WX - 1) / K::WX;
     const long long nblocks = (a.outer * a.nseg + 3) / 4;
     if (nblocks <= 0 || nblocks > 0x7fffffffLL || a.row >= (1LL << 30)) return -2;
+    if (vec4) trace_kernel<K>(dim3((unsigned)nblocks), dim3(K::NT));
+    else trace_kernel<AxisX<T, L, SYN, EW, false>>(dim3((unsigned)nblocks), dim3(K::NT));
     if (vec4) hipLaunchKernelGGL(march_kernel<K>, dim3((unsigned)nblocks), dim3(K::NT), 0, s, a, tp);
     else hipLaunchKernelGGL((march_kernel<AxisX<T, L, SYN, EW, false>>), dim3((unsigned)nblocks), dim3(K::NT), 0, s, a, tp);
     return (int)hipGetLastError();

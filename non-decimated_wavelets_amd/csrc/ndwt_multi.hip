@@ -42,6 +42,7 @@
 #include <unistd.h>
 
 #include "../../include/ndwt.h"
+#include "ndwt_trace.h"
 
 namespace {
 
@@ -273,6 +274,7 @@ static int add_planes(ndwt_mplan* mp, Slab& s, char* dst, const char* src, long 
     long long blocks = (n + 255) / 256;
     if (blocks > 256 * 32) blocks = 256 * 32;
     if (blocks < 1) return NDWT_OK;
+    ndwt::trace_plain(dim3((unsigned)blocks), dim3(256), "add_planes_kernel", mp->dtype == NDWT_F32 ? "float" : "double");
     if (mp->dtype == NDWT_F32) hipLaunchKernelGGL(add_planes_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s.stream, (float*)dst, (const float*)src, n);
     else hipLaunchKernelGGL(add_planes_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, s.stream, (double*)dst, (const double*)src, n);
     MHIP(hipGetLastError());

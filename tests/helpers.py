@@ -55,3 +55,53 @@ def fuzz_cases(n, seed, max_order=10, p_atrous=0.2):
 def fuzz_id(c):
     return (f"{c['d']}d-{'x'.join(map(str, c['sizes']))}-{'.'.join(w[2:] for w in c['wn'])}-L{c['level']}-l2{c['l2']}-"
             f"{c['precision'][0]}{'c' if c['cplx'] else 'r'}-{c['dilation'][0]}")
+
+
+# ---- launch trace (non-decimated_wavelets_amd/trace.py): expected kernels of a call, and the coverage list of the dispatch tests
+from importlib import import_module as _imp                                        # noqa: E402
+
+_trace = _imp("non-decimated_wavelets_amd.trace")
+parse_record = _trace.parse_record
+
+
+def spec(s):
+    """"Fwd3 L=8 TY=32 PIN=false" -> ("Fwd3", {"L": 8, "TY": 32, "PIN": False}): a family and the parameters that pick the branch"""
+    fam, *kv = s.split()
+    return fam, {k: _trace._value(v) for k, v in (p.split("=") for p in kv)}
+
+
+def matches(rec, sp):
+    fam, params = sp
+    return rec.family == fam and all(rec.params.get(k) == v for k, v in params.items())
+
+
+def check_trace(recs, specs, what=""):
+    """every spec was launched at least once, and every launch is one of the specs (a dispatch change fails here, loudly)"""
+    sps = [spec(s) for s in specs]
+    shown = "\n  ".join(map(repr, recs)) or "(nothing launched)"
+    for s, sp in zip(specs, sps):
+        assert any(matches(r, sp) for r in recs), f"{what}: no launch of [{s}]; launched:\n  {shown}"
+    for r in recs:
+        assert any(matches(r, sp) for sp in sps), f"{what}: unexpected launch {r!r}; expected {specs}; launched:\n  {shown}"
+
+
+# Every kernel family of csrc/ndwt_device.h and every plain __global__ kernel of csrc/, with the instances that tell the dispatcher's
+# branches apart.  tests/test_gpu_dispatch.py::test_dispatch_coverage runs a sweep that must launch each entry (and agree with the
+# oracle); tests/test_kernel_trace.py keeps the set of families here equal to the kernels in csrc/.
+COVERAGE = [spec(s) for s in [
+    "Fwd3 VEC4=true", "Fwd3 VEC4=false", "Fwd3 TY=16", "Fwd3 TY=32", "Fwd3 PIN=true", "Fwd3 TPRE=true", "Fwd3 LOWONLY=true",
+    "Fwd3 WLDS=2", "Fwd3 WLDS=4", "Fwd3 EW=1", "Fwd3 EW=2", "Fwd3 EW=4", "Fwd3 T=double", "Fwd3 T=double EW=2",
+    "Inv3 L=8",
+    "Inv3S EW=1", "Inv3S EW=2", "Inv3S EW=4", "Inv3S T=double", "Inv3S L=16",
+    "Inv3Y XSC=false", "Inv3Y XSC=true", "Inv3Y UNIYZ=true", "Inv3Y UNIYZ=false", "Inv3Y EW=1", "Inv3Y EW=2", "Inv3Y EW=4",
+    "Inv3Y VEC4=true", "Inv3Y VEC4=false", "Inv3Y TX=48", "Inv3Y EW=2 XSC=true", "Inv3Y EW=4 XSC=true",
+    "Den3",
+    "Fwd2S VEC4=true", "Fwd2S VEC4=false", "Fwd2S EW=2", "Fwd2S EW=4", "Fwd2S T=double",
+    "Fwd2C NLEV=2", "Fwd2C NLEV=3",
+    "Inv2S VEC4=true", "Inv2S VEC4=false", "Inv2S EW=2", "Inv2S EW=4", "Inv2S T=double",
+    "Inv2P PK=true", "Inv2P PK=false", "Inv2P T=double",
+    "Inv2C NLEV=2", "Inv2C NLEV=3", "Inv2C PD=2",
+    "AxisMarch SYN=false", "AxisMarch SYN=true",
+    "AxisX VEC4=true", "AxisX VEC4=false", "AxisX EW=2",
+    "axis_analysis_kernel", "axis_synthesis_kernel", "shrink_kernel", "segments_kernel", "segments_strided_kernel", "add_planes_kernel",
+]]

@@ -399,7 +399,11 @@ def test_atrous_level3_rec_on_buffers_that_are_not_16_byte_aligned():
         ybuf = torch.zeros(ck.numel() + 4, dtype=torch.float32, device="cuda")
         ybuf[off_in:off_in + ck.numel()] = ck.reshape(-1).cuda()
         xbuf = torch.zeros(vol + 4, dtype=torch.float32, device="cuda")
-        plan.rec(ybuf.data_ptr() + 4 * off_in, xbuf.data_ptr() + 4 * off_out, level, torch.cuda.current_stream().cuda_stream)
+        with ndwt.kernel_trace() as recs:
+            plan.rec(ybuf.data_ptr() + 4 * off_in, xbuf.data_ptr() + 4 * off_out, level, torch.cuda.current_stream().cuda_stream)
+        ew4 = [r for r in recs if r.params.get("EW") == 4]
+        # (level 3 reads the coefficients and writes a scratch volume: only the input offset decides its alignment)
+        assert ew4 and all(r.family == "Inv3S" and r.params["VEC4"] == (off_in == 0) for r in ew4), recs
         torch.cuda.synchronize()
         got = np.transpose(xbuf[off_out:off_out + vol].reshape(sizes[::-1]).cpu().numpy())
         assert _relerr(got, want) <= 4 * TOL["single"], (off_in, off_out)
@@ -510,6 +514,15 @@ def test_pitched_coefficient_layout_gives_the_packed_results(d, sizes, wn, cplx,
         plan.rec(yp.data_ptr(), xr.data_ptr(), level, 0, band_pitch=vol - 1)
 
 
+def _assert_path_families(path, recs_dec, recs_rec):
+    """the kernel families of a dec / rec call agree with Plan.describe()'s path"""
+    axis = {"AxisX", "AxisMarch", "axis_analysis_kernel", "axis_synthesis_kernel"}
+    fd, fr = {r.family for r in recs_dec}, {r.family for r in recs_rec}
+    assert fd and fr
+    assert fd <= (axis if path == "axis" else {"Fwd3"}), (path, recs_dec)
+    assert fr <= (axis if path != "fused3d" else {"Inv3Y", "Inv3S"}), (path, recs_rec)
+
+
 @pytest.mark.parametrize("sizes,wn,path", [
     ([64, 40, 36], "db7", "fused3d"),
     ([68, 41, 30], "db8", "fused3d"),
@@ -529,12 +542,15 @@ def test_long_filters_float(sizes, wn, path):
     x = rng.standard_normal(sizes)
     w = ndwt.nd_dwt_3D(wn, sizes, "pres_l2_norm", 1, "precision", "single")
     xg = _colmajor_gpu(x, "single")
-    y = w.dec(xg, 2)
+    with ndwt.kernel_trace() as recs:
+        y = w.dec(xg, 2)
     assert list(w._plans.values())[0].describe() == path
     wl = [wn] * 3 if isinstance(wn, str) else wn
     assert _relerr(y.cpu().numpy(), orc.spatial_dec(x, wl, 2, 1)) <= TOL["single"]
     c = rng.standard_normal(sizes + [15])
-    got = w.rec(_colmajor_gpu(c, "single")).cpu().numpy()
+    with ndwt.kernel_trace() as recs_r:
+        got = w.rec(_colmajor_gpu(c, "single")).cpu().numpy()
+    _assert_path_families(path, recs, recs_r)
     want = orc.spatial_rec(c, wl, 1)
     assert np.abs(got - want).max() <= TOL["single"] * max(np.abs(want).max(), np.abs(c).max())
     assert _relerr(w.rec(y).cpu().numpy(), x) < 1e-5
@@ -558,7 +574,9 @@ def test_scatter_and_gather_form_of_the_synthesis_x_stage(sizes, wn):
     for variant in (10, 11):
         w = ndwt.nd_dwt_3D(wn, sizes, "pres_l2_norm", 1, "precision", "single")
         w._plan(False, 2, cg.device).set_variant(inv=variant)
-        got[variant] = w.rec(cg).cpu().numpy()
+        with ndwt.kernel_trace() as recs:
+            got[variant] = w.rec(cg).cpu().numpy()
+        assert recs and all(r.family == "Inv3Y" and r.params["XSC"] == (variant == 10) for r in recs), (variant, recs)
         assert list(w._plans.values())[0].describe() == "fused3d"
         assert np.abs(got[variant] - want).max() <= TOL["single"] * scale, variant
     assert np.abs(got[10] - got[11]).max() <= 1e-6 * scale
@@ -578,12 +596,15 @@ def test_long_filters_double_14_16_taps(sizes, wn, path):
     x = rng.standard_normal(sizes)
     w = ndwt.nd_dwt_3D(wn, sizes, "pres_l2_norm", 1, "precision", "double")
     xg = _colmajor_gpu(x, "double")
-    y = w.dec(xg, 2)
+    with ndwt.kernel_trace() as recs:
+        y = w.dec(xg, 2)
     assert list(w._plans.values())[0].describe() == path
     wl = [wn] * 3 if isinstance(wn, str) else wn
     assert _relerr(y.cpu().numpy(), orc.spatial_dec(x, wl, 2, 1)) <= TOL["double"]
     c = rng.standard_normal(sizes + [15])
-    got = w.rec(_colmajor_gpu(c, "double")).cpu().numpy()
+    with ndwt.kernel_trace() as recs_r:
+        got = w.rec(_colmajor_gpu(c, "double")).cpu().numpy()
+    _assert_path_families(path, recs, recs_r)
     want = orc.spatial_rec(c, wl, 1)
     assert np.abs(got - want).max() <= TOL["double"] * max(np.abs(want).max(), np.abs(c).max())
     assert _relerr(w.rec(y).cpu().numpy(), x) < 1e-13
@@ -609,12 +630,15 @@ def test_long_filters_complex(sizes, wn, precision, path):
     x = rng.standard_normal(sizes) + 1j * rng.standard_normal(sizes)
     w = ndwt.nd_dwt_3D(wn, sizes, "pres_l2_norm", 1, "precision", precision)
     xg = _colmajor_gpu(x, precision)
-    y = w.dec(xg, 2)
+    with ndwt.kernel_trace() as recs:
+        y = w.dec(xg, 2)
     assert list(w._plans.values())[0].describe() == path
     wl = [wn] * 3 if isinstance(wn, str) else wn
     assert _relerr(y.cpu().numpy(), orc.spatial_dec(x, wl, 2, 1)) <= TOL[precision]
     c = rng.standard_normal(sizes + [15]) + 1j * rng.standard_normal(sizes + [15])
-    got = w.rec(_colmajor_gpu(c, precision)).cpu().numpy()
+    with ndwt.kernel_trace() as recs_r:
+        got = w.rec(_colmajor_gpu(c, precision)).cpu().numpy()
+    _assert_path_families(path, recs, recs_r)
     want = orc.spatial_rec(c, wl, 1)
     assert np.abs(got - want).max() <= TOL[precision] * max(np.abs(want).max(), np.abs(c).max())
     assert _relerr(w.rec(y).cpu().numpy(), x) < 20 * TOL[precision]
@@ -633,7 +657,11 @@ def test_tall_analysis_tile_against_oracle(sizes, wn, cplx):
     x = rng.standard_normal(sizes) + (1j * rng.standard_normal(sizes) if cplx else 0)
     w = ndwt.nd_dwt_3D(wn, sizes, "pres_l2_norm", 1, "precision", "single")
     xg = _colmajor_gpu(x, "single")
-    y = w.dec(xg, 2)
+    with ndwt.kernel_trace() as recs:
+        y = w.dec(xg, 2)
+    # every row here has >= 32 tall tiles (ceil(n1 * (2 if complex) / 64) * ceil(n2 / 32) = 40)
+    assert recs and all(r.family == "Fwd3" and r.params["TY"] == 32 and r.params["NT"] == 1024 and r.params["EW"] == (2 if cplx else 1)
+                        for r in recs), recs
     wl = [wn] * 3 if isinstance(wn, str) else wn
     assert _relerr(y.cpu().numpy(), orc.spatial_dec(x, wl, 2, 1)) <= TOL["single"]
     assert _relerr(w.rec(y).cpu().numpy(), x) < 1e-5
@@ -650,12 +678,15 @@ def test_long_filters_double_10_12_taps(sizes, wn):
     x = rng.standard_normal(sizes)
     w = ndwt.nd_dwt_3D(wn, sizes, "pres_l2_norm", 1, "precision", "double")
     xg = _colmajor_gpu(x, "double")
-    y = w.dec(xg, 2)
+    with ndwt.kernel_trace() as recs:
+        y = w.dec(xg, 2)
     assert list(w._plans.values())[0].describe() == "fused3d"
     wl = [wn] * 3 if isinstance(wn, str) else wn
     assert _relerr(y.cpu().numpy(), orc.spatial_dec(x, wl, 2, 1)) <= TOL["double"]
     c = rng.standard_normal(sizes + [15])
-    got = w.rec(_colmajor_gpu(c, "double")).cpu().numpy()
+    with ndwt.kernel_trace() as recs_r:
+        got = w.rec(_colmajor_gpu(c, "double")).cpu().numpy()
+    assert all(r.family == "Fwd3" and r.params["T"] == "double" for r in recs) and all(r.family == "Inv3S" for r in recs_r)
     want = orc.spatial_rec(c, wl, 1)
     assert np.abs(got - want).max() <= TOL["double"] * max(np.abs(want).max(), np.abs(c).max())
     assert _relerr(w.rec(y).cpu().numpy(), x) < 20 * TOL["double"]
@@ -851,7 +882,9 @@ def test_cascaded_2d_analysis_against_oracle(sizes, wn, level):
     for variant in (11, 9):                      # cascaded / one launch per level
         w = ndwt.nd_dwt_2D(wn, sizes, "pres_l2_norm", 1, "precision", "single")
         w._plan(False, level, xg.device).set_variant(fwd=variant)
-        res[variant] = w.dec(xg, level)
+        with ndwt.kernel_trace() as recs:
+            res[variant] = w.dec(xg, level)
+        assert any(r.family == "Fwd2C" for r in recs) == (variant == 11), (variant, recs)
         assert _relerr(res[variant].cpu().numpy(), want) <= TOL["single"], variant
     assert float((res[11] - res[9]).abs().max()) == 0.0
     assert _relerr(w.rec(res[11]).cpu().numpy(), x) < 1e-5
@@ -876,7 +909,9 @@ def test_cascaded_2d_synthesis_against_oracle(sizes, wn, level, depth):
     for variant in (11 if depth == 1 else 12, 9):
         w = ndwt.nd_dwt_2D(wn, sizes, "pres_l2_norm", 1, "precision", "single")
         w._plan(False, level, cg.device).set_variant(inv=variant)
-        res[variant] = w.rec(cg)
+        with ndwt.kernel_trace() as recs:
+            res[variant] = w.rec(cg)
+        assert [r.params["PD"] for r in recs if r.family == "Inv2C"][:1] == ([] if variant == 9 else [depth]), (variant, recs)
         assert np.abs(res[variant].cpu().numpy() - want).max() <= 2 * TOL["single"] * max(np.abs(want).max(), np.abs(c).max()), variant
     # ndwt_denoise on the cascaded kernels (thresholding fused into Inv2C's loads) against one launch per level
     xg = _colmajor_gpu(rng.standard_normal(sizes), "single")
@@ -1264,9 +1299,13 @@ def test_denoise_with_fused_level1_against_numpy(sizes, wn, level, l2):
     plan = list(w._plans.values())[0]
     for mode in ("soft", "hard"):
         plan.set_fused_level1(2)                              # 8 taps too (off by default there: not faster)
-        got = w.denoise(xg, level, thr, mode)
+        with ndwt.kernel_trace() as recs:
+            got = w.denoise(xg, level, thr, mode)
+        assert any(r.family == "Den3" for r in recs), recs
         plan.set_fused_level1(0)
-        mat = w.denoise(xg, level, thr, mode)
+        with ndwt.kernel_trace() as recs:
+            mat = w.denoise(xg, level, thr, mode)
+        assert recs and not any(r.family == "Den3" for r in recs), recs
         plan.set_fused_level1(1)
         want = orc.spatial_rec(_np_shrink(y_ref, thr, mode == "hard"), wl, l2)
         scale = max(np.abs(want).max(), 1.0)
@@ -1396,7 +1435,9 @@ def test_2d_synthesis_with_rows_in_flight(sizes, wn, precision):
     wl = [wn] * 2 if isinstance(wn, str) else wn
     c = rng.standard_normal(sizes + [7])
     w = ndwt.nd_dwt_2D(wn, sizes, "pres_l2_norm", 1, "precision", precision)
-    got = w.rec(_colmajor_gpu(c, precision)).cpu().numpy()
+    with ndwt.kernel_trace() as recs:
+        got = w.rec(_colmajor_gpu(c, precision)).cpu().numpy()
+    assert recs and all(r.family == "Inv2P" for r in recs), recs
     want = orc.spatial_rec(c, wl, 1)
     assert np.abs(got - want).max() <= TOL[precision] * max(np.abs(want).max(), np.abs(c).max())
     x = rng.standard_normal(sizes)
@@ -1431,9 +1472,13 @@ def test_4d_analysis_with_folded_t_axis_variant():
     x = rng.standard_normal(sizes)
     w = ndwt.nd_dwt_4D("db4", sizes, "pres_l2_norm", 1, "precision", "single")
     xg = _colmajor_gpu(x, "single")
-    y0 = w.dec(xg, 2)
+    with ndwt.kernel_trace() as recs:
+        y0 = w.dec(xg, 2)
+    assert recs and not any(r.params.get("TPRE") for r in recs), recs
     list(w._plans.values())[0].set_variant(fwd=7)
-    y7 = w.dec(xg, 2)
+    with ndwt.kernel_trace() as recs:
+        y7 = w.dec(xg, 2)
+    assert any(r.family == "Fwd3" and r.params["TPRE"] for r in recs), recs
     list(w._plans.values())[0].set_variant(fwd=0)
     want = orc.spatial_dec(x, ["db4"] * 4, 2, 1)
     assert _relerr(y7.cpu().numpy(), want) <= TOL["single"] and _relerr(y0.cpu().numpy(), want) <= TOL["single"]
