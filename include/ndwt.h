@@ -110,7 +110,13 @@ int ndwt_plan_set_tuning(ndwt_plan* plan, int target_blocks, int force_zchunk);
 /* test / tuning hook of tools/ (interleaved A/B runs): kernel variant per direction, marched chunk per direction, fp64 on the
  * fused (1) or per-axis (0) kernels.  Negative = leave unchanged.  Every variant computes the same transform (bit-identical where
  * only the schedule differs; to rounding where the order of the FMAs does: packed / scalar forms, kernel families); the library never
- * reads the environment. */
+ * reads the environment.  The numbers (named in csrc/ndwt_select.h: FwdVariant / InvVariant, with the full table):
+ *   variant_fwd  0 default | 1 one column per thread, 512 threads | 2 tall 64x32 tile (and denoise's band-0 analysis on it) | 3 keeps the
+ *                small tile / the spilling long-filter forms | 6 tall tile, y items of 2 rows | 7 4-D: t axis folded in | 8 no pinned taps |
+ *                2-D: 9 no cascade (either direction) | 10 cascade always, kernel mode 1 | 11 cascade always
+ *   variant_inv  0 default | 3-D: 2 dilated levels keep Inv3S | 3 LDS kernel Inv3 (8 taps) | 4 Inv3S | 5 Inv3Y depth 1 | 9 no shared y / z
+ *                taps | 10 scatter x stage wherever it exists | 11 gather x stage everywhere | 2-D: 1 keeps Inv2S | 2 / 4 Inv2P depth 2 / 4
+ *                on Inv2S's geometry | 6 depth 2, 1024 waves | 7 unpacked FMAs | cascade: 9 off | 11 always | 12 always, two rows in flight */
 int ndwt_plan_set_variant(ndwt_plan* plan, int variant_fwd, int variant_inv, int zchunk_fwd, int zchunk_inv, int fp64_fused);
 /* test / tuning hook: 0 makes ndwt_denoise keep the level-1 detail bands in memory (dec, thresholding fused into the synthesis
  * loads, rec); 1 (default) = level 1 in one launch that recomputes them where that is faster (float, real, 3-D, one tap length

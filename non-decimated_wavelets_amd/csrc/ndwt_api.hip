@@ -20,6 +20,7 @@
 #include "ndwt_filters.h"
 #include "ndwt_fused.h"
 #include "ndwt_geom.h"
+#include "ndwt_select.h"
 #include "ndwt_trace.h"
 
 using namespace ndwt;
@@ -111,7 +112,8 @@ struct ndwt_plan {
     int target_blocks;                 // fused-kernel grid sizing: 0 = one round of resident workgroups (per kernel), else as given
     int force_zchunk;
     int zchunk_dir[2];                 // per-direction override of the marched chunk: [0] analysis, [1] synthesis (0 = auto)
-    int variant_fwd, variant_inv;      // fused-kernel variants (tuning experiments; same results)
+    int variant_fwd, variant_inv;      // fused-kernel variants (tuning experiments; same results: ndwt_select.h)
+    bool uniform_yz;                   // the y and z axes carry the same synthesis taps: Inv3Y then keeps one set of tap pairs for both
     int num_cus;
     int fp64_fused;                    // fp64: fused 3-D kernels (1) or the per-axis march kernels (0)
     void* taps_dev[2];                 // device tap tables of the fused kernels: [0] analysis, [1] synthesis (Taps3<T, Lp>)
@@ -181,21 +183,10 @@ static void prof_end(const ndwt_plan* p, hipStream_t s, int rc = 0) {
 static long long level_stride(const ndwt_plan* p, int lev) { return p->dilation == NDWT_DILATION_ATROUS ? (1LL << (lev - 1)) : 1LL; }
 
 template <typename T> static bool aligned_vec4(const void* ptr) { return ((uintptr_t)ptr % (4 * sizeof(T))) == 0; }
-template <typename T> static int launch_march(bool syn, int L, const MarchArgs<T>& a, const double* lo, const double* hi, hipStream_t s);
-template <> int launch_march<float>(bool syn, int L, const MarchArgs<float>& a, const double* lo, const double* hi, hipStream_t s) {
-    return launch_march_f32(syn, L, a, lo, hi, s);
-}
-template <> int launch_march<double>(bool syn, int L, const MarchArgs<double>& a, const double* lo, const double* hi, hipStream_t s) {
-    return launch_march_f64(syn, L, a, lo, hi, s);
-}
-
-template <typename T> static int launch_axisx(bool syn, int L, int ew, const AxisXArgs<T>& a, bool vec4, const double* lo, const double* hi, hipStream_t s);
-template <> int launch_axisx<float>(bool syn, int L, int ew, const AxisXArgs<float>& a, bool vec4, const double* lo, const double* hi, hipStream_t s) {
-    return launch_axisx_f32(syn, L, ew, a, vec4, lo, hi, s);
-}
-template <> int launch_axisx<double>(bool syn, int L, int ew, const AxisXArgs<double>& a, bool vec4, const double* lo, const double* hi, hipStream_t s) {
-    return launch_axisx_f64(syn, L, ew, a, vec4, lo, hi, s);
-}
+static int launch_march(bool syn, int L, const MarchArgs<float>& a, const double* lo, const double* hi, hipStream_t s) { return launch_march_f32(syn, L, a, lo, hi, s); }
+static int launch_march(bool syn, int L, const MarchArgs<double>& a, const double* lo, const double* hi, hipStream_t s) { return launch_march_f64(syn, L, a, lo, hi, s); }
+static int launch_axisx(bool syn, int L, int ew, const AxisXArgs<float>& a, bool vec4, const double* lo, const double* hi, hipStream_t s) { return launch_axisx_f32(syn, L, ew, a, vec4, lo, hi, s); }
+static int launch_axisx(bool syn, int L, int ew, const AxisXArgs<double>& a, bool vec4, const double* lo, const double* hi, hipStream_t s) { return launch_axisx_f64(syn, L, ew, a, vec4, lo, hi, s); }
 
 // ------------------------------------------------------------------------------ one axis, one pass
 template <typename T>
@@ -246,7 +237,7 @@ static int axis_pass(const ndwt_plan* p, bool synthesis, int axis, const long lo
         m.chunk = (int)chunk;
         m.nchunks = (int)((m.n + chunk - 1) / chunk);
         prof_begin(p, synthesis ? NDWT_KERNEL_AXIS_SYNTHESIS : NDWT_KERNEL_AXIS_ANALYSIS, s);
-        int rc = launch_march<T>(synthesis, f.len, m, synthesis ? f.syn_lo : f.ana_lo, synthesis ? f.syn_hi : f.ana_hi, s);
+        int rc = launch_march(synthesis, f.len, m, synthesis ? f.syn_lo : f.ana_lo, synthesis ? f.syn_hi : f.ana_hi, s);
         prof_end(p, s, rc);
         if (rc == 0) return NDWT_OK;
         if (rc > 0) return fail(NDWT_ERR_HIP, "march kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -263,7 +254,7 @@ static int axis_pass(const ndwt_plan* p, bool synthesis, int axis, const long lo
         const bool v4ok = x.row % 4 == 0 && aligned_vec4<T>(in0) && (!synthesis || aligned_vec4<T>(in1)) && aligned_vec4<T>(out0) &&
                           (synthesis || aligned_vec4<T>(out1));
         prof_begin(p, synthesis ? NDWT_KERNEL_AXIS_SYNTHESIS : NDWT_KERNEL_AXIS_ANALYSIS, s);
-        int rc = launch_axisx<T>(synthesis, f.len, (int)p->comp, x, v4ok, synthesis ? f.syn_lo : f.ana_lo, synthesis ? f.syn_hi : f.ana_hi, s);
+        int rc = launch_axisx(synthesis, f.len, (int)p->comp, x, v4ok, synthesis ? f.syn_lo : f.ana_lo, synthesis ? f.syn_hi : f.ana_hi, s);
         prof_end(p, s, rc);
         if (rc == 0) return NDWT_OK;
         if (rc > 0) return fail(NDWT_ERR_HIP, "contiguous-axis kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -335,66 +326,12 @@ template <typename T> static int generic_synthesis(GenericCtx<T>& c, int axis, i
 }
 
 // ------------------------------------------------------------------------------------ fused levels
-// dir: 0 analysis, 1 synthesis, -1 both.  Instantiated tap lengths: 2..12 (db1..db6) for every data kind the checks below let
-// through; float real data also 14 .. 20 (db7 .. db10; 18- and 20-tap synthesis with the pair-packed kernel only), double real data 14 and 16.
-static bool inv3y_plan_ok(const ndwt_plan* p, int Lp);
-static bool fused3_eligible(const ndwt_plan* p, long long stride, int* Lp_out, int dir = -1) {
-    if (p->path != NDWT_PATH_AUTO || stride != 1 || p->ndim < 3) return false;
-    if (p->dtype == NDWT_F64 && !p->fp64_fused) return false;
-    int Lp = 2;
-    for (int a = 0; a < 3; ++a) Lp = p->filt[a].len > Lp ? p->filt[a].len : Lp;
-    const int lmax = p->complexity != NDWT_REAL ? (p->dtype == NDWT_F32 && dir == 0 ? 16 : 12) : (p->dtype == NDWT_F32 ? (dir == 0 ? 20 : 16) : 16);
-    // 18- and 20-tap synthesis exist as the pair-packed kernel only (uniform wavelets, or mixed ones with even padding on every axis)
-    if (Lp > lmax && !(dir == 1 && Lp <= 20 && inv3y_plan_ok(p, Lp))) return false;
-    if (p->dtype == NDWT_F64 && Lp > 16) return false;   // double: up to db8 (64x8 tiles with 512 threads keep 10 .. 16 taps in 256 registers)
-    // interleaved complex: the fused kernels with the x taps stepping over (re, im) pairs, tap lengths <= 8 (float: <= 12); rows of an
-    // odd number of elements run the VEC4 = false instances (one access per lane wherever its 4 scalars are contiguous)
-    // (complex128: 10 taps both ways, 12 taps analysis only -- its synthesis spills 500+ registers on every tile)
-    // (complex64: 14 / 16 taps in the analysis, and in the synthesis through the pair-packed kernel -- the Lp > lmax clause above)
-    if (p->complexity != NDWT_REAL && Lp > (p->dtype == NDWT_F32 ? 16 : (dir == 0 ? 12 : 10))) return false;
-    long long nbatch = p->ndim == 4 ? p->dims[3] + 64 : 1;
-    if (!fused3_fits(p->dims[0] * p->comp, p->dims[1], p->dims[2] + 64, nbatch)) return false;
-    *Lp_out = Lp;
-    return true;
-}
-
-// A dilated (a-trous) 3-D level whose axes all divide by the tap stride s is s^3 independent stride-1 problems on the
-// sub-lattices: the fused kernels take x with the taps stepping over s interleaved scalars (the EW parameter, as for
-// interleaved complex data) and the s^2 (y, z) sub-lattices as batch items with row / plane strides s*n1, s*n1*n2.
-static bool fused3_dilated_eligible(const ndwt_plan* p, long long stride, int* Lp_out) {
-    if (p->path != NDWT_PATH_AUTO || p->ndim != 3 || p->complexity != NDWT_REAL) return false;
-    if (stride != 2 && !(stride == 4 && p->dtype == NDWT_F32)) return false;   // instantiated: EW = 2 (float, double), EW = 4 (float)
-    if (p->dtype == NDWT_F64 && !p->fp64_fused) return false;
-    int Lp = 2;
-    for (int a = 0; a < 3; ++a) Lp = p->filt[a].len > Lp ? p->filt[a].len : Lp;
-    if (Lp > 8) return false;
-    for (int a = 0; a < 3; ++a)
-        if (p->dims[a] % stride != 0) return false;
-    if (p->dims[0] % 4 != 0) return false;
-    if (!fused3_fits(p->dims[0], p->dims[1], p->dims[2] + 64, stride * stride)) return false;
-    *Lp_out = Lp;
-    return true;
-}
-
-// the 2-D analogue: x through EW = stride, the `stride` row sub-lattices as batch items
-static bool fused2_dilated_eligible(const ndwt_plan* p, long long stride, int* Lp_out) {
-    if (p->path != NDWT_PATH_AUTO || p->ndim != 2 || p->complexity != NDWT_REAL) return false;
-    if (stride != 2 && !(stride == 4 && p->dtype == NDWT_F32)) return false;
-    int Lp = p->filt[0].len > p->filt[1].len ? p->filt[0].len : p->filt[1].len;
-    if (Lp > 8 || p->dims[0] % stride != 0 || p->dims[1] % stride != 0 || p->dims[0] % 4 != 0) return false;
-    if (p->dims[0] >= (1LL << 30) || p->dims[1] >= (1LL << 30)) return false;
-    *Lp_out = Lp;
-    return true;
-}
-
-static bool fused2_eligible(const ndwt_plan* p, long long stride, int* Lp_out) {
-    if (p->path != NDWT_PATH_AUTO || stride != 1 || p->ndim != 2) return false;
-    int Lp = p->filt[0].len > p->filt[1].len ? p->filt[0].len : p->filt[1].len;
-    // float real: up to db10, complex64 and double real: up to db8 (256-register budget), complex128: up to db4
-    if (Lp > (p->dtype == NDWT_F32 ? (p->complexity == NDWT_REAL ? 20 : 16) : (p->complexity == NDWT_REAL ? 16 : 8))) return false;
-    if (p->dims[0] >= (1LL << 30) || p->dims[1] >= (1LL << 30)) return false;
-    *Lp_out = Lp;
-    return true;
+// The eligibility predicates and the choice of kernel are plain functions of integers (ndwt_select.h); this is what they see of a plan.
+static SelPlan sel(const ndwt_plan* p) {
+    SelPlan q = {p->ndim, (int)p->comp, p->dtype == NDWT_F64, p->complexity == NDWT_REAL, p->path == NDWT_PATH_AUTO,
+                 p->dilation != NDWT_DILATION_REFERENCE, p->fp64_fused != 0, {1, 1, 1, 1}, {2, 2, 2, 2}, p->variant_fwd, p->variant_inv};
+    for (int k = 0; k < p->ndim; ++k) { q.dims[k] = p->dims[k]; q.len[k] = p->filt[k].len; }
+    return q;
 }
 
 static FusedTapsD fused_taps(const ndwt_plan* p, int Lp, bool synthesis) {
@@ -412,49 +349,6 @@ static FusedTapsD fused_taps(const ndwt_plan* p, int Lp, bool synthesis) {
     return t;
 }
 
-template <typename T> static int launch3(bool inverse, const Fused3Args<T>& a, const FusedTapsD& t, bool vec4, int variant, int ew, const void* td, hipStream_t s);
-template <> int launch3<float>(bool inverse, const Fused3Args<float>& a, const FusedTapsD& t, bool vec4, int variant, int ew, const void* td, hipStream_t s) {
-    return inverse ? launch_inv3_f32(a, t, vec4, variant, ew, td, s) : launch_fwd3_f32(a, t, vec4, variant, ew, td, s);
-}
-template <> int launch3<double>(bool inverse, const Fused3Args<double>& a, const FusedTapsD& t, bool vec4, int variant, int ew, const void* td, hipStream_t s) {
-    return inverse ? launch_inv3_f64(a, t, vec4, variant, ew, td, s) : launch_fwd3_f64(a, t, vec4, variant, ew, td, s);
-}
-
-namespace ndwt {
-// the tile the launcher of ndwt_fused_kernels.h will pick (ew = scalars per x element: 1 real, 2 interleaved complex or a level
-// dilated by 2, 4 a level dilated by 4).  The A/B variants exist for real, undilated data only.
-void fused3_tile_shape(bool f64, bool inverse, int variant, int Lp, int* TX, int* TY, int ew) {
-    if (ew != 1) variant = 0;
-    *TX = 64;
-    if (!inverse) {
-        *TY = f64 ? (((Lp == 10 && ew == 1) || (variant == 1 && Lp >= 6 && Lp <= 8 && ew == 1) || (ew == 2 && Lp == 8)) ? 16 : 8) : 16;   // double: db5, complex db4 (db3/db4: variant 1) 64x16 with 512 threads; db6 64x8 with 512
-        if (!f64 && ew == 1 && (((variant == 2 || variant == 6) && Lp <= 8) || (variant != 1 && Lp >= 10 && Lp <= 16))) *TY = 32;   // float, tall tile: 10 .. 16 taps (<= 8: A/B)
-    } else if (f64) {
-        *TY = ((variant == 3 && Lp == 8) || Lp >= 10) ? 8 : 16;                   // lane-shift kernel 64x16 (10 / 12 taps: 64x8); variant 3 = LDS kernel
-    } else {
-        *TY = (variant == 3 && Lp == 8) ? 16 : (ew == 4 ? 16 : 32);              // tall tile; x taps over 4 scalars: 64x16 / 512 threads
-    }
-}
-}  // namespace ndwt
-
-// Float synthesis default: the pair-packed kernel.  It derives the high-pass taps from the low-pass ones (mirror + alternating
-// signs), which holds for the zero-padded taps of an axis when its padding (Lp - len) / 2 is even; it keeps plane offsets in
-// 32-bit BYTE counts.  variant_inv 4 forces the older lane-shift kernel (Inv3S) for A/B runs.
-static bool inv3y_plan_ok(const ndwt_plan* p, int Lp) {
-    if (p->dtype != NDWT_F32 || Lp > (p->comp == 1 ? 20 : 16) || p->variant_inv == 3 || p->variant_inv == 4) return false;
-    for (int ax = 0; ax < 3; ++ax)
-        if (((Lp - p->filt[ax].len) / 2) % 2 != 0) return false;
-    return p->dims[0] * p->comp * p->dims[1] < (1LL << 30);
-}
-
-// the y and z axes carry the same synthesis taps (the same wavelet): the pair-packed kernel then keeps one set of tap pairs for both
-static bool uniform_yz(const ndwt_plan* p) {
-    if (p->ndim < 3 || p->filt[1].len != p->filt[2].len) return false;
-    for (int j = 0; j < p->filt[1].len; ++j)
-        if (p->filt[1].syn_lo[j] != p->filt[2].syn_lo[j]) return false;
-    return true;
-}
-
 // Nontemporal output stores: float data whose output rows are whole 128-byte lines (a nontemporal store of a partly covered line
 // is a read-modify-write in memory; plain stores of neighbouring tiles merge in L2).  Double never (ndwt_device.h: stream_store).
 template <typename T> static int nt_store_ok(long long rs, long long plane, long long bstride, T* const* out, int nout) {
@@ -464,6 +358,23 @@ template <typename T> static int nt_store_ok(long long rs, long long plane, long
     for (int b = 0; b < nout; ++b)
         if (((uintptr_t)out[b]) % 128 != 0) return 0;
     return 1;
+}
+
+// the one launch a pick names (the launchers answer -1 where they have no instance: after a pick that is an internal error)
+static int launch_pick(const Fused3Pick& k, const Fused3Query& q, const Fused3Args<float>& a, const FusedTapsD& t, const void* td, hipStream_t s) {
+    switch (k.family) {
+        case kFwd3FoldT: return launch_fwd3_tpre_f32(a, t.Lp, td, s);
+        case kFwd3Pin: return launch_fwd3_pin_f32(a, t.Lp, td, s);
+        case kLong3: return launch_long3_f32(q.inverse, a, t, q.vec4, k.long_ab, td, s);
+        case kInv3Y: return q.ew == 4 ? launch_inv3y4_f32(a, t.Lp, k.depth, td, s, k.scatter)
+                          : q.ew == 2 ? launch_inv3yc_f32(a, t.Lp, q.vec4, k.depth, td, s, k.scatter)
+                          : k.scatter ? launch_inv3ys_f32(a, t.Lp, k.depth, td, s, k.uniyz) : launch_inv3y_f32(a, t.Lp, q.vec4, k.depth, td, s, k.uniyz);
+        default: return q.inverse ? launch_inv3_f32(a, t, q.vec4, k.V, q.ew, td, s) : launch_fwd3_f32(a, t, q.vec4, k.V, q.ew, td, s);
+    }
+}
+static int launch_pick(const Fused3Pick& k, const Fused3Query& q, const Fused3Args<double>& a, const FusedTapsD& t, const void* td, hipStream_t s) {
+    if (k.family == kLong3) return launch_long3_f64(q.inverse, a, t, q.vec4, td, s);
+    return q.inverse ? launch_inv3_f64(a, t, q.vec4, k.V, q.ew, td, s) : launch_fwd3_f64(a, t, q.vec4, k.V, q.ew, td, s);
 }
 
 // one fused 3-D launch over `nbatch` volumes. n3 = output planes; z_wrap=false: inputs carry the z halo
@@ -506,50 +417,13 @@ static int fused3_run(const ndwt_plan* p, bool inverse, int Lp, const T* const* 
         else for (int b = 0; b < nout; ++b) a.out[b] = out[b] + (b / div) * pad;
     }
 #endif
-    int TX = 0, TY = 0;
-    int variant = inverse ? p->variant_inv : p->variant_fwd;
-    const int ew = dil > 1 ? dil : (int)p->comp;
-    // float analysis, 6 and 8 taps: the tall 64x32 tile with 1024 threads (variant 2) where the volume has the tiles to fill the chip
-    // with it (512^3 db4: 0.95 -> 0.85 ms per launch, db3 -4 %; db1 / db2 +3 %, 256^3 even); NDWT_VARIANT_FWD=3 keeps the 64x16 tile
-    // ... and the same for interleaved complex64 (384^3 db4: 1.19 -> 1.03 ms per launch); NDWT_VARIANT_FWD=3 keeps the 64x16 tile
-    const bool cplx_tall = !inverse && sizeof(T) == 4 && ew == 2 && dil == 1 && variant == 0 && Lp >= 6 && Lp <= 8 &&
-                           (long long)((a.n1 + 63) / 64) * ((a.n2 + 31) / 32) * a.nbatch >= 32;
-    if (!inverse && sizeof(T) == 4 && ew == 1 && variant == 0 && Lp >= 6 && Lp <= 8 &&
-        (long long)((a.n1 + 63) / 64) * ((a.n2 + 31) / 32) * a.nbatch >= 32)
-        variant = 2;
-    if (ttaps) variant = 6;                               // the folded t axis runs on the tall tile with y items of 2 rows
-    // float real analysis with 10 / 12 / 14 taps: the tall-tile kernel with its taps pinned in SGPRs and the high-pass ones derived from
-    // the low-pass ones (Fwd3 PIN: no scalar loads in the plane loop; 512^3 db5 0.945 -> 0.889, db6 1.027 -> 0.967, db7 1.118 -> 1.103 ms
-    // per launch, bit-identical).  Needs vec4 data and an even zero padding of every axis' taps; NDWT_VARIANT_FWD=8 keeps the plain
-    // form (A/B).  (6 / 8 taps: +1 %, not used; 16 taps spill in this form.)
-    bool pin_fwd = false;
-    if (!inverse && sizeof(T) == 4 && ew == 1 && !ttaps && (variant == 0 || variant == 8)) {
-        pin_fwd = variant == 0 && Lp >= 10 && Lp <= 14 && vec4;
-        for (int ax = 0; ax < 3; ++ax) pin_fwd = pin_fwd && (ax >= p->ndim || ((Lp - p->filt[ax].len) / 2) % 2 == 0);
-        if (variant == 8) variant = (Lp >= 6 && Lp <= 8 && (long long)((a.n1 + 63) / 64) * ((a.n2 + 31) / 32) * a.nbatch >= 32) ? 2 : 0;
-    }
-    // double analysis, 6 and 8 taps: 64x16 tile with 512 threads, one column per thread (384^3 db4: 1.29 -> 0.97 ms per launch,
-    // 320^3 -15 %, 512^3 -2 %, 256^3 +2 %); NDWT_VARIANT_FWD=3 keeps the 64x8 tile with 256 threads
-    if (!inverse && sizeof(T) == 8 && ew == 1 && variant == 0 && Lp >= 6 && Lp <= 8) variant = 1;
-    fused3_tile_shape(sizeof(T) == 8, inverse, ew != 1 ? 0 : variant, Lp, &TX, &TY, ew);
-    if (cplx_tall) TY = 32;
-    bool use_y = false;                                   // float synthesis default: the pair-packed kernel and its tile
-    if constexpr (sizeof(T) == 4) {
-        // (plane offsets stay below 2^32 bytes: checked there).  A level dilated by 2 on real data is the interleaved-pair form of the
-        // kernel (the two x sub-lattices are its (re, im) halves): 512^3 db4 synthesis at tap stride 2 1.52 -> see DESIGN 4.6
-        use_y = inverse && (dil == 1 || ((dil == 2 || (dil == 4 && vec4)) && p->comp == 1 && p->variant_inv != 2)) && inv3y_plan_ok(p, Lp);
-        // (the whole-lane-shift form of tap stride 4 exists for 16-byte-aligned data only: anything else keeps Inv3S<.., EW = 4>)
-        if (use_y) { TX = ndwt::inv3y_tx(Lp, ew); TY = ndwt::inv3y_ty(Lp, ew); }
-    }
+    const Fused3Query q = {sizeof(T) == 8, inverse, vec4, p->uniform_yz, ttaps != nullptr, Lp, {p->filt[0].len, p->filt[1].len, p->filt[2].len},
+                           dil > 1 ? dil : (int)p->comp, dil, a.n1, a.n2, a.nbatch, p->variant_fwd, p->variant_inv, p->num_cus, p->target_blocks};
+    const Fused3Pick k = fused3_select(q);
+    if (k.family == kNoFused3) return fail(NDWT_ERR_UNSUPPORTED, "internal: no folded-t analysis kernel for tap length %d / this alignment", Lp);
     const int zc_force = p->zchunk_dir[inverse ? 1 : 0] > 0 ? p->zchunk_dir[inverse ? 1 : 0] : p->force_zchunk;
-    // One round of workgroups that all fit on the chip at once beats several partial rounds (measured, 512^3 float
-    // analysis: 512 workgroups 0.88 ms, 1024: 1.09 ms, 2048: 0.99 ms; 256^3 double synthesis: 256 workgroups 0.36 ms,
-    // 640: 0.48 ms).  Workgroups per CU: synthesis 1 (1024 threads / 94 KB of LDS), analysis 2 (3 fit, 2 run faster).
-    const bool small_inv = inverse && sizeof(T) == 4 && ew == 1 && variant == 3 && Lp == 8;   // 256-thread A/B variant
-    const int per_cu = inverse ? (small_inv ? 3 : 1) : ((dil == 4 || (sizeof(T) == 4 && TY == 32)) ? 1 : 2);   // 1024-thread tiles: one per CU
-    const int target = p->target_blocks > 0 ? p->target_blocks : p->num_cus * per_cu;
     // more tiles than resident slots: fused3_geometry picks the chunk count with the fewest plane steps over all rounds
-    fused3_geometry(a, TX, TY, Lp, target, zc_force);
+    fused3_geometry(a, k.TX, k.TY, Lp, k.target, zc_force);
     if (dil > 1) {
         a.rs = (int)(dil * p->dims[0]);
         a.plane = (long long)dil * p->dims[0] * p->dims[1];
@@ -559,67 +433,25 @@ static int fused3_run(const ndwt_plan* p, bool inverse, int Lp, const T* const* 
     }
     // (a tile narrower than whole lines -- the 48-wide pair-packed tiles of 20 taps / complex 12 taps -- would put tile edges inside
     // a line: two workgroups' partial nontemporal stores of one line, the read-modify-write case again)
-    a.nt = ((long long)TX * (long long)sizeof(T)) % 128 == 0 ? nt_store_ok<T>(a.rs, a.plane, out_bstride, out, nout) : 0;
+    a.nt = ((long long)k.TX * (long long)sizeof(T)) % 128 == 0 ? nt_store_ok<T>(a.rs, a.plane, out_bstride, out, nout) : 0;
     FusedTapsD t = fused_taps(p, Lp, inverse);
     const void* td = p->taps_dev[inverse ? 1 : 0];
     if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
     prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
-    int rc = -1;
-    if constexpr (sizeof(T) == 4) {
-        if (use_y) {
-            // (tap stride 4, 8 taps: the x stage in scatter form -- 512^3 db4 1.78 -> 1.52 ms per level; 6 taps 1.117 / 1.110: the gather form
-            //  stays; variant_inv 10 = scatter form for 4 / 6 taps too, 11 = gather form)
-            rc = ew == 4 ? (vec4 ? launch_inv3y4_f32(a, Lp, variant == 5 ? 1 : 2, td, s, p->variant_inv == 10 || (Lp == 8 && p->variant_inv != 11)) : -1)
-                 // (interleaved pairs: the scatter form from 10 taps on -- complex64 384^3 rec of 3 levels db5 3.78 -> 3.66 ms, db6 5.00 -> 4.66, db8 6.71 -> 5.83;
-                 //  8 taps: 3.07 either way, and real data at tap stride 2 4 % SLOWER (0.97 -> 1.02 ms per level): the gather form stays there)
-                 : ew == 2 ? launch_inv3yc_f32(a, Lp, vec4, variant == 5 ? 1 : 2, td, s, p->variant_inv == 10 || (Lp >= 10 && p->variant_inv != 11))
-                 // real data on rows of whole groups of 4, 10 .. 20 taps: the x stage in scatter form (512^3 per launch db5 1.18 -> 1.09 ms,
-                 // db6 1.34 -> 1.23, db9 2.66 -> 2.41, db10 3.08 -> 2.87; 8 taps: 1.04 either way, the gather form stays.  A/B: variant_inv
-                 // 10 = scatter form for 8 taps too, 11 = gather form for every tap length)
-                 : (vec4 && variant != 11 && (Lp >= 10 || variant == 10)) ? launch_inv3ys_f32(a, Lp, variant == 5 ? 1 : 2, td, s, uniform_yz(p)) : -1;
-            if (rc == -1 && ew == 1) rc = launch_inv3y_f32(a, Lp, vec4, variant == 5 ? 1 : 2, td, s, uniform_yz(p) && variant != 9);
-            if (rc == -1) {                               // the geometry above is this kernel's: never fall through to another one with it
-                prof_end(p, s, rc);
-                return fail(NDWT_ERR_UNSUPPORTED, "pair-packed synthesis kernel not instantiated for tap length %d", Lp);
-            }
-        }
-    }
-    if constexpr (sizeof(T) == 4) {
-        if (ttaps) {
-            rc = vec4 ? launch_fwd3_tpre_f32(a, Lp, td, s) : -1;
-            if (rc == -1) {
-                prof_end(p, s, rc);
-                return fail(NDWT_ERR_UNSUPPORTED, "internal: no folded-t analysis kernel for tap length %d / this alignment", Lp);
-            }
-        }
-        if (rc == -1 && pin_fwd) rc = launch_fwd3_pin_f32(a, Lp, td, s);
-        if (rc == -1 && Lp > 12 && ew == 1) rc = launch_long3_f32(inverse, a, t, vec4, variant, td, s);
-    }
-    if constexpr (sizeof(T) == 8) {
-        if (Lp > 12 && ew == 1) rc = launch_long3_f64(inverse, a, t, vec4, td, s);
-    }
-    if (rc == -1) rc = launch3<T>(inverse, a, t, vec4, ew != 1 ? (cplx_tall ? 2 : 0) : variant, ew, td, s);
+    const int rc = launch_pick(k, q, a, t, td, s);
     prof_end(p, s, rc);
-    if (rc == -1) return fail(NDWT_ERR_UNSUPPORTED, "no fused kernel instantiated for tap length %d", Lp);
-    if (rc == -2) return fail(NDWT_ERR_UNSUPPORTED, "internal: launch geometry (%d x %d tiles) does not match the kernel's tile shape", TX, TY);
+    if (rc == -1) return fail(NDWT_ERR_UNSUPPORTED, "internal: no fused kernel instantiated for the pick (family %d, tap length %d)", (int)k.family, Lp);
+    if (rc == -2) return fail(NDWT_ERR_UNSUPPORTED, "internal: launch geometry (%d x %d tiles) does not match the kernel's tile shape", k.TX, k.TY);
     if (rc != 0) return fail(NDWT_ERR_HIP, "fused kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     return NDWT_OK;
 }
 
-namespace ndwt {
-int fused2_tile_width(bool inverse, int Lp, int ew) {
-    const int LH = inverse ? Lp / 2 : Lp / 2 - 1, RH = inverse ? Lp / 2 - 1 : Lp / 2;
-    return 4 * (64 - (LH * ew + 3) / 4 - (RH * ew + 3) / 4);
-}
-}  // namespace ndwt
-
-template <typename T> static int launch2(bool inverse, const Fused2Args<T>& a, int Lp, bool vec4, int ew, const void* td, hipStream_t s);
-template <> int launch2<float>(bool inverse, const Fused2Args<float>& a, int Lp, bool vec4, int ew, const void* td, hipStream_t s) {
+static int launch2(bool inverse, const Fused2Args<float>& a, int Lp, bool vec4, int ew, const void* td, hipStream_t s) {
     if (ew == 2 && Lp > 8) return inverse ? launch_inv2_c64_10to16(a, Lp, vec4, td, s) : launch_fwd2_c64_10to16(a, Lp, vec4, td, s);
     if (Lp > 12) return ew != 1 ? -1 : (inverse ? launch_inv2_f32_14to20(a, Lp, vec4, td, s) : launch_fwd2_f32_14to20(a, Lp, vec4, td, s));
     return inverse ? launch_inv2_f32(a, Lp, vec4, ew, td, s) : launch_fwd2_f32(a, Lp, vec4, ew, td, s);
 }
-template <> int launch2<double>(bool inverse, const Fused2Args<double>& a, int Lp, bool vec4, int ew, const void* td, hipStream_t s) {
+static int launch2(bool inverse, const Fused2Args<double>& a, int Lp, bool vec4, int ew, const void* td, hipStream_t s) {
     if (Lp > 12) return ew != 1 ? -1 : launch_long2_f64(inverse, a, Lp, vec4, td, s);
     return inverse ? launch_inv2_f64(a, Lp, vec4, ew, td, s) : launch_fwd2_f64(a, Lp, vec4, ew, td, s);
 }
@@ -645,32 +477,18 @@ static int fused2_run(const ndwt_plan* p, bool inverse, int Lp, const T* const* 
     const int nin = inverse ? 4 : 1, nout = inverse ? 1 : 4;
     for (int b = 0; b < nin; ++b) { a.in[b] = in[b]; vec4 = vec4 && aligned_vec4<T>(in[b]); }
     for (int b = 0; b < nout; ++b) { a.out[b] = out[b]; vec4 = vec4 && aligned_vec4<T>(out[b]); }
-    const int ew2 = dil > 1 ? dil : (int)p->comp;
-    // float synthesis of real data in rows of whole groups of 4 scalars, images whose 70-row chunks fit one round of 1024 waves (up to
-    // 4096^2): Inv2P -- 4 rows of band loads in flight per wave, the row loop unrolled in groups of L so that the compiler waits for
-    // exactly the load a row needs, half as many waves on chunks twice as long (the L-1 prologue rows of a chunk are re-read).  Interleaved
-    // A/B, 3 levels of rec: 1024^2 52 -> 43 us, 2048^2 81 -> 80, 4096^2 289 -> 265; 8192^2 927 -> 961 (not taken there: the run needs
-    // more than one round of waves either way).  variant_inv: 1 keeps Inv2S, 2 / 4 = depth on Inv2S's geometry, 6 = depth 2 on 1024 waves.
-    // Depth 4 runs in the packed form (pairs of adjacent x outputs per v_pk_fma_f32, tap pairs pinned in SGPRs; variant_inv 7 = scalar FMAs):
-    // 4096^2 db4 74 us either way (the kernel sits on its memory floor), db6 116 -> 98 us, 2048^2 db4 27.1 -> 25.1 us per level.
-    const int tiles2 = (a.n1 + fused2_tile_width(inverse, Lp, ew2) - 1) / fused2_tile_width(inverse, Lp, ew2);
-    const bool deep = inverse && Lp <= 12 && (sizeof(T) == 4 || Lp <= 8) && ew2 == 1 && dil == 1 && vec4 && p->variant_inv != 1 && n2 >= 64 &&
-                      ((long long)tiles2 * ((n2 + 69) / 70) <= 1280 || p->variant_inv >= 2);
-    const int pdepth = (p->variant_inv == 2 || p->variant_inv == 6) ? 2 : 4;
-    const int waves = (deep && p->variant_inv != 2 && p->variant_inv != 4) ? 1024 : 2048;
-    fused2_geometry(a, fused2_tile_width(inverse, Lp, ew2), Lp, p->target_blocks > 0 ? p->target_blocks * 2 : waves, p->force_zchunk);
+    const Fused2Query q = {sizeof(T) == 8, inverse, vec4, Lp, dil > 1 ? dil : (int)p->comp, dil, a.n1, (int)n2, p->variant_inv};
+    const Fused2Pick k = fused2_select(q);
+    fused2_geometry(a, fused2_tile_width(inverse, Lp, q.ew), Lp, p->target_blocks > 0 ? p->target_blocks * 2 : k.waves, p->force_zchunk);
     if (dil > 1) a.rs = (int)(dil * p->dims[0]);   // 8 waves per CU: one round (measured optimum 1024^2 .. 4096^2)
     a.nt = nt_store_ok<T>(a.rs, a.rs, out_bstride, out, nout);
     const void* td = p->taps_dev[inverse ? 1 : 0];
     if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
     prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
-    int rc = -1;
-    if constexpr (sizeof(T) == 4) {
-        if (deep) rc = launch_inv2p_f32(a, Lp, pdepth, td, s, p->variant_inv != 7);
-    } else {
-        if (deep) rc = launch_inv2p_f64(a, Lp, td, s);
-    }
-    if (rc == -1) rc = launch2<T>(inverse, a, Lp, vec4, ew2, td, s);
+    int rc;
+    if (k.family != kInv2P) rc = launch2(inverse, a, Lp, vec4, q.ew, td, s);
+    else if constexpr (sizeof(T) == 4) rc = launch_inv2p_f32(a, Lp, k.pdepth, td, s, k.packed);
+    else rc = launch_inv2p_f64(a, Lp, td, s);
     prof_end(p, s, rc);
     if (rc == -1) return fail(NDWT_ERR_UNSUPPORTED, "no fused 2-D kernel instantiated for tap length %d", Lp);
     if (rc != 0) return fail(NDWT_ERR_HIP, "fused 2-D kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -685,7 +503,7 @@ static int fused2_run(const ndwt_plan* p, bool inverse, int Lp, const T* const* 
 // Plans the fused kernels do not take (or whose z filter is not the longest: the kernel marches exactly Lp - 1 halo planes) run the
 // per-axis passes, the slab treatment on z.
 static bool zslab_fused(const ndwt_plan* p, long long stride, int* Lp, int dir) {
-    return fused3_eligible(p, stride, Lp, dir) && p->filt[2].len == *Lp;
+    return fused3_eligible(sel(p), stride, Lp, dir) && p->filt[2].len == *Lp;
 }
 
 template <typename T> static int generic_level(ndwt_plan* p, bool synthesis, const T* const* in, T* const* out, long long stride, hipStream_t s);
@@ -770,12 +588,13 @@ static int analysis_level(ndwt_plan* p, const T* in, T* const* out, long long st
     const long long n_top_in = slab ? n_top + (long long)(ftop.len - 1) * stride : n_top;
     const long long vol_in = p->vol / n_top * n_top_in;
     int Lp = 0;
-    if (!slab && fused3_dilated_eligible(p, stride, &Lp)) {
+    const SelPlan sp = sel(p);
+    if (!slab && fused3_dilated_eligible(sp, stride, &Lp)) {
         const T* ins[8] = {in};
         return fused3_run<T>(p, false, Lp, ins, out, p->dims[2], 1, 0, 0, 1, s, 0, LLONG_MIN, 0, 0, (int)stride);
     }
     // slab mode hands over exactly (L_top-1) halo planes: the fused kernel marches with the padded length
-    if (fused3_eligible(p, stride, &Lp, 0) && !(slab && d == 3 && ftop.len != Lp)) {
+    if (fused3_eligible(sp, stride, &Lp, 0) && !(slab && d == 3 && ftop.len != Lp)) {
         const long long vol3 = p->comp * p->dims[0] * p->dims[1] * p->dims[2];
         if (d == 3) {
             const T* ins[8] = {in};
@@ -788,7 +607,7 @@ static int analysis_level(ndwt_plan* p, const T* in, T* const* out, long long st
         // and plane (against 1) go through the same per-CU vector-memory pipe as the 4 stores, and that pipe is what bounds the kernel
         // (68.6 ms per dec+rec step against 53.5 ms).
         if constexpr (sizeof(T) == 4) {
-            bool ok = p->variant_fwd == 7 && !slab && stride == 1 && p->complexity == NDWT_REAL && Lp <= 8 && ftop.len <= Lp && p->dims[0] % 4 == 0 &&
+            bool ok = p->variant_fwd == kFwdFoldT && !slab && stride == 1 && p->complexity == NDWT_REAL && Lp <= 8 && ftop.len <= Lp && p->dims[0] % 4 == 0 &&
                       vol3 % 4 == 0 && p->dims[3] >= 2 && aligned_vec4<T>(in);
             for (int b = 0; ok && b < 16; ++b) ok = aligned_vec4<T>(out[b]);
             if (ok) {
@@ -815,11 +634,11 @@ static int analysis_level(ndwt_plan* p, const T* in, T* const* out, long long st
         if (rc) return rc;
         return fused3_run<T>(p, false, Lp, ins_hi, out + 8, p->dims[2], p->dims[3], vol3, vol3, 1, s);
     }
-    if (!slab && fused2_dilated_eligible(p, stride, &Lp)) {
+    if (!slab && fused2_dilated_eligible(sp, stride, &Lp)) {
         const T* ins[4] = {in};
         return fused2_run<T>(p, false, Lp, ins, out, p->dims[1], 0, 0, true, s, (int)stride);
     }
-    if (fused2_eligible(p, stride, &Lp) && !(slab && ftop.len != Lp)) {
+    if (fused2_eligible(sp, stride, &Lp) && !(slab && ftop.len != Lp)) {
         const T* ins[4] = {in};
         return fused2_run<T>(p, false, Lp, ins, out, p->dims[1], vol_in, p->vol, !slab, s);
     }
@@ -845,11 +664,12 @@ static int synthesis_level(ndwt_plan* p, const T* const* in, T* out, long long s
     const long long n_top_in = slab ? n_top + (long long)(ftop.len - 1) * stride : n_top;
     const long long vol_in = p->vol / n_top * n_top_in;
     int Lp = 0;
-    if (!slab && fused3_dilated_eligible(p, stride, &Lp)) {
+    const SelPlan sp = sel(p);
+    if (!slab && fused3_dilated_eligible(sp, stride, &Lp)) {
         T* outs[8] = {out};
         return fused3_run<T>(p, true, Lp, in, outs, p->dims[2], 1, 0, 0, 1, s, 0, LLONG_MIN, 0, 0, (int)stride);
     }
-    if (fused3_eligible(p, stride, &Lp, 1) && !(slab && d == 3 && ftop.len != Lp)) {
+    if (fused3_eligible(sp, stride, &Lp, 1) && !(slab && d == 3 && ftop.len != Lp)) {
         const long long vol3 = p->comp * p->dims[0] * p->dims[1] * p->dims[2];
         if (d == 3) {
             T* outs[8] = {out};
@@ -868,11 +688,11 @@ static int synthesis_level(ndwt_plan* p, const T* const* in, T* out, long long s
         if (rc) return rc;
         return axis_pass<T>(p, true, 3, p->dims, stride, !slab, a, dd, out, nullptr, s);
     }
-    if (!slab && fused2_dilated_eligible(p, stride, &Lp)) {
+    if (!slab && fused2_dilated_eligible(sp, stride, &Lp)) {
         T* outs[4] = {out};
         return fused2_run<T>(p, true, Lp, in, outs, p->dims[1], 0, 0, true, s, (int)stride);
     }
-    if (fused2_eligible(p, stride, &Lp) && !(slab && ftop.len != Lp)) {
+    if (fused2_eligible(sp, stride, &Lp) && !(slab && ftop.len != Lp)) {
         T* outs[4] = {out};
         return fused2_run<T>(p, true, Lp, in, outs, p->dims[1], vol_in, p->vol, !slab, s);
     }
@@ -907,94 +727,68 @@ static int synthesis_level(ndwt_plan* p, const T* const* in, T* out, long long s
 // 2^d-1 detail bands at [1 + (2^d-1)(level-lev), ...); the coarsest approximation is band 0.  Unlike
 // the reference there is no cat() copy (nd_dwt_3D.m:184) and no in-place overwrite of the input.
 // bs: distance between consecutive bands of y in scalars (p->vol = the packed reference layout; larger = pitched)
-// ---- two or three analysis levels of an image in one launch (Fwd2C, ndwt_device.h): float real data at tap stride 1, rows of whole
-// groups of 4 scalars, up to 8 taps or 12.  variant_fwd 9 keeps one launch per level (A/B); force_zchunk = rows per wave.
-static bool cascade2_eligible(const ndwt_plan* p, int* Lp_out) {
-    int Lp = 0;
-    if (p->dtype != NDWT_F32 || p->complexity != NDWT_REAL || p->dilation != NDWT_DILATION_REFERENCE || p->variant_fwd == 9) return false;
-    if (!fused2_eligible(p, 1, &Lp) || (Lp > 8 && Lp != 12) || p->dims[0] % 4 != 0) return false;
-    if (p->dims[0] * p->dims[1] >= (1LL << 31)) return false;   // the kernel's row * row-stride products are formed in 64 bits, offsets in int
-    *Lp_out = Lp;
-    return true;
-}
-
-static int cascade2_run(ndwt_plan* p, int Lp, int nlev, const float* in, float* const* out, hipStream_t s) {
-    Fused2CArgs<float> a;
-    memset(&a, 0, sizeof a);
-    a.in = in;
-    a.n1 = (int)p->dims[0];
-    a.n2 = (int)p->dims[1];
-    a.rs = a.n1;
-    bool aligned = aligned_vec4<float>(in);
-    for (int b = 0; b < 1 + 3 * nlev; ++b) { a.out[b] = out[b]; aligned = aligned && aligned_vec4<float>(out[b]); }
-    if (!aligned) return -1;
-    const int WX = fwd2c_tile_width(Lp, nlev);
+// ---- two or three levels of an image in one launch (Fwd2C / Inv2C, ndwt_device.h; when: cascade2_levels).  Shared by both directions:
+// the tiling (one round of `per_cu` waves per CU -- analysis 8, synthesis 4: DESIGN.md 4 -- in equal chunks of at least nlev (Lp - 1) rows:
+// the march-in is at most half of a wave's steps; force_zchunk = rows per wave), profiling, the launch and its error mapping.
+// Returns 0, or -1: no instance (the caller takes one launch per level)
+template <class Args, class Launch> static int cascade2_launch(ndwt_plan* p, Args& a, bool inverse, int WX, int min_chunk, int per_cu, hipStream_t s, Launch&& launch) {
     a.ntx = (a.n1 + WX - 1) / WX;
-    // rows per wave: a wave reads nlev (Lp - 1) rows before its chunk produces anything, so chunks are longer than those of the
-    // one-level kernel; one round of `waves` waves (2 per SIMD at the 256-register budget)
-    // (db4, 3 levels, us per dec, one launch per level -> cascaded with 1024 / 2048 / 3584 waves: 4096^2 267 -> 206 / 179 / 190,
-    // 8192^2 1062 -> 692 / 586 / 636; 2048^2 52 -> 52, 1024^2 25 -> 45: the cascade serves images beyond 2048^2, tools/bench2d_cascade.py)
-    const int waves = p->target_blocks > 0 ? p->target_blocks : p->num_cus * 8;
-    int chunks = waves / a.ntx;
-    if (chunks < 1) chunks = 1;
+    const int waves = p->target_blocks > 0 ? p->target_blocks : p->num_cus * per_cu;
+    const int chunks = waves / a.ntx > 1 ? waves / a.ntx : 1;
     int yc = (a.n2 + chunks - 1) / chunks;
-    const int min_chunk = nlev * (Lp - 1);                // the march-in is at most half of a wave's steps
     if (yc < min_chunk) yc = min_chunk;
     if (p->force_zchunk > 0) yc = p->force_zchunk;
     if (yc > a.n2) yc = a.n2;
     a.nyc = (a.n2 + yc - 1) / yc;
     a.ychunk = (a.n2 + a.nyc - 1) / a.nyc;
     a.nyc = (a.n2 + a.ychunk - 1) / a.ychunk;
-    a.nt = nt_store_ok<float>(a.rs, a.rs, 0, out, 1 + 3 * nlev);
-    a.mode = p->variant_fwd == 10 ? 1 : 0;
-    const void* td = p->taps_dev[0];
+    const void* td = p->taps_dev[inverse ? 1 : 0];
     if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
-    prof_begin(p, NDWT_KERNEL_FUSED_ANALYSIS, s);
-    const int rc = launch_fwd2c_f32(a, Lp, nlev, td, s);
+    prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
+    const int rc = launch(td);
     prof_end(p, s, rc);
     if (rc == -2) return fail(NDWT_ERR_UNSUPPORTED, "internal: launch geometry does not match the cascaded 2-D kernel's tile");
-    if (rc > 0) return fail(NDWT_ERR_HIP, "cascaded 2-D analysis launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return rc;                                            // 0, or -1: no instance / unaligned (the caller takes one launch per level)
+    if (rc > 0) return fail(NDWT_ERR_HIP, "cascaded 2-D %s launch failed: %s", inverse ? "synthesis" : "analysis", hipGetErrorString((hipError_t)rc));
+    return rc;
+}
+static int cascade2_run(ndwt_plan* p, int Lp, int nlev, const float* in, float* const* out, hipStream_t s) {
+    Fused2CArgs<float> a;
+    memset(&a, 0, sizeof a);
+    a.in = in;
+    a.n1 = a.rs = (int)p->dims[0];
+    a.n2 = (int)p->dims[1];
+    bool aligned = aligned_vec4<float>(in);
+    for (int b = 0; b < 1 + 3 * nlev; ++b) { a.out[b] = out[b]; aligned = aligned && aligned_vec4<float>(out[b]); }
+    if (!aligned) return -1;                              // not this data: one launch per level
+    a.nt = nt_store_ok<float>(a.rs, a.rs, 0, out, 1 + 3 * nlev);
+    a.mode = p->variant_fwd == kFwdCascadeMode1 ? 1 : 0;
+    return cascade2_launch(p, a, false, fwd2c_tile_width(Lp, nlev), nlev * (Lp - 1), 8, s, [&](const void* td) { return launch_fwd2c_f32(a, Lp, nlev, td, s); });
 }
 
 template <typename T> static int dec_impl(ndwt_plan* p, const T* x, T* y, long long bs, int level, hipStream_t s) {
     const int nb = 1 << p->ndim;
     const T* cur = x;
-    if constexpr (sizeof(T) == 4) {
+    int lev = 1, pp = 0;                                  // pp: the scratch volume the next launch writes (they alternate launch by launch: a
+    if constexpr (sizeof(T) == 4) {                       // launch never writes the approximation it reads)
+        const SelPlan sp = sel(p);
         int Lp = 0;
-        // images beyond 2048^2 (below, the rows a wave reads before its chunk produces anything outweigh the volumes saved), or on request
-        // (variant_fwd 11: tests and A/B runs on small images)
-        if (level >= 2 && p->ndim == 2 && cascade2_eligible(p, &Lp) && p->dims[1] >= 3 * (Lp - 1) &&
-            (p->vol > (6LL << 20) || p->variant_fwd == 11 || p->variant_fwd == 10)) {
-            int lev = 1, pp = 0;                          // pp: the scratch volume the next launch writes (they alternate launch by launch: a
-            while (level - lev + 1 >= 2) {                // launch never writes the approximation it reads); levels lev .. lev + n - 1 in one launch
-                const int n = (level - lev + 1 >= 3 && Lp <= 8) ? 3 : 2;   // (12 taps: two levels fit the 256 registers, three do not)
-                const int last = lev + n - 1;
-                float* out[10];
-                out[0] = (last == level) ? y : (float*)p->approx[pp];
-                for (int l = 0; l < n; ++l)               // cascade level l (0 = first) is transform level lev + l
-                    for (int b = 1; b < nb; ++b) out[1 + 3 * (n - 1 - l) + (b - 1)] = y + (long long)(1 + (nb - 1) * (level - (lev + l)) + (b - 1)) * bs;
-                const int rc = cascade2_run(p, Lp, n, cur, out, s);
-                if (rc == -1) break;                      // not this data (alignment): one launch per level from here on
-                if (rc) return rc;
-                cur = out[0];
-                pp ^= 1;
-                lev = last + 1;
-            }
-            for (; lev <= level; ++lev, pp ^= 1) {
-                T* out[16];
-                out[0] = (lev == level) ? y : (T*)p->approx[pp];
-                for (int b = 1; b < nb; ++b) out[b] = y + (long long)(1 + (nb - 1) * (level - lev) + (b - 1)) * bs;
-                int rc = analysis_level<T>(p, cur, out, level_stride(p, lev), false, s);
-                if (rc) return rc;
-                cur = out[0];
-            }
-            return NDWT_OK;
+        while (const int n = cascade2_levels(sp, false, level - lev + 1, &Lp)) {   // levels lev .. lev + n - 1 in one launch
+            const int last = lev + n - 1;
+            float* out[10];
+            out[0] = (last == level) ? y : (float*)p->approx[pp];
+            for (int l = 0; l < n; ++l)                   // cascade level l (0 = first) is transform level lev + l
+                for (int b = 1; b < nb; ++b) out[1 + 3 * (n - 1 - l) + (b - 1)] = y + (long long)(1 + (nb - 1) * (level - (lev + l)) + (b - 1)) * bs;
+            const int rc = cascade2_run(p, Lp, n, cur, out, s);
+            if (rc == -1) break;                          // not this data (alignment): one launch per level from here on
+            if (rc) return rc;
+            cur = out[0];
+            pp ^= 1;
+            lev = last + 1;
         }
     }
-    for (int lev = 1; lev <= level; ++lev) {
+    for (; lev <= level; ++lev, pp ^= 1) {
         T* out[16];
-        out[0] = (lev == level) ? y : (T*)p->approx[(lev - 1) & 1];
+        out[0] = (lev == level) ? y : (T*)p->approx[pp];
         for (int b = 1; b < nb; ++b) out[b] = y + (long long)(1 + (nb - 1) * (level - lev) + (b - 1)) * bs;
         int rc = analysis_level<T>(p, cur, out, level_stride(p, lev), false, s);
         if (rc) return rc;
@@ -1008,27 +802,11 @@ static int cascade2_rec_run(ndwt_plan* p, int Lp, int nlev, const float* const* 
     Fused2CIArgs<float> a;
     memset(&a, 0, sizeof a);
     a.out = out;
-    a.n1 = (int)p->dims[0];
+    a.n1 = a.rs = (int)p->dims[0];
     a.n2 = (int)p->dims[1];
-    a.rs = a.n1;
     bool aligned = aligned_vec4<float>(out);
     for (int b = 0; b < 1 + 3 * nlev; ++b) { a.in[b] = in[b]; aligned = aligned && aligned_vec4<float>(in[b]); }
     if (!aligned) return -1;
-    const int WX = inv2c_tile_width(Lp, nlev);
-    a.ntx = (a.n1 + WX - 1) / WX;
-    // one wave per SIMD (db4, 3 levels, us per rec with 512 / 768 / 1024 / 1280 / 2048 waves: 4096^2 278 / 206 / 180 / 193 / 223 against 231
-    // for one launch per level, 8192^2 1003 / 708 / 607 / 637 / 707 against 936; two rows of band loads in flight per level: 177 / 608)
-    const int waves = p->target_blocks > 0 ? p->target_blocks : p->num_cus * 4;
-    int chunks = waves / a.ntx;
-    if (chunks < 1) chunks = 1;
-    int yc = (a.n2 + chunks - 1) / chunks;
-    const int min_chunk = nlev * (Lp - 1);
-    if (yc < min_chunk) yc = min_chunk;
-    if (p->force_zchunk > 0) yc = p->force_zchunk;
-    if (yc > a.n2) yc = a.n2;
-    a.nyc = (a.n2 + yc - 1) / yc;
-    a.ychunk = (a.n2 + a.nyc - 1) / a.nyc;
-    a.nyc = (a.n2 + a.ychunk - 1) / a.ychunk;
     float* outs[1] = {out};
     a.nt = nt_store_ok<float>(a.rs, a.rs, 0, outs, 1);
     if (p->shrink_mode) {                                 // ndwt_denoise: threshold the detail bands as their rows are loaded
@@ -1036,58 +814,37 @@ static int cascade2_rec_run(ndwt_plan* p, int Lp, int nlev, const float* const* 
         a.shrink_thr = (float)p->shrink_thr;
         a.shrink_hard = p->shrink_mode == 2;
     }
-    const void* td = p->taps_dev[1];
-    if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
-    prof_begin(p, NDWT_KERNEL_FUSED_SYNTHESIS, s);
-    const int rc = launch_inv2c_f32(a, Lp, nlev, p->variant_inv == 12 ? 2 : 1, td, s);
-    prof_end(p, s, rc);
-    if (rc == -2) return fail(NDWT_ERR_UNSUPPORTED, "internal: launch geometry does not match the cascaded 2-D kernel's tile");
-    if (rc > 0) return fail(NDWT_ERR_HIP, "cascaded 2-D synthesis launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return rc;
+    const int depth = cascade2_rec_depth(p->variant_inv);
+    return cascade2_launch(p, a, true, inv2c_tile_width(Lp, nlev), nlev * (Lp - 1), 4, s, [&](const void* td) { return launch_inv2c_f32(a, Lp, nlev, depth, td, s); });
 }
 
 template <typename T> static int rec_impl(ndwt_plan* p, const T* y, long long bs, T* x, int level, hipStream_t s) {
     const int nb = 1 << p->ndim;
     const T* prev = y;   // band 0
+    int lev = level, pp = 0;                              // coarsest level still to be synthesised; pp: the scratch volume the next launch writes
     if constexpr (sizeof(T) == 4) {
+        const SelPlan sp = sel(p);
         int Lp = 0;
-        // (variant_inv 9: one launch per level; 11 / 12: cascade whatever the image size, one / two rows of band loads in flight)
-        if (level >= 2 && p->ndim == 2 && p->variant_inv != 9 && cascade2_eligible(p, &Lp) && Lp <= 8 &&
-            p->dims[1] >= 3 * (Lp - 1) && (p->vol > (6LL << 20) || p->variant_inv == 11 || p->variant_inv == 12)) {
-            int lev = level, pp = 0;                      // coarsest level still to be synthesised; pp: the scratch volume the next launch writes
-            while (lev >= 2) {
-                const int n = lev >= 3 ? 3 : 2;           // levels lev, lev - 1, .. lev - n + 1 in one launch
-                const float* in[10];
-                in[0] = prev;
-                for (int c = 0; c < n; ++c)               // cascade level c (0 = coarsest) is transform level lev - c
-                    for (int b = 1; b < nb; ++b) in[1 + 3 * c + (b - 1)] = y + (long long)(1 + (nb - 1) * (level - (lev - c)) + (b - 1)) * bs;
-                const int low = lev - n + 1;
-                float* dst = (low == 1) ? x : (float*)p->approx[pp];
-                const int rc = cascade2_rec_run(p, Lp, n, in, dst, s);
-                if (rc == -1) break;
-                if (rc) return rc;
-                prev = dst;
-                pp ^= 1;
-                lev = low - 1;
-            }
-            for (; lev >= 1; --lev, pp ^= 1) {
-                const T* in[16];
-                in[0] = prev;
-                for (int b = 1; b < nb; ++b) in[b] = y + (long long)(1 + (nb - 1) * (level - lev) + (b - 1)) * bs;
-                T* dst = (lev == 1) ? x : (T*)p->approx[pp];
-                int rc = synthesis_level<T>(p, in, dst, level_stride(p, lev), false, s);
-                if (rc) return rc;
-                prev = dst;
-            }
-            return NDWT_OK;
+        while (const int n = cascade2_levels(sp, true, lev, &Lp)) {   // levels lev, lev - 1, .. lev - n + 1 in one launch
+            const float* in[10];
+            in[0] = prev;
+            for (int c = 0; c < n; ++c)                   // cascade level c (0 = coarsest) is transform level lev - c
+                for (int b = 1; b < nb; ++b) in[1 + 3 * c + (b - 1)] = y + (long long)(1 + (nb - 1) * (level - (lev - c)) + (b - 1)) * bs;
+            const int low = lev - n + 1;
+            float* dst = (low == 1) ? x : (float*)p->approx[pp];
+            const int rc = cascade2_rec_run(p, Lp, n, in, dst, s);
+            if (rc == -1) break;
+            if (rc) return rc;
+            prev = dst;
+            pp ^= 1;
+            lev = low - 1;
         }
     }
-    for (int ind = 1; ind <= level; ++ind) {
-        const int lev = level - ind + 1;
+    for (; lev >= 1; --lev, pp ^= 1) {
         const T* in[16];
         in[0] = prev;
         for (int b = 1; b < nb; ++b) in[b] = y + (long long)(1 + (nb - 1) * (level - lev) + (b - 1)) * bs;
-        T* dst = (lev == 1) ? x : (T*)p->approx[(ind - 1) & 1];
+        T* dst = (lev == 1) ? x : (T*)p->approx[pp];
         int rc = synthesis_level<T>(p, in, dst, level_stride(p, lev), false, s);
         if (rc) return rc;
         prev = dst;
@@ -1101,27 +858,15 @@ static int check_level(const ndwt_plan* p, int level) {
         return fail(NDWT_ERR_INVALID_ARG, "level %d outside 1..max_level=%d of this plan", level, p->max_level);
     if (p->thin_slab)
         return fail(NDWT_ERR_FILTER_TOO_LONG, "this slab plan is thinner than its outer-axis filter: only the *_slab entry points apply");
-    if (p->dilation == NDWT_DILATION_ATROUS) {
-        for (int a = 0; a < p->ndim; ++a) {
-            long long span = (long long)(p->filt[a].len - 1) * (1LL << (level - 1)) + 1;
-            (void)span;   // spans longer than the axis wrap several times; the kernels handle it
-        }
-    }
     return NDWT_OK;
 }
 
 // fused 3-D slab forms that avoid haloed copies (multi-GPU fast path)
 static int slab_fast_ok(const ndwt_plan* p, int stride, int* Lp) {
     if (!p) return fail(NDWT_ERR_INVALID_ARG, "null plan");
-    if (p->ndim != 3 || !fused3_eligible(p, stride, Lp) || p->filt[2].len != *Lp)
+    if (p->ndim != 3 || !fused3_eligible(sel(p), stride, Lp) || p->filt[2].len != *Lp)
         return fail(NDWT_ERR_UNSUPPORTED, "split/extended slab entry points need a fused 3-D plan whose outer-axis filter is the longest");
     return NDWT_OK;
-}
-
-template <typename T>
-static int slab_split_impl(ndwt_plan* p, int Lp, const void* in, const void* hb, const void* ha, void* const* out, hipStream_t s) {
-    const T* ins[8] = {(const T*)in, (const T*)hb, (const T*)ha};
-    return fused3_run<T>(p, false, Lp, ins, (T* const*)out, p->dims[2], 1, p->vol, p->vol, 2, s);
 }
 
 template <typename T> static int slab_ext_impl(ndwt_plan* p, int Lp, const void* const* in, void* out, hipStream_t s) {
@@ -1488,6 +1233,7 @@ static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, lon
         }
         p->vol *= dims[a];
     }
+    p->uniform_yz = ndim >= 3 && p->order[1] == p->order[2];   // (the same wavelet: the same taps)
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
         delete p->prof;
@@ -1512,7 +1258,7 @@ static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, lon
         }
     }
     int Lp = 0;
-    if (fused3_eligible(p, 1, &Lp, 0) || fused2_eligible(p, 1, &Lp)) {   // (the analysis side admits the most tap lengths)
+    if (fused3_eligible(sel(p), 1, &Lp, 0) || fused2_eligible(sel(p), 1, &Lp)) {   // (the analysis side admits the most tap lengths)
         for (int inv = 0; inv < 2; ++inv) {
             FusedTapsD t = fused_taps(p, Lp, inv != 0);
             // synthesis table: Taps3Y = Taps3 followed by the x tap pairs (lo[0][k], lo[0][k-1]), k = 0..Lp, of the pair-packed kernel
@@ -1683,10 +1429,10 @@ int ndwt_plan_describe(const ndwt_plan* p, char* buf, int buflen) {
     if (!p || !buf || buflen < 1) return fail(NDWT_ERR_INVALID_ARG, "bad arguments");
     int Lp = 0;
     const char* s = "axis";
-    const bool f3a = fused3_eligible(p, 1, &Lp, 0), f3s = fused3_eligible(p, 1, &Lp, 1);
+    const bool f3a = fused3_eligible(sel(p), 1, &Lp, 0), f3s = fused3_eligible(sel(p), 1, &Lp, 1);
     if (f3a && f3s) s = p->ndim == 3 ? "fused3d" : "axis+fused3d";
     else if (f3a) s = p->ndim == 3 ? "fused3d analysis, axis synthesis" : "axis+fused3d analysis, axis synthesis";
-    else if (fused2_eligible(p, 1, &Lp)) s = "fused2d";
+    else if (fused2_eligible(sel(p), 1, &Lp)) s = "fused2d";
     snprintf(buf, (size_t)buflen, "%s", s);
     return NDWT_OK;
 }
@@ -1924,15 +1670,6 @@ int ndwt_coef_put_host(ndwt_plan* p, int level, const void* y_host, ndwt_coef** 
 int ndwt_dec_host(ndwt_plan* p, const void* x, void* y, int level) { return host_roundtrip(p, false, x, y, level); }
 int ndwt_rec_host(ndwt_plan* p, const void* y, void* x, int level) { return host_roundtrip(p, true, y, x, level); }
 
-// true when every synthesis level of this plan runs a kernel that can shrink its inputs on load (Inv3S / Inv2S)
-static bool fused_shrink_capable(const ndwt_plan* p) {
-    if (p->dilation != NDWT_DILATION_REFERENCE) return false;         // dilated levels take the per-axis kernels
-    int Lp = 0;
-    if (fused2_eligible(p, 1, &Lp)) return true;
-    if (!fused3_eligible(p, 1, &Lp)) return false;
-    return !(p->variant_inv == 3 && Lp == 8);                        // A/B variant 3 = the LDS synthesis kernel
-}
-
 // ---- consumers for iterative solvers (not in the reference: its users threshold in MATLAB) ----
 static int shrink_check(const ndwt_plan* p, int level, double thr, int mode) {
     int rc = check_level(p, level);
@@ -1966,7 +1703,7 @@ static bool den3_eligible(const ndwt_plan* p, int* Lp_out) {
     // measured, 512^3, 3 levels, ndwt_denoise with / without the fused level 1: db1 4.49 / 5.27 ms, db2 5.10 / 5.67, db3 5.72 / 6.09,
     // db4 6.30 / 6.13 -- with 8 taps the recomputation (2.3x the arithmetic of the synthesis kernel, 67 % VALU-busy) costs more than the
     // 13 volume transfers it removes, so 8 taps take the kernel only when asked to (ndwt_plan_set_fused_level1(plan, 2))
-    if (!fused3_eligible(p, 1, &Lp) || Lp > (p->fused_level1 >= 2 ? 8 : 6) || !inv3y_plan_ok(p, Lp)) return false;
+    if (!fused3_eligible(sel(p), 1, &Lp) || Lp > (p->fused_level1 >= 2 ? 8 : 6) || !inv3y_plan_ok(sel(p), Lp)) return false;
     for (int ax = 0; ax < 3; ++ax)
         if (p->filt[ax].len != Lp) return false;
     if (p->dims[0] % 4 != 0) return false;
@@ -2023,7 +1760,7 @@ static int den3_launch(ndwt_plan* p, int kind, int Lp, const float* x, const flo
         a.shrink_hard = p->shrink_mode == 2;
     }
     // one workgroup per CU (1024 threads); Den3's march starts 2 (L - 1) planes before its first output plane
-    const bool small_tile = kind == 0 && p->variant_fwd != 2 && a.n2 > 16;   // the band-0 analysis on 64 x 16 tiles, 3 workgroups per CU (0.36 vs 0.42 ms; variant 2: A/B)
+    const bool small_tile = kind == 0 && p->variant_fwd != kFwdTall && a.n2 > 16;   // the band-0 analysis on 64 x 16 tiles, 3 workgroups per CU (0.36 vs 0.42 ms; kFwdTall: A/B)
     if (small_tile) fused3_geometry(a, 64, 16, Lp, p->target_blocks > 0 ? p->target_blocks : p->num_cus * 3, p->force_zchunk);
     else fused3_geometry(a, 64, 32, kind == 1 ? 2 * Lp - 1 : Lp, p->target_blocks > 0 ? p->target_blocks : p->num_cus, p->force_zchunk);
     float* outs[1] = {out};
@@ -2098,7 +1835,7 @@ int ndwt_denoise(ndwt_plan* p, const void* x, void* out, int level, double thres
     if (rc) return rc;
     rc = ndwt_dec_pitched(p, x, p->coef, pitch, level, stream);
     if (rc) return rc;
-    if (fused_shrink_capable(p)) {
+    if (fused_shrink_capable(sel(p))) {
         // every level is reconstructed by a lane-shift kernel: the detail bands are thresholded in registers as that
         // kernel loads them, and the separate pass (a read and a write of every detail band) disappears
         p->shrink_mode = mode == NDWT_SHRINK_HARD ? 2 : 1;
@@ -2178,7 +1915,7 @@ int ndwt_rec_split_host(ndwt_plan* p, const void* y_re, const void* y_im, void* 
 int ndwt_plan_slab_fast(const ndwt_plan* p) {
     int Lp = 0;
     if (p && p->shard != p->ndim - 1) return zslab_fused(p, 1, &Lp, -1) ? 1 : 0;   // z-slab: the zero-extended synthesis exists
-    return p && p->ndim == 3 && fused3_eligible(p, 1, &Lp) && p->filt[2].len == Lp ? 1 : 0;
+    return p && p->ndim == 3 && fused3_eligible(sel(p), 1, &Lp) && p->filt[2].len == Lp ? 1 : 0;
 }
 
 int ndwt_slab_halo(const ndwt_plan* p, int stride, int64_t* ab, int64_t* aa, int64_t* sb, int64_t* sa) {
@@ -2222,8 +1959,8 @@ int ndwt_analysis_level_slab_split(ndwt_plan* p, const void* in_local, const voi
     if (!in_local || !out || (Lp > 2 && !halo_before) || !halo_after) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
     HIP_TRY(hipSetDevice(p->device));
     if (!halo_before) halo_before = halo_after;   // db1: no plane before the slab is needed
-    return p->dtype == NDWT_F32 ? slab_split_impl<float>(p, Lp, in_local, halo_before, halo_after, out, (hipStream_t)stream)
-                                : slab_split_impl<double>(p, Lp, in_local, halo_before, halo_after, out, (hipStream_t)stream);
+    return p->dtype == NDWT_F32 ? slab_analysis_part_impl<float>(p, Lp, in_local, halo_before, halo_after, out, p->dims[2], (hipStream_t)stream)
+                                : slab_analysis_part_impl<double>(p, Lp, in_local, halo_before, halo_after, out, p->dims[2], (hipStream_t)stream);
 }
 
 int ndwt_synthesis_level_slab_ext(ndwt_plan* p, const void* const* in_local, void* out_ext, int stride, void* stream) {
@@ -2237,7 +1974,7 @@ int ndwt_synthesis_level_slab_ext(ndwt_plan* p, const void* const* in_local, voi
                                     : slab_ext_z_impl<double>(p, Lp, in_local, out_ext, (hipStream_t)stream);
     }
     if (p && p->ndim == 4) {                             // t-sharded 4-D: 3-D part per frame, zero-extended t-axis pass
-        if (stride != 1 || !fused3_eligible(p, 1, &Lp))
+        if (stride != 1 || !fused3_eligible(sel(p), 1, &Lp))
             return fail(NDWT_ERR_UNSUPPORTED, "the zero-extended 4-D slab synthesis needs a plan on the fused 3-D kernels (stride 1)");
         if (!in_local || !out_ext) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
         HIP_TRY(hipSetDevice(p->device));

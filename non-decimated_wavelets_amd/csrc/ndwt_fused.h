@@ -15,9 +15,6 @@ struct FusedTapsD {       // per axis (0 = x, 1 = y, 2 = z), zero-padded to Lp, 
     double hi[3][kMaxTaps];
 };
 
-// tile shape a variant uses (for the launch geometry)
-void fused3_tile_shape(bool f64, bool inverse, int variant, int Lp, int* TX, int* TY, int ew);
-
 int launch_fwd3_f32(const Fused3Args<float>& a, const FusedTapsD& t, bool vec4, int variant, int ew, const void* taps_dev, hipStream_t s);
 int launch_inv3_f32(const Fused3Args<float>& a, const FusedTapsD& t, bool vec4, int variant, int ew, const void* taps_dev, hipStream_t s);
 int launch_fwd3_pin_f32(const Fused3Args<float>& a, int Lp, const void* taps_dev, hipStream_t s);   // 10 / 12 / 14 taps, tall tile, taps pinned in SGPRs (vec4 data)
@@ -44,7 +41,6 @@ int launch_long3_f32(bool inverse, const Fused3Args<float>& a, const FusedTapsD&
 int launch_long3_f64(bool inverse, const Fused3Args<double>& a, const FusedTapsD& t, bool vec4, const void* taps_dev, hipStream_t s);   // 14 / 16 taps
 
 // fused 2-D kernels (register-only, one wave per tile)
-int fused2_tile_width(bool inverse, int Lp, int ew);
 int launch_fwd2_f32(const Fused2Args<float>& a, int Lp, bool vec4, int ew, const void* taps_dev, hipStream_t s);
 int launch_inv2_f32(const Fused2Args<float>& a, int Lp, bool vec4, int ew, const void* taps_dev, hipStream_t s);
 int launch_inv2p_f32(const Fused2Args<float>& a, int Lp, int depth, const void* taps_dev, hipStream_t s, int packed = 0);

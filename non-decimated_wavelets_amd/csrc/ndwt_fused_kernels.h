@@ -78,15 +78,8 @@ template <class K> int launch_fused2(const typename K::Args& a, const void* taps
         default: return -1;           \
     }
 
-// dispatch on variant, padded tap length and vector path
-#define NDWT_FUSED_K(KIND, INV, T, LL, V, VEC)                                                               \
-    KIND<T, LL, Fused3Tile<T, INV, V>::TX, Fused3Tile<T, INV, V>::TY, Fused3Tile<T, INV, V>::NT,             \
-         Fused3Tile<T, INV, V>::RY, VEC, Fused3Tile<T, INV, V>::WPE>
-// interleaved complex (2 scalars per x element)
-#define NDWT_FUSED_KC(KIND, INV, T, LL, V, VEC)                                                              \
-    KIND<T, LL, Fused3Tile<T, INV, V>::TX, Fused3Tile<T, INV, V>::TY, Fused3Tile<T, INV, V>::NT,             \
-         Fused3Tile<T, INV, V>::RY, VEC, Fused3Tile<T, INV, V>::WPE, 2>
-// x taps stepping over EWV interleaved scalars (EWV = 4: a level dilated by 4)
+// dispatch on tile index V (ndwt_select.h: Fused3Pick::V), padded tap length and vector path; EWV = scalars the x taps step over
+// (1: real data, 2: interleaved complex or a level dilated by 2, 4: a level dilated by 4)
 #define NDWT_FUSED_KE(KIND, INV, T, LL, V, VEC, EWV)                                                         \
     KIND<T, LL, Fused3Tile<T, INV, V>::TX, Fused3Tile<T, INV, V>::TY, Fused3Tile<T, INV, V>::NT,             \
          Fused3Tile<T, INV, V>::RY, VEC, Fused3Tile<T, INV, V>::WPE, EWV>
@@ -94,15 +87,8 @@ template <class K> int launch_fused2(const typename K::Args& a, const void* taps
     case LL:                                                                                                 \
         return vec4 ? launch_fused3<NDWT_FUSED_KE(KIND, INV, T, LL, V, true, EWV)>(a, t, taps_dev, s)        \
                     : launch_fused3<NDWT_FUSED_KE(KIND, INV, T, LL, V, false, EWV)>(a, t, taps_dev, s);
-#define NDWT_FUSED_CASE_C(KIND, INV, T, LL, V)                                                                \
-    case LL:                                                                                                 \
-        return vec4 ? launch_fused3<NDWT_FUSED_KC(KIND, INV, T, LL, V, true)>(a, t, taps_dev, s)             \
-                    : launch_fused3<NDWT_FUSED_KC(KIND, INV, T, LL, V, false)>(a, t, taps_dev, s);
-
-#define NDWT_FUSED_CASE(KIND, INV, T, LL, V)                                                                  \
-    case LL:                                                                                                 \
-        return vec4 ? launch_fused3<NDWT_FUSED_K(KIND, INV, T, LL, V, true)>(a, t, taps_dev, s)                        \
-                    : launch_fused3<NDWT_FUSED_K(KIND, INV, T, LL, V, false)>(a, t, taps_dev, s);
+#define NDWT_FUSED_CASE_C(KIND, INV, T, LL, V) NDWT_FUSED_CASE_E(KIND, INV, T, LL, V, 2)
+#define NDWT_FUSED_CASE(KIND, INV, T, LL, V) NDWT_FUSED_CASE_E(KIND, INV, T, LL, V, 1)
 
 // float synthesis other than the pair-packed kernel (ndwt_fused3_f32_invy*.hip, the default wherever it applies): the lane-shift
 // kernel Inv3S on a tall 64x32 tile (1024 threads, one workgroup per CU; db6: 512 threads with two items each -- the 1024-thread

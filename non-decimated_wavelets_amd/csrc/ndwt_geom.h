@@ -3,6 +3,7 @@
 #include <cstdint>
 
 #include "ndwt_device.h"
+#include "ndwt_select.h"
 
 namespace ndwt {
 
@@ -49,11 +50,6 @@ inline void fused3_geometry(Fused3Args<T>& a, int TX, int TY, int Lp, int target
     if (force_zchunk <= 0) zc = (a.n3 + a.nzc - 1) / a.nzc;      // equal chunks: the slowest workgroup sets the time
     a.zchunk = zc;
     a.nzc = (a.n3 + zc - 1) / zc;
-}
-
-// the fused kernels keep intra-plane offsets in 32-bit ints
-inline bool fused3_fits(long long n1, long long n2, long long n3, long long nbatch) {
-    return n1 * n2 < (1LL << 31) && n3 < (1LL << 30) && nbatch < (1LL << 20) && n1 >= 1 && n2 >= 1 && n3 >= 1;
 }
 
 // fused 2-D kernels: one wave (64 lanes x 4 columns, minus halo groups) marches `ychunk` rows

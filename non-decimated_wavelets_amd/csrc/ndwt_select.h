@@ -1,0 +1,276 @@
+// ndwt_select.h -- which kernel a level runs: plain host C++ on integers (no HIP header; any host compiler takes it).
+// ndwt_api.hip fills the queries from the plan and the launch's pointers, asks here, and launches what the pick names.
+#pragma once
+#include "ndwt_fused_tile.h"
+
+namespace ndwt {
+
+// ---- the A/B variants of ndwt_plan_set_variant (tools/: interleaved A/B runs).  The C ABI, api.py, tools/ and the tests pass the numbers;
+// every variant computes the same values.  A number that a column does not name selects that column's default.
+//  fwd | 3-D analysis (fused3_select)                                        | 2-D
+//   0  | default: tall tile for 6 / 8 taps on volumes that fill the chip, pinned taps for 10 .. 14
+//   1  | 64x16 tile, 512 threads, one column per thread (float 10 .. 16 taps, double 6 / 8)
+//   2  | float: the tall 64x32 tile whatever the volume; ndwt_denoise: its band-0 analysis on the tall tile
+//   3  | keeps the small tile (float 64x16, double 64x8); 16 / 20 taps: the spilling forms without window slots in LDS
+//   6  | float: tall tile with y items of 2 rows (8 .. 12 taps)
+//   7  | 4-D: the t axis folded into the fused launches (Fwd3 TPRE)
+//   8  | as 0 without the pinned taps
+//   9  |                                                                     | no cascade (analysis AND synthesis): one launch per level
+//  10  |                                                                     | cascade whatever the image size, kernel mode 1 (no take-in-only steps)
+//  11  |                                                                     | cascade whatever the image size
+//  inv | 3-D synthesis (fused3_select)                                       | 2-D (fused2_select)                | 2-D cascade (cascade2_levels)
+//   0  | default: Inv3Y (gather <= 8 taps, scatter from 10), else Inv3S      | Inv2P depth 4 packed, 1024 waves, where the image fits one round
+//   1  |                                                                     | keeps Inv2S
+//   2  | dilated levels keep Inv3S                                           | Inv2P depth 2 on Inv2S's geometry  |
+//   3  | the LDS kernel Inv3 (8 taps); otherwise Inv3S                       | (>= 2: Inv2P whatever the size)    |
+//   4  | Inv3S, the lane-shift kernel                                        | Inv2P depth 4 on Inv2S's geometry  |
+//   5  | Inv3Y with one register set of band loads (depth 1)                 |                                    |
+//   6  |                                                                     | Inv2P depth 2, 1024 waves          |
+//   7  |                                                                     | Inv2P with scalar FMAs (unpacked)  |
+//   9  | Inv3Y gather form without the shared y / z tap pairs                |                                    | off
+//  10  | Inv3Y scatter form wherever it exists (8 taps; EW 4: 4 / 6 too)     |                                    |
+//  11  | Inv3Y gather form for every tap length                              |                                    | whatever the image size
+//  12  |                                                                     |                                    | ... with two rows of band loads in flight
+// (tests/emu/ndwt_emu.cpp takes a `variant` of its own -- 5 / 8 / 10 pick the emulated kernel form; that numbering is local to the emulator.)
+enum FwdVariant { kFwdDefault = 0, kFwdOneColumn = 1, kFwdTall = 2, kFwdSmallTile = 3, kFwdTallRY2 = 6, kFwdFoldT = 7, kFwdNoPin = 8,
+                  kFwdNoCascade = 9, kFwdCascadeMode1 = 10, kFwdCascadeAlways = 11 };
+enum InvVariant { kInvDefault = 0, kInvDilatedKeep3S = 2, kInvLds = 3, kInvLaneShift = 4, kInvDepth1 = 5, kInvNoUniYZ = 9, kInvScatter = 10, kInvGather = 11,   // 3-D
+                  kInv2Keep2S = 1, kInv2Depth2Geom = 2, kInv2Depth4Geom = 4, kInv2Depth2Round = 6, kInv2Unpacked = 7,                                        // 2-D
+                  kInvCascadeOff = 9, kInvCascadeAlways = 11, kInvCascadeDepth2 = 12 };                                                                       // 2-D cascade
+
+// ---- what the predicates need of a plan
+struct SelPlan {
+    int ndim, comp;                    // comp: scalars per element (2: interleaved complex)
+    bool f64, real, path_auto, atrous, fp64_fused;
+    long long dims[4];
+    int len[4];                        // tap length per axis
+    int variant_fwd, variant_inv;
+};
+
+inline int padded_len(const int* len) { int Lp = 2; for (int a = 0; a < 3; ++a) Lp = len[a] > Lp ? len[a] : Lp; return Lp; }
+// the zero padding (Lp - len) / 2 of every axis' taps is even: the kernels that derive the high-pass taps from the low-pass ones
+// (mirror + alternating signs) need it
+inline bool padding_even(const int* len, int Lp) {
+    for (int a = 0; a < 3; ++a)
+        if (((Lp - len[a]) / 2) % 2 != 0) return false;
+    return true;
+}
+// the fused kernels keep intra-plane offsets in 32-bit ints
+inline bool fused3_fits(long long n1, long long n2, long long n3, long long nbatch) {
+    return n1 * n2 < (1LL << 31) && n3 < (1LL << 30) && nbatch < (1LL << 20) && n1 >= 1 && n2 >= 1 && n3 >= 1;
+}
+
+// Float synthesis default: the pair-packed kernel Inv3Y.  It derives the high-pass taps from the low-pass ones and keeps plane offsets in
+// 32-bit BYTE counts (plane = scalars per undilated plane).  kInvLds / kInvLaneShift force the older kernels for A/B runs.
+inline bool inv3y_ok(bool f64, int comp, const int* len, int Lp, long long plane, int variant_inv) {
+    if (f64 || Lp > (comp == 1 ? 20 : 16) || variant_inv == kInvLds || variant_inv == kInvLaneShift) return false;
+    return padding_even(len, Lp) && plane < (1LL << 30);
+}
+inline bool inv3y_plan_ok(const SelPlan& p, int Lp) { return inv3y_ok(p.f64, p.comp, p.len, Lp, p.dims[0] * p.comp * p.dims[1], p.variant_inv); }
+
+// dir: 0 analysis, 1 synthesis, -1 both.  Instantiated tap lengths: 2..12 (db1..db6) for every data kind the checks below let
+// through; float real data also 14 .. 20 (db7 .. db10; 18- and 20-tap synthesis with the pair-packed kernel only), double real data 14 and 16.
+inline bool fused3_eligible(const SelPlan& p, long long stride, int* Lp_out, int dir = -1) {
+    if (!p.path_auto || stride != 1 || p.ndim < 3) return false;
+    if (p.f64 && !p.fp64_fused) return false;
+    const int Lp = padded_len(p.len);
+    const int lmax = !p.real ? (!p.f64 && dir == 0 ? 16 : 12) : (!p.f64 ? (dir == 0 ? 20 : 16) : 16);
+    // 18- and 20-tap synthesis exist as the pair-packed kernel only (uniform wavelets, or mixed ones with even padding on every axis)
+    if (Lp > lmax && !(dir == 1 && Lp <= 20 && inv3y_plan_ok(p, Lp))) return false;
+    if (p.f64 && Lp > 16) return false;   // double: up to db8 (64x8 tiles with 512 threads keep 10 .. 16 taps in 256 registers)
+    // interleaved complex: the fused kernels with the x taps stepping over (re, im) pairs, tap lengths <= 8 (float: <= 12); rows of an
+    // odd number of elements run the VEC4 = false instances (one access per lane wherever its 4 scalars are contiguous)
+    // (complex128: 10 taps both ways, 12 taps analysis only -- its synthesis spills 500+ registers on every tile)
+    // (complex64: 14 / 16 taps in the analysis, and in the synthesis through the pair-packed kernel -- the Lp > lmax clause above)
+    if (!p.real && Lp > (!p.f64 ? 16 : (dir == 0 ? 12 : 10))) return false;
+    if (!fused3_fits(p.dims[0] * p.comp, p.dims[1], p.dims[2] + 64, p.ndim == 4 ? p.dims[3] + 64 : 1)) return false;
+    *Lp_out = Lp;
+    return true;
+}
+
+// A dilated (a-trous) 3-D level whose axes all divide by the tap stride s is s^3 independent stride-1 problems on the
+// sub-lattices: the fused kernels take x with the taps stepping over s interleaved scalars (the EW parameter, as for
+// interleaved complex data) and the s^2 (y, z) sub-lattices as batch items with row / plane strides s*n1, s*n1*n2.
+inline bool fused3_dilated_eligible(const SelPlan& p, long long stride, int* Lp_out) {
+    if (!p.path_auto || p.ndim != 3 || !p.real) return false;
+    if (stride != 2 && !(stride == 4 && !p.f64)) return false;   // instantiated: EW = 2 (float, double), EW = 4 (float)
+    if (p.f64 && !p.fp64_fused) return false;
+    const int Lp = padded_len(p.len);
+    if (Lp > 8 || p.dims[0] % stride != 0 || p.dims[1] % stride != 0 || p.dims[2] % stride != 0 || p.dims[0] % 4 != 0) return false;
+    if (!fused3_fits(p.dims[0], p.dims[1], p.dims[2] + 64, stride * stride)) return false;
+    *Lp_out = Lp;
+    return true;
+}
+
+// the 2-D analogue: x through EW = stride, the `stride` row sub-lattices as batch items
+inline bool fused2_dilated_eligible(const SelPlan& p, long long stride, int* Lp_out) {
+    if (!p.path_auto || p.ndim != 2 || !p.real) return false;
+    if (stride != 2 && !(stride == 4 && !p.f64)) return false;
+    const int Lp = p.len[0] > p.len[1] ? p.len[0] : p.len[1];
+    if (Lp > 8 || p.dims[0] % stride != 0 || p.dims[1] % stride != 0 || p.dims[0] % 4 != 0) return false;
+    if (p.dims[0] >= (1LL << 30) || p.dims[1] >= (1LL << 30)) return false;
+    *Lp_out = Lp;
+    return true;
+}
+
+inline bool fused2_eligible(const SelPlan& p, long long stride, int* Lp_out) {
+    if (!p.path_auto || stride != 1 || p.ndim != 2) return false;
+    const int Lp = p.len[0] > p.len[1] ? p.len[0] : p.len[1];
+    // float real: up to db10, complex64 and double real: up to db8 (256-register budget), complex128: up to db4
+    if (Lp > (!p.f64 ? (p.real ? 20 : 16) : (p.real ? 16 : 8))) return false;
+    if (p.dims[0] >= (1LL << 30) || p.dims[1] >= (1LL << 30)) return false;
+    *Lp_out = Lp;
+    return true;
+}
+
+// true when every synthesis level of this plan runs a kernel that can shrink its inputs on load (Inv3S / Inv3Y / Inv2S / Inv2P)
+inline bool fused_shrink_capable(const SelPlan& p) {
+    if (p.atrous) return false;                                       // dilated levels take the per-axis kernels
+    int Lp = 0;
+    if (fused2_eligible(p, 1, &Lp)) return true;
+    return fused3_eligible(p, 1, &Lp) && !(p.variant_inv == kInvLds && Lp == 8);   // the LDS synthesis kernel does not
+}
+
+// ---- two or three levels of an image in one launch (Fwd2C / Inv2C): float real data at tap stride 1, rows of whole groups of 4
+// scalars, up to 8 taps (analysis: or 12, two levels -- three do not fit the 256 registers).  Images beyond 2048^2 (below, the rows a
+// wave reads before its chunk produces anything outweigh the volumes saved), or on request.  `left` = levels still to do; returns how
+// many the next launch takes (and the padded tap length), 0 = one launch per level.
+inline int cascade2_levels(const SelPlan& p, bool inverse, int left, int* Lp_out) {
+    int& Lp = *Lp_out;
+    if (left < 2 || p.f64 || !p.real || p.atrous || p.variant_fwd == kFwdNoCascade || !fused2_eligible(p, 1, &Lp)) return 0;
+    if ((Lp > 8 && (Lp != 12 || inverse)) || p.dims[0] % 4 != 0 || p.dims[1] < 3 * (Lp - 1)) return 0;
+    if (p.dims[0] * p.dims[1] >= (1LL << 31)) return 0;   // the kernel's row * row-stride products are formed in 64 bits, offsets in int
+    const bool big = p.dims[0] * p.dims[1] > (6LL << 20);
+    if (inverse ? (p.variant_inv == kInvCascadeOff || !(big || p.variant_inv == kInvCascadeAlways || p.variant_inv == kInvCascadeDepth2))
+                : !(big || p.variant_fwd == kFwdCascadeAlways || p.variant_fwd == kFwdCascadeMode1)) return 0;
+    return (left >= 3 && Lp <= 8) ? 3 : 2;
+}
+constexpr int cascade2_rec_depth(int variant_inv) { return variant_inv == kInvCascadeDepth2 ? 2 : 1; }   // Inv2C: rows of band loads in flight per level
+
+// ---- one fused 3-D launch
+struct Fused3Query {
+    bool f64, inverse, vec4, uniform_yz, tfold;   // vec4: rows, strides and pointers in whole groups of 4 scalars; tfold: 4-D analysis with the t axis folded in
+    int Lp, len[3];                    // padded tap length; the three axes' own
+    int ew, dil;                       // scalars per x element (2: interleaved complex or a level dilated by 2, 4: dilated by 4); tap stride
+    int n1, n2, nbatch;                // scalars along x, rows and batch items of the launch (one sub-lattice of a dilated level)
+    int variant_fwd, variant_inv, num_cus, target_blocks;
+};
+enum Fused3Family { kFwd3, kFwd3Pin, kFwd3FoldT, kLong3, kInv3Y, kInv3S, kInv3, kNoFused3 };   // kLong3: Fwd3 / Inv3S of 14 .. 20 taps; kInv3Y: by ew and scatter
+struct Fused3Pick {
+    Fused3Family family;
+    int V;                             // index into Fused3Tile (the launchers' tile argument); unused by the Inv3Y families
+    int TX, TY, depth, scatter, uniyz; // depth / scatter / uniyz: the Inv3Y instance (register sets of band loads, x stage, shared y / z tap pairs)
+    int per_cu, target;                // workgroups per CU the grid is sized for; target workgroups of fused3_geometry
+    int long_ab;                       // kLong3 analysis: kFwdOneColumn / kFwdSmallTile as asked for, else 0
+};
+
+// the tile a pick runs on: read from the table the kernels are compiled from
+struct TileXY { int TX, TY; };
+template <typename T, bool INV, int V> constexpr TileXY tile_of() { return {Fused3Tile<T, INV, V>::TX, Fused3Tile<T, INV, V>::TY}; }
+template <typename T, int V> constexpr TileXY tile_of(bool inverse) { return inverse ? tile_of<T, true, V>() : tile_of<T, false, V>(); }
+constexpr TileXY fused3_tile_shape(Fused3Family fam, bool f64, bool inverse, int V, int Lp, int ew) {
+    if (fam == kInv3Y) return {inv3y_tx(Lp, ew), inv3y_ty(Lp, ew)};
+    if (f64) return V == 0 ? tile_of<double, 0>(inverse) : V == 1 ? tile_of<double, 1>(inverse) : V == 3 ? tile_of<double, 3>(inverse)
+                  : V == 5 ? tile_of<double, 5>(inverse) : TileXY{0, 0};
+    if (V == 4 || V == 6) return (V == 4) != inverse ? TileXY{0, 0} : inverse ? tile_of<float, true, 4>() : tile_of<float, false, 6>();
+    return V == 0 ? tile_of<float, 0>(inverse) : V == 1 ? tile_of<float, 1>(inverse) : V == 2 ? tile_of<float, 2>(inverse)
+         : V == 3 ? tile_of<float, 3>(inverse) : TileXY{0, 0};   // no such tile: the launcher's geometry check answers -2
+}
+
+// instance lists of the launchers whose answer is part of the decision
+constexpr bool inv3ys_exists(int Lp, int depth) { return Lp % 2 == 0 && ((Lp >= 14 && Lp <= 20) || (depth == 2 && Lp >= 8 && Lp <= 12)); }   // launch_inv3ys_f32
+constexpr bool inv3y_depth2(int Lp, bool vec4) { return Lp == 2 || Lp == 8 || (vec4 && (Lp == 10 || Lp == 12)); }   // launch_inv3y_f32: two register sets without spills
+
+inline Fused3Pick fused3_select(const Fused3Query& q) {
+    Fused3Pick k = {kFwd3, 0, 0, 0, 1, 0, 0, 1, 0, 0};
+    const int L = q.Lp, vf = q.variant_fwd, vi = q.variant_inv;
+    const bool f32 = !q.f64, plain = q.ew == 1;
+    if (q.inverse) {
+        // A level dilated by 2 on real data is the interleaved-pair form of Inv3Y (the two x sub-lattices are its (re, im) halves); the
+        // whole-lane-shift form of tap stride 4 exists for 16-byte-aligned data only: anything else keeps Inv3S<.., EW = 4>
+        const bool use_y = (q.dil == 1 || ((q.dil == 2 || (q.dil == 4 && q.vec4)) && vi != kInvDilatedKeep3S)) &&
+                           inv3y_ok(q.f64, q.dil > 1 ? 1 : q.ew, q.len, L, (long long)q.n1 * q.n2 * q.dil, vi);
+        const int want = vi == kInvDepth1 ? 1 : 2;          // register sets of band loads, where the instance has them
+        if (use_y) {
+            // the x stage in scatter form: real data from 10 taps on rows of whole groups of 4, interleaved pairs the same, tap stride 4 for
+            // 8 taps; kInvScatter: wherever the form exists, kInvGather: nowhere (measurements: DESIGN.md 4, "how a kernel is chosen")
+            k.family = kInv3Y;
+            const bool ask = vi == kInvScatter || (vi != kInvGather && L >= (q.ew == 4 ? 8 : 10));
+            k.scatter = ask && (q.ew == 4 ? L >= 4 : q.ew == 2 ? q.vec4 && L >= 8 : q.vec4 && inv3ys_exists(L, want));
+            k.depth = (want == 2 && (q.ew == 1 ? (k.scatter ? L < 14 : inv3y_depth2(L, q.vec4)) : (q.ew == 4 || q.vec4) && (L == 2 || L == 8))) ? 2 : 1;
+            k.uniyz = q.ew == 1 && q.uniform_yz && q.vec4 && (k.scatter ? L >= 12 : vi != kInvNoUniYZ && ((L == 12 && k.depth == 2) || L >= 14));
+        } else if (L > 12 && plain) {
+            k.family = kLong3;                               // Inv3S, 14 / 16 taps
+            k.V = f32 ? 2 : 5;
+        } else if (plain && vi == kInvLds && L == 8) {
+            k.family = kInv3;
+            k.V = 3;
+        } else {
+            // the lane-shift kernel: float on the tall tile (x taps over 4 scalars: 64x16, 512 threads; long filters: 512 threads x 2 items),
+            // double 64x16 (10 / 12 taps: 64x8)
+            k.family = kInv3S;
+            k.V = f32 ? (q.ew == 4 ? 4 : (L == 12 || (q.ew == 2 && L == 10)) ? 2 : 1) : (L >= 10 ? 5 : 1);
+        }
+    } else if (q.f64) {
+        // double, 6 / 8 taps: 64x16 tile with 512 threads, one column per thread; kFwdSmallTile keeps 64x8 / 256.  Complex db4 the same; 10 taps 64x16, 12: 64x8 / 512
+        const bool col68 = (vf == kFwdDefault || vf == kFwdOneColumn) && L >= 6 && L <= 8;
+        if (L > 12 && plain) { k.family = kLong3; k.V = 5; }
+        else k.V = q.ew == 2 ? (L >= 10 ? 5 : L == 8 ? 1 : 0) : (L == 12 ? 5 : (L == 10 || col68) ? 1 : 0);
+    } else {
+        // float (and complex64), 6 / 8 taps: the tall 64x32 tile with 1024 threads where the volume has the tiles to fill the chip with it
+        const bool tall68 = L >= 6 && L <= 8 && (long long)((q.n1 + 63) / 64) * ((q.n2 + 31) / 32) * q.nbatch >= 32;
+        const int v = (vf == kFwdDefault || vf == kFwdNoPin) ? (tall68 ? kFwdTall : kFwdDefault) : vf;
+        if (q.tfold) {
+            k.family = q.vec4 ? kFwd3FoldT : kNoFused3;     // the folded t axis runs on the tall tile with y items of 2 rows
+            k.V = 6;
+        } else if (plain && vf == kFwdDefault && L >= 10 && L <= 14 && q.vec4 && padding_even(q.len, L)) {
+            // real data, 10 / 12 / 14 taps, rows of whole groups of 4, even padding: the tall-tile kernel with its taps pinned in SGPRs
+            k.family = kFwd3Pin;
+            k.V = 6;
+        } else if (plain && L > 12) {
+            k.family = kLong3;                               // 14 / 16 taps: the tall tile; 18 / 20 (kFwdOneColumn: all): 64x16 with 512 threads
+            k.V = (vf != kFwdOneColumn && L <= 16) ? 6 : 1;
+            k.long_ab = (vf == kFwdOneColumn || vf == kFwdSmallTile) ? vf : 0;
+        } else if (q.ew == 4) k.V = 1;
+        else if (q.ew == 2) k.V = L >= 10 ? 1 : (q.dil == 1 && vf == kFwdDefault && tall68) ? 2 : 0;
+        else k.V = v == kFwdTall ? 2 : (v == kFwdOneColumn && L >= 10) ? 1 : v == kFwdTallRY2 ? 6 : (L <= 8 ? 0 : L == 10 ? 2 : 6);
+    }
+    const TileXY tile = fused3_tile_shape(k.family, q.f64, q.inverse, k.V, L, q.ew);
+    k.TX = tile.TX, k.TY = tile.TY;
+    // one round of resident workgroups: synthesis 1 per CU (the 256-thread LDS kernel 3), analysis 2, 1024-thread tiles 1
+    k.per_cu = q.inverse ? ((k.family == kInv3 && f32) ? 3 : 1) : ((q.dil == 4 || (f32 && k.TY == 32)) ? 1 : 2);
+    k.target = q.target_blocks > 0 ? q.target_blocks : q.num_cus * k.per_cu;
+    return k;
+}
+
+// ---- one fused 2-D launch
+constexpr int fused2_tile_width(bool inverse, int Lp, int ew) {
+    const int LH = inverse ? Lp / 2 : Lp / 2 - 1, RH = inverse ? Lp / 2 - 1 : Lp / 2;
+    return 4 * (64 - (LH * ew + 3) / 4 - (RH * ew + 3) / 4);
+}
+struct Fused2Query {
+    bool f64, inverse, vec4;
+    int Lp, ew, dil, n1, n2;           // n1: scalars along x; n2: rows of the whole (undilated) image
+    int variant_inv;
+};
+enum Fused2Family { kFused2S, kInv2P };   // Fwd2S / Inv2S by direction, or the synthesis with rows of band loads in flight
+struct Fused2Pick {
+    Fused2Family family;
+    int pdepth, packed, waves;         // Inv2P: rows in flight, packed FMAs; target waves of fused2_geometry
+};
+// synthesis of real data in rows of whole groups of 4 scalars, images whose 70-row chunks fit one round of 1024 waves (up to 4096^2): Inv2P,
+// 4 rows of band loads in flight per wave, packed FMAs where that form exists (float 4 / 8 / 12 taps); double up to 8 taps, depth 4 for 4 taps
+inline Fused2Pick fused2_select(const Fused2Query& q) {
+    const int vi = q.variant_inv, WX = fused2_tile_width(q.inverse, q.Lp, q.ew), L = q.Lp;
+    const bool deep = q.inverse && L <= 12 && (!q.f64 || L <= 8) && q.ew == 1 && q.dil == 1 && q.vec4 && vi != kInv2Keep2S && q.n2 >= 64 &&
+                      ((long long)((q.n1 + WX - 1) / WX) * ((q.n2 + 69) / 70) <= 1280 || vi != kInvDefault);
+    Fused2Pick k = {deep ? kInv2P : kFused2S, 0, 0, (deep && vi != kInv2Depth2Geom && vi != kInv2Depth4Geom) ? 1024 : 2048};
+    if (deep) {
+        const bool d4 = q.f64 ? L == 4 : (vi != kInv2Depth2Geom && vi != kInv2Depth2Round && (L == 4 || L == 8 || L == 12));
+        k.pdepth = d4 ? 4 : 2;
+        k.packed = !q.f64 && d4 && vi != kInv2Unpacked;
+    }
+    return k;
+}
+
+}  // namespace ndwt

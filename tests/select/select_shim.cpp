@@ -1,0 +1,49 @@
+// C entry points to csrc/ndwt_select.h for tests/test_dispatch_select.py (host C++ only: g++ -std=c++17 -shared -fPIC)
+#include "../../non-decimated_wavelets_amd/csrc/ndwt_select.h"
+using namespace ndwt;
+
+static SelPlan plan_of(const int* v) {   // ndim, comp, f64, real, path_auto, atrous, fp64_fused, dims[4], len[4], variant_fwd, variant_inv
+    SelPlan p = {v[0], v[1], v[2] != 0, v[3] != 0, v[4] != 0, v[5] != 0, v[6] != 0, {v[7], v[8], v[9], v[10]}, {v[11], v[12], v[13], v[14]}, v[15], v[16]};
+    return p;
+}
+
+// which fused path a level at tap stride `stride` takes: 3 = fused 3-D, 2 = fused 2-D, 0 = neither; *dilated: through the EW sub-lattice form
+extern "C" int sel_level_path(const int* plan, int stride, int dir, int* Lp, int* dilated) {
+    const SelPlan p = plan_of(plan);
+    *dilated = 1;
+    if (fused3_dilated_eligible(p, stride, Lp)) return 3;
+    *dilated = 0;
+    if (fused3_eligible(p, stride, Lp, dir)) return 3;
+    *dilated = 1;
+    if (fused2_dilated_eligible(p, stride, Lp)) return 2;
+    *dilated = 0;
+    return fused2_eligible(p, stride, Lp) ? 2 : 0;
+}
+
+extern "C" int sel_cascade2_levels(const int* plan, int inverse, int left) { int Lp = 0; return cascade2_levels(plan_of(plan), inverse != 0, left, &Lp); }
+
+// v: f64, inverse, vec4, uniform_yz, tfold, Lp, len[3], ew, dil, n1, n2, nbatch, variant_fwd, variant_inv, num_cus, target_blocks
+// out: V, TX, TY, depth, scatter, uniyz, per_cu, target, pinned, folded t;  returns the kernel family's name as the launch trace spells it
+extern "C" const char* sel_fused3(const int* v, int* out) {
+    const Fused3Query q = {v[0] != 0, v[1] != 0, v[2] != 0, v[3] != 0, v[4] != 0, v[5], {v[6], v[7], v[8]}, v[9], v[10], v[11], v[12], v[13],
+                           v[14], v[15], v[16], v[17]};
+    const Fused3Pick k = fused3_select(q);
+    const int r[10] = {k.V, k.TX, k.TY, k.depth, k.scatter, k.uniyz, k.per_cu, k.target, k.family == kFwd3Pin, k.family == kFwd3FoldT};
+    for (int i = 0; i < 10; ++i) out[i] = r[i];
+    switch (k.family) {
+        case kInv3Y: return "Inv3Y";
+        case kInv3S: return "Inv3S";
+        case kInv3: return "Inv3";
+        case kLong3: return q.inverse ? "Inv3S" : "Fwd3";
+        case kNoFused3: return "none";
+        default: return "Fwd3";
+    }
+}
+
+// v: f64, inverse, vec4, Lp, ew, dil, n1, n2, variant_inv;  out: family, pdepth, packed, waves
+extern "C" void sel_fused2(const int* v, int* out) {
+    const Fused2Query q = {v[0] != 0, v[1] != 0, v[2] != 0, v[3], v[4], v[5], v[6], v[7], v[8]};
+    const Fused2Pick k = fused2_select(q);
+    out[0] = (int)k.family; out[1] = k.pdepth; out[2] = k.packed; out[3] = k.waves;
+}
+extern "C" int sel_cascade2_rec_depth(int variant_inv) { return cascade2_rec_depth(variant_inv); }

@@ -1,0 +1,101 @@
+"""The dispatch pins of tests/test_gpu_dispatch.py, checked without a device: kernel selection is a function of integers
+(csrc/ndwt_select.h), so every row whose level-1 launch is a fused 2-D / 3-D kernel is replayed against that header through a small
+host shim (tests/select/select_shim.cpp, compiled with g++).  The GPU test reads what ran from the launch trace; this one asks the
+same code what it would run."""
+import ctypes
+import os
+import shutil
+import subprocess
+
+import pytest
+
+import helpers
+from test_gpu_dispatch import ROWS
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+NUM_CUS = 256
+# template parameters that follow from the tile table inside the kernel units: the pick does not carry them
+NOT_IN_PICK = ("NT", "RY", "WLDS", "ZLDS")
+# rows without a fused level-1 launch in either direction (1-D signals, the per-axis path on request, double with 18 taps)
+LEFT_OUT = ["1d-vec4", "1d-ragged", "1d-c64", "1d-db7-plain", "generic-path", "f64-db9-per-axis"]
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    if not shutil.which("g++"):
+        pytest.skip("no g++ to compile tests/select/select_shim.cpp")
+    out = str(tmp_path_factory.mktemp("select") / "libselect_shim.so")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", os.path.join(HERE, "select", "select_shim.cpp"), "-o", out],
+                   check=True)
+    lib = ctypes.CDLL(out)
+    lib.sel_fused3.restype = ctypes.c_char_p
+    return lib
+
+
+def _ints(v):
+    return (ctypes.c_int * len(v))(*[int(x) for x in v])
+
+
+def _picks(shim, row, inverse):
+    """the launches of the row's dec (rec) that kernel selection decides at tap stride 1, as (family, params)"""
+    dims, d = row["dims"], len(row["dims"])
+    wl = [row["wn"]] * d if isinstance(row["wn"], str) else row["wn"]
+    lens = [2 * int(w[2:]) for w in wl]
+    f64, comp = row["prec"] == "double", 2 if row["cplx"] else 1
+    vf, vi = max(row["fwd"], 0), max(row["inv"], 0)
+    plan = _ints([d, comp, f64, not row["cplx"], not row["path"], row["dil"] == "atrous", 1] + (dims + [1] * 4)[:4] + (lens + [2] * 4)[:4] + [vf, vi])
+    n1 = dims[0] * comp
+    vec4 = row["layout"] == "packed" and n1 % 4 == 0           # rows, band distances and pointers in whole groups of 4 scalars
+    T = "double" if f64 else "float"
+    Lp, dilated = ctypes.c_int(0), ctypes.c_int(0)
+    path = shim.sel_level_path(plan, 1, 1 if inverse else 0, ctypes.byref(Lp), ctypes.byref(dilated))
+    L, out = Lp.value, []
+    if path == 3:
+        tfold = d == 4 and not inverse and vf == 7 and vec4      # (the caller's conditions for the folded t axis: analysis_level)
+        q = _ints([f64, inverse, vec4, wl[1] == wl[2], tfold, L] + lens[:3] + [comp, 1, n1, dims[1], dims[3] if d == 4 else 1, vf, vi, NUM_CUS, 0])
+        r = (ctypes.c_int * 10)()
+        name = shim.sel_fused3(q, r).decode()
+        V, TX, TY, depth, scatter, uniyz, per_cu, target, pin, tpre = list(r)
+        assert target == NUM_CUS * per_cu
+        p = {"T": T, "L": L, "EW": comp, "TX": TX, "TY": TY, "VEC4": vec4}
+        if name == "Fwd3":
+            p.update(PIN=bool(pin), TPRE=bool(tpre))
+        if name == "Inv3Y":
+            p.update(XSC=bool(scatter), UNIYZ=bool(uniyz), DEPTH=depth)
+        out.append((name, p))
+    elif path == 2:
+        left = row["level"]
+        while True:                                              # the cascaded launches, then one launch per level
+            n = shim.sel_cascade2_levels(plan, inverse, left)
+            if n == 0:
+                break
+            p = {"T": T, "L": L, "NLEV": n}
+            if inverse:
+                p["PD"] = shim.sel_cascade2_rec_depth(vi)
+            out.append(("Inv2C" if inverse else "Fwd2C", p))
+            left -= n
+        if left > 0:
+            r = (ctypes.c_int * 4)()
+            shim.sel_fused2(_ints([f64, inverse, vec4, L, comp, 1, n1, dims[1], vi]), r)
+            if r[0] == 1:
+                out.append(("Inv2P", {"T": T, "L": L, "PD": r[1], "PK": bool(r[2])}))
+            else:
+                out.append(("Inv2S" if inverse else "Fwd2S", {"T": T, "L": L, "EW": comp, "VEC4": vec4}))
+    return out
+
+
+def test_rows_pick_their_pinned_kernels(shim):
+    checked = 0
+    for prm in ROWS:
+        row = prm.values[0]
+        n = 0
+        for inverse in (False, True):
+            specs = [helpers.spec(s) for s in row["rec" if inverse else "dec"]]
+            specs = [(fam, {k: v for k, v in p.items() if k not in NOT_IN_PICK}) for fam, p in specs]
+            for fam, params in _picks(shim, row, inverse):
+                rec = helpers._trace.KernelLaunch(fam, params)
+                assert any(helpers.matches(rec, sp) for sp in specs), (prm.id, "rec" if inverse else "dec", rec, specs)
+                n += 1
+        assert (n == 0) == (prm.id in LEFT_OUT), (prm.id, n)
+        checked += n > 0
+    assert checked >= 73 and checked == len(ROWS) - len(LEFT_OUT)

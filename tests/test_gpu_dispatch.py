@@ -1,7 +1,8 @@
 """Every branch of the kernel dispatcher, pinned: each row names the kernels a call must launch (read from the library's launch trace,
 include/ndwt.h: ndwt_trace_enable) and checks that call against the fp64 oracle.
 
-The shapes sit on both sides of the dispatcher's thresholds (csrc/ndwt_api.hip: fused3_run, fused2_run, dec_impl / rec_impl, ndwt_denoise):
+The shapes sit on both sides of the dispatcher's thresholds (csrc/ndwt_select.h: fused3_select, fused2_select, cascade2_levels and the
+eligibility predicates; ndwt_denoise in csrc/ndwt_api.hip):
 if dispatch moves, the trace assertion of the row fails and names what ran instead.  The oracle is oracle/ndwt_spatial.c (signal-domain
 C restatement of the transform, computed in double on the input rounded to the device precision).
 """
