@@ -280,7 +280,6 @@ template <typename T> struct GenericCtx {
     long long stride;
     bool slab;
     long long dims_cur[NDWT_MAX_DIMS];
-    long long vol_cur;       // scalars per volume with the current dims
     T* tmp;                  // 2*(ndim-1) volumes of vol_tmp scalars
     long long vol_tmp;
     hipStream_t s;
@@ -289,9 +288,9 @@ template <typename T> struct GenericCtx {
 
 // dims a pass on `axis` sees in slab mode: the sharded axis carries its halo planes until its own pass trims them (analysis: the
 // passes of the axes above it run on the haloed slab; synthesis: the passes of the axes below it do).  Outer-axis slabs: every pass
-// sees the local planes (the outer pass is the first of the analysis and the last of the synthesis).
+// sees the local planes in the analysis (the outer pass is its first) and the haloed slab up to the last pass of the synthesis.
 template <typename T> static const long long* generic_dims(const GenericCtx<T>& c, int axis, bool synthesis, long long* buf) {
-    if (!c.slab || c.p->shard == c.p->ndim - 1) return c.dims_cur;
+    if (!c.slab) return c.dims_cur;
     for (int k = 0; k < c.p->ndim; ++k) buf[k] = c.dims_cur[k];
     if (synthesis ? axis < c.p->shard : axis > c.p->shard) buf[c.p->shard] = c.n_in;
     return buf;
@@ -323,6 +322,21 @@ template <typename T> static int generic_synthesis(GenericCtx<T>& c, int axis, i
     rc = generic_synthesis(c, axis - 1, prefix | (1 << axis), in, d);
     if (rc) return rc;
     return axis_pass<T>(c.p, true, axis, dims, c.stride, wrap, a, d, dst, nullptr, c.s);
+}
+
+// one level by per-axis passes: in[0] -> the 2^d bands out[], or the 2^d bands in[] -> out[0]; slab: halo on the sharded axis p->shard
+template <typename T> static int per_axis_level(ndwt_plan* p, bool synthesis, const T* const* in, T* const* out, long long stride, bool slab, hipStream_t s) {
+    const int d = p->ndim, sh = p->shard;
+    GenericCtx<T> c;
+    c.p = p; c.stride = stride; c.slab = slab; c.s = s;
+    for (int k = 0; k < d; ++k) c.dims_cur[k] = p->dims[k];
+    c.n_in = p->dims[sh] + (slab ? (long long)(p->filt[sh].len - 1) * stride : 0);
+    // the temporaries hold haloed slabs, except in the analysis of an outer-axis slab: its first pass trims the halo
+    c.vol_tmp = (synthesis || sh != d - 1) ? p->vol / p->dims[sh] * c.n_in : p->vol;
+    int rc = ensure_tmp(p, (size_t)(2 * (d - 1)) * (size_t)c.vol_tmp * sizeof(T));
+    if (rc) return rc;
+    c.tmp = (T*)p->tmp;
+    return synthesis ? generic_synthesis<T>(c, d - 1, 0, in, out[0]) : generic_analysis<T>(c, d - 1, in[0], 0, out);
 }
 
 // ------------------------------------------------------------------------------------ fused levels
@@ -377,34 +391,51 @@ static int launch_pick(const Fused3Pick& k, const Fused3Query& q, const Fused3Ar
     return q.inverse ? launch_inv3_f64(a, t, q.vec4, k.V, q.ew, td, s) : launch_fwd3_f64(a, t, q.vec4, k.V, q.ew, td, s);
 }
 
-// one fused 3-D launch over `nbatch` volumes. n3 = output planes; z_wrap=false: inputs carry the z halo
-template <typename T>
-static int fused3_run(const ndwt_plan* p, bool inverse, int Lp, const T* const* in, T* const* out, long long n3, long long nbatch,
-                      long long in_bstride, long long out_bstride, int z_mode, hipStream_t s, long long zlo = 0, long long zhi = LLONG_MIN, long long zbs = 0, int shrink_mask = 0, int dil = 1,
-                      const double* ttaps = nullptr) {
+// one fused 3-D launch: what a call site says of it (the rest follows from the plan).  ZMode: the values Fused3Args::z_wrap documents
+enum ZMode { kZHalo = 0, kZPeriodic = 1, kZSplitHalo = 2, kZZeroExt = 3 };   // inputs with their z halo | periodic | halo planes in in[1] / in[2] | zero-extended slab
+constexpr int kShrinkTLowDetails = 0xFE, kShrinkTHighAll = 0xFF;   // bands shrunk on load (ndwt_denoise): the details of a 3-D level / of the t-low half, every band of the t-high half
+template <typename T> struct Fused3Launch {
+    bool inverse;
+    int Lp;
+    const T* const* in;                // analysis: in[0] (kZSplitHalo: in[0 .. 2]); synthesis: the 8 bands
+    T* const* out;                     // analysis: the 8 bands; synthesis: out[0]
+    long long n3;                      // output planes
+    long long nbatch = 1, in_bstride = 0, out_bstride = 0;   // volumes of the launch and the scalars between them
+    ZMode z = kZPeriodic;
+    long long zlo = 0, zhi = 0, zbs = 0;   // kZZeroExt: input planes outside [zlo, zhi) read as zero, batch item i testing plane + i * zbs
+    int shrink_mask = 0;
+    int dil = 1;                       // tap stride of a dilated level on its sub-lattices
+    const double* ttaps = nullptr;     // kRouteFused3FoldT: the t taps of this launch's t-band
+};
+template <typename T> static int fused3_run(const ndwt_plan* p, const Fused3Launch<T>& l, hipStream_t s) {
+    const bool inverse = l.inverse;
+    const int Lp = l.Lp, dil = l.dil;
+    const T* const* in = l.in;
+    T* const* out = l.out;
+    const long long in_bstride = l.in_bstride, out_bstride = l.out_bstride;
     Fused3Args<T> a;
     memset(&a, 0, sizeof a);
-    if (ttaps) {                                          // 4-D analysis, t axis folded in: taps of this launch's t-band, frames = batch items
-        for (int j = 0; j < Lp; ++j) a.tt[j] = (T)ttaps[j];
+    if (l.ttaps) {                                        // 4-D analysis, t axis folded in: taps of this launch's t-band, frames = batch items
+        for (int j = 0; j < Lp; ++j) a.tt[j] = (T)l.ttaps[j];
     }
-    a.zlo = (int)zlo;                                     // mode 3: input planes outside [zlo, zhi) read as zero
-    a.zhi = (int)(zhi != LLONG_MIN ? zhi : n3 - (Lp - 1));
-    a.zbs = (int)zbs;
-    if (inverse && p->shrink_mode && shrink_mask) {        // only reached with a lane-shift synthesis kernel (fused_shrink_capable)
+    a.zlo = (int)l.zlo;
+    a.zhi = (int)(l.z == kZZeroExt ? l.zhi : l.n3 - (Lp - 1));   // (the other modes never read the window)
+    a.zbs = (int)l.zbs;
+    if (inverse && p->shrink_mode && l.shrink_mask) {      // only reached with a lane-shift synthesis kernel (fused_shrink_capable)
         a.shrink_thr = (T)p->shrink_thr;
-        a.shrink_mask = shrink_mask;
+        a.shrink_mask = l.shrink_mask;
         a.shrink_hard = p->shrink_mode == 2;
     }
     a.n1 = (int)(p->dims[0] * p->comp);                   // scalars along x (interleaved complex: 2 per element)
     a.n2 = (int)(p->dims[1] / dil);                       // dil > 1: one (y, z) sub-lattice per batch item
-    a.n3 = (int)(n3 / dil);
-    a.nbatch = (int)(dil > 1 ? dil * dil : nbatch);
+    a.n3 = (int)(l.n3 / dil);
+    a.nbatch = (int)(dil > 1 ? dil * dil : l.nbatch);
     a.in_bstride = in_bstride;
     a.out_bstride = out_bstride;
-    a.z_wrap = z_mode;
+    a.z_wrap = l.z;
     a.stamps = p->stamps;
     bool vec4 = (a.n1 % 4 == 0) && (in_bstride % 4 == 0) && (out_bstride % 4 == 0);
-    const int nin = inverse ? 8 : (z_mode == 2 ? 3 : 1), nout = inverse ? 1 : 8;
+    const int nin = inverse ? 8 : (l.z == kZSplitHalo ? 3 : 1), nout = inverse ? 1 : 8;
     for (int b = 0; b < nin; ++b) { a.in[b] = in[b]; vec4 = vec4 && aligned_vec4<T>(in[b]); }
     for (int b = 0; b < nout; ++b) { a.out[b] = out[b]; vec4 = vec4 && aligned_vec4<T>(out[b]); }
 #ifdef NDWT_EXP_BANDPAD   // diagnostic build (timing only, results are garbage): skew the band streams against each other
@@ -417,7 +448,7 @@ static int fused3_run(const ndwt_plan* p, bool inverse, int Lp, const T* const* 
         else for (int b = 0; b < nout; ++b) a.out[b] = out[b] + (b / div) * pad;
     }
 #endif
-    const Fused3Query q = {sizeof(T) == 8, inverse, vec4, p->uniform_yz, ttaps != nullptr, Lp, {p->filt[0].len, p->filt[1].len, p->filt[2].len},
+    const Fused3Query q = {sizeof(T) == 8, inverse, vec4, p->uniform_yz, l.ttaps != nullptr, Lp, {p->filt[0].len, p->filt[1].len, p->filt[2].len},
                            dil > 1 ? dil : (int)p->comp, dil, a.n1, a.n2, a.nbatch, p->variant_fwd, p->variant_inv, p->num_cus, p->target_blocks};
     const Fused3Pick k = fused3_select(q);
     if (k.family == kNoFused3) return fail(NDWT_ERR_UNSUPPORTED, "internal: no folded-t analysis kernel for tap length %d / this alignment", Lp);
@@ -456,18 +487,31 @@ static int launch2(bool inverse, const Fused2Args<double>& a, int Lp, bool vec4,
     return inverse ? launch_inv2_f64(a, Lp, vec4, ew, td, s) : launch_fwd2_f64(a, Lp, vec4, ew, td, s);
 }
 
-// one fused 2-D launch; n2 = output rows; y_wrap=false: inputs carry the y halo (slab mode)
-template <typename T>
-static int fused2_run(const ndwt_plan* p, bool inverse, int Lp, const T* const* in, T* const* out, long long n2, long long in_bstride,
-                      long long out_bstride, bool y_wrap, hipStream_t s, int dil = 1) {
+// one fused 2-D launch, as a call site describes it
+template <typename T> struct Fused2Launch {
+    bool inverse;
+    int Lp;
+    const T* const* in;                // analysis: in[0]; synthesis: the 4 bands
+    T* const* out;
+    long long n2;                      // output rows
+    long long in_bstride = 0, out_bstride = 0;
+    bool y_wrap = true;                // false: the inputs carry the y halo (slab mode)
+    int dil = 1;                       // tap stride of a dilated level on its row sub-lattices
+};
+template <typename T> static int fused2_run(const ndwt_plan* p, const Fused2Launch<T>& l, hipStream_t s) {
+    const bool inverse = l.inverse;
+    const int Lp = l.Lp, dil = l.dil;
+    const T* const* in = l.in;
+    T* const* out = l.out;
+    const long long n2 = l.n2, out_bstride = l.out_bstride;
     Fused2Args<T> a;
     memset(&a, 0, sizeof a);
     a.n1 = (int)(p->dims[0] * p->comp);
     a.n2 = (int)(n2 / dil);                               // dil > 1: the dil row sub-lattices are the batch items
     a.nbatch = dil;
-    a.in_bstride = dil > 1 ? p->dims[0] : in_bstride;
+    a.in_bstride = dil > 1 ? p->dims[0] : l.in_bstride;
     a.out_bstride = dil > 1 ? p->dims[0] : out_bstride;
-    a.y_wrap = y_wrap ? 1 : 0;
+    a.y_wrap = l.y_wrap ? 1 : 0;
     if (inverse && p->shrink_mode) {                     // ndwt_denoise: threshold the 3 detail bands as they are loaded
         a.shrink_thr = (T)p->shrink_thr;
         a.shrink_mask = 0xE;
@@ -496,109 +540,85 @@ static int fused2_run(const ndwt_plan* p, bool inverse, int Lp, const T* const* 
 }
 
 // ------------------------------------------------------------------------------------------ levels
-// analysis of one level: in (vol scalars, + halo planes on the outer axis in slab mode) -> 2^d bands
-// A 4-D slab sharded on z (p->shard == 2): the input / every synthesis input carries the z halo of every frame, (nt, nz + L_z - 1, ny, nx).
-// The plan's fused path (nd_dwt_4D.m dec / rec: the t filter pair, then the 3-D level of both t-bands) keeps t whole: a periodic t pass
-// over the z-extended frames, then the fused 3-D kernel with the halo on z (z_mode 0), batched over the frames with per-frame strides.
-// Plans the fused kernels do not take (or whose z filter is not the longest: the kernel marches exactly Lp - 1 halo planes) run the
-// per-axis passes, the slab treatment on z.
-static bool zslab_fused(const ndwt_plan* p, long long stride, int* Lp, int dir) {
-    return fused3_eligible(sel(p), stride, Lp, dir) && p->filt[2].len == *Lp;
+// slab mode: the input (every synthesis input) carries the halo planes of the sharded axis p->shard
+static SlabMode slab_mode(const ndwt_plan* p, bool slab = true) { return !slab ? kWholeArray : p->shard == p->ndim - 1 ? kSlabOuter : kSlabZ; }
+static long long slab_planes(const ndwt_plan* p, long long stride, bool slab) {
+    return p->dims[p->shard] + (slab ? (long long)(p->filt[p->shard].len - 1) * stride : 0);
 }
 
-template <typename T> static int generic_level(ndwt_plan* p, bool synthesis, const T* const* in, T* const* out, long long stride, hipStream_t s);
-
+// kRouteFused3T, analysis: the t pass over frames of nz_in planes (periodic, or t_wrap = false: the slab's t halo) into two t-bands, the
+// second 256 B off a power-of-two distance from the first (see ndwt_band_pitch), then the 3-D level of both halves batched over the frames
 template <typename T>
-static int analysis_level_z(ndwt_plan* p, const T* in, T* const* out, long long stride, hipStream_t s) {
-    const long long n_in = p->dims[2] + (long long)(p->filt[2].len - 1) * stride;
-    const long long vol3 = p->comp * p->dims[0] * p->dims[1] * p->dims[2], vol3_in = vol3 / p->dims[2] * n_in;
-    const long long vol_in = vol3_in * p->dims[3];
-    int Lp = 0;
-    if (!zslab_fused(p, stride, &Lp, 0)) {
-        const T* ins[1] = {in};
-        return generic_level<T>(p, false, ins, out, stride, s);
-    }
-    const long long skew = 256 / (long long)sizeof(T);
-    int rc = ensure_tmp(p, (size_t)(2 * vol_in + skew) * sizeof(T));
+static int analysis_4d(ndwt_plan* p, int Lp, const T* in, T* const* out, long long stride, long long nz_in, ZMode z, bool t_wrap, hipStream_t s) {
+    const long long plane = p->comp * p->dims[0] * p->dims[1], band = plane * nz_in * p->dims[3], skew = 256 / (long long)sizeof(T);
+    int rc = ensure_tmp(p, (size_t)(2 * band + skew) * sizeof(T));
     if (rc) return rc;
     T* lo = (T*)p->tmp;
-    T* hi = lo + vol_in + skew;
-    long long dims_in[NDWT_MAX_DIMS] = {p->dims[0], p->dims[1], n_in, p->dims[3]};
-    rc = axis_pass<T>(p, false, 3, dims_in, stride, true, in, nullptr, lo, hi, s);
-    if (rc) return rc;
-    const T* ins_lo[8] = {lo};
-    const T* ins_hi[8] = {hi};
-    rc = fused3_run<T>(p, false, Lp, ins_lo, out, p->dims[2], p->dims[3], vol3_in, vol3, 0, s);
-    if (rc) return rc;
-    return fused3_run<T>(p, false, Lp, ins_hi, out + 8, p->dims[2], p->dims[3], vol3_in, vol3, 0, s);
-}
-
-template <typename T>
-static int synthesis_level_z(ndwt_plan* p, const T* const* in, T* out, long long stride, hipStream_t s) {
-    const long long n_in = p->dims[2] + (long long)(p->filt[2].len - 1) * stride;
-    const long long vol3 = p->comp * p->dims[0] * p->dims[1] * p->dims[2], vol3_in = vol3 / p->dims[2] * n_in;
-    int Lp = 0;
-    if (!zslab_fused(p, stride, &Lp, 1)) {
-        T* outs[1] = {out};
-        return generic_level<T>(p, true, in, outs, stride, s);
+    T* hi = lo + band + skew;
+    const long long dims_t[NDWT_MAX_DIMS] = {p->dims[0], p->dims[1], nz_in, p->dims[3]};
+    rc = axis_pass<T>(p, false, 3, dims_t, stride, t_wrap, in, nullptr, lo, hi, s);
+    for (int h = 0; h < 2 && !rc; ++h) {
+        const T* ins[8] = {h ? hi : lo};
+        Fused3Launch<T> l = {false, Lp, ins, out + 8 * h, p->dims[2]};
+        l.nbatch = p->dims[3]; l.in_bstride = plane * nz_in; l.out_bstride = plane * p->dims[2]; l.z = z;
+        rc = fused3_run<T>(p, l, s);
     }
-    const long long skew = 256 / (long long)sizeof(T);
-    int rc = ensure_tmp(p, (size_t)(2 * p->vol + skew) * sizeof(T));
-    if (rc) return rc;
-    T* a = (T*)p->tmp;
-    T* dd = a + p->vol + skew;
-    T* outs_a[8] = {a};
-    T* outs_d[8] = {dd};
-    rc = fused3_run<T>(p, true, Lp, in, outs_a, p->dims[2], p->dims[3], vol3_in, vol3, 0, s, 0, LLONG_MIN, 0, 0xFE);
-    if (rc) return rc;
-    rc = fused3_run<T>(p, true, Lp, in + 8, outs_d, p->dims[2], p->dims[3], vol3_in, vol3, 0, s, 0, LLONG_MIN, 0, 0xFF);
-    if (rc) return rc;
-    return axis_pass<T>(p, true, 3, p->dims, stride, true, a, dd, out, nullptr, s);
+    return rc;
 }
 
-// per-axis passes of one slab level, halo on the sharded axis p->shard (z-slabs; outer-axis slabs keep the code below)
-template <typename T> static int generic_level(ndwt_plan* p, bool synthesis, const T* const* in, T* const* out, long long stride, hipStream_t s) {
-    const int d = p->ndim;
-    GenericCtx<T> c;
-    c.p = p; c.stride = stride; c.slab = true; c.s = s;
-    for (int k = 0; k < d; ++k) c.dims_cur[k] = p->dims[k];
-    c.n_in = p->dims[p->shard] + (long long)(p->filt[p->shard].len - 1) * stride;
-    c.vol_cur = p->vol;
-    c.vol_tmp = p->vol / p->dims[p->shard] * c.n_in;
-    int rc = ensure_tmp(p, (size_t)(2 * (d - 1)) * (size_t)c.vol_tmp * sizeof(T));
+// kRouteFused3T, synthesis, and the zero-extended forms of the slab entry points: the 3-D level of both t-halves (`frames` frames of nz_in
+// coefficient planes -> nz_out planes each) into two t-bands, then the t pass over them -> nt_out frames of nz_out planes.
+struct Syn4 {
+    long long frames, nz_in, nz_out, nt_out;
+    ZMode z = kZPeriodic;
+    bool t_wrap = true;
+    long long t_pad = 0;               // zero frames on either side of the t-bands (zero-extended t; these bands lie back to back, without the 256 B)
+};
+template <typename T>
+static int synthesis_4d(ndwt_plan* p, int Lp, const T* const* in, T* out, long long stride, const Syn4& f, hipStream_t s) {
+    const long long plane = p->comp * p->dims[0] * p->dims[1], vol3_out = plane * f.nz_out, pad = f.t_pad * vol3_out;
+    const long long band = (f.frames + 2 * f.t_pad) * vol3_out, skew = f.t_pad ? 0 : 256 / (long long)sizeof(T);
+    int rc = ensure_tmp(p, (size_t)(2 * band + skew) * sizeof(T));
     if (rc) return rc;
-    c.tmp = (T*)p->tmp;
-    if (!synthesis) return generic_analysis<T>(c, d - 1, in[0], 0, out);
-    T* a = c.tmp + (long long)(2 * (d - 2)) * c.vol_tmp;
-    T* dd = a + c.vol_tmp;
-    rc = generic_synthesis<T>(c, d - 2, 0, in, a);
-    if (rc) return rc;
-    rc = generic_synthesis<T>(c, d - 2, 1 << (d - 1), in, dd);
-    if (rc) return rc;
-    long long dbuf[NDWT_MAX_DIMS];
-    return axis_pass<T>(p, true, d - 1, generic_dims(c, d - 1, true, dbuf), stride, d - 1 != p->shard, a, dd, out[0], nullptr, s);
+    T* bands[2] = {(T*)p->tmp, (T*)p->tmp + band + skew};
+    for (int h = 0; h < 2 && pad; ++h) {
+        HIP_TRY(hipMemsetAsync(bands[h], 0, (size_t)pad * sizeof(T), s));
+        HIP_TRY(hipMemsetAsync(bands[h] + band - pad, 0, (size_t)pad * sizeof(T), s));
+    }
+    for (int h = 0; h < 2; ++h) {                          // in[0] = approximation: the t-low half shrinks its details, the t-high half every band
+        T* outs[8] = {bands[h] + pad};
+        Fused3Launch<T> l = {true, Lp, in + 8 * h, outs, f.nz_out};
+        l.nbatch = f.frames; l.in_bstride = plane * f.nz_in; l.out_bstride = vol3_out; l.z = f.z; l.zhi = f.nz_in;
+        l.shrink_mask = h ? kShrinkTHighAll : kShrinkTLowDetails;
+        rc = fused3_run<T>(p, l, s);
+        if (rc) return rc;
+    }
+    const long long dims_t[NDWT_MAX_DIMS] = {p->dims[0], p->dims[1], f.nz_out, f.nt_out};
+    return axis_pass<T>(p, true, 3, dims_t, stride, f.t_wrap, bands[0], bands[1], out, nullptr, s);
 }
 
+// analysis of one level: in (vol scalars, + halo planes in slab mode) -> 2^d bands
 template <typename T>
 static int analysis_level(ndwt_plan* p, const T* in, T* const* out, long long stride, bool slab, hipStream_t s) {
-    if (slab && p->shard != p->ndim - 1) return analysis_level_z<T>(p, in, out, stride, s);
-    const int d = p->ndim;
-    const AxisFilter& ftop = p->filt[d - 1];
-    const long long n_top = p->dims[d - 1];
-    const long long n_top_in = slab ? n_top + (long long)(ftop.len - 1) * stride : n_top;
-    const long long vol_in = p->vol / n_top * n_top_in;
-    int Lp = 0;
-    const SelPlan sp = sel(p);
-    if (!slab && fused3_dilated_eligible(sp, stride, &Lp)) {
-        const T* ins[8] = {in};
-        return fused3_run<T>(p, false, Lp, ins, out, p->dims[2], 1, 0, 0, 1, s, 0, LLONG_MIN, 0, 0, (int)stride);
+    const long long n_sh = slab_planes(p, stride, slab), vol_in = p->vol / p->dims[p->shard] * n_sh;
+    const bool on_z = p->shard == 2;                       // (of a 4-D level: the sharded axis is z, else t)
+    const T* ins[8] = {in};
+    LevelRoute r = level_route(sel(p), stride, 0, slab_mode(p, slab));
+    if (r.kind == kRouteFused3FoldT) {
+        bool ok = aligned_vec4<T>(in);
+        for (int b = 0; ok && b < 16; ++b) ok = aligned_vec4<T>(out[b]);
+        if (!ok) r.kind = kRouteFused3T;
     }
-    // slab mode hands over exactly (L_top-1) halo planes: the fused kernel marches with the padded length
-    if (fused3_eligible(sp, stride, &Lp, 0) && !(slab && d == 3 && ftop.len != Lp)) {
-        const long long vol3 = p->comp * p->dims[0] * p->dims[1] * p->dims[2];
-        if (d == 3) {
-            const T* ins[8] = {in};
-            return fused3_run<T>(p, false, Lp, ins, out, p->dims[2], 1, vol_in, p->vol, slab ? 0 : 1, s);
+    switch (r.kind) {
+        case kRouteFused3Dilated: {
+            Fused3Launch<T> l = {false, r.Lp, ins, out, p->dims[2]};
+            l.dil = (int)stride;
+            return fused3_run<T>(p, l, s);
+        }
+        case kRouteFused3: {
+            Fused3Launch<T> l = {false, r.Lp, ins, out, p->dims[2]};
+            l.in_bstride = vol_in; l.out_bstride = p->vol; l.z = slab ? kZHalo : kZPeriodic;
+            return fused3_run<T>(p, l, s);
         }
         // A/B variant 7 (Plan.set_variant(fwd=7)) -- MEASURED AND NOT THE DEFAULT: the t axis folded into the fused launches, each raw plane a
         // workgroup takes being the t-filtered combination of the same plane of L frames (read where the neighbouring frames' workgroups
@@ -606,120 +626,68 @@ static int analysis_level(ndwt_plan* p, const T* in, T* const* out, long long st
         // the time goes up: cfg5 (256^3 x 32, db4) 6.55 ms per launch against 3.41 ms + half of the 1.36 ms t pass -- the 8 loads per lane
         // and plane (against 1) go through the same per-CU vector-memory pipe as the 4 stores, and that pipe is what bounds the kernel
         // (68.6 ms per dec+rec step against 53.5 ms).
-        if constexpr (sizeof(T) == 4) {
-            bool ok = p->variant_fwd == kFwdFoldT && !slab && stride == 1 && p->complexity == NDWT_REAL && Lp <= 8 && ftop.len <= Lp && p->dims[0] % 4 == 0 &&
-                      vol3 % 4 == 0 && p->dims[3] >= 2 && aligned_vec4<T>(in);
-            for (int b = 0; ok && b < 16; ++b) ok = aligned_vec4<T>(out[b]);
-            if (ok) {
-                double tlo[kMaxTaps], thi[kMaxTaps];
-                pad_taps(ftop.ana_lo, ftop.len, Lp, tlo);
-                pad_taps(ftop.ana_hi, ftop.len, Lp, thi);
-                const T* ins[8] = {in};
-                int rc = fused3_run<T>(p, false, Lp, ins, out, p->dims[2], p->dims[3], vol3, vol3, 1, s, 0, LLONG_MIN, 0, 0, 1, tlo);
+        case kRouteFused3FoldT: {
+            const long long vol3 = p->vol / p->dims[3];
+            double tt[2][kMaxTaps];
+            pad_taps(p->filt[3].ana_lo, p->filt[3].len, r.Lp, tt[0]);
+            pad_taps(p->filt[3].ana_hi, p->filt[3].len, r.Lp, tt[1]);
+            for (int h = 0; h < 2; ++h) {
+                Fused3Launch<T> l = {false, r.Lp, ins, out + 8 * h, p->dims[2]};
+                l.nbatch = p->dims[3]; l.in_bstride = l.out_bstride = vol3; l.ttaps = tt[h];
+                const int rc = fused3_run<T>(p, l, s);
                 if (rc) return rc;
-                return fused3_run<T>(p, false, Lp, ins, out + 8, p->dims[2], p->dims[3], vol3, vol3, 1, s, 0, LLONG_MIN, 0, 0, 1, thi);
             }
+            return NDWT_OK;
         }
-        // otherwise: outer axis per-axis (1 -> 2), then the fused 3-D kernel on both halves, batched over n4
-        const long long skew = 256 / (long long)sizeof(T);   // the two halves 256 B off a power-of-two distance (see ndwt_band_pitch)
-        int rc = ensure_tmp(p, (size_t)(2 * p->vol + skew) * sizeof(T));
-        if (rc) return rc;
-        T* lo = (T*)p->tmp;
-        T* hi = lo + p->vol + skew;
-        rc = axis_pass<T>(p, false, 3, p->dims, stride, !slab, in, nullptr, lo, hi, s);
-        if (rc) return rc;
-        const T* ins_lo[8] = {lo};
-        const T* ins_hi[8] = {hi};
-        rc = fused3_run<T>(p, false, Lp, ins_lo, out, p->dims[2], p->dims[3], vol3, vol3, 1, s);
-        if (rc) return rc;
-        return fused3_run<T>(p, false, Lp, ins_hi, out + 8, p->dims[2], p->dims[3], vol3, vol3, 1, s);
+        case kRouteFused3T: return analysis_4d<T>(p, r.Lp, in, out, stride, on_z ? n_sh : p->dims[2], slab && on_z ? kZHalo : kZPeriodic, !slab || on_z, s);
+        case kRouteFused2Dilated: {
+            Fused2Launch<T> l = {false, r.Lp, ins, out, p->dims[1]};
+            l.dil = (int)stride;
+            return fused2_run<T>(p, l, s);
+        }
+        case kRouteFused2: {
+            Fused2Launch<T> l = {false, r.Lp, ins, out, p->dims[1]};
+            l.in_bstride = vol_in; l.out_bstride = p->vol; l.y_wrap = !slab;
+            return fused2_run<T>(p, l, s);
+        }
+        default: return per_axis_level<T>(p, false, ins, out, stride, slab, s);   // kRoutePerAxis
     }
-    if (!slab && fused2_dilated_eligible(sp, stride, &Lp)) {
-        const T* ins[4] = {in};
-        return fused2_run<T>(p, false, Lp, ins, out, p->dims[1], 0, 0, true, s, (int)stride);
-    }
-    if (fused2_eligible(sp, stride, &Lp) && !(slab && ftop.len != Lp)) {
-        const T* ins[4] = {in};
-        return fused2_run<T>(p, false, Lp, ins, out, p->dims[1], vol_in, p->vol, !slab, s);
-    }
-    GenericCtx<T> c;
-    c.p = p; c.stride = stride; c.slab = slab; c.s = s;
-    for (int k = 0; k < d; ++k) c.dims_cur[k] = p->dims[k];
-    c.vol_cur = p->vol;
-    c.vol_tmp = p->vol;
-    if (d > 1) {
-        int rc = ensure_tmp(p, (size_t)(2 * (d - 1)) * (size_t)c.vol_tmp * sizeof(T));
-        if (rc) return rc;
-    }
-    c.tmp = (T*)p->tmp;
-    return generic_analysis<T>(c, d - 1, in, 0, out);
 }
 
 template <typename T>
 static int synthesis_level(ndwt_plan* p, const T* const* in, T* out, long long stride, bool slab, hipStream_t s) {
-    if (slab && p->shard != p->ndim - 1) return synthesis_level_z<T>(p, in, out, stride, s);
-    const int d = p->ndim;
-    const AxisFilter& ftop = p->filt[d - 1];
-    const long long n_top = p->dims[d - 1];
-    const long long n_top_in = slab ? n_top + (long long)(ftop.len - 1) * stride : n_top;
-    const long long vol_in = p->vol / n_top * n_top_in;
-    int Lp = 0;
-    const SelPlan sp = sel(p);
-    if (!slab && fused3_dilated_eligible(sp, stride, &Lp)) {
-        T* outs[8] = {out};
-        return fused3_run<T>(p, true, Lp, in, outs, p->dims[2], 1, 0, 0, 1, s, 0, LLONG_MIN, 0, 0, (int)stride);
-    }
-    if (fused3_eligible(sp, stride, &Lp, 1) && !(slab && d == 3 && ftop.len != Lp)) {
-        const long long vol3 = p->comp * p->dims[0] * p->dims[1] * p->dims[2];
-        if (d == 3) {
-            T* outs[8] = {out};
-            return fused3_run<T>(p, true, Lp, in, outs, p->dims[2], 1, vol_in, p->vol, slab ? 0 : 1, s, 0, LLONG_MIN, 0, 0xFE);
+    const long long n_sh = slab_planes(p, stride, slab), vol_in = p->vol / p->dims[p->shard] * n_sh;
+    const bool on_z = p->shard == 2;
+    T* outs[8] = {out};
+    const LevelRoute r = level_route(sel(p), stride, 1, slab_mode(p, slab));
+    switch (r.kind) {
+        case kRouteFused3Dilated: {
+            Fused3Launch<T> l = {true, r.Lp, in, outs, p->dims[2]};
+            l.dil = (int)stride;
+            return fused3_run<T>(p, l, s);
         }
-        const long long skew = 256 / (long long)sizeof(T);
-        int rc = ensure_tmp(p, (size_t)(2 * vol_in + skew) * sizeof(T));
-        if (rc) return rc;
-        T* a = (T*)p->tmp;
-        T* dd = a + vol_in + skew;
-        T* outs_a[8] = {a};
-        T* outs_d[8] = {dd};
-        rc = fused3_run<T>(p, true, Lp, in, outs_a, p->dims[2], n_top_in, vol3, vol3, 1, s, 0, LLONG_MIN, 0, 0xFE);   // in[0] = approximation
-        if (rc) return rc;
-        rc = fused3_run<T>(p, true, Lp, in + 8, outs_d, p->dims[2], n_top_in, vol3, vol3, 1, s, 0, LLONG_MIN, 0, 0xFF);   // t-high half: all details
-        if (rc) return rc;
-        return axis_pass<T>(p, true, 3, p->dims, stride, !slab, a, dd, out, nullptr, s);
+        case kRouteFused3: {
+            Fused3Launch<T> l = {true, r.Lp, in, outs, p->dims[2]};
+            l.in_bstride = vol_in; l.out_bstride = p->vol; l.z = slab ? kZHalo : kZPeriodic; l.shrink_mask = kShrinkTLowDetails;
+            return fused3_run<T>(p, l, s);
+        }
+        case kRouteFused3T: {                              // (a slab on t: the 3-D part runs on the halo frames too)
+            Syn4 f = {on_z ? p->dims[3] : n_sh, on_z ? n_sh : p->dims[2], p->dims[2], p->dims[3]};
+            f.z = slab && on_z ? kZHalo : kZPeriodic; f.t_wrap = !slab || on_z;
+            return synthesis_4d<T>(p, r.Lp, in, out, stride, f, s);
+        }
+        case kRouteFused2Dilated: {
+            Fused2Launch<T> l = {true, r.Lp, in, outs, p->dims[1]};
+            l.dil = (int)stride;
+            return fused2_run<T>(p, l, s);
+        }
+        case kRouteFused2: {
+            Fused2Launch<T> l = {true, r.Lp, in, outs, p->dims[1]};
+            l.in_bstride = vol_in; l.out_bstride = p->vol; l.y_wrap = !slab;
+            return fused2_run<T>(p, l, s);
+        }
+        default: return per_axis_level<T>(p, true, in, outs, stride, slab, s);   // kRoutePerAxis
     }
-    if (!slab && fused2_dilated_eligible(sp, stride, &Lp)) {
-        T* outs[4] = {out};
-        return fused2_run<T>(p, true, Lp, in, outs, p->dims[1], 0, 0, true, s, (int)stride);
-    }
-    if (fused2_eligible(sp, stride, &Lp) && !(slab && ftop.len != Lp)) {
-        T* outs[4] = {out};
-        return fused2_run<T>(p, true, Lp, in, outs, p->dims[1], vol_in, p->vol, !slab, s);
-    }
-    GenericCtx<T> c;
-    c.p = p; c.stride = stride; c.slab = slab; c.s = s;
-    for (int k = 0; k < d; ++k) c.dims_cur[k] = p->dims[k];
-    c.dims_cur[d - 1] = n_top_in;          // inner axes run on the haloed slab; the outer pass trims it
-    c.vol_cur = vol_in;
-    c.vol_tmp = vol_in;
-    if (d > 1) {
-        int rc = ensure_tmp(p, (size_t)(2 * (d - 1)) * (size_t)c.vol_tmp * sizeof(T));
-        if (rc) return rc;
-    }
-    c.tmp = (T*)p->tmp;
-    // the outermost pass must see dims_cur[d-1] == local length
-    if (d == 1) {
-        c.dims_cur[0] = n_top;
-        return generic_synthesis<T>(c, 0, 0, in, out);
-    }
-    T* a = c.tmp + (long long)(2 * (d - 2)) * c.vol_tmp;
-    T* dd = a + c.vol_tmp;
-    int rc = generic_synthesis<T>(c, d - 2, 0, in, a);
-    if (rc) return rc;
-    rc = generic_synthesis<T>(c, d - 2, 1 << (d - 1), in, dd);
-    if (rc) return rc;
-    c.dims_cur[d - 1] = n_top;
-    return axis_pass<T>(p, true, d - 1, c.dims_cur, stride, !slab, a, dd, out, nullptr, s);
 }
 
 // --------------------------------------------------------------------------------- multi-level
@@ -864,7 +832,7 @@ static int check_level(const ndwt_plan* p, int level) {
 // fused 3-D slab forms that avoid haloed copies (multi-GPU fast path)
 static int slab_fast_ok(const ndwt_plan* p, int stride, int* Lp) {
     if (!p) return fail(NDWT_ERR_INVALID_ARG, "null plan");
-    if (p->ndim != 3 || !fused3_eligible(sel(p), stride, Lp) || p->filt[2].len != *Lp)
+    if (p->ndim != 3 || !(*Lp = slab_fused3(sel(p), stride, -1, kSlabOuter)))
         return fail(NDWT_ERR_UNSUPPORTED, "split/extended slab entry points need a fused 3-D plan whose outer-axis filter is the longest");
     return NDWT_OK;
 }
@@ -872,7 +840,9 @@ static int slab_fast_ok(const ndwt_plan* p, int stride, int* Lp) {
 template <typename T> static int slab_ext_impl(ndwt_plan* p, int Lp, const void* const* in, void* out, hipStream_t s) {
     T* outs[8] = {(T*)out};
     const long long n_out = p->dims[2] + (Lp - 1);
-    return fused3_run<T>(p, true, Lp, (const T* const*)in, outs, n_out, 1, p->vol, p->vol / p->dims[2] * n_out, 3, s);
+    Fused3Launch<T> l = {true, Lp, (const T* const*)in, outs, n_out};
+    l.in_bstride = p->vol; l.out_bstride = p->vol / p->dims[2] * n_out; l.z = kZZeroExt; l.zhi = p->dims[2];
+    return fused3_run<T>(p, l, s);
 }
 
 
@@ -945,30 +915,13 @@ template <typename T> static int shrink_run(ndwt_plan* p, T* d, long long n, dou
 
 // 4-D slab, zero-extended synthesis (scatter scheme of the t-sharded driver): the 3-D part is local to every frame, so
 // the 16 bands of the slab are synthesised to the two t-bands (a, d) for the local frames only, in buffers that carry
-// L-1 zero frames on each side; the t-axis pass over them yields the n_local + L-1 frames of the zero-extended result.
+// L-1 zero frames on each side; the t-axis pass over them (slab mode: it reads L-1 frames more than it writes) yields the
+// n_local + L-1 frames of the zero-extended result.
 template <typename T> static int slab_ext4_impl(ndwt_plan* p, int Lp, const void* const* in, void* out, hipStream_t s) {
-    const long long vol3 = p->comp * p->dims[0] * p->dims[1] * p->dims[2];
     const long long n = p->dims[3], h = p->filt[3].len - 1;
-    const long long nin = n + 2 * h, nout = n + h;
-    int rc = ensure_tmp(p, (size_t)(2 * nin * vol3) * sizeof(T));
-    if (rc) return rc;
-    T* a = (T*)p->tmp;
-    T* dd = a + nin * vol3;
-    for (T* b : {a, dd}) {
-        HIP_TRY(hipMemsetAsync(b, 0, (size_t)(h * vol3) * sizeof(T), s));
-        HIP_TRY(hipMemsetAsync(b + (h + n) * vol3, 0, (size_t)(h * vol3) * sizeof(T), s));
-    }
-    const T* const* inT = (const T* const*)in;
-    T* outs_a[8] = {a + h * vol3};
-    T* outs_d[8] = {dd + h * vol3};
-    rc = fused3_run<T>(p, true, Lp, inT, outs_a, p->dims[2], n, vol3, vol3, 1, s, 0, LLONG_MIN, 0, 0xFE);
-    if (rc) return rc;
-    rc = fused3_run<T>(p, true, Lp, inT + 8, outs_d, p->dims[2], n, vol3, vol3, 1, s, 0, LLONG_MIN, 0, 0xFF);
-    if (rc) return rc;
-    long long dims_ext[NDWT_MAX_DIMS];
-    for (int k = 0; k < 4; ++k) dims_ext[k] = p->dims[k];
-    dims_ext[3] = nout;                                  // outputs; the pass reads nout + L-1 = nin frames (slab mode)
-    return axis_pass<T>(p, true, 3, dims_ext, 1, false, a, dd, (T*)out, nullptr, s);
+    Syn4 f = {n, p->dims[2], p->dims[2], n + h};
+    f.t_wrap = false; f.t_pad = h;
+    return synthesis_4d<T>(p, Lp, (const T* const*)in, (T*)out, 1, f, s);
 }
 
 // a run of output planes of the slab transform (the caller offsets the pointers): what lets the halo exchange
@@ -977,7 +930,9 @@ template <typename T>
 static int slab_analysis_part_impl(ndwt_plan* p, int Lp, const void* in, const void* hb, const void* ha, void* const* out,
                                    long long n_planes, hipStream_t s) {
     const T* ins[8] = {(const T*)in, (const T*)hb, (const T*)ha};
-    return fused3_run<T>(p, false, Lp, ins, (T* const*)out, n_planes, 1, p->vol, p->vol, 2, s);
+    Fused3Launch<T> l = {false, Lp, ins, (T* const*)out, n_planes};
+    l.in_bstride = l.out_bstride = p->vol; l.z = kZSplitHalo;
+    return fused3_run<T>(p, l, s);
 }
 
 template <typename T>
@@ -985,7 +940,9 @@ static int slab_analysis_runs_impl(ndwt_plan* p, int Lp, const void* in, void* c
                                    long long run_stride, hipStream_t s) {
     const long long plane = p->vol / p->dims[2];
     const T* ins[8] = {(const T*)in};
-    return fused3_run<T>(p, false, Lp, ins, (T* const*)out, n_planes, n_runs, run_stride * plane, run_stride * plane, 0, s);
+    Fused3Launch<T> l = {false, Lp, ins, (T* const*)out, n_planes};
+    l.nbatch = n_runs; l.in_bstride = l.out_bstride = run_stride * plane; l.z = kZHalo;
+    return fused3_run<T>(p, l, s);
 }
 
 // run r: planes [e0 + r*e_stride, +n_out) of the zero-extended synthesis of n_in coefficient planes -> out + r*n_out planes
@@ -996,7 +953,10 @@ static int slab_synthesis_runs_impl(ndwt_plan* p, int Lp, const void* const* in,
     const T* ins[8];
     for (int b = 0; b < 8; ++b) ins[b] = (const T*)in[b] + e0 * plane;      // never dereferenced outside [0, n_in)
     T* outs[8] = {(T*)out};
-    return fused3_run<T>(p, true, Lp, ins, outs, n_out, n_runs, e_stride * plane, n_out * plane, 3, s, -e0, n_in - e0, e_stride);
+    Fused3Launch<T> l = {true, Lp, ins, outs, n_out};
+    l.nbatch = n_runs; l.in_bstride = e_stride * plane; l.out_bstride = n_out * plane;
+    l.z = kZZeroExt; l.zlo = -e0; l.zhi = n_in - e0; l.zbs = e_stride;
+    return fused3_run<T>(p, l, s);
 }
 
 // ------------------------------------------------------------------------------------------ C ABI
@@ -1136,28 +1096,15 @@ static int slab_split_z_impl(ndwt_plan* p, const void* in, const void* hb, const
     dst[k] = z + (ab + n) * P; src[k] = ha; cnt[k] = aa * P; dstr[k] = nin * P; sstr[k] = aa * P; ++k;
     const int rc = segments_strided_launch<T>(NDWT_SEG_COPY, k, dst, src, cnt, p->dims[3], dstr, sstr, s);
     if (rc != 0) return fail(NDWT_ERR_HIP, "segment kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return analysis_level_z<T>(p, z, (T* const*)out, stride, s);
+    return analysis_level<T>(p, z, (T* const*)out, stride, true, s);
 }
 
-// z-slab, zero-extended synthesis (scatter scheme): the 3-D part of both t-bands on the zero-extended z axis of every frame (z_mode 3,
-// the frames as batch items, each tested against the same [0, n)), then the periodic t pass: (nt, n + L - 1, ny, nx)
+// z-slab, zero-extended synthesis (scatter scheme): the 3-D part of both t-bands on the zero-extended z axis of every frame (the frames
+// as batch items, each tested against the same [0, n)), then the periodic t pass: (nt, n + L - 1, ny, nx)
 template <typename T> static int slab_ext_z_impl(ndwt_plan* p, int Lp, const void* const* in, void* out, hipStream_t s) {
-    const long long n = p->dims[2], next = n + Lp - 1;
-    const long long vol3 = p->comp * p->dims[0] * p->dims[1] * n, vol3_ext = vol3 / n * next, vol_ext = vol3_ext * p->dims[3];
-    const long long skew = 256 / (long long)sizeof(T);
-    int rc = ensure_tmp(p, (size_t)(2 * vol_ext + skew) * sizeof(T));
-    if (rc) return rc;
-    T* a = (T*)p->tmp;
-    T* dd = a + vol_ext + skew;
-    const T* const* inT = (const T* const*)in;
-    T* outs_a[8] = {a};
-    T* outs_d[8] = {dd};
-    rc = fused3_run<T>(p, true, Lp, inT, outs_a, next, p->dims[3], vol3, vol3_ext, 3, s, 0, n, 0);
-    if (rc) return rc;
-    rc = fused3_run<T>(p, true, Lp, inT + 8, outs_d, next, p->dims[3], vol3, vol3_ext, 3, s, 0, n, 0);
-    if (rc) return rc;
-    long long dims_ext[NDWT_MAX_DIMS] = {p->dims[0], p->dims[1], next, p->dims[3]};
-    return axis_pass<T>(p, true, 3, dims_ext, 1, true, a, dd, (T*)out, nullptr, s);
+    Syn4 f = {p->dims[3], p->dims[2], p->dims[2] + Lp - 1, p->dims[3]};
+    f.z = kZZeroExt;
+    return synthesis_4d<T>(p, Lp, (const T* const*)in, (T*)out, 1, f, s);
 }
 
 extern "C" {
@@ -1257,8 +1204,7 @@ static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, lon
             return fail(NDWT_ERR_ALLOC, "hipMalloc of the approximation scratch failed: %s", hipGetErrorString(e));
         }
     }
-    int Lp = 0;
-    if (fused3_eligible(sel(p), 1, &Lp, 0) || fused2_eligible(sel(p), 1, &Lp)) {   // (the analysis side admits the most tap lengths)
+    if (const int Lp = level_route(sel(p), 1, 0, kWholeArray).Lp) {   // a plan with fused levels (the analysis side admits the most tap lengths)
         for (int inv = 0; inv < 2; ++inv) {
             FusedTapsD t = fused_taps(p, Lp, inv != 0);
             // synthesis table: Taps3Y = Taps3 followed by the x tap pairs (lo[0][k], lo[0][k-1]), k = 0..Lp, of the pair-packed kernel
@@ -1427,12 +1373,12 @@ int ndwt_plan_set_fused_level1(ndwt_plan* p, int enable) {
 
 int ndwt_plan_describe(const ndwt_plan* p, char* buf, int buflen) {
     if (!p || !buf || buflen < 1) return fail(NDWT_ERR_INVALID_ARG, "bad arguments");
-    int Lp = 0;
     const char* s = "axis";
-    const bool f3a = fused3_eligible(sel(p), 1, &Lp, 0), f3s = fused3_eligible(sel(p), 1, &Lp, 1);
+    const LevelRouteKind ra = level_route(sel(p), 1, 0, kWholeArray).kind, rs = level_route(sel(p), 1, 1, kWholeArray).kind;
+    const bool f3a = route_fused3(ra), f3s = route_fused3(rs);
     if (f3a && f3s) s = p->ndim == 3 ? "fused3d" : "axis+fused3d";
     else if (f3a) s = p->ndim == 3 ? "fused3d analysis, axis synthesis" : "axis+fused3d analysis, axis synthesis";
-    else if (fused2_eligible(sel(p), 1, &Lp)) s = "fused2d";
+    else if (ra == kRouteFused2) s = "fused2d";
     snprintf(buf, (size_t)buflen, "%s", s);
     return NDWT_OK;
 }
@@ -1699,11 +1645,12 @@ int ndwt_shrink(ndwt_plan* p, void* y, int level, double threshold, int mode, vo
 static bool den3_eligible(const ndwt_plan* p, int* Lp_out) {
     if (!p->fused_level1 || p->dtype != NDWT_F32 || p->complexity != NDWT_REAL || p->ndim != 3 || p->dilation != NDWT_DILATION_REFERENCE)
         return false;
-    int Lp = 0;
+    const LevelRoute r = level_route(sel(p), 1, -1, kWholeArray);
+    const int Lp = r.Lp;
     // measured, 512^3, 3 levels, ndwt_denoise with / without the fused level 1: db1 4.49 / 5.27 ms, db2 5.10 / 5.67, db3 5.72 / 6.09,
     // db4 6.30 / 6.13 -- with 8 taps the recomputation (2.3x the arithmetic of the synthesis kernel, 67 % VALU-busy) costs more than the
     // 13 volume transfers it removes, so 8 taps take the kernel only when asked to (ndwt_plan_set_fused_level1(plan, 2))
-    if (!fused3_eligible(sel(p), 1, &Lp) || Lp > (p->fused_level1 >= 2 ? 8 : 6) || !inv3y_plan_ok(sel(p), Lp)) return false;
+    if (r.kind != kRouteFused3 || Lp > (p->fused_level1 >= 2 ? 8 : 6) || !inv3y_plan_ok(sel(p), Lp)) return false;
     for (int ax = 0; ax < 3; ++ax)
         if (p->filt[ax].len != Lp) return false;
     if (p->dims[0] % 4 != 0) return false;
@@ -1913,9 +1860,7 @@ int ndwt_rec_split_host(ndwt_plan* p, const void* y_re, const void* y_im, void* 
 }
 
 int ndwt_plan_slab_fast(const ndwt_plan* p) {
-    int Lp = 0;
-    if (p && p->shard != p->ndim - 1) return zslab_fused(p, 1, &Lp, -1) ? 1 : 0;   // z-slab: the zero-extended synthesis exists
-    return p && p->ndim == 3 && fused3_eligible(sel(p), 1, &Lp) && p->filt[2].len == Lp ? 1 : 0;
+    return p && slab_fused3(sel(p), 1, -1, slab_mode(p)) ? 1 : 0;      // 3-D slabs and 4-D ones sharded on z: the zero-extended synthesis exists
 }
 
 int ndwt_slab_halo(const ndwt_plan* p, int stride, int64_t* ab, int64_t* aa, int64_t* sb, int64_t* sa) {
@@ -1966,7 +1911,7 @@ int ndwt_analysis_level_slab_split(ndwt_plan* p, const void* in_local, const voi
 int ndwt_synthesis_level_slab_ext(ndwt_plan* p, const void* const* in_local, void* out_ext, int stride, void* stream) {
     int Lp = 0;
     if (p && p->shard != p->ndim - 1) {                  // z-sharded 4-D: the fused kernels with the z filter the longest, tap stride 1
-        if (stride != 1 || !zslab_fused(p, 1, &Lp, 1))
+        if (stride != 1 || !(Lp = slab_fused3(sel(p), 1, 1, kSlabZ)))
             return fail(NDWT_ERR_UNSUPPORTED, "the zero-extended z-slab synthesis needs a plan on the fused 3-D kernels whose z filter is the longest (stride 1)");
         if (!in_local || !out_ext) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
         HIP_TRY(hipSetDevice(p->device));
@@ -1974,7 +1919,9 @@ int ndwt_synthesis_level_slab_ext(ndwt_plan* p, const void* const* in_local, voi
                                     : slab_ext_z_impl<double>(p, Lp, in_local, out_ext, (hipStream_t)stream);
     }
     if (p && p->ndim == 4) {                             // t-sharded 4-D: 3-D part per frame, zero-extended t-axis pass
-        if (stride != 1 || !fused3_eligible(sel(p), 1, &Lp))
+        const LevelRoute r = level_route(sel(p), 1, -1, kSlabOuter);
+        Lp = r.Lp;
+        if (stride != 1 || r.kind != kRouteFused3T)
             return fail(NDWT_ERR_UNSUPPORTED, "the zero-extended 4-D slab synthesis needs a plan on the fused 3-D kernels (stride 1)");
         if (!in_local || !out_ext) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
         HIP_TRY(hipSetDevice(p->device));

@@ -123,12 +123,52 @@ inline bool fused2_eligible(const SelPlan& p, long long stride, int* Lp_out) {
     return true;
 }
 
+// ---- the route of one level: which fused form it takes, or the per-axis passes, and with which padded tap length.  ndwt_api.hip asks
+// once per level and switches on the answer; the predicates above are what the answer is written in.
+enum LevelRouteKind {
+    kRouteFused3Dilated,               // a dilated 3-D level: the fused 3-D kernels on its sub-lattices
+    kRouteFused3,                      // one fused 3-D launch
+    kRouteFused3T,                     // 4-D (nd_dwt_4D.m dec / rec): the t filter pair as a per-axis pass, the 3-D level of both t-bands as two fused
+                                       // launches batched over the frames.  t stays whole on a slab sharded on z: the pass is periodic over the
+                                       // z-extended frames (nt, nz + L_z - 1, ny, nx), and the fused launches take the halo on z with per-frame strides
+    kRouteFused3FoldT,                 // 4-D analysis, kFwdFoldT: t folded into those two launches (16-byte-aligned pointers only: the caller falls back to kRouteFused3T)
+    kRouteFused2Dilated,               // a dilated 2-D level: the fused 2-D kernels on its row sub-lattices
+    kRouteFused2,                      // one fused 2-D launch
+    kRoutePerAxis                      // one pass per axis; on a slab, the halo treatment on the sharded axis
+};
+struct LevelRoute { LevelRouteKind kind; int Lp; };   // Lp: the padded tap length of the fused forms, 0 for the per-axis passes
+constexpr bool route_fused3(LevelRouteKind k) { return k == kRouteFused3 || k == kRouteFused3T || k == kRouteFused3FoldT; }
+
+// On a slab the input (every synthesis input) carries the halo planes of the sharded axis: the outermost one, or z of a 4-D volume.
+enum SlabMode { kWholeArray, kSlabOuter, kSlabZ };
+// Slabs have no sub-lattice form, and a fused kernel marches exactly Lp - 1 halo planes: where the halo is on the kernel's own outer axis
+// (z of a 3-D slab or of a 4-D volume sharded on z, y of an image) that axis' filter has to be the longest.  (A 4-D slab on t: t is the
+// per-axis pass.)
+inline LevelRoute level_route(const SelPlan& p, long long stride, int dir, SlabMode mode) {
+    const bool slab = mode != kWholeArray, halo_on_z = mode == kSlabZ || (mode == kSlabOuter && p.ndim == 3);
+    int Lp = 0;
+    if (!slab && fused3_dilated_eligible(p, stride, &Lp)) return {kRouteFused3Dilated, Lp};
+    if (fused3_eligible(p, stride, &Lp, dir) && !(halo_on_z && p.len[2] != Lp)) {
+        if (p.ndim == 3) return {kRouteFused3, Lp};
+        const bool fold = p.variant_fwd == kFwdFoldT && dir == 0 && !slab && stride == 1 && !p.f64 && p.real && Lp <= 8 && p.len[3] <= Lp &&
+                          p.dims[0] % 4 == 0 && (p.comp * p.dims[0] * p.dims[1] * p.dims[2]) % 4 == 0 && p.dims[3] >= 2;
+        return {fold ? kRouteFused3FoldT : kRouteFused3T, Lp};
+    }
+    if (!slab && fused2_dilated_eligible(p, stride, &Lp)) return {kRouteFused2Dilated, Lp};
+    if (fused2_eligible(p, stride, &Lp) && !(slab && p.len[1] != Lp)) return {kRouteFused2, Lp};
+    return {kRoutePerAxis, 0};
+}
+// a slab level on the fused 3-D kernel with the halo on z (what the split-halo / zero-extended slab entry points need): its Lp, else 0
+inline int slab_fused3(const SelPlan& p, long long stride, int dir, SlabMode mode) {
+    const LevelRoute r = level_route(p, stride, dir, mode);
+    return (r.kind == kRouteFused3 || (r.kind == kRouteFused3T && mode == kSlabZ)) ? r.Lp : 0;
+}
+
 // true when every synthesis level of this plan runs a kernel that can shrink its inputs on load (Inv3S / Inv3Y / Inv2S / Inv2P)
 inline bool fused_shrink_capable(const SelPlan& p) {
     if (p.atrous) return false;                                       // dilated levels take the per-axis kernels
-    int Lp = 0;
-    if (fused2_eligible(p, 1, &Lp)) return true;
-    return fused3_eligible(p, 1, &Lp) && !(p.variant_inv == kInvLds && Lp == 8);   // the LDS synthesis kernel does not
+    const LevelRoute r = level_route(p, 1, -1, kWholeArray);
+    return r.kind == kRouteFused2 || (route_fused3(r.kind) && !(p.variant_inv == kInvLds && r.Lp == 8));   // the LDS synthesis kernel does not
 }
 
 // ---- two or three levels of an image in one launch (Fwd2C / Inv2C): float real data at tap stride 1, rows of whole groups of 4

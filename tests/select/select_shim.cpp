@@ -7,17 +7,11 @@ static SelPlan plan_of(const int* v) {   // ndim, comp, f64, real, path_auto, at
     return p;
 }
 
-// which fused path a level at tap stride `stride` takes: 3 = fused 3-D, 2 = fused 2-D, 0 = neither; *dilated: through the EW sub-lattice form
-extern "C" int sel_level_path(const int* plan, int stride, int dir, int* Lp, int* dilated) {
-    const SelPlan p = plan_of(plan);
-    *dilated = 1;
-    if (fused3_dilated_eligible(p, stride, Lp)) return 3;
-    *dilated = 0;
-    if (fused3_eligible(p, stride, Lp, dir)) return 3;
-    *dilated = 1;
-    if (fused2_dilated_eligible(p, stride, Lp)) return 2;
-    *dilated = 0;
-    return fused2_eligible(p, stride, Lp) ? 2 : 0;
+// the route of a level at tap stride `stride` (dir: 0 analysis, 1 synthesis; slab: a SlabMode): its LevelRouteKind
+extern "C" int sel_level_path(const int* plan, int stride, int dir, int slab, int* Lp) {
+    const LevelRoute r = level_route(plan_of(plan), stride, dir, (SlabMode)slab);
+    *Lp = r.Lp;
+    return (int)r.kind;
 }
 
 extern "C" int sel_cascade2_levels(const int* plan, int inverse, int left) { int Lp = 0; return cascade2_levels(plan_of(plan), inverse != 0, left, &Lp); }

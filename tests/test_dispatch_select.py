@@ -18,6 +18,9 @@ NUM_CUS = 256
 NOT_IN_PICK = ("NT", "RY", "WLDS", "ZLDS")
 # rows without a fused level-1 launch in either direction (1-D signals, the per-axis path on request, double with 18 taps)
 LEFT_OUT = ["1d-vec4", "1d-ragged", "1d-c64", "1d-db7-plain", "generic-path", "f64-db9-per-axis"]
+# LevelRouteKind of csrc/ndwt_select.h
+FUSED3_DILATED, FUSED3, FUSED3_T, FUSED3_FOLD_T, FUSED2_DILATED, FUSED2, PER_AXIS = range(7)
+WHOLE_ARRAY, SLAB_OUTER, SLAB_Z = range(3)                      # SlabMode
 
 
 @pytest.fixture(scope="module")
@@ -36,6 +39,16 @@ def _ints(v):
     return (ctypes.c_int * len(v))(*[int(x) for x in v])
 
 
+def _plan(dims, lens, f64=False, cplx=False, generic=False, atrous=False, vf=0, vi=0):
+    return _ints([len(dims), 2 if cplx else 1, f64, not cplx, not generic, atrous, 1] + (list(dims) + [1] * 4)[:4] + (list(lens) + [2] * 4)[:4] + [vf, vi])
+
+
+def _route(shim, plan, stride, inverse, slab=WHOLE_ARRAY):
+    Lp = ctypes.c_int(0)
+    kind = shim.sel_level_path(plan, stride, 1 if inverse else 0, int(slab), ctypes.byref(Lp))
+    return kind, Lp.value
+
+
 def _picks(shim, row, inverse):
     """the launches of the row's dec (rec) that kernel selection decides at tap stride 1, as (family, params)"""
     dims, d = row["dims"], len(row["dims"])
@@ -43,15 +56,13 @@ def _picks(shim, row, inverse):
     lens = [2 * int(w[2:]) for w in wl]
     f64, comp = row["prec"] == "double", 2 if row["cplx"] else 1
     vf, vi = max(row["fwd"], 0), max(row["inv"], 0)
-    plan = _ints([d, comp, f64, not row["cplx"], not row["path"], row["dil"] == "atrous", 1] + (dims + [1] * 4)[:4] + (lens + [2] * 4)[:4] + [vf, vi])
+    plan = _plan(dims, lens, f64, row["cplx"], row["path"], row["dil"] == "atrous", vf, vi)
     n1 = dims[0] * comp
     vec4 = row["layout"] == "packed" and n1 % 4 == 0           # rows, band distances and pointers in whole groups of 4 scalars
     T = "double" if f64 else "float"
-    Lp, dilated = ctypes.c_int(0), ctypes.c_int(0)
-    path = shim.sel_level_path(plan, 1, 1 if inverse else 0, ctypes.byref(Lp), ctypes.byref(dilated))
-    L, out = Lp.value, []
-    if path == 3:
-        tfold = d == 4 and not inverse and vf == 7 and vec4      # (the caller's conditions for the folded t axis: analysis_level)
+    (kind, L), out = _route(shim, plan, 1, inverse), []
+    if kind in (FUSED3, FUSED3_T, FUSED3_FOLD_T):
+        tfold = kind == FUSED3_FOLD_T and vec4                   # (the caller keeps the route for 16-byte-aligned pointers only)
         q = _ints([f64, inverse, vec4, wl[1] == wl[2], tfold, L] + lens[:3] + [comp, 1, n1, dims[1], dims[3] if d == 4 else 1, vf, vi, NUM_CUS, 0])
         r = (ctypes.c_int * 10)()
         name = shim.sel_fused3(q, r).decode()
@@ -63,7 +74,7 @@ def _picks(shim, row, inverse):
         if name == "Inv3Y":
             p.update(XSC=bool(scatter), UNIYZ=bool(uniyz), DEPTH=depth)
         out.append((name, p))
-    elif path == 2:
+    elif kind == FUSED2:
         left = row["level"]
         while True:                                              # the cascaded launches, then one launch per level
             n = shim.sel_cascade2_levels(plan, inverse, left)
@@ -99,3 +110,34 @@ def test_rows_pick_their_pinned_kernels(shim):
         assert (n == 0) == (prm.id in LEFT_OUT), (prm.id, n)
         checked += n > 0
     assert checked >= 73 and checked == len(ROWS) - len(LEFT_OUT)
+
+
+# The route of a level on the whole array and on a slab, as the level functions and the slab entry points took it before level_route
+# existed (written down from their if-chains, not from running it): (dims, wavelet orders x .. t, shard axis, stride, whole, slab), the
+# same in both directions.  float real data; z-sharded plans 1 and 2 are plans of tests/test_gpu_zshard.py::test_mplan_z_slabs.
+ROUTES = [
+    ("3d-db4", [64, 64, 32], [4, 4, 4], 2, 1, FUSED3, FUSED3),
+    ("3d-mixed-z-short", [64, 64, 32], [1, 3, 2], 2, 1, FUSED3, PER_AXIS),                 # the kernel would march 5 halo planes, the slab has 3
+    ("4d-db4-on-t", [32, 32, 16, 16], [4, 4, 4, 4], 3, 1, FUSED3_T, FUSED3_T),              # t is the per-axis pass: any t filter
+    ("4d-db4-on-t-t-longest", [32, 32, 16, 16], [2, 2, 2, 4], 3, 1, FUSED3_T, FUSED3_T),
+    ("4d-db4-on-z", [24, 20, 24, 8], [4, 4, 4, 4], 2, 1, FUSED3_T, FUSED3_T),
+    ("4d-mixed-z-short-on-z", [16, 12, 14, 5], [4, 2, 3, 2], 2, 1, FUSED3_T, PER_AXIS),
+    ("4d-mixed-z-longest-on-z", [16, 12, 18, 5], [2, 3, 4, 2], 2, 1, FUSED3_T, FUSED3_T),
+    ("2d-db4", [256, 256], [4, 4], 1, 1, FUSED2, FUSED2),
+    ("2d-mixed-y-short", [256, 256], [4, 2], 1, 1, FUSED2, PER_AXIS),
+    ("3d-atrous-stride2", [64, 64, 32], [4, 4, 4], 2, 2, FUSED3_DILATED, PER_AXIS),        # no sub-lattice form on slabs
+    ("2d-atrous-stride2", [256, 256], [4, 4], 1, 2, FUSED2_DILATED, PER_AXIS),
+    ("4d-atrous-stride2-on-z", [16, 12, 24, 4], [2, 2, 2, 2], 2, 2, PER_AXIS, PER_AXIS),
+]
+
+
+@pytest.mark.parametrize("name,dims,orders,shard,stride,whole,slab", ROUTES, ids=[r[0] for r in ROUTES])
+def test_level_routes_whole_and_slab(shim, name, dims, orders, shard, stride, whole, slab):
+    lens = [2 * k for k in orders]
+    plan = _plan(dims, lens, atrous=stride > 1)
+    Lp = max(lens[:3])
+    for inverse in (False, True):
+        assert _route(shim, plan, stride, inverse) == (whole, 0 if whole == PER_AXIS else Lp), (name, inverse)
+        assert _route(shim, plan, stride, inverse, SLAB_OUTER if shard == len(dims) - 1 else SLAB_Z) == (slab, 0 if slab == PER_AXIS else Lp), (name, inverse)
+    if len(dims) == 4 and shard == 2 and stride == 1:           # test_mplan_z_slabs: "scatter-add" in describe() for reference dilation
+        assert (slab == FUSED3_T) == (lens[2] == max(lens[:3]))
