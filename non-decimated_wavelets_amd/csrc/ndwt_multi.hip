@@ -25,6 +25,18 @@
 //              results are deterministic; they equal the single-device ones to rounding, the order of summation differs).
 //              NDWT_EXCHANGE_GATHER: the halo planes of all 2^d bands are assembled with the slab in a scratch array (a copy of
 //              every band per level) -- bit-identical to one device, and the path of plans whose levels run per-axis kernels.
+//
+// How the file is built:
+//   one walk    "the planes from periodic global plane g, cut at the slabs' ends" is ndwt::for_each_run of ndwt_slabs.h (HIP-free, with the
+//               slab partition and the neighbour sets; tested on the CPU).  walk() applies it to the plan's slabs and is the only place that
+//               reports a plane without owner; every halo copy (copy_planes) and every scatter (scatter_margin, the destination side of
+//               the overlapped synthesis) is a call of it.
+//   one mover   move_planes copies or adds planes of every frame between two slabs: outermost-axis slabs (one frame) by asynchronous or
+//               peer copies and add_planes_kernel, z-slabs of a 4-D volume (nt frames) by strided segment launches or a peer copy per frame.
+//   one level loop per direction, for both kinds of slab (frame factor R, margin H): mdec_core and mrec_core work out a level's pointers
+//               once and pick its step -- DecStep: overlapped, split-halo, in-line halo; RecStep: overlapped scatter, scatter by three
+//               parts, scatter by zero-extended scratch (z-slabs), gather.  The plain scatter steps run on the caller's thread in slab
+//               order, the overlapped steps and the analysis through phase(): the order of the event records depends on it.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -42,6 +54,7 @@
 #include <unistd.h>
 
 #include "../../include/ndwt.h"
+#include "ndwt_slabs.h"
 #include "ndwt_trace.h"
 
 namespace {
@@ -235,50 +248,76 @@ static long long stride_of(const ndwt_mplan* mp, int lev) { return mp->dilation 
 
 static long long axis_len(const ndwt_mplan* mp) { return mp->dims[mp->shard]; }
 
-static Slab* owner_of(ndwt_mplan* mp, long long gp) {
-    for (auto& s : mp->slabs)
-        if (gp >= s.z0 && gp < s.z0 + s.n) return &s;
-    return nullptr;
+static bool z_slabs(const ndwt_mplan* mp) { return mp->shard != mp->ndim - 1; }
+
+static size_t index_of(const ndwt_mplan* mp, const Slab& s) { return (size_t)(&s - &mp->slabs[0]); }
+
+// band b >= 1 of level lev in a band-planar coefficient array of `level` levels (band 0: the approximation of the last level)
+static long long band_index(const ndwt_mplan* mp, int level, int lev, int b) { return 1 + (long long)(mp->nb - 1) * (level - lev) + (b - 1); }
+
+// The one walk over planes (ndwt::for_each_run of ndwt_slabs.h on the plan's slabs): the `count` planes from GLOBAL plane g (periodic) in
+// maximal runs inside one slab, fn(owner index, local plane in the owner, planes done so far, run length) -> NDWT_OK or an error.
+template <class Fn> static int walk(ndwt_mplan* mp, long long g, long long count, Fn&& fn) {
+    long long orphan = 0;
+    const int rc = ndwt::for_each_run(mp->slabs, axis_len(mp), g, count, fn, &orphan);
+    return rc == ndwt::kNoOwner ? mfail(NDWT_ERR_INVALID_ARG, "plane %lld has no owner", orphan) : rc;
 }
 
-static int copy_run(ndwt_mplan* mp, Slab& to, char* dst, const Slab& from, const char* src, long long planes, hipStream_t st = nullptr) {
-    const size_t bytes = (size_t)planes * mp->plane_bytes;
-    if (!st) st = to.stream;
-    if (from.device == to.device) MHIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
-    else MHIP(hipMemcpyPeerAsync(dst, to.device, src, from.device, bytes, st));
-    return NDWT_OK;
+// kernels on to_dev may read from_dev's memory
+static bool direct_access(const ndwt_mplan* mp, int to_dev, int from_dev) {
+    if (to_dev == from_dev) return true;
+    for (auto& pr : mp->peer)
+        if (pr.first == to_dev && pr.second == from_dev) return true;
+    return false;
 }
 
-// copy `count` planes starting at GLOBAL plane g (periodic) of a per-slab plane array into dst on slab `to`, on `to`'s stream.
-// plane_ptr(slab, local plane) gives the source address; wait_parity >= 0: wait for the source slab's ready[wait_parity] first.
-template <class SrcFn>
-static int copy_planes(ndwt_mplan* mp, Slab& to, char* dst, long long g, long long count, SrcFn plane_ptr, int wait_parity, hipStream_t st = nullptr) {
-    const long long N = axis_len(mp);
-    long long done = 0;
-    while (done < count) {
-        const long long gp = ((g + done) % N + N) % N;
-        Slab* src = owner_of(mp, gp);
-        if (!src) return mfail(NDWT_ERR_INVALID_ARG, "plane %lld has no owner", gp);
-        long long run = src->z0 + src->n - gp;
-        if (run > count - done) run = count - done;
-        if (wait_parity >= 0 && src != &to) MHIP(hipStreamWaitEvent(st ? st : to.stream, src->ready[wait_parity], 0));
-        MRET(copy_run(mp, to, dst + (size_t)done * mp->plane_bytes, *src, plane_ptr(*src, gp - src->z0), run, st));
-        done += run;
+// The one plane mover.  `planes` planes of every frame: dst (dst_fp planes per frame) = (op NDWT_SEG_COPY) or += (NDWT_SEG_ADD) src (src_fp
+// planes per frame), on `to`'s stream st.  Slabs of the outermost axis are one frame (dst_fp, src_fp unused): an asynchronous copy, a peer
+// copy between devices, or add_planes_kernel on a src in `to`'s memory.  z-slabs, nrep frames: one strided segment launch on the
+// destination's device (ndwt_slab_segments_strided: it reads the source in place where the devices are the same or have peer access),
+// else one peer copy per frame, and no add.
+static int move_planes(ndwt_mplan* mp, Slab& to, char* dst, long long dst_fp, const Slab& from, const char* src, long long src_fp,
+                       long long planes, int op, hipStream_t st) {
+    const size_t pb = mp->plane_bytes, es = mp->dtype == NDWT_F32 ? 4 : 8;
+    if (planes <= 0) return NDWT_OK;
+    if (mp->nrep == 1 && op == NDWT_SEG_COPY) {
+        const size_t bytes = (size_t)planes * pb;
+        if (from.device == to.device) MHIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st));
+        else MHIP(hipMemcpyPeerAsync(dst, to.device, src, from.device, bytes, st));
+        return NDWT_OK;
     }
+    if (mp->nrep == 1) {
+        const long long n = (long long)((size_t)planes * pb / es);
+        long long blocks = (n + 255) / 256;
+        if (blocks > 256 * 32) blocks = 256 * 32;
+        ndwt::trace_plain(dim3((unsigned)blocks), dim3(256), "add_planes_kernel", mp->dtype == NDWT_F32 ? "float" : "double");
+        if (mp->dtype == NDWT_F32) hipLaunchKernelGGL(add_planes_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, st, (float*)dst, (const float*)src, n);
+        else hipLaunchKernelGGL(add_planes_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, st, (double*)dst, (const double*)src, n);
+        MHIP(hipGetLastError());
+        return NDWT_OK;
+    }
+    if (direct_access(mp, to.device, from.device)) {
+        const long long spp = (long long)(pb / es);       // scalars per plane
+        void* d[1] = {dst};
+        const void* sr[1] = {src};
+        const int64_t cnt = planes * spp, ds = dst_fp * spp, ss = src_fp * spp;
+        MTRY(ndwt_slab_segments_strided(to.plan, op, 1, d, sr, &cnt, mp->nrep, &ds, &ss, st));
+        return NDWT_OK;
+    }
+    if (op != NDWT_SEG_COPY) return mfail(NDWT_ERR_UNSUPPORTED, "internal: adds across devices without peer access are staged");
+    for (long long q = 0; q < mp->nrep; ++q)
+        MHIP(hipMemcpyPeerAsync(dst + (size_t)(q * dst_fp) * pb, to.device, src + (size_t)(q * src_fp) * pb, from.device, (size_t)planes * pb, st));
     return NDWT_OK;
 }
 
-static int add_planes(ndwt_mplan* mp, Slab& s, char* dst, const char* src, long long planes) {
-    const size_t es = mp->dtype == NDWT_F32 ? 4 : 8;
-    const long long n = (long long)((size_t)planes * mp->plane_bytes / es);
-    long long blocks = (n + 255) / 256;
-    if (blocks > 256 * 32) blocks = 256 * 32;
-    if (blocks < 1) return NDWT_OK;
-    ndwt::trace_plain(dim3((unsigned)blocks), dim3(256), "add_planes_kernel", mp->dtype == NDWT_F32 ? "float" : "double");
-    if (mp->dtype == NDWT_F32) hipLaunchKernelGGL(add_planes_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, s.stream, (float*)dst, (const float*)src, n);
-    else hipLaunchKernelGGL(add_planes_kernel<double>, dim3((unsigned)blocks), dim3(256), 0, s.stream, (double*)dst, (const double*)src, n);
-    MHIP(hipGetLastError());
-    return NDWT_OK;
+// copy `count` planes starting at GLOBAL plane g (periodic) of a per-slab plane array into dst (dst_fp planes per frame) on slab `to`, on
+// `to`'s stream st.  plane_ptr(slab, local plane) = the source address in frame 0 of that slab's array (n planes per frame).
+template <class SrcFn>
+static int copy_planes(ndwt_mplan* mp, Slab& to, char* dst, long long dst_fp, long long g, long long count, SrcFn plane_ptr, hipStream_t st) {
+    return walk(mp, g, count, [&](size_t o, long long lp, long long done, long long run) -> int {
+        Slab& src = mp->slabs[o];
+        return move_planes(mp, to, dst + (size_t)done * mp->plane_bytes, dst_fp, src, plane_ptr(src, lp), src.n, run, NDWT_SEG_COPY, st);
+    });
 }
 
 // The level barrier between slabs (events only, the host does not block): every stream waits for ready[k] of the slabs within halo reach of
@@ -317,8 +356,9 @@ static int sync_all(ndwt_mplan* mp) {
 }
 
 // the overlapped schedules cut a slab into the planes that need no neighbour and the rest: every slab must be thick enough for that
+// (z-slabs have no run-of-planes entry points: the overlapped schedule is not offered)
 static bool can_overlap(const ndwt_mplan* mp, long long before, long long after) {
-    if (!mp->overlap || !mp->fast) return false;
+    if (!mp->overlap || !mp->fast || z_slabs(mp)) return false;
     const long long m = before > after ? before : after;
     for (auto& s : mp->slabs)
         if (s.n < 2 * m + 1 || s.n <= before + after) return false;
@@ -339,74 +379,82 @@ static int mcheck(const ndwt_mplan* mp, int level) {
     return NDWT_OK;
 }
 
+// Both level loops serve both kinds of slab.  A slab of the outermost axis is one frame (R = 1) and its approximation buffers are
+// [halo_max | n | halo_max] planes: the slab sits behind a margin of H = halo_max planes that takes the neighbours' planes in line.  A z-slab
+// of a 4-D volume holds all nt frames of its planes, (nt, n, ny, nx) per band: a plane index of the sharded axis is R = nrep = nt runs of
+// plane_bytes, frame q of a slab's array at q * n planes, and its buffers carry no margin (H = 0; the halo planes travel in hb / ha).
+
 // ------------------------------------------------------------------------------------------------ analysis
 // x[i]: the slab of the signal on slab i's device (n_i planes); y[i]: its coefficient slab, band b at b * n_i planes.  Queues the
 // whole transform on the slabs' streams; the caller synchronises.
-static int mdec_core_z(ndwt_mplan* mp, const void* const* x, void* const* y, int level);
+enum class DecStep {
+    Overlapped,   // halo planes on the copy stream while the planes that need none of them are computed, then the two ends
+    SplitHalo,    // halo planes into hb / ha, the slab read where it lies (z-slabs: every level; outermost axis: the caller's x at level 1)
+    InlineHalo    // halo planes into the margins of the approximation buffer, in line with the slab
+};
+
 static int mdec_core(ndwt_mplan* mp, const void* const* x, void* const* y, int level) {
-    if (mp->shard != mp->ndim - 1) return mdec_core_z(mp, x, y, level);
     const size_t pb = mp->plane_bytes;
-    const long long H = mp->halo_max;
+    const long long R = mp->nrep, H = z_slabs(mp) ? 0 : mp->halo_max;
     const int nb = mp->nb;
     for (int lev = 1; lev <= level; ++lev) {
         const long long st = stride_of(mp, lev);
-        const long long ab = (long long)(mp->L_outer / 2 - 1) * st, aa = (long long)(mp->L_outer / 2) * st;
+        const long long ab = (long long)(mp->L_outer / 2 - 1) * st, aa = (long long)(mp->L_outer / 2) * st, m = ab > aa ? ab : aa;
         // level lev reads approx[rd] (level 1: the caller's x) and writes its approximation into approx[wr] (the last level: band 0 of y)
         const int rd = ((lev - 1) & 1) ^ 1, wr = (lev - 1) & 1;
+        const DecStep step = z_slabs(mp)                      ? DecStep::SplitHalo
+                             : st == 1 && can_overlap(mp, ab, aa) ? DecStep::Overlapped
+                             : lev == 1 && mp->fast && st == 1    ? DecStep::SplitHalo
+                                                                  : DecStep::InlineHalo;
+        // the level's input on a slab, and the source of its halo planes: the neighbours' inputs (produced in place by level lev - 1;
+        // the producers were waited for at the end of that level)
+        auto input = [&](Slab& o) -> const char* { return lev == 1 ? (const char*)x[index_of(mp, o)] : o.approx[rd] + (size_t)H * pb; };
+        auto src = [&](Slab& o, long long lp) -> const char* { return input(o) + (size_t)lp * pb; };
         // one slab's work of this level (its copies out of the neighbours' buffers, its launches) and the record of its ready[wr]
         auto body = [&](size_t i) -> int {
             Slab& s = mp->slabs[i];
             MHIP(hipSetDevice(s.device));
             void* outs[16];
             outs[0] = lev == level ? y[i] : (void*)(s.approx[wr] + (size_t)H * pb);
-            for (int b = 1; b < nb; ++b) outs[b] = (char*)y[i] + (size_t)((1 + (nb - 1) * (level - lev) + (b - 1)) * s.n) * pb;
-            const bool ov = st == 1 && can_overlap(mp, ab, aa);
-            const long long m = ab > aa ? ab : aa;
-            if (ov) {
-                // halo planes on the copy stream; the planes [ab, n - aa) that need none of them meanwhile; then the two ends
+            for (int b = 1; b < nb; ++b) outs[b] = (char*)y[i] + (size_t)(band_index(mp, level, lev, b) * R * s.n) * pb;
+            const char* in = input(s);
+            char* mid = s.approx[rd] + (size_t)H * pb;         // the margins before and after it take the neighbours' planes
+            switch (step) {
+            case DecStep::Overlapped: {
+                // the caller's x has no margins around it: its halo planes go to hb / ha
+                char* hb = lev == 1 ? s.hb : mid - (size_t)ab * pb;
+                char* ha = lev == 1 ? s.ha : mid + (size_t)s.n * pb;
                 void* oi[16];
                 for (int b = 0; b < nb; ++b) oi[b] = (char*)outs[b] + (size_t)ab * pb;
-                if (lev == 1) {
-                    auto src = [&](Slab& o, long long lp) -> const char* { return (const char*)x[&o - &mp->slabs[0]] + (size_t)lp * pb; };
-                    const char* xs = (const char*)x[i];
-                    MRET(copy_planes(mp, s, s.hb, s.z0 - ab, ab, src, -1, s.cstream));
-                    MRET(copy_planes(mp, s, s.ha, s.z0 + s.n, aa, src, -1, s.cstream));
-                    MHIP(hipEventRecord(s.copied, s.cstream));
-                    MTRY(ndwt_analysis_level_slab_part(s.plan, xs + (size_t)ab * pb, ab ? xs : nullptr, xs + (size_t)(s.n - aa) * pb, oi, 1, s.n - ab - aa, s.stream));
-                    MHIP(hipStreamWaitEvent(s.stream, s.copied, 0));
-                    // the slab of x is the caller's (no margins around it): the ends are two launches, halo planes from hb / ha
-                    MTRY(ndwt_analysis_level_slab_part(s.plan, xs, ab ? s.hb : nullptr, xs + (size_t)m * pb, outs, 1, m, s.stream));
+                MRET(copy_planes(mp, s, hb, ab, s.z0 - ab, ab, src, s.cstream));
+                MRET(copy_planes(mp, s, ha, aa, s.z0 + s.n, aa, src, s.cstream));
+                MHIP(hipEventRecord(s.copied, s.cstream));
+                MTRY(ndwt_analysis_level_slab_part(s.plan, in + (size_t)ab * pb, ab ? in : nullptr, in + (size_t)(s.n - aa) * pb, oi, 1, s.n - ab - aa, s.stream));
+                MHIP(hipStreamWaitEvent(s.stream, s.copied, 0));
+                if (lev == 1) {                               // the ends are two launches, halo planes from hb / ha
+                    MTRY(ndwt_analysis_level_slab_part(s.plan, in, ab ? s.hb : nullptr, in + (size_t)m * pb, outs, 1, m, s.stream));
                     void* oe[16];
                     for (int b = 0; b < nb; ++b) oe[b] = (char*)outs[b] + (size_t)(s.n - m) * pb;
-                    MTRY(ndwt_analysis_level_slab_part(s.plan, xs + (size_t)(s.n - m) * pb, ab ? xs + (size_t)(s.n - m - ab) * pb : nullptr, s.ha, oe, 1, m, s.stream));
+                    MTRY(ndwt_analysis_level_slab_part(s.plan, in + (size_t)(s.n - m) * pb, ab ? in + (size_t)(s.n - m - ab) * pb : nullptr, s.ha, oe, 1, m, s.stream));
                 } else {
-                    char* mid = s.approx[rd] + (size_t)H * pb;
-                    auto src = [&](Slab& o, long long lp) -> const char* { return o.approx[rd] + (size_t)(H + lp) * pb; };
-                    MRET(copy_planes(mp, s, mid - (size_t)ab * pb, s.z0 - ab, ab, src, -1, s.cstream));
-                    MRET(copy_planes(mp, s, mid + (size_t)s.n * pb, s.z0 + s.n, aa, src, -1, s.cstream));
-                    MHIP(hipEventRecord(s.copied, s.cstream));
-                    MTRY(ndwt_analysis_level_slab_part(s.plan, mid + (size_t)ab * pb, ab ? mid : nullptr, mid + (size_t)(s.n - aa) * pb, oi, 1, s.n - ab - aa, s.stream));
-                    MHIP(hipStreamWaitEvent(s.stream, s.copied, 0));
                     MTRY(ndwt_analysis_level_slab_runs(s.plan, mid - (size_t)ab * pb, outs, 1, m, 2, s.n - m, s.stream));   // both ends, one launch
                 }
-            } else if (lev == 1) {
-                // the slab of x is read where it lies; its halo planes come from the neighbours' slabs of x
-                auto src = [&](Slab& o, long long lp) -> const char* { return (const char*)x[&o - &mp->slabs[0]] + (size_t)lp * pb; };
-                if (mp->fast && st == 1) {
-                    MRET(copy_planes(mp, s, s.hb, s.z0 - ab, ab, src, -1));
-                    MRET(copy_planes(mp, s, s.ha, s.z0 + s.n, aa, src, -1));
-                    MTRY(ndwt_analysis_level_slab_split(s.plan, x[i], ab ? s.hb : nullptr, s.ha, outs, 1, s.stream));
-                } else {                                  // kernels that want the halo planes in line with the slab: one copy of the slab
-                    char* mid = s.approx[rd] + (size_t)H * pb;
-                    MRET(copy_planes(mp, s, mid - (size_t)ab * pb, s.z0 - ab, ab + s.n + aa, src, -1));
-                    MTRY(ndwt_analysis_level_slab(s.plan, mid - (size_t)ab * pb, outs, (int)st, s.stream));
+                break;
+            }
+            case DecStep::SplitHalo:
+                MRET(copy_planes(mp, s, s.hb, ab, s.z0 - ab, ab, src, s.stream));
+                MRET(copy_planes(mp, s, s.ha, aa, s.z0 + s.n, aa, src, s.stream));
+                MTRY(ndwt_analysis_level_slab_split(s.plan, in, ab ? s.hb : nullptr, s.ha, outs, (int)st, s.stream));
+                break;
+            case DecStep::InlineHalo:
+                if (lev == 1) {                               // kernels that want the halo planes in line with the slab: one copy of the slab of x
+                    MRET(copy_planes(mp, s, mid - (size_t)ab * pb, 0, s.z0 - ab, ab + s.n + aa, src, s.stream));
+                } else {
+                    MRET(copy_planes(mp, s, mid - (size_t)ab * pb, 0, s.z0 - ab, ab, src, s.stream));
+                    MRET(copy_planes(mp, s, mid + (size_t)s.n * pb, 0, s.z0 + s.n, aa, src, s.stream));
                 }
-            } else {
-                char* mid = s.approx[rd] + (size_t)H * pb;   // produced in place by level lev - 1; the margins take the neighbours' planes
-                auto src = [&](Slab& o, long long lp) -> const char* { return o.approx[rd] + (size_t)(H + lp) * pb; };
-                MRET(copy_planes(mp, s, mid - (size_t)ab * pb, s.z0 - ab, ab, src, -1));   // (producers: waited for at the end of level lev - 1)
-                MRET(copy_planes(mp, s, mid + (size_t)s.n * pb, s.z0 + s.n, aa, src, -1));
                 MTRY(ndwt_analysis_level_slab(s.plan, mid - (size_t)ab * pb, outs, (int)st, s.stream));
+                break;
             }
             return barrier_record(mp, i, wr);
         };
@@ -419,59 +467,65 @@ static int mdec_core(ndwt_mplan* mp, const void* const* x, void* const* y, int l
 }
 
 // ----------------------------------------------------------------------------------------------- synthesis
-// partial sums of `count` planes starting at global plane g (periodic), held in `buf` on slab `from`: to their owners, added there.
-// dst_of(slab) = where that slab's n planes of this level's result live.
+// partial sums of `count` planes starting at global plane g (periodic), held in `buf` on slab `from` (src_fp planes per frame): to their
+// owners, added there.  dst_of(slab) = where that slab's n planes of this level's result live.
 template <class DstFn>
-static int scatter_margin(ndwt_mplan* mp, Slab& from, const char* buf, long long g, long long count, DstFn dst_of) {
-    const long long N = axis_len(mp);
-    long long done = 0;
-    while (done < count) {
-        const long long gp = ((g + done) % N + N) % N;
-        Slab* to = owner_of(mp, gp);
-        if (!to) return mfail(NDWT_ERR_INVALID_ARG, "plane %lld has no owner", gp);
-        long long run = to->z0 + to->n - gp;
-        if (run > count - done) run = count - done;
-        MHIP(hipSetDevice(to->device));
-        if (to != &from) MHIP(hipStreamWaitEvent(to->stream, from.margins, 0));
-        const char* src = buf + (size_t)done * mp->plane_bytes;
-        char* dst = dst_of(*to) + (size_t)(gp - to->z0) * mp->plane_bytes;
-        if (to->device == from.device) {                  // same memory: add straight from the producer's buffer
-            MRET(add_planes(mp, *to, dst, src, run));
-        } else {
-            MRET(copy_run(mp, *to, to->recv, from, src, run));
-            MRET(add_planes(mp, *to, dst, to->recv, run));
-        }
-        done += run;
-    }
-    return NDWT_OK;
+static int scatter_margin(ndwt_mplan* mp, Slab& from, const char* buf, long long src_fp, long long g, long long count, DstFn dst_of) {
+    const size_t pb = mp->plane_bytes;
+    return walk(mp, g, count, [&](size_t o, long long lp, long long done, long long run) -> int {
+        Slab& to = mp->slabs[o];
+        MHIP(hipSetDevice(to.device));
+        if (&to != &from) MHIP(hipStreamWaitEvent(to.stream, from.margins, 0));
+        const char* src = buf + (size_t)done * pb;
+        char* dst = dst_of(to) + (size_t)lp * pb;
+        // add straight from the producer's buffer where the adding kernel can read it: the same memory, or (the segment kernel of z-slabs) a peer's
+        if (mp->nrep > 1 ? direct_access(mp, to.device, from.device) : to.device == from.device)
+            return move_planes(mp, to, dst, to.n, from, src, src_fp, run, NDWT_SEG_ADD, to.stream);
+        MRET(move_planes(mp, to, to.recv, run, from, src, src_fp, run, NDWT_SEG_COPY, to.stream));   // staged: into the receive buffer, added from there
+        return move_planes(mp, to, dst, to.n, to, to.recv, run, run, NDWT_SEG_ADD, to.stream);
+    });
 }
 
-static int mrec_core_z(ndwt_mplan* mp, const void* const* y, void* const* x, int level);
+enum class RecStep {
+    OverlappedScatter,   // the margins first, travelling on the destinations' copy streams while every slab synthesises its own planes
+    ScatterParts,        // zero-extended synthesis in three parts: the slab's own planes in place, the margins into mb / ma
+    ScatterExt,          // z-slabs: zero-extended synthesis into the slab's scratch, its own planes copied out
+    Gather               // the halo planes of all bands assembled with the slab in the scratch
+};
+
 static int mrec_core(ndwt_mplan* mp, const void* const* y, void* const* x, int level) {
-    if (mp->shard != mp->ndim - 1) return mrec_core_z(mp, y, x, level);
     const size_t pb = mp->plane_bytes;
-    const long long H = mp->halo_max;
+    const long long R = mp->nrep, H = z_slabs(mp) ? 0 : mp->halo_max;
     const int nb = mp->nb;
+    const long long smax = mp->dilation == NDWT_DILATION_ATROUS ? (1LL << (mp->max_level - 1)) : 1LL;
     for (int ind = 1; ind <= level; ++ind) {
         const int lev = level - ind + 1;
         const long long st = stride_of(mp, lev);
-        const long long sb = (long long)(mp->L_outer / 2) * st, sa = (long long)(mp->L_outer / 2 - 1) * st;
+        const long long sb = (long long)(mp->L_outer / 2) * st, sa = (long long)(mp->L_outer / 2 - 1) * st, m = sa > sb ? sa : sb;
         const int rd = ind & 1, wr = rd ^ 1;             // level index ind > 1 reads the approximation level ind - 1 wrote into approx[rd]
         const bool scatter = mp->exchange == NDWT_EXCHANGE_SCATTER && mp->fast && st == 1;
-        auto band_ptr = [&](size_t i, Slab& o, int b) -> const char* {
-            if (b == 0) return ind == 1 ? (const char*)y[i] : o.approx[rd] + (size_t)H * pb;
-            return (const char*)y[i] + (size_t)((1 + (long long)(nb - 1) * (level - lev) + (b - 1)) * o.n) * pb;
+        const RecStep step = !scatter                 ? RecStep::Gather
+                             : z_slabs(mp)            ? RecStep::ScatterExt
+                             : can_overlap(mp, sa, sb) ? RecStep::OverlappedScatter
+                                                       : RecStep::ScatterParts;
+        auto band_ptr = [&](Slab& o, int b) -> const char* {
+            const char* yo = (const char*)y[index_of(mp, o)];
+            if (b == 0) return ind == 1 ? yo : o.approx[rd] + (size_t)H * pb;
+            return yo + (size_t)(band_index(mp, level, lev, b) * R * o.n) * pb;
         };
-        auto dst_of = [&](Slab& o) -> char* { return lev == 1 ? (char*)x[&o - &mp->slabs[0]] : o.approx[wr] + (size_t)H * pb; };
-        if (scatter && can_overlap(mp, sa, sb)) {
+        auto dst_of = [&](Slab& o) -> char* { return lev == 1 ? (char*)x[index_of(mp, o)] : o.approx[wr] + (size_t)H * pb; };
+        // the scratch of a slab: 2^d bands of its planes with their halo planes (z-slabs: their zero-extended result too), allocated on first use
+        if (step == RecStep::Gather || step == RecStep::ScatterExt)
+            for (auto& s : mp->slabs) MRET(lazy_alloc(s, &s.gather, (size_t)((long long)nb * R * (s.n + (long long)(mp->L_outer - 1) * smax)) * pb));
+        switch (step) {
+        case RecStep::OverlappedScatter:
             // margins first (one launch: two runs of m planes at the ends of the zero-extended result), so that they travel -- on the
             // destinations' copy streams -- while every slab synthesises its own planes; the adds follow that launch in stream order
-            const long long m = sa > sb ? sa : sb;
             MRET(phase(mp, [&](size_t i) -> int {
                 Slab& s = mp->slabs[i];
                 MHIP(hipSetDevice(s.device));
                 const void* ins[16];
-                for (int b = 0; b < nb; ++b) ins[b] = band_ptr(i, s, b);
+                for (int b = 0; b < nb; ++b) ins[b] = band_ptr(s, b);
                 MTRY(ndwt_synthesis_level_slab_runs(s.plan, ins, s.n, 0, s.n + sa + sb - m, 2, m, s.mb, 1, s.stream));   // mb: [run 0 | run 1]
                 MHIP(hipEventRecord(s.margins, s.stream));
                 MTRY(ndwt_synthesis_level_slab_part(s.plan, ins, s.n, sa, s.n, dst_of(s), 1, s.stream));
@@ -483,7 +537,6 @@ static int mrec_core(ndwt_mplan* mp, const void* const* y, void* const* x, int l
             // "before" margins first, behind the destination's own launch: the same fixed order of summation as without overlap.
             // Every DESTINATION slab queues what arrives at it (its own streams only): the producers' margins events were recorded in the
             // phase above.  The record of its ready[wr] (level barrier) closes the phase.
-            const long long N = axis_len(mp);
             MRET(phase(mp, [&](size_t ti) -> int {
                 Slab& t = mp->slabs[ti];
                 MHIP(hipSetDevice(t.device));
@@ -492,221 +545,61 @@ static int mrec_core(ndwt_mplan* mp, const void* const* y, void* const* x, int l
                 t.recv_used = 0;
                 for (auto& from : mp->slabs) {
                     for (int side = 0; side < 2; ++side) {
-                        const long long count = side == 0 ? sa : sb;
-                        const long long g = side == 0 ? from.z0 - sa : from.z0 + from.n;
                         const char* buf = side == 0 ? from.mb : from.mb + (size_t)(m + (m - sb)) * pb;
-                        long long done = 0;
-                        while (done < count) {
-                            const long long gp = ((g + done) % N + N) % N;
-                            Slab* to = owner_of(mp, gp);
-                            if (!to) return mfail(NDWT_ERR_INVALID_ARG, "plane %lld has no owner", gp);
-                            long long run = to->z0 + to->n - gp;
-                            if (run > count - done) run = count - done;
-                            if (to == &t) {
-                                const char* src = buf + (size_t)done * pb;
-                                char* dst = dst_of(t) + (size_t)(gp - t.z0) * pb;
-                                if (t.device != from.device || mp->overlap == 2) {   // (2: test hook -- the staged path between slabs of one device)
-                                    if (t.recv_used + run > 2 * H) return mfail(NDWT_ERR_UNSUPPORTED, "internal: receive buffer of the overlapped synthesis exhausted");
-                                    char* rb = t.recv + (size_t)t.recv_used * pb;
-                                    t.recv_used += run;
-                                    MHIP(hipStreamWaitEvent(t.cstream, from.margins, 0));
-                                    MRET(copy_run(mp, t, rb, from, src, run, t.cstream));
-                                    src = rb;
-                                } else if (&t != &from) {
-                                    MHIP(hipStreamWaitEvent(t.stream, from.margins, 0));   // same memory: added straight from the producer's buffer
-                                }
-                                adds.push_back({dst, src, run});
+                        MRET(walk(mp, side == 0 ? from.z0 - sa : from.z0 + from.n, side == 0 ? sa : sb,
+                                  [&](size_t o, long long lp, long long done, long long run) -> int {
+                            if (o != ti) return NDWT_OK;
+                            const char* src = buf + (size_t)done * pb;
+                            char* dst = dst_of(t) + (size_t)lp * pb;
+                            if (t.device != from.device || mp->overlap == 2) {   // (2: test hook -- the staged path between slabs of one device)
+                                if (t.recv_used + run > 2 * mp->halo_max) return mfail(NDWT_ERR_UNSUPPORTED, "internal: receive buffer of the overlapped synthesis exhausted");
+                                char* rb = t.recv + (size_t)t.recv_used * pb;
+                                t.recv_used += run;
+                                MHIP(hipStreamWaitEvent(t.cstream, from.margins, 0));
+                                MRET(move_planes(mp, t, rb, run, from, src, run, run, NDWT_SEG_COPY, t.cstream));
+                                src = rb;
+                            } else if (&t != &from) {
+                                MHIP(hipStreamWaitEvent(t.stream, from.margins, 0));   // same memory: added straight from the producer's buffer
                             }
-                            done += run;
-                        }
+                            adds.push_back({dst, src, run});
+                            return NDWT_OK;
+                        }));
                     }
                 }
                 MHIP(hipEventRecord(t.copied, t.cstream));
                 MHIP(hipStreamWaitEvent(t.stream, t.copied, 0));
-                for (auto& a : adds) MRET(add_planes(mp, t, a.dst, a.src, a.run));
+                for (auto& a : adds) MRET(move_planes(mp, t, a.dst, t.n, t, a.src, a.run, a.run, NDWT_SEG_ADD, t.stream));
                 return barrier_record(mp, ti, wr);
             }));
             MRET(phase(mp, [&](size_t i) { return barrier_wait(mp, i, wr); }));
             continue;
-        } else if (scatter) {
+        case RecStep::ScatterParts:
+        case RecStep::ScatterExt:
             // zero-extended synthesis: plane k of the extended result = global plane z0 - sa + k.  The slab's own n planes go where
             // the result lives; the sa planes before and the sb planes after it are partial sums owed to their owners.
-            size_t i = 0;
             for (auto& s : mp->slabs) {
                 MHIP(hipSetDevice(s.device));
                 const void* ins[16];
-                for (int b = 0; b < nb; ++b) ins[b] = band_ptr(i, s, b);
-                MTRY(ndwt_synthesis_level_slab_part(s.plan, ins, s.n, sa, s.n, dst_of(s), 1, s.stream));
-                if (sa) MTRY(ndwt_synthesis_level_slab_part(s.plan, ins, s.n, 0, sa, s.mb, 1, s.stream));
-                MTRY(ndwt_synthesis_level_slab_part(s.plan, ins, s.n, sa + s.n, sb, s.ma, 1, s.stream));
+                for (int b = 0; b < nb; ++b) ins[b] = band_ptr(s, b);
+                if (step == RecStep::ScatterExt) {            // the whole extended result in the scratch, (nt, sa + n + sb) planes
+                    MTRY(ndwt_synthesis_level_slab_ext(s.plan, ins, s.gather, 1, s.stream));
+                    MRET(move_planes(mp, s, dst_of(s), s.n, s, s.gather + (size_t)sa * pb, s.n + sa + sb, s.n, NDWT_SEG_COPY, s.stream));
+                } else {
+                    MTRY(ndwt_synthesis_level_slab_part(s.plan, ins, s.n, sa, s.n, dst_of(s), 1, s.stream));
+                    if (sa) MTRY(ndwt_synthesis_level_slab_part(s.plan, ins, s.n, 0, sa, s.mb, 1, s.stream));
+                    MTRY(ndwt_synthesis_level_slab_part(s.plan, ins, s.n, sa + s.n, sb, s.ma, 1, s.stream));
+                }
                 MHIP(hipEventRecord(s.margins, s.stream));
-                ++i;
             }
             // a destination's own planes are written by its own stream before anything is added to them (stream order); the addends
             // arrive in slab order, "before" margins first: a fixed order of summation
             for (auto& s : mp->slabs) {
-                if (sa) MRET(scatter_margin(mp, s, s.mb, s.z0 - sa, sa, dst_of));
-                MRET(scatter_margin(mp, s, s.ma, s.z0 + s.n, sb, dst_of));
+                const bool ext = step == RecStep::ScatterExt;
+                MRET(scatter_margin(mp, s, ext ? s.gather : s.mb, s.n + sa + sb, s.z0 - sa, sa, dst_of));
+                MRET(scatter_margin(mp, s, ext ? s.gather + (size_t)(sa + s.n) * pb : s.ma, s.n + sa + sb, s.z0 + s.n, sb, dst_of));
             }
-        } else {
-            for (auto& s : mp->slabs) {
-                MHIP(hipSetDevice(s.device));
-                const long long nh = s.n + sb + sa;
-                const long long smax = mp->dilation == NDWT_DILATION_ATROUS ? (1LL << (mp->max_level - 1)) : 1LL;
-                MRET(lazy_alloc(s, &s.gather, (size_t)((long long)nb * (s.n + (long long)(mp->L_outer - 1) * smax)) * pb));
-                const void* ins[16];
-                for (int b = 0; b < nb; ++b) {
-                    char* dst = s.gather + (size_t)((long long)b * nh) * pb;
-                    ins[b] = dst;
-                    auto src = [&, b](Slab& o, long long lp) -> const char* { return band_ptr(&o - &mp->slabs[0], o, b) + (size_t)lp * pb; };
-                    MRET(copy_planes(mp, s, dst, s.z0 - sb, nh, src, -1));   // all producers were waited for at the end of the previous level
-                }
-                MTRY(ndwt_synthesis_level_slab(s.plan, ins, dst_of(s), (int)st, s.stream));
-            }
-        }
-        MRET(level_barrier(mp, wr));
-    }
-    return NDWT_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ z-slabs
-// A 4-D volume sharded on z: every slab holds all nt frames of its planes, (nt, n, ny, nx) per band.  A plane index of the sharded axis is
-// nrep = nt runs of plane_bytes, frame q of a slab's array at q * n planes.  Moving planes between slabs is one strided segment launch per
-// run of planes (ndwt_slab_segments_strided on the destination's device: it reads the source in place where the devices are the same or
-// have peer access), else one peer copy per frame.  The levels run the z-slab entry points (split-halo analysis, zero-extended or gathered
-// synthesis); the overlapped schedule is not offered.
-static bool direct_access(const ndwt_mplan* mp, int to_dev, int from_dev) {
-    if (to_dev == from_dev) return true;
-    for (auto& pr : mp->peer)
-        if (pr.first == to_dev && pr.second == from_dev) return true;
-    return false;
-}
-
-// `planes` planes of every frame: dst (dst_fp planes per frame) = / += src (src_fp planes per frame), on `to`'s stream st
-static int copy_frames(ndwt_mplan* mp, Slab& to, char* dst, long long dst_fp, const Slab& from, const char* src, long long src_fp,
-                       long long planes, int op, hipStream_t st) {
-    const size_t pb = mp->plane_bytes;
-    if (planes <= 0) return NDWT_OK;
-    if (direct_access(mp, to.device, from.device)) {
-        const long long spp = (long long)(pb / (mp->dtype == NDWT_F32 ? 4 : 8));   // scalars per plane
-        void* d[1] = {dst};
-        const void* sr[1] = {src};
-        const int64_t cnt = planes * spp, ds = dst_fp * spp, ss = src_fp * spp;
-        MTRY(ndwt_slab_segments_strided(to.plan, op, 1, d, sr, &cnt, mp->nrep, &ds, &ss, st));
-        return NDWT_OK;
-    }
-    if (op != NDWT_SEG_COPY) return mfail(NDWT_ERR_UNSUPPORTED, "internal: adds across devices without peer access are staged");
-    for (long long q = 0; q < mp->nrep; ++q)
-        MHIP(hipMemcpyPeerAsync(dst + (size_t)(q * dst_fp) * pb, to.device, src + (size_t)(q * src_fp) * pb, from.device, (size_t)planes * pb, st));
-    return NDWT_OK;
-}
-
-// `count` planes starting at GLOBAL plane g (periodic) into dst (dst_fp planes per frame) on slab `to`; plane_ptr(slab, local plane) =
-// the source address in frame 0 of that slab's array (n planes per frame)
-template <class SrcFn>
-static int copy_planes_z(ndwt_mplan* mp, Slab& to, char* dst, long long dst_fp, long long g, long long count, SrcFn plane_ptr) {
-    const long long N = axis_len(mp);
-    long long done = 0;
-    while (done < count) {
-        const long long gp = ((g + done) % N + N) % N;
-        Slab* src = owner_of(mp, gp);
-        if (!src) return mfail(NDWT_ERR_INVALID_ARG, "plane %lld has no owner", gp);
-        long long run = src->z0 + src->n - gp;
-        if (run > count - done) run = count - done;
-        MRET(copy_frames(mp, to, dst + (size_t)done * mp->plane_bytes, dst_fp, *src, plane_ptr(*src, gp - src->z0), src->n, run, NDWT_SEG_COPY, to.stream));
-        done += run;
-    }
-    return NDWT_OK;
-}
-
-static int mdec_core_z(ndwt_mplan* mp, const void* const* x, void* const* y, int level) {
-    const size_t pb = mp->plane_bytes;
-    const long long R = mp->nrep;
-    const int nb = mp->nb;
-    for (int lev = 1; lev <= level; ++lev) {
-        const long long st = stride_of(mp, lev);
-        const long long ab = (long long)(mp->L_outer / 2 - 1) * st, aa = (long long)(mp->L_outer / 2) * st;
-        const int rd = ((lev - 1) & 1) ^ 1, wr = (lev - 1) & 1;
-        auto input = [&](Slab& o) -> const char* { return lev == 1 ? (const char*)x[&o - &mp->slabs[0]] : o.approx[rd]; };
-        auto body = [&](size_t i) -> int {
-            Slab& s = mp->slabs[i];
-            MHIP(hipSetDevice(s.device));
-            void* outs[16];
-            outs[0] = lev == level ? y[i] : (void*)s.approx[wr];
-            for (int b = 1; b < nb; ++b) outs[b] = (char*)y[i] + (size_t)((1 + (nb - 1) * (level - lev) + (b - 1)) * R * s.n) * pb;
-            // the halo planes of every frame from their owners' inputs of this level (producers: waited for at the end of level lev - 1)
-            auto src = [&](Slab& o, long long lp) -> const char* { return input(o) + (size_t)lp * pb; };
-            MRET(copy_planes_z(mp, s, s.hb, ab, s.z0 - ab, ab, src));
-            MRET(copy_planes_z(mp, s, s.ha, aa, s.z0 + s.n, aa, src));
-            MTRY(ndwt_analysis_level_slab_split(s.plan, input(s), ab ? s.hb : nullptr, s.ha, outs, (int)st, s.stream));
-            return barrier_record(mp, i, wr);
-        };
-        MRET(phase(mp, body));
-        MRET(phase(mp, [&](size_t i) { return barrier_wait(mp, i, wr); }));
-    }
-    return NDWT_OK;
-}
-
-static int mrec_core_z(ndwt_mplan* mp, const void* const* y, void* const* x, int level) {
-    const size_t pb = mp->plane_bytes;
-    const long long R = mp->nrep, N = axis_len(mp);
-    const int nb = mp->nb;
-    const long long smax = mp->dilation == NDWT_DILATION_ATROUS ? (1LL << (mp->max_level - 1)) : 1LL;
-    for (int ind = 1; ind <= level; ++ind) {
-        const int lev = level - ind + 1;
-        const long long st = stride_of(mp, lev);
-        const long long sb = (long long)(mp->L_outer / 2) * st, sa = (long long)(mp->L_outer / 2 - 1) * st;
-        const int rd = ind & 1, wr = rd ^ 1;
-        const bool scatter = mp->exchange == NDWT_EXCHANGE_SCATTER && mp->fast && st == 1;
-        auto band_ptr = [&](size_t i, Slab& o, int b) -> const char* {
-            if (b == 0) return ind == 1 ? (const char*)y[i] : o.approx[rd];
-            return (const char*)y[i] + (size_t)((1 + (long long)(nb - 1) * (level - lev) + (b - 1)) * R * o.n) * pb;
-        };
-        auto dst_of = [&](Slab& o) -> char* { return lev == 1 ? (char*)x[&o - &mp->slabs[0]] : o.approx[wr]; };
-        for (auto& s : mp->slabs)
-            MRET(lazy_alloc(s, &s.gather, (size_t)((long long)nb * R * (s.n + (long long)(mp->L_outer - 1) * smax)) * pb));
-        if (scatter) {
-            // zero-extended synthesis into the slab's scratch, (nt, sa + n + sb) planes: its own n planes are copied to where the result
-            // lives, the sa planes before and the sb planes after them are partial sums added by their owners, producers in slab order,
-            // "before" margins first (a fixed order of summation)
-            const long long margin = sa + sb;                 // planes of the zero-extended result beyond the slab's own
-            size_t i = 0;
-            for (auto& s : mp->slabs) {
-                MHIP(hipSetDevice(s.device));
-                const void* ins[16];
-                for (int b = 0; b < nb; ++b) ins[b] = band_ptr(i, s, b);
-                MTRY(ndwt_synthesis_level_slab_ext(s.plan, ins, s.gather, 1, s.stream));
-                MRET(copy_frames(mp, s, dst_of(s), s.n, s, s.gather + (size_t)sa * pb, s.n + margin, s.n, NDWT_SEG_COPY, s.stream));
-                MHIP(hipEventRecord(s.margins, s.stream));
-                ++i;
-            }
-            for (auto& from : mp->slabs) {
-                for (int side = 0; side < 2; ++side) {
-                    const long long count = side == 0 ? sa : sb;
-                    const long long g = side == 0 ? from.z0 - sa : from.z0 + from.n;
-                    const char* buf = from.gather + (size_t)(side == 0 ? 0 : sa + from.n) * pb;
-                    long long done = 0;
-                    while (done < count) {
-                        const long long gp = ((g + done) % N + N) % N;
-                        Slab* to = owner_of(mp, gp);
-                        if (!to) return mfail(NDWT_ERR_INVALID_ARG, "plane %lld has no owner", gp);
-                        long long run = to->z0 + to->n - gp;
-                        if (run > count - done) run = count - done;
-                        MHIP(hipSetDevice(to->device));
-                        if (to != &from) MHIP(hipStreamWaitEvent(to->stream, from.margins, 0));
-                        char* dst = dst_of(*to) + (size_t)(gp - to->z0) * pb;
-                        const char* src = buf + (size_t)done * pb;
-                        if (direct_access(mp, to->device, from.device)) {
-                            MRET(copy_frames(mp, *to, dst, to->n, from, src, from.n + margin, run, NDWT_SEG_ADD, to->stream));
-                        } else {                          // staged: the frames' runs into the receive buffer, then added from there
-                            MRET(copy_frames(mp, *to, to->recv, run, from, src, from.n + margin, run, NDWT_SEG_COPY, to->stream));
-                            MRET(copy_frames(mp, *to, dst, to->n, *to, to->recv, run, run, NDWT_SEG_ADD, to->stream));
-                        }
-                        done += run;
-                    }
-                }
-            }
-        } else {
+            break;
+        case RecStep::Gather:
             for (auto& s : mp->slabs) {
                 MHIP(hipSetDevice(s.device));
                 const long long nh = s.n + sb + sa;
@@ -714,11 +607,12 @@ static int mrec_core_z(ndwt_mplan* mp, const void* const* y, void* const* x, int
                 for (int b = 0; b < nb; ++b) {
                     char* dst = s.gather + (size_t)((long long)b * R * nh) * pb;
                     ins[b] = dst;
-                    auto src = [&, b](Slab& o, long long lp) -> const char* { return band_ptr(&o - &mp->slabs[0], o, b) + (size_t)lp * pb; };
-                    MRET(copy_planes_z(mp, s, dst, nh, s.z0 - sb, nh, src));   // all producers were waited for at the end of the previous level
+                    auto src = [&, b](Slab& o, long long lp) -> const char* { return band_ptr(o, b) + (size_t)lp * pb; };
+                    MRET(copy_planes(mp, s, dst, nh, s.z0 - sb, nh, src, s.stream));   // all producers were waited for at the end of the previous level
                 }
                 MTRY(ndwt_synthesis_level_slab(s.plan, ins, dst_of(s), (int)st, s.stream));
             }
+            break;
         }
         MRET(level_barrier(mp, wr));
     }
@@ -766,25 +660,16 @@ int ndwt_mplan_create_axis(ndwt_mplan** out, int ndim, const int64_t* dims, cons
     const long long smax = dilation == NDWT_DILATION_ATROUS ? (1LL << (max_level - 1)) : 1LL;
     mp->halo_max = (long long)(L / 2) * smax;
     std::vector<int64_t> ld(dims, dims + ndim);
+    const std::vector<ndwt::SlabPart> parts = ndwt::slab_partition(N, ndev);
     for (int i = 0; i < ndev; ++i) {
         Slab s;
         memset(&s, 0, sizeof s);
         s.device = devices[i];
-        s.z0 = (long long)i * N / ndev;
-        s.n = (long long)(i + 1) * N / ndev - s.z0;
+        s.z0 = parts[(size_t)i].z0;
+        s.n = parts[(size_t)i].n;
         mp->slabs.push_back(s);
     }
-    mp->nbr.resize(mp->slabs.size());
-    for (size_t i = 0; i < mp->slabs.size(); ++i) {
-        const Slab& si = mp->slabs[i];
-        for (long long d = -mp->halo_max; d < si.n + mp->halo_max; ++d) {
-            const Slab* o = owner_of(mp, ((si.z0 + d) % N + N) % N);
-            const int j = o ? (int)(o - &mp->slabs[0]) : (int)i;
-            bool have = false;
-            for (int q : mp->nbr[i]) have = have || q == j;
-            if (!have) mp->nbr[i].push_back(j);
-        }
-    }
+    for (size_t i = 0; i < mp->slabs.size(); ++i) mp->nbr.push_back(ndwt::slab_neighbours(mp->slabs, N, i, mp->halo_max));
     int rc = NDWT_OK;
     mp->fast = 1;
     for (auto& s : mp->slabs) {
@@ -895,38 +780,29 @@ int ndwt_mplan_describe(const ndwt_mplan* mp, char* buf, int buflen) {
     return NDWT_OK;
 }
 
+typedef int (*CoreFn)(ndwt_mplan*, const void* const*, void* const*, int);   // mdec_core / mrec_core: (plan, slabs in, slabs out, level)
+
 // device-resident form: x_slabs[i] / y_slabs[i] live on slab i's device (ndwt_mplan_slab: n_i planes of x; band b of the coefficient
 // slab at b * n_i planes).  The data must be complete when the call is made (no stream of the caller is waited for); the call returns
 // when the result is.
-int ndwt_mdec(ndwt_mplan* mp, const void* const* x_slabs, void* const* y_slabs, int level) {
+static int run_slabs(ndwt_mplan* mp, CoreFn core, const void* const* in, void* const* out, int level) {
     int rc = mcheck(mp, level);
     if (rc) return rc;
-    if (!x_slabs || !y_slabs) return mfail(NDWT_ERR_INVALID_ARG, "null pointer array");
+    if (!in || !out) return mfail(NDWT_ERR_INVALID_ARG, "null pointer array");
     for (size_t i = 0; i < mp->slabs.size(); ++i)
-        if (!x_slabs[i] || !y_slabs[i]) return mfail(NDWT_ERR_INVALID_ARG, "null slab pointer %zu", i);
+        if (!in[i] || !out[i]) return mfail(NDWT_ERR_INVALID_ARG, "null slab pointer %zu", i);
     const auto t0 = std::chrono::steady_clock::now();
     team_begin(mp);
-    rc = mdec_core(mp, x_slabs, y_slabs, level);
+    rc = core(mp, in, out, level);
     team_end(mp);
     mp->last_enqueue_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
     const int rs = sync_all(mp);                          // (also after an error: nothing stays queued on buffers the caller owns)
     return rc ? rc : rs;
 }
 
-int ndwt_mrec(ndwt_mplan* mp, const void* const* y_slabs, void* const* x_slabs, int level) {
-    int rc = mcheck(mp, level);
-    if (rc) return rc;
-    if (!x_slabs || !y_slabs) return mfail(NDWT_ERR_INVALID_ARG, "null pointer array");
-    for (size_t i = 0; i < mp->slabs.size(); ++i)
-        if (!x_slabs[i] || !y_slabs[i]) return mfail(NDWT_ERR_INVALID_ARG, "null slab pointer %zu", i);
-    const auto t0 = std::chrono::steady_clock::now();
-    team_begin(mp);
-    rc = mrec_core(mp, y_slabs, x_slabs, level);
-    team_end(mp);
-    mp->last_enqueue_us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    const int rs = sync_all(mp);
-    return rc ? rc : rs;
-}
+int ndwt_mdec(ndwt_mplan* mp, const void* const* x_slabs, void* const* y_slabs, int level) { return run_slabs(mp, mdec_core, x_slabs, y_slabs, level); }
+
+int ndwt_mrec(ndwt_mplan* mp, const void* const* y_slabs, void* const* x_slabs, int level) { return run_slabs(mp, mrec_core, y_slabs, x_slabs, level); }
 
 // whole-volume host arrays in, whole-volume host arrays out (the layout the MATLAB gateway holds): x is prod(dims) elements,
 // y prod(dims) * ndwt_num_bands(ndim, level), band-planar.  Blocks until the result is in y.
@@ -941,85 +817,51 @@ static int host_buffers(ndwt_mplan* mp, std::vector<void*>& xs, std::vector<void
     return NDWT_OK;
 }
 
-int ndwt_mdec_host(ndwt_mplan* mp, const void* x_host, void* y_host, int level) {
+// slab i's share of a whole-volume host array to (to_device) or from its buffer `dev`, on the slab's stream.  The host array is `rows`
+// planar arrays of the volume (1: x; the number of bands: coefficients), the buffer the same rows of the slab.
+static int stage(ndwt_mplan* mp, size_t i, char* host, char* dev, long long rows, bool to_device) {
+    Slab& s = mp->slabs[i];
+    const size_t pb = mp->plane_bytes, run = (size_t)s.n * pb, pitch = (size_t)axis_len(mp) * pb;
+    const hipMemcpyKind kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    MHIP(hipSetDevice(s.device));
+    host += (size_t)s.z0 * pb;
+    if (mp->nrep > 1) {
+        // z-slab: a run of n planes from every frame of the volume (rows of N planes); row b, frame q is row b * nt + q on both sides
+        if (to_device) MHIP(hipMemcpy2DAsync(dev, run, host, pitch, run, (size_t)(rows * mp->nrep), kind, s.stream));
+        else MHIP(hipMemcpy2DAsync(host, pitch, dev, run, run, (size_t)(rows * mp->nrep), kind, s.stream));
+        return NDWT_OK;
+    }
+    for (long long b = 0; b < rows; ++b) {
+        if (to_device) MHIP(hipMemcpyAsync(dev + (size_t)b * run, host + (size_t)b * pitch, run, kind, s.stream));
+        else MHIP(hipMemcpyAsync(host + (size_t)b * pitch, dev + (size_t)b * run, run, kind, s.stream));
+    }
+    return NDWT_OK;
+}
+
+// analysis: x_host -> xbuf, mdec_core, coef -> y_host; synthesis: y_host -> coef, mrec_core, xbuf -> x_host
+static int run_host(ndwt_mplan* mp, bool analysis, const void* in_host, void* out_host, int level) {
     int rc = mcheck(mp, level);
     if (rc) return rc;
-    if (!x_host || !y_host) return mfail(NDWT_ERR_INVALID_ARG, "null data pointer");
-    const size_t pb = mp->plane_bytes;
-    const long long N = axis_len(mp);
+    if (!in_host || !out_host) return mfail(NDWT_ERR_INVALID_ARG, "null data pointer");
     const long long nbt = (long long)ndwt_num_bands(mp->ndim, level);
     std::vector<void*> xs, ys;
     MRET(host_buffers(mp, xs, ys));
+    std::vector<void*>&in = analysis ? xs : ys, &out = analysis ? ys : xs;
     // the copies between the host arrays and the slabs are queued by the slabs' own threads too: from pageable memory (what MATLAB holds) a
     // copy occupies its calling thread until it is staged, and one thread would serve the devices' links one after the other
     team_begin(mp);
-    rc = phase(mp, [&](size_t i) -> int {
-        Slab& s = mp->slabs[i];
-        MHIP(hipSetDevice(s.device));
-        if (mp->nrep > 1)                                 // z-slab: a run of n planes from every frame of the volume (rows of N planes)
-            MHIP(hipMemcpy2DAsync(s.xbuf, (size_t)s.n * pb, (const char*)x_host + (size_t)s.z0 * pb, (size_t)N * pb, (size_t)s.n * pb,
-                                  (size_t)mp->nrep, hipMemcpyHostToDevice, s.stream));
-        else
-            MHIP(hipMemcpyAsync(s.xbuf, (const char*)x_host + (size_t)s.z0 * pb, (size_t)s.n * pb, hipMemcpyHostToDevice, s.stream));
-        return NDWT_OK;
-    });
-    if (rc == NDWT_OK) rc = level_barrier(mp, 1);         // every slab of x is in place before a neighbour reads its halo planes
-    if (rc == NDWT_OK) rc = mdec_core(mp, xs.data(), ys.data(), level);
-    if (rc == NDWT_OK)
-        rc = phase(mp, [&](size_t i) -> int {
-            Slab& s = mp->slabs[i];
-            MHIP(hipSetDevice(s.device));
-            if (mp->nrep > 1)                             // (bands x frames) rows: band b, frame q is row b * nt + q on both sides
-                MHIP(hipMemcpy2DAsync((char*)y_host + (size_t)s.z0 * pb, (size_t)N * pb, s.coef, (size_t)s.n * pb, (size_t)s.n * pb,
-                                      (size_t)(nbt * mp->nrep), hipMemcpyDeviceToHost, s.stream));
-            else
-                for (long long b = 0; b < nbt; ++b)
-                    MHIP(hipMemcpyAsync((char*)y_host + (size_t)(b * N + s.z0) * pb, s.coef + (size_t)(b * s.n) * pb, (size_t)s.n * pb, hipMemcpyDeviceToHost, s.stream));
-            return NDWT_OK;
-        });
+    rc = phase(mp, [&](size_t i) { return stage(mp, i, (char*)in_host, (char*)in[i], analysis ? 1 : nbt, true); });
+    if (rc == NDWT_OK) rc = level_barrier(mp, 1);         // every slab of the input is in place before a neighbour reads its halo planes
+    if (rc == NDWT_OK) rc = (analysis ? mdec_core : mrec_core)(mp, in.data(), out.data(), level);
+    if (rc == NDWT_OK) rc = phase(mp, [&](size_t i) { return stage(mp, i, (char*)out_host, (char*)out[i], analysis ? nbt : 1, false); });
     team_end(mp);
     const int rs = sync_all(mp);
     return rc ? rc : rs;
 }
 
-int ndwt_mrec_host(ndwt_mplan* mp, const void* y_host, void* x_host, int level) {
-    int rc = mcheck(mp, level);
-    if (rc) return rc;
-    if (!x_host || !y_host) return mfail(NDWT_ERR_INVALID_ARG, "null data pointer");
-    const size_t pb = mp->plane_bytes;
-    const long long N = axis_len(mp);
-    const long long nbt = (long long)ndwt_num_bands(mp->ndim, level);
-    std::vector<void*> xs, ys;
-    MRET(host_buffers(mp, xs, ys));
-    team_begin(mp);
-    rc = phase(mp, [&](size_t i) -> int {
-        Slab& s = mp->slabs[i];
-        MHIP(hipSetDevice(s.device));
-        if (mp->nrep > 1)
-            MHIP(hipMemcpy2DAsync(s.coef, (size_t)s.n * pb, (const char*)y_host + (size_t)s.z0 * pb, (size_t)N * pb, (size_t)s.n * pb,
-                                  (size_t)(nbt * mp->nrep), hipMemcpyHostToDevice, s.stream));
-        else
-            for (long long b = 0; b < nbt; ++b)
-                MHIP(hipMemcpyAsync(s.coef + (size_t)(b * s.n) * pb, (const char*)y_host + (size_t)(b * N + s.z0) * pb, (size_t)s.n * pb, hipMemcpyHostToDevice, s.stream));
-        return NDWT_OK;
-    });
-    if (rc == NDWT_OK) rc = level_barrier(mp, 1);
-    if (rc == NDWT_OK) rc = mrec_core(mp, ys.data(), xs.data(), level);
-    if (rc == NDWT_OK)
-        rc = phase(mp, [&](size_t i) -> int {
-            Slab& s = mp->slabs[i];
-            MHIP(hipSetDevice(s.device));
-            if (mp->nrep > 1)
-                MHIP(hipMemcpy2DAsync((char*)x_host + (size_t)s.z0 * pb, (size_t)N * pb, s.xbuf, (size_t)s.n * pb, (size_t)s.n * pb,
-                                      (size_t)mp->nrep, hipMemcpyDeviceToHost, s.stream));
-            else
-                MHIP(hipMemcpyAsync((char*)x_host + (size_t)s.z0 * pb, s.xbuf, (size_t)s.n * pb, hipMemcpyDeviceToHost, s.stream));
-            return NDWT_OK;
-        });
-    team_end(mp);
-    const int rs = sync_all(mp);
-    return rc ? rc : rs;
-}
+int ndwt_mdec_host(ndwt_mplan* mp, const void* x_host, void* y_host, int level) { return run_host(mp, true, x_host, y_host, level); }
+
+int ndwt_mrec_host(ndwt_mplan* mp, const void* y_host, void* x_host, int level) { return run_host(mp, false, y_host, x_host, level); }
 
 const char* ndwt_mplan_last_error(void) { return g_merr.c_str(); }
 
