@@ -132,7 +132,7 @@ int dispatch(int Lp, int vec4, ndwt::Fused3Args<T>& a, const double* lo, const d
 template <typename T, bool INV>
 int emu3(int Lp, int vec4, const T* in, T* out, int n1, int n2, int n3, int nbatch, int zchunk,
          const double* lo, const double* hi, int z_wrap, int small_tile, int variant, int ew, double shrink_thr, int shrink_mask,
-         int shrink_hard, int dil) {
+         int shrink_hard, int dil, const T* halo_before, const T* halo_after) {
     ndwt::Fused3Args<T> a;
     std::memset(&a, 0, sizeof(a));
     a.n1 = n1; a.n2 = n2; a.n3 = n3; a.nbatch = nbatch;
@@ -150,6 +150,8 @@ int emu3(int Lp, int vec4, const T* in, T* out, int n1, int n2, int n3, int nbat
     a.in_bstride = vol_in; a.out_bstride = vol;
     if constexpr (!INV) {
         a.in[0] = in;
+        a.in[1] = halo_before;      // z_wrap = 2: the Lp/2 - 1 planes before the slab and the Lp/2 after it, in buffers of their own
+        a.in[2] = halo_after;
         for (int b = 0; b < 8; ++b) a.out[b] = out + b * vol * nbatch;
     } else {
         for (int b = 0; b < 8; ++b) a.in[b] = in + b * vol_in * nbatch;
@@ -688,11 +690,12 @@ template <int LL> static int run_pin3(ndwt::Fused3Args<float>& a, const double* 
     typedef ndwt::Fused3Tile<float, false, 6> TL;
     return run<ndwt::Fwd3<float, LL, TL::TX, TL::TY, TL::NT, TL::RY, true, 2, 1, false, false, true>, float>(a, lo, hi);
 }
-extern "C" int ndwt_emu_pin3_f32(int Lp, const float* x, float* out, int n1, int n2, int n3, int zchunk, const double* alo, const double* ahi) {
+extern "C" int ndwt_emu_pin3_f32(int Lp, const float* x, float* out, int n1, int n2, int n3, int zchunk, const double* alo, const double* ahi,
+                                 int z_wrap, const float* halo_before, const float* halo_after) {
     ndwt::Fused3Args<float> a;
     std::memset(&a, 0, sizeof(a));
-    a.n1 = n1; a.n2 = n2; a.n3 = n3; a.nbatch = 1; a.z_wrap = 1;
-    a.in[0] = x;
+    a.n1 = n1; a.n2 = n2; a.n3 = n3; a.nbatch = 1; a.z_wrap = z_wrap;   // n3: output planes (0: x carries Lp - 1 halo planes, 2: they lie in the two buffers)
+    a.in[0] = x; a.in[1] = halo_before; a.in[2] = halo_after;
     for (int b = 0; b < 8; ++b) a.out[b] = out + (long long)b * n1 * n2 * n3;
     ndwt::fused3_geometry(a, 64, 32, Lp, 4, zchunk);
     switch (Lp) {
@@ -818,10 +821,13 @@ int ndwt_emu2_f64(int inverse, int Lp, int vec4, const double* in, double* out, 
 }
 #endif
 // in/out: band-planar, batch inside band: [band][batch][n3(+halo)][n2][n1]; lo/hi: [3][20] padded kernel-form taps
+// z_wrap: Fused3Args::z_wrap.  0: `in` carries Lp - 1 halo planes; 2 (analysis): `in` is the slab alone, halo_before / halo_after hold
+// its halo planes; 3 (synthesis): n3 = the planes of the zero-extended result
 #define EMU3_ARGS(T) int Lp, int vec4, const T* in, T* out, int n1, int n2, int n3, int nbatch, int zchunk, const double* lo, \
                      const double* hi, int z_wrap, int small_tile, int variant, int ew, double shrink_thr, int shrink_mask, \
-                     int shrink_hard, int dil
-#define EMU3_PASS Lp, vec4, in, out, n1, n2, n3, nbatch, zchunk, lo, hi, z_wrap, small_tile, variant, ew, shrink_thr, shrink_mask, shrink_hard, dil
+                     int shrink_hard, int dil, const T* halo_before, const T* halo_after
+#define EMU3_PASS Lp, vec4, in, out, n1, n2, n3, nbatch, zchunk, lo, hi, z_wrap, small_tile, variant, ew, shrink_thr, shrink_mask, shrink_hard, dil, \
+                  halo_before, halo_after
 #if EMU_IN(5)
 int ndwt_emu3_f32_fwd(EMU3_ARGS(float)) { return emu3<float, false>(EMU3_PASS); }
 #endif

@@ -49,6 +49,11 @@ def _route(shim, plan, stride, inverse, slab=WHOLE_ARRAY):
     return kind, Lp.value
 
 
+def _route_dir(shim, plan, stride, direction, slab):
+    Lp = ctypes.c_int(0)
+    return shim.sel_level_path(plan, stride, int(direction), int(slab), ctypes.byref(Lp)), Lp.value
+
+
 def _picks(shim, row, inverse):
     """the launches of the row's dec (rec) that kernel selection decides at tap stride 1, as (family, params)"""
     dims, d = row["dims"], len(row["dims"])
@@ -141,3 +146,56 @@ def test_level_routes_whole_and_slab(shim, name, dims, orders, shard, stride, wh
         assert _route(shim, plan, stride, inverse, SLAB_OUTER if shard == len(dims) - 1 else SLAB_Z) == (slab, 0 if slab == PER_AXIS else Lp), (name, inverse)
     if len(dims) == 4 and shard == 2 and stride == 1:           # test_mplan_z_slabs: "scatter-add" in describe() for reference dilation
         assert (slab == FUSED3_T) == (lens[2] == max(lens[:3]))
+
+
+def test_slab_rows_pick_their_pinned_kernels(shim):
+    """the rows of tests/test_gpu_slab_dispatch.py, replayed the same way: level_route with the SlabMode of the row, then fused3_select /
+    fused2_select with the local n1, n2 and the batch of every launch the slab entry points make (1; 2 in the _runs forms; the frames of a
+    4-D volume) -- per cut and direction"""
+    from test_gpu_slab_dispatch import ROWS as SLAB_ROWS
+    fused = ("Fwd3", "Inv3", "Inv3S", "Inv3Y", "Fwd2S", "Inv2S", "Inv2P")
+    checked = 0
+    for prm in SLAB_ROWS:
+        row = prm.values[0]
+        dims, wl, ax, stride = row["dims"], row["wl"], row["axis"], row["stride"]
+        d, lens = len(dims), [2 * int(w[2:]) for w in wl]
+        f64, comp = row["prec"] == "double", 2 if row["cplx"] else 1
+        T, n1 = "double" if f64 else "float", dims[0] * comp
+        vec4 = n1 % 4 == 0 and (n1 * dims[1]) % 4 == 0
+        mode = SLAB_OUTER if ax == d - 1 else SLAB_Z
+        for z0, z1, _ in row["cuts"]:
+            local = list(dims)
+            local[ax] = z1 - z0
+            plan = _plan(local, lens, f64, row["cplx"], False, stride > 1, max(row["fwd"], 0), max(row["inv"], 0))
+            for inverse in (False, True):
+                specs = [helpers.spec(s.lstrip("~")) for s in row["syn" if inverse else "ana"]]
+                specs = [(fam, {k: v for k, v in p.items() if k not in NOT_IN_PICK}) for fam, p in specs]
+                kind, L = _route(shim, plan, stride, inverse, mode)
+                picks = []
+                if kind in (FUSED3, FUSED3_T):
+                    for nbatch in ([1, 2] if d == 3 else [local[3]] if ax == 2 else [local[3], local[3] + lens[3] - 1]):
+                        q = _ints([f64, inverse, vec4, wl[1] == wl[2], 0, L] + lens[:3] + [comp, 1, n1, dims[1], nbatch, max(row["fwd"], 0),
+                                  max(row["inv"], 0), NUM_CUS, 0])
+                        r = (ctypes.c_int * 10)()
+                        name = shim.sel_fused3(q, r).decode()
+                        V, TX, TY, depth, scatter, uniyz, per_cu, target, pin, tpre = list(r)
+                        p = {"T": T, "L": L, "EW": comp, "TX": TX, "TY": TY, "VEC4": vec4}
+                        if name == "Fwd3":
+                            p.update(PIN=bool(pin), TPRE=bool(tpre))
+                        if name == "Inv3Y":
+                            p.update(XSC=bool(scatter), UNIYZ=bool(uniyz), DEPTH=depth)
+                        picks.append((name, p))
+                elif kind == FUSED2:
+                    r = (ctypes.c_int * 4)()
+                    shim.sel_fused2(_ints([f64, inverse, vec4, L, comp, 1, n1, local[1], max(row["inv"], 0)]), r)
+                    picks.append(("Inv2P", {"T": T, "L": L, "PD": r[1], "PK": bool(r[2])}) if r[0] == 1 else
+                                 ("Inv2S" if inverse else "Fwd2S", {"T": T, "L": L, "EW": comp, "VEC4": vec4}))
+                else:
+                    assert kind == PER_AXIS and not any(fam in fused for fam, _ in specs), (prm.id, kind, specs)
+                both, _ = _route_dir(shim, plan, 1, -1, mode)      # ndwt_plan_slab_fast: slab_fused3 for both directions at once, tap stride 1
+                assert stride > 1 or row["fast"] == (both == FUSED3 or (both == FUSED3_T and mode == SLAB_Z)), (prm.id, both)
+                for fam, params in picks:
+                    rec = helpers._trace.KernelLaunch(fam, params)
+                    assert any(helpers.matches(rec, sp) for sp in specs), (prm.id, (z0, z1), "syn" if inverse else "ana", rec, specs)
+                    checked += 1
+    assert checked >= 2 * 2 * 30

@@ -29,7 +29,18 @@ def emu():
     return ctypes.CDLL(os.path.join(ROOT, "tests", "emu", target))
 
 
-def _run(emu, x_mat_or_bands, wnames, l2, inverse, dtype, vec4, zchunk, small, z_wrap=1, variant=0, cplx=False, shrink=(0.0, 0, 0), dil=1):
+def _nan_guarded(a):
+    """kernel-order planes between one plane of NaN on either side: a kernel that reads a plane too far returns NaN (and, under ASan, a
+    read past those is an error); returns the holder and the address of the first real plane"""
+    pad = np.full((1,) + a.shape[1:], np.nan, dtype=a.dtype)
+    held = np.ascontiguousarray(np.concatenate([pad, a, pad]))
+    return held, ctypes.c_void_p(held.ctypes.data + held[0].nbytes)
+
+
+def _run(emu, x_mat_or_bands, wnames, l2, inverse, dtype, vec4, zchunk, small, z_wrap=1, variant=0, cplx=False, shrink=(0.0, 0, 0), dil=1,
+         halo=None):
+    """z_wrap = 0: the input (every band of a synthesis) carries the Lp - 1 halo planes of the slab; 2 (analysis): the input is the slab
+    alone, halo = (planes before, planes after) in arrays of their own"""
     Ls = [len(orc.wave_filters(w)[0]) for w in wnames]
     Lp = max(Ls)
     lo = np.zeros((3, 20))
@@ -40,19 +51,26 @@ def _run(emu, x_mat_or_bands, wnames, l2, inverse, dtype, vec4, zchunk, small, z
         hi[ax, :Lp] = t["syn_hi" if inverse else "ana_hi"]
     cdt = (np.complex64 if dtype == np.float32 else np.complex128) if cplx else dtype
     src = to_kernel_order(x_mat_or_bands).astype(cdt)
-    if inverse:
-        n3, n2, n1 = src.shape[1:]
-        out = np.full((n3, n2, n1), np.nan, dtype=cdt)
-    else:
-        n3, n2, n1 = src.shape
-        out = np.full((8, n3, n2, n1), np.nan, dtype=cdt)
+    n3, n2, n1 = src.shape[1:] if inverse else src.shape
+    if z_wrap == 0:
+        n3 -= Lp - 1                  # the kernels count output planes
+    out = np.full((n3, n2, n1) if inverse else (8, n3, n2, n1), np.nan, dtype=cdt)
     if cplx:
         n1 *= 2                       # the kernels see scalars along x
+    keep, src_p, hb_p, ha_p = [], src.ctypes.data_as(ctypes.c_void_p), None, None
+    if not inverse and z_wrap in (0, 2):
+        held, src_p = _nan_guarded(src)
+        keep.append(held)
+    if halo is not None:
+        for k, h in enumerate(halo):
+            held, p = _nan_guarded(to_kernel_order(h).astype(cdt).reshape((-1,) + src.shape[1:]))
+            keep.append(held)
+            hb_p, ha_p = (p, ha_p) if k == 0 else (hb_p, p)
     fn = emu.ndwt_emu3_f32 if dtype == np.float32 else emu.ndwt_emu3_f64
     fn.restype = ctypes.c_int
-    rc = fn(int(inverse), Lp, int(vec4), src.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p),
+    rc = fn(int(inverse), Lp, int(vec4), src_p, out.ctypes.data_as(ctypes.c_void_p),
             n1, n2, n3, 1, zchunk, lo.ctypes.data_as(ctypes.c_void_p), hi.ctypes.data_as(ctypes.c_void_p), z_wrap,
-            int(small), int(variant), 2 if cplx else 1, ctypes.c_double(shrink[0]), int(shrink[1]), int(shrink[2]), int(dil))
+            int(small), int(variant), 2 if cplx else 1, ctypes.c_double(shrink[0]), int(shrink[1]), int(shrink[2]), int(dil), hb_p, ha_p)
     assert rc == 0
     return np.transpose(out)
 
@@ -327,7 +345,7 @@ def test_emulated_cascaded_2d_synthesis(emu, sizes, wn, nlev, ychunk, depth, l2)
     assert np.abs(got - want).max() <= 4e-6 * max(np.abs(want).max(), 1.0)
 
 
-def _run2(emu, arr, wnames, l2, inverse, dtype, vec4, ychunk, cplx=False, shrink=(0.0, 0, 0), dil=1):
+def _run2(emu, arr, wnames, l2, inverse, dtype, vec4, ychunk, cplx=False, shrink=(0.0, 0, 0), dil=1, y_wrap=1):
     Ls = [len(orc.wave_filters(w)[0]) for w in wnames]
     Lp = max(Ls)
     lo = np.zeros((3, 20))
@@ -338,18 +356,16 @@ def _run2(emu, arr, wnames, l2, inverse, dtype, vec4, ychunk, cplx=False, shrink
         hi[ax, :Lp] = t["syn_hi" if inverse else "ana_hi"]
     cdt = (np.complex64 if dtype == np.float32 else np.complex128) if cplx else dtype
     src = to_kernel_order(arr).astype(cdt)
-    if inverse:
-        n2, n1 = src.shape[1:]
-        out = np.full((n2, n1), np.nan, dtype=cdt)
-    else:
-        n2, n1 = src.shape
-        out = np.full((4, n2, n1), np.nan, dtype=cdt)
+    n2, n1 = src.shape[1:] if inverse else src.shape
+    if not y_wrap:
+        n2 -= Lp - 1                  # the input (every band of a synthesis) carries the Lp - 1 halo rows; the kernels count output rows
+    out = np.full((n2, n1) if inverse else (4, n2, n1), np.nan, dtype=cdt)
     if cplx:
         n1 *= 2
     fn = emu.ndwt_emu2_f32 if dtype == np.float32 else emu.ndwt_emu2_f64
     fn.restype = ctypes.c_int
     rc = fn(int(inverse), Lp, int(vec4), src.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p), n1, n2, ychunk,
-            lo.ctypes.data_as(ctypes.c_void_p), hi.ctypes.data_as(ctypes.c_void_p), 1, 2 if cplx else 1, ctypes.c_double(shrink[0]),
+            lo.ctypes.data_as(ctypes.c_void_p), hi.ctypes.data_as(ctypes.c_void_p), int(y_wrap), 2 if cplx else 1, ctypes.c_double(shrink[0]),
             int(shrink[1]), int(shrink[2]), int(dil))
     assert rc == 0
     return np.transpose(out)
@@ -700,7 +716,7 @@ def test_emulated_analysis_with_pinned_taps(emu, sizes, wnames, zchunk):
     n3, n2, n1 = xs.shape
     out = np.full((8, n3, n2, n1), np.nan, dtype=np.float32)
     p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    assert emu.ndwt_emu_pin3_f32(L, p(xs), p(out), n1, n2, n3, zchunk, p(t["ana_lo"]), p(t["ana_hi"])) == 0
+    assert emu.ndwt_emu_pin3_f32(L, p(xs), p(out), n1, n2, n3, zchunk, p(t["ana_lo"]), p(t["ana_hi"]), 1, None, None) == 0
     got = np.transpose(out)
     assert np.isfinite(got).all()
     assert np.abs(got - want).max() <= 2e-6 * np.abs(want).max()
@@ -755,3 +771,149 @@ def test_emulated_fused2_synthesis_with_rows_in_flight(emu, sizes, wname, ychunk
     assert np.isfinite(got).all()
     bad = np.abs(got - want) > 4e-6 * max(np.abs(want).max(), 1.0)
     assert bad.mean() <= (2e-3 if shrink and shrink[2] else 0.0), float(np.abs(got - want).max())
+
+
+# ---- the halo modes of the run-time switch Fused3Args::z_wrap / Fused2Args::y_wrap (the slab entry points of include/ndwt.h): slabs
+# cropped from ONE periodic volume against the oracle on that volume.  Two cuts per case: 2 L + 1 planes from plane 3 (more than
+# twice the halo; the forced chunk starts fall inside the slab) and 3 planes (2 under 6 taps) across the wrap, thinner than the halo.
+def _slab_cuts(L, N):
+    return [(3, 2 * L + 4), (N - 1, N - 1 + (3 if L > 4 else 2))]
+
+
+def _crop(a, lo, hi, axis=2):
+    """planes [lo, hi) of the periodic axis"""
+    return np.take(a, np.arange(lo, hi) % a.shape[axis], axis=axis)
+
+
+SLAB_ANA = [
+    # sizes (n1, n2, N),  wavelets (z the longest),  vec4, zchunk, small_tile, complex
+    ((20, 17, 24), ("db4", "db4", "db4"), True, 5, True, False),
+    ((16, 9, 16), ("db1", "db2", "db3"), True, 0, True, False),
+    ((68, 18, 24), ("db4", "db4", "db4"), True, 4, False, False),      # production tile (and variant 1: one column per thread)
+    ((70, 19, 24), ("db2", "db1", "db4"), False, 6, False, False),     # ragged rows
+    ((13, 10, 12), ("db2", "db2", "db2"), False, 4, True, False),
+    ((24, 17, 24), ("db4", "db4", "db4"), True, 5, True, True),        # interleaved complex
+    ((22, 15, 30), ("db5", "db3", "db5"), True, 0, True, True),
+    ((70, 19, 24), ("db4", "db2", "db4"), True, 6, False, True),       # ... on the production tile
+]
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("sizes,wn,vec4,zchunk,small,cplx", SLAB_ANA)
+def test_emulated_fused3_analysis_of_a_slab_with_its_halo(emu, sizes, wn, vec4, zchunk, small, cplx):
+    """Fwd3 with z_wrap = 0 (the input carries L/2 - 1 planes before and L/2 after the slab) and z_wrap = 2 (those planes in buffers of
+    their own): the planes of the periodic level, to the bit the same in both modes; every input lies between planes of NaN"""
+    rng = np.random.default_rng(41)
+    x = rng.standard_normal(sizes) + (1j * rng.standard_normal(sizes) if cplx else 0)
+    filt = [orc.wave_filters(w) for w in wn]
+    want = orc.spatial_level_dec(x, filt, 1)
+    L = max(len(f[0]) for f in filt)
+    assert len(filt[2][0]) == L
+    ab, aa = L // 2 - 1, L // 2
+    for z0, z1 in _slab_cuts(L, sizes[2]):
+        for dtype, tol in ((np.float64, 1e-13), (np.float32, 2e-6)):
+            for variant in ((0, 1) if not small and not cplx and dtype == np.float32 else (0,)):
+                got0 = _run(emu, _crop(x, z0 - ab, z1 + aa), wn, 1, False, dtype, vec4, zchunk, small, z_wrap=0, variant=variant, cplx=cplx)
+                got2 = _run(emu, _crop(x, z0, z1), wn, 1, False, dtype, vec4, zchunk, small, z_wrap=2, variant=variant, cplx=cplx,
+                            halo=(_crop(x, z0 - ab, z0), _crop(x, z1, z1 + aa)))
+                assert np.isfinite(got0).all() and np.isfinite(got2).all(), (z0, z1, variant)
+                assert np.abs(got0 - _crop(want, z0, z1)).max() <= tol * np.abs(want).max(), (z0, z1, variant)
+                assert np.array_equal(got0, got2), (z0, z1, variant)
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("sizes,wnames,zchunk", [((68, 36, 40), ("db5",) * 3, 6), ((68, 36, 48), ("db6",) * 3, 0), ((64, 32, 56), ("db7",) * 3, 5),
+                                                 ((128, 33, 48), ("db2", "db4", "db6"), 3), ((68, 36, 64), ("db8",) * 3, 7),
+                                                 ((68, 20, 80), ("db10",) * 3, 9)])
+def test_emulated_analysis_with_pinned_taps_of_a_slab_with_its_halo(emu, sizes, wnames, zchunk):
+    """Fwd3<.., PIN> (10 / 12 / 14 taps) and Fwd3<.., WLDS = 2 / 4> (16 / 20 taps) with z_wrap = 0 and 2"""
+    rng = np.random.default_rng(42)
+    x = rng.standard_normal(sizes)
+    filt = [orc.wave_filters(w) for w in wnames]
+    want = orc.spatial_level_dec(x, filt, 1)
+    L = max(len(f[0]) for f in filt)
+    assert len(filt[2][0]) == L
+    ab, aa = L // 2 - 1, L // 2
+    t = {k: np.zeros((3, 20)) for k in ("ana_lo", "ana_hi")}
+    for ax, w in enumerate(wnames):
+        assert ((L - len(filt[ax][0])) // 2) % 2 == 0
+        ka = kernel_taps(w, 1, L)
+        for k in t:
+            t[k][ax, :L] = ka[k]
+    p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    for z0, z1 in _slab_cuts(L, sizes[2]):
+        got = {}
+        for z_wrap in (0, 2):
+            held, xp = _nan_guarded(to_kernel_order(_crop(x, z0 - ab, z1 + aa) if z_wrap == 0 else _crop(x, z0, z1)).astype(np.float32))
+            hb, hbp = _nan_guarded(to_kernel_order(_crop(x, z0 - ab, z0)).astype(np.float32))
+            ha, hap = _nan_guarded(to_kernel_order(_crop(x, z1, z1 + aa)).astype(np.float32))
+            n3, (n2, n1) = z1 - z0, held.shape[1:]
+            out = np.full((8, n3, n2, n1), np.nan, dtype=np.float32)
+            assert emu.ndwt_emu_pin3_f32(L, xp, p(out), n1, n2, n3, zchunk, p(t["ana_lo"]), p(t["ana_hi"]), z_wrap,
+                                         hbp if z_wrap == 2 else None, hap if z_wrap == 2 else None) == 0
+            got[z_wrap] = np.transpose(out)
+            assert np.isfinite(got[z_wrap]).all(), (z0, z1, z_wrap)
+            assert np.abs(got[z_wrap] - _crop(want, z0, z1)).max() <= 2e-6 * np.abs(want).max(), (z0, z1, z_wrap)
+        assert np.array_equal(got[0], got[2]), (z0, z1)
+
+
+SLAB_SYN = [
+    # sizes (n1, n2, N),  wavelets,  vec4, zchunk, small_tile, complex, emulator variants
+    # (0: Inv3, the LDS kernel; 1 / 3: Inv3S on the production tiles, 2: on the small one; 5 / 8: Inv3Y in gather form; 10: in scatter form)
+    ((20, 17, 24), ("db4", "db4", "db4"), True, 5, True, False, (0, 2, 5, 8, 10)),
+    ((13, 10, 12), ("db2", "db2", "db2"), False, 4, True, False, (0, 2, 5)),
+    ((68, 39, 24), ("db4", "db4", "db4"), True, 4, False, False, (0, 1, 3, 5, 8, 10)),
+    ((72, 37, 30), ("db6", "db6", "db6"), True, 0, False, False, (5, 8, 10)),
+    ((24, 22, 48), ("db10", "db10", "db10"), True, 6, True, False, (5, 10)),          # pending z sums in LDS
+    ((21, 14, 30), ("db1", "db3", "db5"), False, 5, True, False, (0, 2, 5)),
+    ((14, 17, 24), ("db4", "db4", "db4"), True, 5, True, True, (0, 5, 8, 10)),         # interleaved complex (0: Inv3S, EW = 2)
+]
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("sizes,wn,vec4,zchunk,small,cplx,variants", SLAB_SYN)
+def test_emulated_fused3_synthesis_of_a_slab_with_its_halo(emu, sizes, wn, vec4, zchunk, small, cplx, variants):
+    """Inv3, Inv3S and Inv3Y (gather and scatter x stage) with z_wrap = 0: every band carries L/2 planes before and L/2 - 1 after the slab"""
+    rng = np.random.default_rng(43)
+    shape = tuple(sizes) + (8,)
+    c = rng.standard_normal(shape) + (1j * rng.standard_normal(shape) if cplx else 0)
+    filt = [orc.wave_filters(w) for w in wn]
+    want = orc.spatial_level_rec(c, filt, 1)
+    L = max(len(f[0]) for f in filt)
+    assert len(filt[2][0]) == L
+    sb, sa = L // 2, L // 2 - 1
+    for z0, z1 in _slab_cuts(L, sizes[2]):
+        for variant in variants:
+            for dtype, tol in ((np.float32, 2e-6),) if variant in (5, 8, 10) else ((np.float64, 1e-13), (np.float32, 2e-6)):
+                if dtype == np.float64 and variant == 3:
+                    continue                                     # (3: the float default configuration)
+                got = _run(emu, _crop(c, z0 - sb, z1 + sa), wn, 1, True, dtype, vec4, zchunk, small, z_wrap=0, variant=variant, cplx=cplx)
+                assert np.isfinite(got).all(), (z0, z1, variant)
+                assert np.abs(got - _crop(want, z0, z1)).max() <= tol * max(np.abs(want).max(), 1.0), (z0, z1, variant, dtype)
+
+
+@pytest.mark.slow
+@pytest.mark.parametrize("sizes,wn,vec4,ychunk,cplx", [
+    ((40, 16), ("db1", "db3"), True, 0, False),
+    ((255, 24), ("db2", "db4"), False, 4, False),      # more than one wave tile along x, odd width
+    ((516, 32), ("db4", "db4"), True, 7, False),       # three wave tiles, several row chunks
+    ((36, 48), ("db5", "db6"), True, 11, False),       # two-lane shifts
+    ((301, 32), ("db4", "db4"), False, 0, False),      # the second tile anchored at the end of the row
+    ((150, 32), ("db4", "db4"), True, 7, True),        # interleaved complex
+])
+def test_emulated_fused2_of_a_slab_with_its_halo(emu, sizes, wn, vec4, ychunk, cplx):
+    """Fwd2S / Inv2S with y_wrap = 0: rows [y0, y1) of the periodic level from an input that carries its halo rows"""
+    rng = np.random.default_rng(44)
+    x = rng.standard_normal(sizes) + (1j * rng.standard_normal(sizes) if cplx else 0)
+    c = rng.standard_normal(tuple(sizes) + (4,)) + (1j * rng.standard_normal(tuple(sizes) + (4,)) if cplx else 0)
+    filt = [orc.wave_filters(w) for w in wn]
+    want_y = orc.spatial_level_dec(x, filt, 1)
+    want_r = orc.spatial_level_rec(c, filt, 1)
+    L = max(len(f[0]) for f in filt)
+    assert len(filt[1][0]) == L
+    for y0, y1 in _slab_cuts(L, sizes[1]):
+        for dtype, tol in ((np.float64, 1e-13), (np.float32, 2e-6)):
+            got = _run2(emu, _crop(x, y0 - (L // 2 - 1), y1 + L // 2, 1), wn, 1, False, dtype, vec4, ychunk, cplx=cplx, y_wrap=0)
+            assert np.isfinite(got).all() and np.abs(got - _crop(want_y, y0, y1, 1)).max() <= tol * np.abs(want_y).max(), (y0, y1)
+            got = _run2(emu, _crop(c, y0 - L // 2, y1 + L // 2 - 1, 1), wn, 1, True, dtype, vec4, ychunk, cplx=cplx, y_wrap=0)
+            assert np.isfinite(got).all() and np.abs(got - _crop(want_r, y0, y1, 1)).max() <= tol * max(np.abs(want_r).max(), 1.0), (y0, y1)
