@@ -374,23 +374,6 @@ template <typename T> static int nt_store_ok(long long rs, long long plane, long
     return 1;
 }
 
-// the one launch a pick names (the launchers answer -1 where they have no instance: after a pick that is an internal error)
-static int launch_pick(const Fused3Pick& k, const Fused3Query& q, const Fused3Args<float>& a, const FusedTapsD& t, const void* td, hipStream_t s) {
-    switch (k.family) {
-        case kFwd3FoldT: return launch_fwd3_tpre_f32(a, t.Lp, td, s);
-        case kFwd3Pin: return launch_fwd3_pin_f32(a, t.Lp, td, s);
-        case kLong3: return launch_long3_f32(q.inverse, a, t, q.vec4, k.long_ab, td, s);
-        case kInv3Y: return q.ew == 4 ? launch_inv3y4_f32(a, t.Lp, k.depth, td, s, k.scatter)
-                          : q.ew == 2 ? launch_inv3yc_f32(a, t.Lp, q.vec4, k.depth, td, s, k.scatter)
-                          : k.scatter ? launch_inv3ys_f32(a, t.Lp, k.depth, td, s, k.uniyz) : launch_inv3y_f32(a, t.Lp, q.vec4, k.depth, td, s, k.uniyz);
-        default: return q.inverse ? launch_inv3_f32(a, t, q.vec4, k.V, q.ew, td, s) : launch_fwd3_f32(a, t, q.vec4, k.V, q.ew, td, s);
-    }
-}
-static int launch_pick(const Fused3Pick& k, const Fused3Query& q, const Fused3Args<double>& a, const FusedTapsD& t, const void* td, hipStream_t s) {
-    if (k.family == kLong3) return launch_long3_f64(q.inverse, a, t, q.vec4, td, s);
-    return q.inverse ? launch_inv3_f64(a, t, q.vec4, k.V, q.ew, td, s) : launch_fwd3_f64(a, t, q.vec4, k.V, q.ew, td, s);
-}
-
 // one fused 3-D launch: what a call site says of it (the rest follows from the plan).  ZMode: the values Fused3Args::z_wrap documents
 enum ZMode { kZHalo = 0, kZPeriodic = 1, kZSplitHalo = 2, kZZeroExt = 3 };   // inputs with their z halo | periodic | halo planes in in[1] / in[2] | zero-extended slab
 constexpr int kShrinkTLowDetails = 0xFE, kShrinkTHighAll = 0xFF;   // bands shrunk on load (ndwt_denoise): the details of a 3-D level / of the t-low half, every band of the t-high half
@@ -451,7 +434,7 @@ template <typename T> static int fused3_run(const ndwt_plan* p, const Fused3Laun
     const Fused3Query q = {sizeof(T) == 8, inverse, vec4, p->uniform_yz, l.ttaps != nullptr, Lp, {p->filt[0].len, p->filt[1].len, p->filt[2].len},
                            dil > 1 ? dil : (int)p->comp, dil, a.n1, a.n2, a.nbatch, p->variant_fwd, p->variant_inv, p->num_cus, p->target_blocks};
     const Fused3Pick k = fused3_select(q);
-    if (k.family == kNoFused3) return fail(NDWT_ERR_UNSUPPORTED, "internal: no folded-t analysis kernel for tap length %d / this alignment", Lp);
+    if (k.kernel == kNoFused3) return fail(NDWT_ERR_UNSUPPORTED, "internal: no fused 3-D kernel of this variant for tap length %d / this alignment", Lp);
     const int zc_force = p->zchunk_dir[inverse ? 1 : 0] > 0 ? p->zchunk_dir[inverse ? 1 : 0] : p->force_zchunk;
     // more tiles than resident slots: fused3_geometry picks the chunk count with the fewest plane steps over all rounds
     fused3_geometry(a, k.TX, k.TY, Lp, k.target, zc_force);
@@ -465,26 +448,15 @@ template <typename T> static int fused3_run(const ndwt_plan* p, const Fused3Laun
     // (a tile narrower than whole lines -- the 48-wide pair-packed tiles of 20 taps / complex 12 taps -- would put tile edges inside
     // a line: two workgroups' partial nontemporal stores of one line, the read-modify-write case again)
     a.nt = ((long long)k.TX * (long long)sizeof(T)) % 128 == 0 ? nt_store_ok<T>(a.rs, a.plane, out_bstride, out, nout) : 0;
-    FusedTapsD t = fused_taps(p, Lp, inverse);
     const void* td = p->taps_dev[inverse ? 1 : 0];
     if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
     prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
-    const int rc = launch_pick(k, q, a, t, td, s);
+    const int rc = launch_fused3_pick(k, a, td, s);   // (-1: no unit has the instance -- after a pick that is an internal error)
     prof_end(p, s, rc);
-    if (rc == -1) return fail(NDWT_ERR_UNSUPPORTED, "internal: no fused kernel instantiated for the pick (family %d, tap length %d)", (int)k.family, Lp);
+    if (rc == -1) return fail(NDWT_ERR_UNSUPPORTED, "internal: no fused kernel instantiated for the pick (kernel %d, tap length %d)", (int)k.kernel, Lp);
     if (rc == -2) return fail(NDWT_ERR_UNSUPPORTED, "internal: launch geometry (%d x %d tiles) does not match the kernel's tile shape", k.TX, k.TY);
     if (rc != 0) return fail(NDWT_ERR_HIP, "fused kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     return NDWT_OK;
-}
-
-static int launch2(bool inverse, const Fused2Args<float>& a, int Lp, bool vec4, int ew, const void* td, hipStream_t s) {
-    if (ew == 2 && Lp > 8) return inverse ? launch_inv2_c64_10to16(a, Lp, vec4, td, s) : launch_fwd2_c64_10to16(a, Lp, vec4, td, s);
-    if (Lp > 12) return ew != 1 ? -1 : (inverse ? launch_inv2_f32_14to20(a, Lp, vec4, td, s) : launch_fwd2_f32_14to20(a, Lp, vec4, td, s));
-    return inverse ? launch_inv2_f32(a, Lp, vec4, ew, td, s) : launch_fwd2_f32(a, Lp, vec4, ew, td, s);
-}
-static int launch2(bool inverse, const Fused2Args<double>& a, int Lp, bool vec4, int ew, const void* td, hipStream_t s) {
-    if (Lp > 12) return ew != 1 ? -1 : launch_long2_f64(inverse, a, Lp, vec4, td, s);
-    return inverse ? launch_inv2_f64(a, Lp, vec4, ew, td, s) : launch_fwd2_f64(a, Lp, vec4, ew, td, s);
 }
 
 // one fused 2-D launch, as a call site describes it
@@ -529,10 +501,7 @@ template <typename T> static int fused2_run(const ndwt_plan* p, const Fused2Laun
     const void* td = p->taps_dev[inverse ? 1 : 0];
     if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
     prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
-    int rc;
-    if (k.family != kInv2P) rc = launch2(inverse, a, Lp, vec4, q.ew, td, s);
-    else if constexpr (sizeof(T) == 4) rc = launch_inv2p_f32(a, Lp, k.pdepth, td, s, k.packed);
-    else rc = launch_inv2p_f64(a, Lp, td, s);
+    const int rc = launch_fused2_pick(k, q, a, td, s);
     prof_end(p, s, rc);
     if (rc == -1) return fail(NDWT_ERR_UNSUPPORTED, "no fused 2-D kernel instantiated for tap length %d", Lp);
     if (rc != 0) return fail(NDWT_ERR_HIP, "fused 2-D kernel launch failed: %s", hipGetErrorString((hipError_t)rc));

@@ -1,19 +1,20 @@
-// fused 2-D levels, double: analysis (Fwd2S) and the rows-in-flight synthesis (Inv2P); Inv2S: ndwt_fused2_f64_inv.hip
+// fused 2-D levels, double: analysis (Fwd2S), the rows-in-flight synthesis (Inv2P) and the double entry of the launch layer; Inv2S: ndwt_fused2_f64_inv.hip
 #include "ndwt_fused_kernels.h"
 namespace ndwt {
-int launch_fwd2_f64(const Fused2Args<double>& a, int Lp, bool vec4, int ew, const void* taps_dev, hipStream_t s) {
+static int launch_fwd2_f64(const Fused2Args<double>& a, int Lp, bool vec4, int ew, const void* taps_dev, hipStream_t s) {
     if (Lp > 6) { NDWT_FUSED2_SWITCH_LONG(Fwd2S, double) }
     NDWT_FUSED2_SWITCH_SHORT(Fwd2S, double)
 }
-// double synthesis of real data, rows of whole groups of 4 scalars: rows of band loads in flight, the row loop unrolled in groups of L
-// (Inv2P); up to 8 taps fit the 256-register budget without spills (4 rows in flight with 4 taps, 2 otherwise)
-int launch_inv2p_f64(const Fused2Args<double>& a, int Lp, const void* taps_dev, hipStream_t s) {
-    switch (Lp) {
-        case 2: return launch_fused2<Inv2P<double, 2, 2, 2>>(a, taps_dev, s);
-        case 4: return launch_fused2<Inv2P<double, 4, 4, 2>>(a, taps_dev, s);
-        case 6: return launch_fused2<Inv2P<double, 6, 2, 2>>(a, taps_dev, s);
-        case 8: return launch_fused2<Inv2P<double, 8, 2, 2>>(a, taps_dev, s);
-        default: return -1;
-    }
+int launch_inv2_f64(const Fused2Args<double>& a, int Lp, bool vec4, int ew, const void* taps_dev, hipStream_t s);
+int launch_long2_f64(bool inverse, const Fused2Args<double>& a, int Lp, bool vec4, const void* taps_dev, hipStream_t s);   // double real, db7 / db8
+static int launch_inv2p_f64(const Fused2PInstance& k, const Fused2Args<double>& a, const void* taps_dev, hipStream_t s) {
+    NDWT_LIST_F64_INV2P(NDWT_LAUNCH_P)
+    return -1;
+}
+// the double entry of the launch layer
+int launch_fused2_pick(const Fused2Pick& k, const Fused2Query& q, const Fused2Args<double>& a, const void* taps_dev, hipStream_t s) {
+    if (k.family == kInv2P) return launch_inv2p_f64({true, q.Lp, k.pdepth, k.packed != 0}, a, taps_dev, s);
+    if (q.Lp > 12) return q.ew != 1 ? -1 : launch_long2_f64(q.inverse, a, q.Lp, q.vec4, taps_dev, s);
+    return q.inverse ? launch_inv2_f64(a, q.Lp, q.vec4, q.ew, taps_dev, s) : launch_fwd2_f64(a, q.Lp, q.vec4, q.ew, taps_dev, s);
 }
 }  // namespace ndwt

@@ -1,14 +1,12 @@
 // Level 1 of a denoising step (dec -> shrink -> rec) without its detail bands in memory, float, real data, tap lengths 2 .. 8:
 // Den3 (analysis of the haloed tile + thresholding + synthesis in one launch) and the approximation-only analysis Fwd3<.., LOWONLY>
-// that feeds the deeper levels.  Reference use case: README.md:2 ("iterative algorithm").
+// that feeds the deeper levels (ndwt_denoise chooses both).  Reference use case: README.md:2 ("iterative algorithm").
 #include "ndwt_fused_kernels.h"
 namespace ndwt {
 
 template <int LL> static int go_den(const Fused3Args<float>& a, const void* taps_dev, hipStream_t s) {
     typedef Den3<float, LL, 1024, 4, (LL == 8 ? 6 : 0)> K;   // 8 taps: 6 of the 8 pending z sums in LDS (no spills)
-    FusedTapsD unused;
-    unused.Lp = LL;
-    return launch_fused3<K>(a, unused, taps_dev, s);
+    return launch_fused3<K>(a, taps_dev, s);
 }
 
 int launch_den3_f32(const Fused3Args<float>& a, int Lp, const void* taps_dev, hipStream_t s) {
@@ -25,9 +23,7 @@ int launch_den3_f32(const Fused3Args<float>& a, int Lp, const void* taps_dev, hi
 template <int LL, bool V, int TILE = 2> static int go_low(const Fused3Args<float>& a, const void* taps_dev, hipStream_t s) {
     typedef Fused3Tile<float, false, TILE> TL;
     typedef Fwd3<float, LL, TL::TX, TL::TY, TL::NT, TL::RY, V, TL::WPE, 1, true> K;
-    FusedTapsD unused;
-    unused.Lp = LL;
-    return launch_fused3<K>(a, unused, taps_dev, s);
+    return launch_fused3<K>(a, taps_dev, s);
 }
 
 int launch_fwd3_low_f32(const Fused3Args<float>& a, int Lp, bool vec4, const void* taps_dev, hipStream_t s) {
@@ -49,23 +45,9 @@ int launch_fwd3_low_f32(const Fused3Args<float>& a, int Lp, bool vec4, const voi
     }
 }
 
-// 4-D analysis with the t axis folded in (Fwd3<.., TPRE>): the tall tile with y items of 2 rows (Fused3Tile<float, false, 6>: the 8
-// prefetched frames fit its register budget), rows of whole groups of 4 scalars
-template <int LL> static int go_tpre(const Fused3Args<float>& a, const void* taps_dev, hipStream_t s) {
-    typedef Fused3Tile<float, false, 6> TL;
-    typedef Fwd3<float, LL, TL::TX, TL::TY, TL::NT, TL::RY, true, TL::WPE, 1, false, true> K;
-    FusedTapsD unused;
-    unused.Lp = LL;
-    return launch_fused3<K>(a, unused, taps_dev, s);
-}
-
-int launch_fwd3_tpre_f32(const Fused3Args<float>& a, int Lp, const void* taps_dev, hipStream_t s) {
-    switch (Lp) {
-        case 2: return go_tpre<2>(a, taps_dev, s);
-        case 4: return go_tpre<4>(a, taps_dev, s);
-        case 6: return go_tpre<6>(a, taps_dev, s);
-        case 8: return go_tpre<8>(a, taps_dev, s);
-        default: return -1;
-    }
+// 4-D analysis with the t axis folded in (Fwd3<.., TPRE>): chosen by the pick, as every instance of the other units
+int launch3_f32_den(const Fused3Instance& k, const Fused3Args<float>& a, const void* taps_dev, hipStream_t s) {
+    NDWT_LIST_F32_DEN(NDWT_LAUNCH_F)
+    return -1;
 }
 }  // namespace ndwt

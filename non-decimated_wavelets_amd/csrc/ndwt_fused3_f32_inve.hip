@@ -2,8 +2,8 @@
 // (a level dilated by 4) scalars
 #include "ndwt_fused_kernels.h"
 namespace ndwt {
-int launch_inv3_f32_ew(const Fused3Args<float>& a, const FusedTapsD& t, bool vec4, int ew, const void* taps_dev, hipStream_t s) {
-    NDWT_FUSED_SWITCH_INV_F32_EW(float)
+int launch3_f32_inve(const Fused3Instance& k, const Fused3Args<float>& a, const void* taps_dev, hipStream_t s) {
+    NDWT_LIST_F32_INVE(NDWT_LAUNCH_S)
     return -1;
 }
 }  // namespace ndwt

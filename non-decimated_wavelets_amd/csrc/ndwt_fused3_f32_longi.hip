@@ -2,11 +2,8 @@
 // padding, which the pair-packed kernel does not take)
 #include "ndwt_fused_kernels.h"
 namespace ndwt {
-int launch_long3_f32_inv(const Fused3Args<float>& a, const FusedTapsD& t, bool vec4, const void* taps_dev, hipStream_t s) {
-    switch (t.Lp) {
-        NDWT_FUSED_CASE(Inv3S, true, float, 14, 2)
-        NDWT_FUSED_CASE(Inv3S, true, float, 16, 2)
-        default: return -1;
-    }
+int launch3_f32_longi(const Fused3Instance& k, const Fused3Args<float>& a, const void* taps_dev, hipStream_t s) {
+    NDWT_LIST_F32_LONGI(NDWT_LAUNCH_S)
+    return -1;
 }
 }  // namespace ndwt

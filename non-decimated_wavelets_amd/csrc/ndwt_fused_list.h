@@ -1,0 +1,187 @@
+// ndwt_fused_list.h -- the instances of the fused kernels that kernel selection can name, one list per launch unit (no HIP header: the
+// launch units expand a list into launches, ndwt_select.h and the host tests into questions).  An instance lives in exactly one list: the
+// unit decides how its device code is compiled (csrc/Makefile: NOSLP), and the split over units is what keeps the build parallel.
+#pragma once
+#include "ndwt_fused_tile.h"
+
+namespace ndwt {
+
+// ---- the full name of a fused 3-D instance: every template argument of the kernel that runs
+enum Fused3Kernel { kFwd3, kInv3, kInv3S, kInv3Y, kNoFused3 };
+struct Fused3Instance {
+    Fused3Kernel kernel;
+    bool f64, vec4;                    // vec4: rows, strides and pointers in whole groups of 4 scalars
+    int Lp, ew;                        // padded tap length; scalars the x taps step over
+    int V;                             // Fwd3 / Inv3 / Inv3S: index into Fused3Tile (TX, TY, NT, RY, WPE)
+    bool pin, tpre;                    // Fwd3: taps pinned in SGPRs; the t axis of a 4-D level folded in
+    int wlds;                          // Fwd3: slots of the z window kept in LDS
+    int depth;                         // Inv3Y: register sets of band loads (ZLDS follows: inv3y_zlds)
+    bool uniyz, scatter;               // Inv3Y: shared y / z tap pairs; the x stage in scatter form
+};
+constexpr bool operator==(const Fused3Instance& a, const Fused3Instance& b) {
+    return a.kernel == b.kernel && a.f64 == b.f64 && a.vec4 == b.vec4 && a.Lp == b.Lp && a.ew == b.ew && a.V == b.V && a.pin == b.pin &&
+           a.tpre == b.tpre && a.wlds == b.wlds && a.depth == b.depth && a.uniyz == b.uniyz && a.scatter == b.scatter;
+}
+constexpr Fused3Instance fwd3_instance(bool f64, int L, int V, bool vec4, int ew, bool pin, bool tpre, int wlds) {
+    return {kFwd3, f64, vec4, L, ew, V, pin, tpre, wlds, 0, false, false};
+}
+constexpr Fused3Instance inv3s_instance(Fused3Kernel kernel, bool f64, int L, int V, bool vec4, int ew) {
+    return {kernel, f64, vec4, L, ew, V, false, false, 0, 0, false, false};
+}
+constexpr Fused3Instance inv3y_instance(int L, bool vec4, int ew, int depth, bool uniyz, bool scatter) {
+    return {kInv3Y, false, vec4, L, ew, 0, false, false, 0, depth, uniyz, scatter};
+}
+struct Fused2PInstance { bool f64; int Lp, pdepth; bool packed; };   // Inv2P<T, Lp, PD, 2, PK>
+constexpr bool operator==(const Fused2PInstance& a, const Fused2PInstance& b) {
+    return a.f64 == b.f64 && a.Lp == b.Lp && a.pdepth == b.pdepth && a.packed == b.packed;
+}
+
+// ---- the lists.  Entries:  F(T, L, V, VEC4, EW, PIN, TPRE, WLDS)  Fwd3 on tile V
+//                            S(KIND, T, L, V, VEC4, EW)             Inv3 / Inv3S on tile V
+//                            Y(L, VEC4, EW, DEPTH, UNIYZ, XSC)      Inv3Y (float)
+//                            P(T, L, PD, PK)                        Inv2P
+// NDWT_F2 / NDWT_S2 / NDWT_Y2: the plain form of an entry for rows of whole groups of 4 scalars and for the rest
+#define NDWT_F2(F, T, L, V, EW) F(T, L, V, true, EW, false, false, 0) F(T, L, V, false, EW, false, false, 0)
+#define NDWT_S2(S, KIND, T, L, V, EW) S(KIND, T, L, V, true, EW) S(KIND, T, L, V, false, EW)
+#define NDWT_Y2(Y, L, EW, DEPTH) Y(L, true, EW, DEPTH, false, false) Y(L, false, EW, DEPTH, false, false)
+
+// float analysis: 256-thread kernel for tap lengths <= 8, the tall 64x32 tile with 1024 threads for 10 and 12 (and 14, 16:
+// ndwt_fused3_f32_long.hip); tile 1 = 512 threads, one column per thread (A/B; the kernel of interleaved complex data with 10 .. 16 taps)
+#define NDWT_LIST_F32_FWD(F)                                                                                              \
+    NDWT_F2(F, float, 2, 1, 4) NDWT_F2(F, float, 4, 1, 4) NDWT_F2(F, float, 6, 1, 4) NDWT_F2(F, float, 8, 1, 4)           \
+    NDWT_F2(F, float, 6, 2, 2) NDWT_F2(F, float, 8, 2, 2)   /* interleaved complex on the tall tile */                    \
+    NDWT_F2(F, float, 2, 0, 2) NDWT_F2(F, float, 4, 0, 2) NDWT_F2(F, float, 6, 0, 2) NDWT_F2(F, float, 8, 0, 2)           \
+    NDWT_F2(F, float, 10, 1, 2) NDWT_F2(F, float, 12, 1, 2) NDWT_F2(F, float, 14, 1, 2) NDWT_F2(F, float, 16, 1, 2)       \
+    NDWT_F2(F, float, 2, 0, 1) NDWT_F2(F, float, 4, 0, 1) NDWT_F2(F, float, 6, 0, 1) NDWT_F2(F, float, 8, 0, 1)           \
+    NDWT_F2(F, float, 2, 2, 1) NDWT_F2(F, float, 4, 2, 1) NDWT_F2(F, float, 6, 2, 1) NDWT_F2(F, float, 8, 2, 1)           \
+    NDWT_F2(F, float, 10, 2, 1)   /* 10 .. 16 taps: the tall tile (db6 analysis 1.33 -> 1.02 ms per launch) */            \
+    NDWT_F2(F, float, 12, 2, 1)                                                                                           \
+    NDWT_F2(F, float, 10, 1, 1) NDWT_F2(F, float, 12, 1, 1)                                                               \
+    NDWT_F2(F, float, 8, 6, 1) NDWT_F2(F, float, 10, 6, 1)                                                                \
+    NDWT_F2(F, float, 12, 6, 1)   /* 12 .. 16 taps: y items of 2 rows (10 of the 16 waves in the y stage instead of 5: db6 -6 %) */
+// float real, 10 / 12 / 14 taps: tall tile with y items of 2 rows, taps pinned in SGPRs (Fwd3 PIN)
+#define NDWT_LIST_F32_FWDP(F) F(float, 10, 6, true, 1, true, false, 0) F(float, 12, 6, true, 1, true, false, 0) F(float, 14, 6, true, 1, true, false, 0)
+// 4-D analysis with the t axis folded in (Fwd3 TPRE): the tall tile with y items of 2 rows (the 8 prefetched frames fit its register
+// budget), rows of whole groups of 4 scalars
+#define NDWT_LIST_F32_DEN(F) \
+    F(float, 2, 6, true, 1, false, true, 0) F(float, 4, 6, true, 1, false, true, 0) F(float, 6, 6, true, 1, false, true, 0) F(float, 8, 6, true, 1, false, true, 0)
+// float analysis, 14 / 16 taps on the tall 64x32 tile with 1024 threads (db7 analysis 1.45 -> 1.15 ms per launch; 16 taps on ragged rows
+// spill 8 registers); 16 taps on rows of whole groups of 4 with two of the 16 slots of the z window in LDS
+#define NDWT_LIST_F32_LONG(F) NDWT_F2(F, float, 14, 6, 1) NDWT_F2(F, float, 16, 6, 1) F(float, 16, 6, true, 1, false, false, 2)
+// float analysis, 14 .. 20 taps on the 512-thread 64x16 tile (256-register budget); 20 taps with 4 (ragged rows: 6) window slots of each of
+// a thread's two columns in LDS, 18 taps on ragged rows with 2 (the plain 20-tap form spills 18 of its 256 registers)
+#define NDWT_LIST_F32_LONGB(F)                                                                                            \
+    NDWT_F2(F, float, 14, 1, 1) NDWT_F2(F, float, 16, 1, 1) NDWT_F2(F, float, 18, 1, 1) NDWT_F2(F, float, 20, 1, 1)       \
+    F(float, 20, 1, true, 1, false, false, 4) F(float, 18, 1, false, 1, false, false, 2) F(float, 20, 1, false, 1, false, false, 6)
+// float synthesis other than the pair-packed kernel (ndwt_fused3_f32_invy*.hip, the default wherever it applies): the lane-shift
+// kernel Inv3S on a tall 64x32 tile (1024 threads, one workgroup per CU; db6: 512 threads with two items each -- the 1024-thread
+// form spills there) for mixed wavelets with odd tap padding, dilated levels and A/B runs; the LDS kernel Inv3 (A/B, db4 only)
+#define NDWT_LIST_F32_INV(S)                                                                                              \
+    NDWT_S2(S, Inv3, float, 8, 3, 1)                                                                                      \
+    NDWT_S2(S, Inv3S, float, 2, 1, 1) NDWT_S2(S, Inv3S, float, 4, 1, 1) NDWT_S2(S, Inv3S, float, 6, 1, 1) NDWT_S2(S, Inv3S, float, 8, 1, 1) \
+    NDWT_S2(S, Inv3S, float, 10, 1, 1)                                                                                    \
+    NDWT_S2(S, Inv3S, float, 12, 2, 1)   /* db6: 512 threads x 2 items, no spills (1.78 vs 2.05 ms) */
+#define NDWT_LIST_F32_INVE(S)                                                                                             \
+    NDWT_S2(S, Inv3S, float, 2, 4, 4) NDWT_S2(S, Inv3S, float, 4, 4, 4) NDWT_S2(S, Inv3S, float, 6, 4, 4) NDWT_S2(S, Inv3S, float, 8, 4, 4) \
+    NDWT_S2(S, Inv3S, float, 2, 1, 2) NDWT_S2(S, Inv3S, float, 4, 1, 2) NDWT_S2(S, Inv3S, float, 6, 1, 2) NDWT_S2(S, Inv3S, float, 8, 1, 2) \
+    NDWT_S2(S, Inv3S, float, 10, 2, 2)   /* complex db5 / db6: 512 threads x 2 items (db6 spills 42 of 256 registers) */  \
+    NDWT_S2(S, Inv3S, float, 12, 2, 2)
+// float synthesis, 14 / 16 taps: the lane-shift kernel on the 64x32 tile with 512 threads x 2 items
+#define NDWT_LIST_F32_LONGI(S) NDWT_S2(S, Inv3S, float, 14, 2, 1) NDWT_S2(S, Inv3S, float, 16, 2, 1)
+
+// The pair-packed synthesis, real data.  Depth 2 (two register sets of band loads, staggered refill) exists where it fits the 128
+// registers of a 1024-thread workgroup without spills: tap lengths 2, 8 and 10 as they are; 12 with 6 of the pending z sums in LDS
+// (inv3y_zlds; 4 and 6 taps fit that way too and run slower than depth 1; a spill reload in the plane loop would wait vmcnt(0), i.e. for
+// every load in flight).  On rows that are not whole groups of 4 scalars (the VEC4 = false instance keeps 4 offsets per lane) 2 and 8
+// taps fit, 10 and 12 would spill.
+// UNIYZ (the same taps on the y and z axes, rows of whole groups of 4, 12 .. 20 taps): the z stage reads the y tap pairs (L fewer SGPRs
+// held: 512^3 synthesis db6 -1.8 %, db10 -2.4 % per launch, identical results).  8 taps: -0.6 % on cfg3 and +1.2 % on cfg5's batched
+// volumes in interleaved A/B runs -- within noise of each other, so the 8- and 10-tap kernels stay as they were.
+#define NDWT_LIST_F32_INVY_DB4(Y) NDWT_Y2(Y, 8, 1, 2) NDWT_Y2(Y, 8, 1, 1)
+#ifdef NDWT_INVY_DB4_ONLY
+#define NDWT_LIST_F32_INVY(Y) NDWT_LIST_F32_INVY_DB4(Y)
+#else
+#define NDWT_LIST_F32_INVY(Y)                                                                                             \
+    NDWT_LIST_F32_INVY_DB4(Y)                                                                                             \
+    Y(12, true, 1, 2, true, false) Y(14, true, 1, 1, true, false) Y(16, true, 1, 1, true, false) Y(18, true, 1, 1, true, false) \
+    Y(20, true, 1, 1, true, false)                                                                                        \
+    NDWT_Y2(Y, 2, 1, 2) NDWT_Y2(Y, 2, 1, 1) NDWT_Y2(Y, 4, 1, 1) NDWT_Y2(Y, 6, 1, 1)                                        \
+    Y(10, true, 1, 2, false, false) NDWT_Y2(Y, 10, 1, 1) Y(12, true, 1, 2, false, false) NDWT_Y2(Y, 12, 1, 1)             \
+    NDWT_Y2(Y, 14, 1, 1) NDWT_Y2(Y, 16, 1, 1)                                                                             \
+    NDWT_Y2(Y, 18, 1, 1)   /* 64 x 24 tile: 41 haloed rows on 14 waves */                                                 \
+    NDWT_Y2(Y, 20, 1, 1)   /* 48 x 28 tile: 47 haloed rows on 16 waves (3 spilled registers, reloaded once per plane) */
+#endif
+// ... with its x stage in scatter form: rows of whole groups of 4 scalars; two register sets up to 12 taps, one from 14
+#define NDWT_LIST_F32_INVYS(Y)                                                                                            \
+    Y(8, true, 1, 2, false, true) Y(10, true, 1, 2, false, true) Y(12, true, 1, 2, false, true) Y(12, true, 1, 2, true, true) \
+    Y(14, true, 1, 1, false, true) Y(14, true, 1, 1, true, true) Y(16, true, 1, 1, false, true) Y(16, true, 1, 1, true, true) \
+    Y(18, true, 1, 1, false, true) Y(18, true, 1, 1, true, true) Y(20, true, 1, 1, false, true) Y(20, true, 1, 1, true, true)
+// ... on interleaved complex data (EW = 2, tap lengths 2 .. 16; depth 2 where it fits 128 registers without spills, as for real data --
+// 10 taps: 1 spilled register; 14 / 16 taps: 48-wide tiles), its scatter form on rows of whole groups of 4 scalars from 8 taps, and on a
+// level dilated by 4 (EW = 4, rows of whole groups of 4 scalars only; scatter form: the sums walk from lane to lane instead of the samples)
+#define NDWT_LIST_F32_INVYC(Y)                                                                                            \
+    Y(8, true, 2, 2, false, true) Y(8, true, 2, 1, false, true) Y(10, true, 2, 1, false, true) Y(12, true, 2, 1, false, true) \
+    Y(14, true, 2, 1, false, true) Y(16, true, 2, 1, false, true)                                                         \
+    Y(2, true, 2, 2, false, false) NDWT_Y2(Y, 2, 2, 1) NDWT_Y2(Y, 4, 2, 1) NDWT_Y2(Y, 6, 2, 1)                             \
+    Y(8, true, 2, 2, false, false) NDWT_Y2(Y, 8, 2, 1) NDWT_Y2(Y, 10, 2, 1) NDWT_Y2(Y, 12, 2, 1) NDWT_Y2(Y, 14, 2, 1) NDWT_Y2(Y, 16, 2, 1) \
+    Y(4, true, 4, 1, false, true) Y(6, true, 4, 1, false, true) Y(8, true, 4, 2, false, true) Y(8, true, 4, 1, false, true) \
+    Y(2, true, 4, 2, false, false) Y(2, true, 4, 1, false, false) Y(4, true, 4, 1, false, false) Y(6, true, 4, 1, false, false) \
+    Y(8, true, 4, 2, false, false) Y(8, true, 4, 1, false, false)
+
+// double analysis: 64x8 tile with 256 threads; 6 / 8 taps on request and 10 taps: 64x16 with 512 threads, one column per thread; 12 taps:
+// 64x8 with 512 threads, no spills (64x16 spills 137 registers).  Complex128: 8 taps on 64x16 / 512 (the 256-thread tile spills 16
+// registers; 256^3: 0.97 -> 0.58 ms per launch), 10 / 12 on 64x8 / 512 (12: 16 spilled registers; on rows of whole groups of 4 two of
+// the 12 z-window slots in LDS: 2 spilled registers)
+#define NDWT_LIST_F64_FWD(F)                                                                                              \
+    F(double, 12, 5, true, 2, false, false, 2)                                                                            \
+    NDWT_F2(F, double, 2, 0, 2) NDWT_F2(F, double, 4, 0, 2) NDWT_F2(F, double, 6, 0, 2) NDWT_F2(F, double, 8, 1, 2)       \
+    NDWT_F2(F, double, 10, 5, 2) NDWT_F2(F, double, 12, 5, 2)                                                             \
+    NDWT_F2(F, double, 6, 1, 1) NDWT_F2(F, double, 8, 1, 1)                                                               \
+    NDWT_F2(F, double, 2, 0, 1) NDWT_F2(F, double, 4, 0, 1) NDWT_F2(F, double, 6, 0, 1) NDWT_F2(F, double, 8, 0, 1)       \
+    NDWT_F2(F, double, 10, 1, 1) NDWT_F2(F, double, 12, 5, 1)
+// double synthesis: the lane-shift kernel on a 64x16 tile with 512 threads; 10 / 12 taps (complex128: 10, 6 spilled registers): 64x8 tile,
+// 512 threads, no spills (64x16: 32 / 71 spilled registers); the LDS kernel Inv3 (A/B runs, db4 only)
+#define NDWT_LIST_F64_INV(S)                                                                                              \
+    NDWT_S2(S, Inv3S, double, 2, 1, 2) NDWT_S2(S, Inv3S, double, 4, 1, 2) NDWT_S2(S, Inv3S, double, 6, 1, 2) NDWT_S2(S, Inv3S, double, 8, 1, 2) \
+    NDWT_S2(S, Inv3S, double, 10, 5, 2)                                                                                   \
+    NDWT_S2(S, Inv3, double, 8, 3, 1)                                                                                     \
+    NDWT_S2(S, Inv3S, double, 2, 1, 1) NDWT_S2(S, Inv3S, double, 4, 1, 1) NDWT_S2(S, Inv3S, double, 6, 1, 1) NDWT_S2(S, Inv3S, double, 8, 1, 1) \
+    NDWT_S2(S, Inv3S, double, 10, 5, 1) NDWT_S2(S, Inv3S, double, 12, 5, 1)
+// double real, 14 and 16 taps (db7, db8): 64x8 tiles with 512 threads and the 256-register budget (no spills on rows of whole 4-element
+// groups; 10 .. 31 spilled registers in the 16-tap analysis and on ragged rows); the 16-tap analysis on rows of whole groups of 4 with two
+// of the 16 z-window slots in LDS: no spills (13 without)
+#define NDWT_LIST_F64_LONG(F, S)                                                                                          \
+    F(double, 16, 5, true, 1, false, false, 2) NDWT_F2(F, double, 14, 5, 1) NDWT_F2(F, double, 16, 5, 1)                  \
+    NDWT_S2(S, Inv3S, double, 14, 5, 1) NDWT_S2(S, Inv3S, double, 16, 5, 1)
+
+// 2-D synthesis with rows of band loads in flight (Inv2P), real data in rows of whole groups of 4 scalars.  float: PD rows in flight per
+// wave; packed FMAs on pairs of adjacent x outputs with the tap pairs pinned in SGPRs for 4 / 8 / 12 taps at depth 4.  double: up to 8
+// taps fit the 256-register budget without spills (4 rows in flight with 4 taps, 2 otherwise)
+#define NDWT_LIST_F32_INV2P(P)                                                                                            \
+    P(float, 4, 4, true) P(float, 8, 4, true) P(float, 12, 4, true)                                                       \
+    P(float, 2, 2, false) P(float, 4, 2, false) P(float, 4, 4, false) P(float, 6, 2, false) P(float, 8, 2, false) P(float, 8, 4, false) \
+    P(float, 10, 2, false) P(float, 12, 2, false) P(float, 12, 4, false)
+#define NDWT_LIST_F64_INV2P(P) P(double, 2, 2, false) P(double, 4, 4, false) P(double, 6, 2, false) P(double, 8, 2, false)
+
+// ---- questions to the lists
+#define NDWT_IS_F(T, L, V, VEC4, EW, PIN, TPRE, WLDS) if (k == fwd3_instance(sizeof(T) == 8, L, V, VEC4, EW, PIN, TPRE, WLDS)) return true;
+#define NDWT_IS_S(KIND, T, L, V, VEC4, EW) if (k == inv3s_instance(k##KIND, sizeof(T) == 8, L, V, VEC4, EW)) return true;
+#define NDWT_IS_Y(L, VEC4, EW, DEPTH, UNIYZ, XSC) if (k == inv3y_instance(L, VEC4, EW, DEPTH, UNIYZ, XSC)) return true;
+#define NDWT_IS_P(T, L, PD, PK) if (k == Fused2PInstance{sizeof(T) == 8, L, PD, PK}) return true;
+inline bool inv3y_instantiated(const Fused3Instance& k) {
+    NDWT_LIST_F32_INVY(NDWT_IS_Y) NDWT_LIST_F32_INVYS(NDWT_IS_Y) NDWT_LIST_F32_INVYC(NDWT_IS_Y)
+    return false;
+}
+inline bool fused3_instantiated(const Fused3Instance& k) {
+    if (k.kernel == kInv3Y) return inv3y_instantiated(k);
+    NDWT_LIST_F32_FWD(NDWT_IS_F) NDWT_LIST_F32_FWDP(NDWT_IS_F) NDWT_LIST_F32_DEN(NDWT_IS_F) NDWT_LIST_F32_LONG(NDWT_IS_F)
+    NDWT_LIST_F32_LONGB(NDWT_IS_F) NDWT_LIST_F32_INV(NDWT_IS_S) NDWT_LIST_F32_INVE(NDWT_IS_S) NDWT_LIST_F32_LONGI(NDWT_IS_S)
+    NDWT_LIST_F64_FWD(NDWT_IS_F) NDWT_LIST_F64_INV(NDWT_IS_S) NDWT_LIST_F64_LONG(NDWT_IS_F, NDWT_IS_S)
+    return false;
+}
+inline bool inv2p_instantiated(const Fused2PInstance& k) {
+    NDWT_LIST_F32_INV2P(NDWT_IS_P) NDWT_LIST_F64_INV2P(NDWT_IS_P)
+    return false;
+}
+
+}  // namespace ndwt

@@ -1,7 +1,7 @@
 // ndwt_select.h -- which kernel a level runs: plain host C++ on integers (no HIP header; any host compiler takes it).
 // ndwt_api.hip fills the queries from the plan and the launch's pointers, asks here, and launches what the pick names.
 #pragma once
-#include "ndwt_fused_tile.h"
+#include "ndwt_fused_list.h"
 
 namespace ndwt {
 
@@ -195,92 +195,97 @@ struct Fused3Query {
     int n1, n2, nbatch;                // scalars along x, rows and batch items of the launch (one sub-lattice of a dilated level)
     int variant_fwd, variant_inv, num_cus, target_blocks;
 };
-enum Fused3Family { kFwd3, kFwd3Pin, kFwd3FoldT, kLong3, kInv3Y, kInv3S, kInv3, kNoFused3 };   // kLong3: Fwd3 / Inv3S of 14 .. 20 taps; kInv3Y: by ew and scatter
-struct Fused3Pick {
-    Fused3Family family;
-    int V;                             // index into Fused3Tile (the launchers' tile argument); unused by the Inv3Y families
-    int TX, TY, depth, scatter, uniyz; // depth / scatter / uniyz: the Inv3Y instance (register sets of band loads, x stage, shared y / z tap pairs)
+// what a launch runs: the instance by its full name (ndwt_fused_list.h), and the geometry the host lays out for it
+struct Fused3Pick : Fused3Instance {
+    int TX, TY;                        // the instance's tile
     int per_cu, target;                // workgroups per CU the grid is sized for; target workgroups of fused3_geometry
-    int long_ab;                       // kLong3 analysis: kFwdOneColumn / kFwdSmallTile as asked for, else 0
 };
 
-// the tile a pick runs on: read from the table the kernels are compiled from
-struct TileXY { int TX, TY; };
-template <typename T, bool INV, int V> constexpr TileXY tile_of() { return {Fused3Tile<T, INV, V>::TX, Fused3Tile<T, INV, V>::TY}; }
-template <typename T, int V> constexpr TileXY tile_of(bool inverse) { return inverse ? tile_of<T, true, V>() : tile_of<T, false, V>(); }
-constexpr TileXY fused3_tile_shape(Fused3Family fam, bool f64, bool inverse, int V, int Lp, int ew) {
-    if (fam == kInv3Y) return {inv3y_tx(Lp, ew), inv3y_ty(Lp, ew)};
+// the tile an instance runs on: read from the table the kernels are compiled from (Inv3Y: 1024 threads, 4 waves per SIMD, no y items)
+struct TileShape { int TX, TY, NT, RY, WPE; };
+template <typename T, bool INV, int V> constexpr TileShape tile_of() {
+    return {Fused3Tile<T, INV, V>::TX, Fused3Tile<T, INV, V>::TY, Fused3Tile<T, INV, V>::NT, Fused3Tile<T, INV, V>::RY, Fused3Tile<T, INV, V>::WPE};
+}
+template <typename T, int V> constexpr TileShape tile_of(bool inverse) { return inverse ? tile_of<T, true, V>() : tile_of<T, false, V>(); }
+constexpr TileShape fused3_tile_shape(Fused3Kernel kernel, bool f64, int V, int Lp, int ew) {
+    const bool inverse = kernel != kFwd3;
+    if (kernel == kInv3Y) return {inv3y_tx(Lp, ew), inv3y_ty(Lp, ew), 1024, 0, 4};
     if (f64) return V == 0 ? tile_of<double, 0>(inverse) : V == 1 ? tile_of<double, 1>(inverse) : V == 3 ? tile_of<double, 3>(inverse)
-                  : V == 5 ? tile_of<double, 5>(inverse) : TileXY{0, 0};
-    if (V == 4 || V == 6) return (V == 4) != inverse ? TileXY{0, 0} : inverse ? tile_of<float, true, 4>() : tile_of<float, false, 6>();
+                  : V == 5 ? tile_of<double, 5>(inverse) : TileShape{0, 0, 0, 0, 0};
+    if (V == 4 || V == 6) return (V == 4) != inverse ? TileShape{0, 0, 0, 0, 0} : inverse ? tile_of<float, true, 4>() : tile_of<float, false, 6>();
     return V == 0 ? tile_of<float, 0>(inverse) : V == 1 ? tile_of<float, 1>(inverse) : V == 2 ? tile_of<float, 2>(inverse)
-         : V == 3 ? tile_of<float, 3>(inverse) : TileXY{0, 0};   // no such tile: the launcher's geometry check answers -2
+         : V == 3 ? tile_of<float, 3>(inverse) : TileShape{0, 0, 0, 0, 0};   // no such tile: the launcher's geometry check answers -2
 }
 
-// instance lists of the launchers whose answer is part of the decision
-constexpr bool inv3ys_exists(int Lp, int depth) { return Lp % 2 == 0 && ((Lp >= 14 && Lp <= 20) || (depth == 2 && Lp >= 8 && Lp <= 12)); }   // launch_inv3ys_f32
-constexpr bool inv3y_depth2(int Lp, bool vec4) { return Lp == 2 || Lp == 8 || (vec4 && (Lp == 10 || Lp == 12)); }   // launch_inv3y_f32: two register sets without spills
-
 inline Fused3Pick fused3_select(const Fused3Query& q) {
-    Fused3Pick k = {kFwd3, 0, 0, 0, 1, 0, 0, 1, 0, 0};
     const int L = q.Lp, vf = q.variant_fwd, vi = q.variant_inv;
     const bool f32 = !q.f64, plain = q.ew == 1;
+    Fused3Instance k = fwd3_instance(q.f64, L, 0, q.vec4, q.ew, false, false, 0);
     if (q.inverse) {
         // A level dilated by 2 on real data is the interleaved-pair form of Inv3Y (the two x sub-lattices are its (re, im) halves); the
         // whole-lane-shift form of tap stride 4 exists for 16-byte-aligned data only: anything else keeps Inv3S<.., EW = 4>
         const bool use_y = (q.dil == 1 || ((q.dil == 2 || (q.dil == 4 && q.vec4)) && vi != kInvDilatedKeep3S)) &&
                            inv3y_ok(q.f64, q.dil > 1 ? 1 : q.ew, q.len, L, (long long)q.n1 * q.n2 * q.dil, vi);
         const int want = vi == kInvDepth1 ? 1 : 2;          // register sets of band loads, where the instance has them
+        const auto y = [&](int depth, bool uniyz, bool scatter) { return inv3y_instance(L, q.vec4, q.ew, depth, uniyz, scatter); };
         if (use_y) {
             // the x stage in scatter form: real data from 10 taps on rows of whole groups of 4, interleaved pairs the same, tap stride 4 for
-            // 8 taps; kInvScatter: wherever the form exists, kInvGather: nowhere (measurements: DESIGN.md 4, "how a kernel is chosen")
-            k.family = kInv3Y;
+            // 8 taps; kInvScatter: wherever the form exists, kInvGather: nowhere (measurements: DESIGN.md 4, "how a kernel is chosen").
+            // Which depths and forms exist, and why, is in the lists of ndwt_fused_list.h: the wanted depth where there is such an instance,
+            // one register set otherwise (a scatter form of 8 .. 12 taps has two sets only: kInvDepth1 runs the gather form there); the
+            // shared y / z tap pairs wherever the instance has them (gather form: unless kInvNoUniYZ)
             const bool ask = vi == kInvScatter || (vi != kInvGather && L >= (q.ew == 4 ? 8 : 10));
-            k.scatter = ask && (q.ew == 4 ? L >= 4 : q.ew == 2 ? q.vec4 && L >= 8 : q.vec4 && inv3ys_exists(L, want));
-            k.depth = (want == 2 && (q.ew == 1 ? (k.scatter ? L < 14 : inv3y_depth2(L, q.vec4)) : (q.ew == 4 || q.vec4) && (L == 2 || L == 8))) ? 2 : 1;
-            k.uniyz = q.ew == 1 && q.uniform_yz && q.vec4 && (k.scatter ? L >= 12 : vi != kInvNoUniYZ && ((L == 12 && k.depth == 2) || L >= 14));
+            const bool scatter = ask && (inv3y_instantiated(y(want, false, true)) || inv3y_instantiated(y(1, false, true)));
+            const int depth = (want == 2 && inv3y_instantiated(y(2, false, scatter))) ? 2 : 1;
+            k = y(depth, q.uniform_yz && (scatter || vi != kInvNoUniYZ) && inv3y_instantiated(y(depth, true, scatter)), scatter);
         } else if (L > 12 && plain) {
-            k.family = kLong3;                               // Inv3S, 14 / 16 taps
-            k.V = f32 ? 2 : 5;
+            k = inv3s_instance(kInv3S, q.f64, L, f32 ? 2 : 5, q.vec4, 1);   // 14 / 16 taps
         } else if (plain && vi == kInvLds && L == 8) {
-            k.family = kInv3;
-            k.V = 3;
+            k = inv3s_instance(kInv3, q.f64, L, 3, q.vec4, 1);
         } else {
             // the lane-shift kernel: float on the tall tile (x taps over 4 scalars: 64x16, 512 threads; long filters: 512 threads x 2 items),
             // double 64x16 (10 / 12 taps: 64x8)
-            k.family = kInv3S;
-            k.V = f32 ? (q.ew == 4 ? 4 : (L == 12 || (q.ew == 2 && L == 10)) ? 2 : 1) : (L >= 10 ? 5 : 1);
+            k = inv3s_instance(kInv3S, q.f64, L, f32 ? (q.ew == 4 ? 4 : (L == 12 || (q.ew == 2 && L == 10)) ? 2 : 1) : (L >= 10 ? 5 : 1), q.vec4, q.ew);
         }
     } else if (q.f64) {
         // double, 6 / 8 taps: 64x16 tile with 512 threads, one column per thread; kFwdSmallTile keeps 64x8 / 256.  Complex db4 the same; 10 taps 64x16, 12: 64x8 / 512
         const bool col68 = (vf == kFwdDefault || vf == kFwdOneColumn) && L >= 6 && L <= 8;
-        if (L > 12 && plain) { k.family = kLong3; k.V = 5; }
+        if (L > 12 && plain) k.V = 5;
         else k.V = q.ew == 2 ? (L >= 10 ? 5 : L == 8 ? 1 : 0) : (L == 12 ? 5 : (L == 10 || col68) ? 1 : 0);
+        // two of the z-window slots in LDS (Fwd3 WLDS) on rows of whole groups of 4: 16 taps -- no spills (13 without); complex128 db6 --
+        // 2 spilled registers instead of 16
+        k.wlds = (q.vec4 && (plain ? L == 16 : L == 12)) ? 2 : 0;
     } else {
         // float (and complex64), 6 / 8 taps: the tall 64x32 tile with 1024 threads where the volume has the tiles to fill the chip with it
         const bool tall68 = L >= 6 && L <= 8 && (long long)((q.n1 + 63) / 64) * ((q.n2 + 31) / 32) * q.nbatch >= 32;
         const int v = (vf == kFwdDefault || vf == kFwdNoPin) ? (tall68 ? kFwdTall : kFwdDefault) : vf;
         if (q.tfold) {
-            k.family = q.vec4 ? kFwd3FoldT : kNoFused3;     // the folded t axis runs on the tall tile with y items of 2 rows
-            k.V = 6;
+            if (!q.vec4) k.kernel = kNoFused3;
+            k.V = 6, k.tpre = true;                           // the folded t axis runs on the tall tile with y items of 2 rows
         } else if (plain && vf == kFwdDefault && L >= 10 && L <= 14 && q.vec4 && padding_even(q.len, L)) {
             // real data, 10 / 12 / 14 taps, rows of whole groups of 4, even padding: the tall-tile kernel with its taps pinned in SGPRs
-            k.family = kFwd3Pin;
-            k.V = 6;
+            k.V = 6, k.pin = true;
         } else if (plain && L > 12) {
-            k.family = kLong3;                               // 14 / 16 taps: the tall tile; 18 / 20 (kFwdOneColumn: all): 64x16 with 512 threads
+            // 14 / 16 taps: the tall tile with y items of 2 rows; 18 / 20 (kFwdOneColumn: all): 64x16 with 512 threads, one column per thread
             k.V = (vf != kFwdOneColumn && L <= 16) ? 6 : 1;
-            k.long_ab = (vf == kFwdOneColumn || vf == kFwdSmallTile) ? vf : 0;
+            // Slots of the z window in LDS (Fwd3 WLDS) take the spills out; kFwdSmallTile: the spilling forms without them.
+            // tall tile, 16 taps on rows of whole groups of 4: two of the 16 slots -- 512^3 db8 analysis 1.53 -> 1.16 ms per launch,
+            // bit-identical (pinned taps on top: 1.20, not used).
+            // 512 threads, 20 taps: 4 of the 20 slots of each of a thread's two columns -- the tile without its 18 spilled registers:
+            // 512^3 db10 analysis 2.79 -> 1.95 ms per launch, bit-identical; 18 taps do not spill and gain nothing from it.  Ragged rows:
+            // 2 / 6 slots for 18 / 20 taps, no spills (8 / 33 without)
+            if (vf != kFwdSmallTile) k.wlds = k.V == 6 ? ((L == 16 && q.vec4) ? 2 : 0) : L == 20 ? (q.vec4 ? 4 : 6) : (L == 18 && !q.vec4) ? 2 : 0;
         } else if (q.ew == 4) k.V = 1;
         else if (q.ew == 2) k.V = L >= 10 ? 1 : (q.dil == 1 && vf == kFwdDefault && tall68) ? 2 : 0;
+        // real data by tap length: 256 threads up to 8 taps, the tall tile for 10, with y items of 2 rows for 12; on request the tall tile
+        // (any length), one column per thread (10 / 12 taps) or y items of 2 rows (8 .. 12 taps: no other instance exists)
+        else if (v == kFwdTallRY2 && L < 8) k.kernel = kNoFused3;
         else k.V = v == kFwdTall ? 2 : (v == kFwdOneColumn && L >= 10) ? 1 : v == kFwdTallRY2 ? 6 : (L <= 8 ? 0 : L == 10 ? 2 : 6);
     }
-    const TileXY tile = fused3_tile_shape(k.family, q.f64, q.inverse, k.V, L, q.ew);
-    k.TX = tile.TX, k.TY = tile.TY;
+    const TileShape tile = fused3_tile_shape(k.kernel, q.f64, k.V, L, q.ew);
     // one round of resident workgroups: synthesis 1 per CU (the 256-thread LDS kernel 3), analysis 2, 1024-thread tiles 1
-    k.per_cu = q.inverse ? ((k.family == kInv3 && f32) ? 3 : 1) : ((q.dil == 4 || (f32 && k.TY == 32)) ? 1 : 2);
-    k.target = q.target_blocks > 0 ? q.target_blocks : q.num_cus * k.per_cu;
-    return k;
+    const int per_cu = q.inverse ? ((k.kernel == kInv3 && f32) ? 3 : 1) : ((q.dil == 4 || (f32 && tile.TY == 32)) ? 1 : 2);
+    return {k, tile.TX, tile.TY, per_cu, q.target_blocks > 0 ? q.target_blocks : q.num_cus * per_cu};
 }
 
 // ---- one fused 2-D launch

@@ -17,27 +17,30 @@ extern "C" int sel_level_path(const int* plan, int stride, int dir, int slab, in
 extern "C" int sel_cascade2_levels(const int* plan, int inverse, int left) { int Lp = 0; return cascade2_levels(plan_of(plan), inverse != 0, left, &Lp); }
 
 // v: f64, inverse, vec4, uniform_yz, tfold, Lp, len[3], ew, dil, n1, n2, nbatch, variant_fwd, variant_inv, num_cus, target_blocks
-// out: V, TX, TY, depth, scatter, uniyz, per_cu, target, pinned, folded t;  returns the kernel family's name as the launch trace spells it
+// out: the pick in full -- V, TX, TY, NT, RY, WPE, PIN, TPRE, WLDS, DEPTH, ZLDS, UNIYZ, XSC, per_cu, target, VEC4, EW, Lp, f64, and whether
+// the instance lists (ndwt_fused_list.h) hold it;  returns the kernel's name as the launch trace spells it
 extern "C" const char* sel_fused3(const int* v, int* out) {
     const Fused3Query q = {v[0] != 0, v[1] != 0, v[2] != 0, v[3] != 0, v[4] != 0, v[5], {v[6], v[7], v[8]}, v[9], v[10], v[11], v[12], v[13],
                            v[14], v[15], v[16], v[17]};
     const Fused3Pick k = fused3_select(q);
-    const int r[10] = {k.V, k.TX, k.TY, k.depth, k.scatter, k.uniyz, k.per_cu, k.target, k.family == kFwd3Pin, k.family == kFwd3FoldT};
-    for (int i = 0; i < 10; ++i) out[i] = r[i];
-    switch (k.family) {
+    const TileShape t = fused3_tile_shape(k.kernel, k.f64, k.V, k.Lp, k.ew);
+    const int r[20] = {k.V, k.TX, k.TY, t.NT, t.RY, t.WPE, k.pin, k.tpre, k.wlds, k.depth, k.kernel == kInv3Y ? inv3y_zlds(k.Lp, k.depth, k.ew) : 0,
+                       k.uniyz, k.scatter, k.per_cu, k.target, k.vec4, k.ew, k.Lp, k.f64, fused3_instantiated(k)};
+    for (int i = 0; i < 20; ++i) out[i] = r[i];
+    switch (k.kernel) {
+        case kFwd3: return "Fwd3";
         case kInv3Y: return "Inv3Y";
         case kInv3S: return "Inv3S";
         case kInv3: return "Inv3";
-        case kLong3: return q.inverse ? "Inv3S" : "Fwd3";
-        case kNoFused3: return "none";
-        default: return "Fwd3";
+        default: return "none";
     }
 }
 
-// v: f64, inverse, vec4, Lp, ew, dil, n1, n2, variant_inv;  out: family, pdepth, packed, waves
+// v: f64, inverse, vec4, Lp, ew, dil, n1, n2, variant_inv;  out: family, pdepth, packed, waves, and (Inv2P) whether the lists hold the instance
 extern "C" void sel_fused2(const int* v, int* out) {
     const Fused2Query q = {v[0] != 0, v[1] != 0, v[2] != 0, v[3], v[4], v[5], v[6], v[7], v[8]};
     const Fused2Pick k = fused2_select(q);
     out[0] = (int)k.family; out[1] = k.pdepth; out[2] = k.packed; out[3] = k.waves;
+    out[4] = k.family == kInv2P && inv2p_instantiated({q.f64, q.Lp, k.pdepth, k.packed != 0});
 }
 extern "C" int sel_cascade2_rec_depth(int variant_inv) { return cascade2_rec_depth(variant_inv); }

@@ -14,8 +14,8 @@ from test_gpu_dispatch import ROWS
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 NUM_CUS = 256
-# template parameters that follow from the tile table inside the kernel units: the pick does not carry them
-NOT_IN_PICK = ("NT", "RY", "WLDS", "ZLDS")
+# template parameters of a pinned kernel that the pick does not name: none -- the pick is the instance's full name
+NOT_IN_PICK = ()
 # rows without a fused level-1 launch in either direction (1-D signals, the per-axis path on request, double with 18 taps)
 LEFT_OUT = ["1d-vec4", "1d-ragged", "1d-c64", "1d-db7-plain", "generic-path", "f64-db9-per-axis"]
 # LevelRouteKind of csrc/ndwt_select.h
@@ -33,6 +33,23 @@ def shim(tmp_path_factory):
     lib = ctypes.CDLL(out)
     lib.sel_fused3.restype = ctypes.c_char_p
     return lib
+
+
+def _fused3(shim, q):
+    """fused3_select for the query: (kernel name, the trace parameters of the instance it names, the raw answer by field)"""
+    r = (ctypes.c_int * 20)()
+    name = shim.sel_fused3(_ints(q), r).decode()
+    f = dict(zip(("V", "TX", "TY", "NT", "RY", "WPE", "PIN", "TPRE", "WLDS", "DEPTH", "ZLDS", "UNIYZ", "XSC", "per_cu", "target", "VEC4", "EW",
+                  "L", "f64", "listed"), r))
+    p = {"T": "double" if f["f64"] else "float", "L": f["L"], "EW": f["EW"], "TX": f["TX"], "TY": f["TY"], "NT": f["NT"], "WPE": f["WPE"],
+         "VEC4": bool(f["VEC4"])}
+    if name == "Fwd3":
+        p.update(RY=f["RY"], PIN=bool(f["PIN"]), TPRE=bool(f["TPRE"]), WLDS=f["WLDS"], LOWONLY=False)
+    if name in ("Inv3", "Inv3S"):
+        p.update(RY=f["RY"])
+    if name == "Inv3Y":
+        p.update(XSC=bool(f["XSC"]), UNIYZ=bool(f["UNIYZ"]), DEPTH=f["DEPTH"], ZLDS=f["ZLDS"])
+    return name, p, f
 
 
 def _ints(v):
@@ -68,16 +85,10 @@ def _picks(shim, row, inverse):
     (kind, L), out = _route(shim, plan, 1, inverse), []
     if kind in (FUSED3, FUSED3_T, FUSED3_FOLD_T):
         tfold = kind == FUSED3_FOLD_T and vec4                   # (the caller keeps the route for 16-byte-aligned pointers only)
-        q = _ints([f64, inverse, vec4, wl[1] == wl[2], tfold, L] + lens[:3] + [comp, 1, n1, dims[1], dims[3] if d == 4 else 1, vf, vi, NUM_CUS, 0])
-        r = (ctypes.c_int * 10)()
-        name = shim.sel_fused3(q, r).decode()
-        V, TX, TY, depth, scatter, uniyz, per_cu, target, pin, tpre = list(r)
-        assert target == NUM_CUS * per_cu
-        p = {"T": T, "L": L, "EW": comp, "TX": TX, "TY": TY, "VEC4": vec4}
-        if name == "Fwd3":
-            p.update(PIN=bool(pin), TPRE=bool(tpre))
-        if name == "Inv3Y":
-            p.update(XSC=bool(scatter), UNIYZ=bool(uniyz), DEPTH=depth)
+        name, p, f = _fused3(shim, [f64, inverse, vec4, wl[1] == wl[2], tfold, L] + lens[:3] + [comp, 1, n1, dims[1], dims[3] if d == 4 else 1, vf, vi,
+                                    NUM_CUS, 0])
+        assert f["target"] == NUM_CUS * f["per_cu"] and (f["L"], f["EW"], bool(f["VEC4"]), bool(f["f64"])) == (L, comp, vec4, f64)
+        assert f["listed"], (row, name, p)
         out.append((name, p))
     elif kind == FUSED2:
         left = row["level"]
@@ -91,7 +102,7 @@ def _picks(shim, row, inverse):
             out.append(("Inv2C" if inverse else "Fwd2C", p))
             left -= n
         if left > 0:
-            r = (ctypes.c_int * 4)()
+            r = (ctypes.c_int * 5)()
             shim.sel_fused2(_ints([f64, inverse, vec4, L, comp, 1, n1, dims[1], vi]), r)
             if r[0] == 1:
                 out.append(("Inv2P", {"T": T, "L": L, "PD": r[1], "PK": bool(r[2])}))
@@ -174,19 +185,12 @@ def test_slab_rows_pick_their_pinned_kernels(shim):
                 picks = []
                 if kind in (FUSED3, FUSED3_T):
                     for nbatch in ([1, 2] if d == 3 else [local[3]] if ax == 2 else [local[3], local[3] + lens[3] - 1]):
-                        q = _ints([f64, inverse, vec4, wl[1] == wl[2], 0, L] + lens[:3] + [comp, 1, n1, dims[1], nbatch, max(row["fwd"], 0),
-                                  max(row["inv"], 0), NUM_CUS, 0])
-                        r = (ctypes.c_int * 10)()
-                        name = shim.sel_fused3(q, r).decode()
-                        V, TX, TY, depth, scatter, uniyz, per_cu, target, pin, tpre = list(r)
-                        p = {"T": T, "L": L, "EW": comp, "TX": TX, "TY": TY, "VEC4": vec4}
-                        if name == "Fwd3":
-                            p.update(PIN=bool(pin), TPRE=bool(tpre))
-                        if name == "Inv3Y":
-                            p.update(XSC=bool(scatter), UNIYZ=bool(uniyz), DEPTH=depth)
+                        name, p, f = _fused3(shim, [f64, inverse, vec4, wl[1] == wl[2], 0, L] + lens[:3] + [comp, 1, n1, dims[1], nbatch,
+                                                    max(row["fwd"], 0), max(row["inv"], 0), NUM_CUS, 0])
+                        assert f["listed"], (prm.id, name, p)
                         picks.append((name, p))
                 elif kind == FUSED2:
-                    r = (ctypes.c_int * 4)()
+                    r = (ctypes.c_int * 5)()
                     shim.sel_fused2(_ints([f64, inverse, vec4, L, comp, 1, n1, local[1], max(row["inv"], 0)]), r)
                     picks.append(("Inv2P", {"T": T, "L": L, "PD": r[1], "PK": bool(r[2])}) if r[0] == 1 else
                                  ("Inv2S" if inverse else "Fwd2S", {"T": T, "L": L, "EW": comp, "VEC4": vec4}))
@@ -199,3 +203,77 @@ def test_slab_rows_pick_their_pinned_kernels(shim):
                     assert any(helpers.matches(rec, sp) for sp in specs), (prm.id, (z0, z1), "syn" if inverse else "ana", rec, specs)
                     checked += 1
     assert checked >= 2 * 2 * 30
+
+
+# every number of the two variant columns of csrc/ndwt_select.h (0: the default)
+FWD_NUMBERS = (0, 1, 2, 3, 6, 7, 8, 9, 10, 11)
+INV_NUMBERS = (0, 1, 2, 3, 4, 5, 6, 7, 9, 10, 11, 12)
+
+
+def test_every_pick_names_an_instance(shim):
+    """fused3_select over everything level_route lets through -- both scalar types, real and interleaved complex, 3-D and 4-D, padded tap
+    lengths 2 .. 20, uniform wavelets and mixed ones with even / odd padding (on y, so uniform_yz goes off, and on x, where it stays on),
+    rows and pointers in whole groups of 4 scalars or not, volumes on both sides of the 32-tile threshold, the dilated levels (ew = dil = 2, 4),
+    the folded t axis, every variant number of its direction: the pick is an entry of the instance lists (csrc/ndwt_fused_list.h), or the
+    selector says that there is no kernel (the folded t axis on unaligned pointers; fwd 6 below 8 taps)"""
+    picks, none = set(), 0
+    for f64 in (False, True):
+        for cplx in (False, True):
+            comp = 2 if cplx else 1
+            for L in range(2, 21, 2):
+                mixes = [[L, L, L]] + ([[L, L - 2, L], [L - 2, L, L]] if L >= 4 else []) + ([[L, L - 4, L], [L - 4, L, L]] if L >= 6 else [])
+                for lens in mixes:
+                    for dims, stride in (([64, 40, 36], 1), ([70, 40, 36], 1), ([256, 256, 36], 1), ([64, 40, 36, 8], 1), ([72, 40, 36, 8], 1),
+                                         ([64, 40, 36], 2), ([64, 40, 36], 4)):
+                        for inverse in (False, True):
+                            for number in (INV_NUMBERS if inverse else FWD_NUMBERS):
+                                vf, vi = (0, number) if inverse else (number, 0)
+                                plan = _plan(dims, lens + [4], f64, cplx, False, stride > 1, vf, vi)
+                                kind, Lp = _route(shim, plan, stride, inverse)
+                                if kind not in (FUSED3_DILATED, FUSED3, FUSED3_T, FUSED3_FOLD_T):
+                                    continue
+                                for vec4 in ((False, True) if (dims[0] * comp) % 4 == 0 else (False,)):
+                                    tfold = kind == FUSED3_FOLD_T and vec4   # (unaligned pointers: the caller takes kRouteFused3T)
+                                    if kind == FUSED3_DILATED:
+                                        q = [f64, inverse, vec4, lens[1] == lens[2], 0, Lp] + lens + [stride, stride, dims[0], dims[1] // stride,
+                                             stride * stride, vf, vi, NUM_CUS, 0]
+                                    else:
+                                        q = [f64, inverse, vec4, lens[1] == lens[2], tfold, Lp] + lens + [comp, 1, dims[0] * comp, dims[1],
+                                             dims[3] if len(dims) == 4 else 1, vf, vi, NUM_CUS, 0]
+                                    name, p, f = _fused3(shim, q)
+                                    if name == "none":
+                                        assert (vf == 6 and Lp < 8 and not f64 and not cplx) or (kind == FUSED3_FOLD_T and not vec4), q
+                                        none += 1
+                                        continue
+                                    assert f["listed"], (name, p, q)
+                                    assert (name == "Fwd3") == (not inverse)
+                                    picks.add((name, tuple(sorted(p.items()))))
+    # the sweep reaches the instances of every launch unit: by kernel, scalar type, x step and the flags that tell the units apart
+    for fam, want in (("Fwd3", dict(T="float", PIN=True)), ("Fwd3", dict(T="float", TPRE=True)), ("Fwd3", dict(T="float", L=16, WLDS=2)),
+                      ("Fwd3", dict(T="float", L=20, WLDS=4)), ("Fwd3", dict(T="float", L=20, WLDS=6)), ("Fwd3", dict(T="float", L=18, WLDS=2)),
+                      ("Fwd3", dict(T="float", L=20, WLDS=0)), ("Fwd3", dict(T="float", EW=4)), ("Fwd3", dict(T="double", L=16, WLDS=2)),
+                      ("Fwd3", dict(T="double", L=12, EW=2, WLDS=2)), ("Fwd3", dict(T="double", L=12, EW=2, WLDS=0)),
+                      ("Inv3", dict(T="float")), ("Inv3", dict(T="double")), ("Inv3S", dict(T="float", L=16)), ("Inv3S", dict(T="float", EW=4)),
+                      ("Inv3S", dict(T="float", EW=2)), ("Inv3S", dict(T="double", L=16)), ("Inv3S", dict(T="double", EW=2)),
+                      ("Inv3Y", dict(XSC=True, EW=1, UNIYZ=True)), ("Inv3Y", dict(XSC=False, UNIYZ=True)), ("Inv3Y", dict(EW=2, XSC=True)),
+                      ("Inv3Y", dict(EW=4, XSC=True)), ("Inv3Y", dict(EW=4, XSC=False)), ("Inv3Y", dict(L=12, ZLDS=6)), ("Inv3Y", dict(L=20, ZLDS=8)),
+                      ("Inv3Y", dict(L=8, DEPTH=1, VEC4=False))):
+        assert any(name == fam and all(dict(p).get(k) == v for k, v in want.items()) for name, p in picks), (fam, want)
+    assert len(picks) >= 200 and none > 0, (len(picks), none)
+
+
+def test_every_inv2p_pick_names_an_instance(shim):
+    """fused2_select the same way against the Inv2P lists: both scalar types, tap lengths 2 .. 20, both sides of n2 >= 64 and of the one-round
+    budget, every variant number"""
+    seen = set()
+    for f64 in (False, True):
+        for L in range(2, 21, 2):
+            for vec4 in (False, True):
+                for n1, n2 in ((256, 63), (256, 64), (4096, 5250), (4096, 5251)):
+                    for vi in INV_NUMBERS:
+                        r = (ctypes.c_int * 5)()
+                        shim.sel_fused2(_ints([f64, True, vec4, L, 1, 1, n1, n2, vi]), r)
+                        if r[0] == 1:
+                            assert r[4], (f64, L, vec4, n1, n2, vi, list(r))
+                            seen.add((f64, L, r[1], r[2]))
+    assert len(seen) == 12 + 4                                  # every entry of the two lists is some pick

@@ -155,6 +155,25 @@ ROWS = [
     R("fwd10-inv12-small-cascade", [256, 96], "db3", level=2, fwd=10, inv=12, dec=["Fwd2C L=6 NLEV=2"], rec=["Inv2C L=6 NLEV=2 PD=2"]),
     R("fwd11-db6-cascade-2lev", [256, 96], "db6", level=3, fwd=11, dec=["Fwd2C L=12 NLEV=2", "Fwd2S L=12"], rec=["Inv2P L=12"]),
     R("inv7-inv2p-scalar", [256, 64], "db4", inv=7, dec=["Fwd2S L=8"], rec=["Inv2P L=8 PK=false"]),
+    # ... and the instance each 3-D number names where the default would run another one (the other direction stays the default's)
+    R("fwd1-db7-one-column", [64, 40, 36], "db7", fwd=1, dec=["Fwd3 L=14 TY=16 NT=512 WLDS=0 PIN=false"],
+      rec=["Inv3Y L=14 XSC=true UNIYZ=true DEPTH=1"]),
+    R("fwd1-db8-one-column", [64, 40, 36], "db8", fwd=1, dec=["Fwd3 L=16 TY=16 NT=512 WLDS=0"], rec=["Inv3Y L=16 XSC=true UNIYZ=true"]),
+    R("fwd3-db8-no-window-slots", [64, 40, 36], "db8", fwd=3, dec=["Fwd3 L=16 TY=32 NT=1024 RY=2 WLDS=0"],
+      rec=["Inv3Y L=16 XSC=true UNIYZ=true"]),
+    R("fwd3-db10-no-window-slots", [64, 40, 36], "db10", fwd=3, dec=["Fwd3 L=20 TY=16 NT=512 WLDS=0"],
+      rec=["Inv3Y L=20 TX=48 TY=28 XSC=true UNIYZ=true"]),
+    R("fwd1-db5-one-column", [64, 40, 36], "db5", fwd=1, dec=["Fwd3 L=10 TY=16 NT=512 PIN=false"],
+      rec=["Inv3Y L=10 XSC=true UNIYZ=false DEPTH=2"]),
+    R("fwd2-db2-tall", [64, 40, 36], "db2", fwd=2, dec=["Fwd3 L=4 TY=32 NT=1024 RY=4"], rec=["Inv3Y L=4"]),
+    R("fwd6-db4-tall-ry2", [64, 40, 36], "db4", fwd=6, dec=["Fwd3 L=8 TY=32 RY=2"], rec=["Inv3Y L=8 XSC=false VEC4=true DEPTH=2"]),
+    R("inv5-db4-depth1", [64, 40, 36], "db4", inv=5, dec=["Fwd3 L=8 TY=16"], rec=["Inv3Y L=8 DEPTH=1"]),
+    R("inv2-atrous-keeps-inv3s", [32, 32, 32], "db4", dil="atrous", level=3, inv=2, dec=["Fwd3 L=8 EW=1", "Fwd3 L=8 EW=2", "Fwd3 L=8 EW=4"],
+      rec=["Inv3Y L=8 EW=1", "Inv3S L=8 EW=2", "Inv3S L=8 EW=4"]),
+    R("fwd1-f64-db3-one-column", [64, 40, 36], "db3", prec="double", fwd=1, dec=["Fwd3 T=double L=6 TY=16 NT=512"],
+      rec=["Inv3S T=double L=6 TY=16 NT=512"]),
+    R("fwd3-f64-db3-small-tile", [64, 40, 36], "db3", prec="double", fwd=3, dec=["Fwd3 T=double L=6 TY=8 NT=256"],
+      rec=["Inv3S T=double L=6 TY=16 NT=512"]),
 ]
 
 

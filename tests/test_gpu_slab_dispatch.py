@@ -77,7 +77,7 @@ ROWS = [
     S("db7-pinned", [64, 40, 56], "db7", ["Fwd3 L=14 PIN=true TY=32"], ["Inv3Y L=14 XSC=true UNIYZ=true DEPTH=1"]),
     # (10 - 8) / 2 = 1, odd padding of x: no pinned taps (64x32 tile, V = 2), no Inv3Y -> Inv3S on its tall tile (V = 1)
     S("odd-padding-10", [64, 40, 40], ["db4", "db5", "db5"], ["Fwd3 L=10 PIN=false TY=32 NT=1024 VEC4=true"], ["Inv3S L=10 TY=32 NT=1024 VEC4=true"]),
-    # (16 - 14) / 2 = 1: Inv3S of 16 taps (kLong3, 512 threads x 2 items); analysis 16 taps: 2 window slots in LDS
+    # (16 - 14) / 2 = 1: Inv3S of 16 taps (512 threads x 2 items); analysis 16 taps: 2 window slots in LDS
     S("odd-padding-16", [64, 40, 64], ["db7", "db7", "db8"], ["Fwd3 L=16 WLDS=2 TY=32"], ["Inv3S L=16 TY=32 NT=512"]),
     S("db8-wlds2", [64, 40, 64], "db8", ["Fwd3 L=16 WLDS=2 TY=32 VEC4=true"], ["Inv3Y L=16 XSC=true UNIYZ=true"]),
     # 18 / 20 taps: fused in each direction (analysis up to 20 taps; synthesis above 16 through Inv3Y), but ndwt_plan_slab_fast asks
