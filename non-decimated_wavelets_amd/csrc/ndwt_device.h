@@ -2147,9 +2147,9 @@ template <typename T, int L> struct TapsDen {
     T axp[L + 1][2];         // (alo_x[k], alo_x[k-1]), k = 0..L, taps outside [0, L) = 0: the x stage works on pairs of adjacent x
 };
 
-template <typename T, int L_, int NT_ = 1024, int WPE_ = 4, int ZLDS_ = 0> struct Den3 {
+template <typename T, int L_, int NT_ = 1024, int WPE_ = 4, int ZLDS_ = 0, int TX_ = 64, int TY_ = 32> struct Den3 {
     static_assert(sizeof(T) == 4, "float only");
-    static constexpr int L = L_, TX = 64, TY = 32, NT = NT_, WPE = WPE_;
+    static constexpr int L = L_, TX = TX_, TY = TY_, NT = NT_, WPE = WPE_;   // (the tile is a parameter so that the launch trace names it)
     static constexpr int ALH = L / 2 - 1, ARH = L / 2;   // analysis: samples left / right of the output index
     static constexpr int XH = (ARH + 3) / 4;             // extra lanes per side of a haloed row
     typedef Inv3Y<T, L, TX, TY, NT, true, WPE, 1, 1, ZLDS_, XH> Y;   // (ZLDS_ of the L pending z sums in LDS: Inv3Y)

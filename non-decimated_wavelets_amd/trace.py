@@ -23,7 +23,7 @@ FAMILY_PARAMS = {
     "Inv3S": [("T", None), ("L", None), ("TX", None), ("TY", None), ("NT", None), ("RY", None), ("VEC4", None), ("WPE", 2), ("EW", 1)],
     "Inv3Y": [("T", None), ("L", None), ("TX", None), ("TY", None), ("NT", None), ("VEC4", None), ("WPE", 4), ("DEPTH", 1), ("EW", 1),
               ("ZLDS", 0), ("XH", 0), ("UNIYZ", False), ("XSC", False)],
-    "Den3": [("T", None), ("L", None), ("NT", 1024), ("WPE", 4), ("ZLDS", 0)],
+    "Den3": [("T", None), ("L", None), ("NT", 1024), ("WPE", 4), ("ZLDS", 0), ("TX", 64), ("TY", 32)],
     "Fwd2S": [("T", None), ("L", None), ("VEC4", None), ("WPE", 4), ("EW", 1)],
     "Fwd2C": [("T", None), ("L", None), ("NLEV", None), ("WPE", 2)],
     "Inv2S": [("T", None), ("L", None), ("VEC4", None), ("WPE", 4), ("EW", 1)],

@@ -3,6 +3,11 @@
 Catches indexing mistakes (global and LDS out-of-bounds, wrong halo/wrap arithmetic, band order) on
 the CPU; the -m gpu tests then check the real kernels.  Reference semantics: one level of
 Functions/nd_dwt_3D.m:345-374 (level_1_dec / level_1_rec).
+
+Long marches: every case table below ends with one case of n3 = 3 L + 2 planes (rows) in forced chunks of 2 L + 1 at the largest tap
+length its form is emulated for -- the first chunk takes every one of the L compile-time rotations of the plane window through more than
+two full turns WITH its stores, the second starts off plane 0 and ends on the periodic wrap (tests/test_gpu_long_march.py does the same
+on the device).  The shorter cases above them reach the first few rotations only.
 """
 import ctypes
 import os
@@ -84,6 +89,8 @@ CASES = [
     ((70, 19, 10), ("db2", "db1", "db4"), False, 6, False),
     ((134, 20, 7), ("db4", "db4", "db4"), False, 0, False),      # three production tiles along x, the last anchored at the end of the row
     ((130, 18, 6), ("db4", "db4", "db4"), False, 0, False),      # a 2-column last tile; the tile before it reaches past the end too
+    ((20, 10, 38), ("db6", "db6", "db6"), True, 25, True),       # long march, 12 taps: Fwd3 / Inv3 / Inv3S through every rotation
+    ((68, 18, 26), ("db4", "db4", "db4"), True, 17, False),      # ... on the production tiles (8 taps)
 ]
 
 
@@ -139,6 +146,8 @@ CASES_Y = [
     ((24, 22, 21), ("db10", "db10", "db10"), True, 0, True),      # 27 haloed rows: three rounds of rows on the small tile
     ((21, 20, 20), ("db10", "db8", "db6"), False, 4, True),
     ((72, 37, 12), ("db6", "db6", "db6"), True, 0, False),       # production tile shape, 12 taps: 15 of the 16 waves hold rows
+    ((24, 22, 62), ("db10", "db10", "db10"), True, 41, True),    # long march, 20 taps (pending z sums in LDS with two register sets)
+    ((68, 34, 38), ("db6", "db6", "db6"), True, 25, False),      # ... on the production tile (12 taps, shared y / z tap pairs)
 ]
 
 
@@ -207,6 +216,8 @@ def test_emulated_pair_packed_synthesis_of_a_zero_extended_slab(emu, sizes, wn, 
     ((72, 37, 12), ("db6", "db6", "db6"), 0, False),              # 12 taps with the shared y / z tap pairs,
     ((72, 37, 12), ("db6", "db6", "db4"), 4, False),              # 12 taps, y and z taps apart,
     ((52, 30, 9), ("db10", "db10", "db10"), 0, False),            # 20 taps on the 48 x 28 tile
+    ((24, 22, 62), ("db10", "db10", "db10"), 41, True),           # long march, 20 taps
+    ((52, 30, 62), ("db10", "db10", "db10"), 41, False),          # ... the library's 20-tap instance on its 48 x 28 tile
 ])
 def test_emulated_pair_packed_synthesis_scatter_x_stage(emu, sizes, wn, zchunk, small):
     """Inv3Y<..., XSC>: the x stage in scatter form (partial sums travel between lanes instead of samples; the library's default for
@@ -247,6 +258,7 @@ CASES_YC = [
     ((22, 17, 15), ("db7", "db7", "db7"), True, 0),              # 14 / 16 taps (fused for complex64 since round 3)
     ((24, 18, 17), ("db8", "db6", "db4"), True, 7),
     ((21, 16, 16), ("db8", "db8", "db8"), False, 0),
+    ((22, 16, 50), ("db8", "db8", "db8"), True, 33),             # long march, 16 taps (gather form, one and two register sets, and scatter form)
 ]
 
 
@@ -286,6 +298,8 @@ def test_emulated_pair_packed_synthesis_complex_scatter_form_production_tiles(em
     ((244, 26), ("db4", "db1"), 3, 0),           # 232 columns per wave with 8 taps: a 12-column second tile
     ((64, 45), ("db6", "db6"), 2, 20),           # 12 taps: halo of two lanes per level on the right
     ((32, 30), ("db1", "db1"), 3, 7),
+    ((64, 50), ("db4", "db4"), 3, 17),           # long march: three waves along y of 17 + 17 + 16 rows, 8 taps, three levels
+    ((64, 74), ("db6", "db6"), 2, 25),           # ... 25 + 25 + 24 rows, 12 taps, two levels
 ])
 @pytest.mark.parametrize("l2", [0, 1])
 def test_emulated_cascaded_2d_analysis(emu, sizes, wn, nlev, ychunk, l2):
@@ -320,6 +334,8 @@ def test_emulated_cascaded_2d_analysis(emu, sizes, wn, nlev, ychunk, l2):
     ((244, 26), ("db4", "db2"), 3, 0, 1),
     ((64, 45), ("db3", "db3"), 2, 20, 2),
     ((32, 30), ("db1", "db1"), 3, 7, 1),
+    ((64, 50), ("db4", "db4"), 3, 17, 1),        # long march: three waves along y of 17 + 17 + 16 rows, 8 taps, three levels
+    ((64, 50), ("db4", "db4"), 2, 17, 2),        # ... two levels with two rows of band loads in flight
 ])
 @pytest.mark.parametrize("l2", [0, 1])
 def test_emulated_cascaded_2d_synthesis(emu, sizes, wn, nlev, ychunk, depth, l2):
@@ -380,6 +396,7 @@ CASES2 = [
     ((30, 12), ("db2", "db6"), False, 0),
     ((301, 9), ("db4", "db4"), False, 0),      # two wave tiles, the second anchored at the end of the row (ndwt_device.h: tile_origin)
     ((250, 8), ("db3", "db4"), False, 3),      # a second tile of 2 columns that cannot be anchored (the row is shorter than a tile + halo)
+    ((36, 38), ("db6", "db6"), True, 25),      # long march, 12 taps: Fwd2S / Inv2S through every rotation
 ]
 
 
@@ -408,6 +425,7 @@ MARCH = [
     ((1, 37, 1028), "db2", 10),      # more than one 256-thread block along the contiguous run
     ((2, 24, 4), "db6", 0),
     ((1, 45, 16), "db10", 9),
+    ((1, 62, 16), "db10", 41),       # long march, 20 taps
 ]
 
 
@@ -493,6 +511,7 @@ CPLX3 = [
     ((70, 19, 10), ("db4", "db2", "db4"), True, 6, False),     # production tiles (analysis 64x16, synthesis 64x32)
     ((22, 15, 13), ("db5", "db5", "db5"), True, 0, True),      # 10 / 12 taps over (re, im) pairs: 5- and 6-group halos
     ((26, 14, 12), ("db6", "db3", "db6"), True, 5, True),
+    ((22, 15, 38), ("db6", "db6", "db6"), True, 25, True),     # long march, 12 taps over (re, im) pairs
 ]
 
 
@@ -515,7 +534,8 @@ def test_emulated_fused3_interleaved_complex(emu, sizes, wn, vec4, zchunk, small
 
 @pytest.mark.slow
 @pytest.mark.parametrize("sizes,wn,vec4,ychunk", [((40, 13), ("db1", "db2"), True, 0), ((150, 20), ("db4", "db4"), True, 7),
-                                                    ((33, 12), ("db4", "db1"), False, 0)])
+                                                    ((33, 12), ("db4", "db1"), False, 0),
+                                                    ((34, 26), ("db4", "db4"), True, 17)])     # long march, 8 taps over (re, im) pairs
 def test_emulated_fused2_interleaved_complex(emu, sizes, wn, vec4, ychunk):
     rng = np.random.default_rng(9)
     x = rng.standard_normal(sizes) + 1j * rng.standard_normal(sizes)
@@ -642,6 +662,7 @@ def _taps3(wname, l2, L):
     ((64, 32, 5), "db3", 0),
     ((12, 10, 6), "db2", 0),          # a volume smaller than the halo: every axis wraps more than once
     ((76, 40, 7), "db1", 3),
+    ((64, 34, 26), "db4", 17),        # long march, 8 taps (6 of the 8 pending z sums in LDS)
 ])
 @pytest.mark.parametrize("l2,hard", [(1, 0), (0, 1)])
 def test_emulated_fused_level1_denoise(emu, sizes, wname, zchunk, l2, hard):
@@ -672,7 +693,8 @@ def test_emulated_fused_level1_denoise(emu, sizes, wname, zchunk, l2, hard):
 
 
 @pytest.mark.slow
-@pytest.mark.parametrize("sizes,wname,vec4,zchunk", [((68, 36, 9), "db4", True, 0), ((70, 33, 12), "db3", False, 5), ((64, 32, 6), "db1", True, 0)])
+@pytest.mark.parametrize("sizes,wname,vec4,zchunk", [((68, 36, 9), "db4", True, 0), ((70, 33, 12), "db3", False, 5), ((64, 32, 6), "db1", True, 0),
+                                                       ((68, 34, 26), "db4", True, 17)])     # long march, 8 taps
 def test_emulated_approximation_only_analysis(emu, sizes, wname, vec4, zchunk):
     """Fwd3<.., LOWONLY>: band 0 of one analysis level, the other seven neither computed through nor stored"""
     rng = np.random.default_rng(32)
@@ -694,7 +716,9 @@ def test_emulated_approximation_only_analysis(emu, sizes, wname, vec4, zchunk):
 @pytest.mark.parametrize("sizes,wnames,zchunk", [((68, 36, 9), ("db6",) * 3, 0), ((72, 40, 16), ("db5",) * 3, 6), ((64, 32, 5), ("db7",) * 3, 0),
                                                  ((128, 33, 7), ("db6", "db2", "db4"), 3), ((16, 12, 14), ("db6",) * 3, 0),
                                                  ((68, 36, 9), ("db8",) * 3, 0), ((72, 40, 20), ("db8", "db4", "db8"), 7),
-                                                 ((68, 20, 22), ("db10",) * 3, 0), ((64, 33, 24), ("db10", "db6", "db8"), 9)])
+                                                 ((68, 20, 22), ("db10",) * 3, 0), ((64, 33, 24), ("db10", "db6", "db8"), 9),
+                                                 # long marches: pinned taps at 14 taps, window slots in LDS at 16 and 20
+                                                 ((64, 34, 44), ("db7",) * 3, 29), ((64, 34, 50), ("db8",) * 3, 33), ((68, 18, 62), ("db10",) * 3, 41)])
 def test_emulated_analysis_with_pinned_taps(emu, sizes, wnames, zchunk):
     """16 / 20 taps: Fwd3<.., WLDS = 2 / 4> -- that many slots of every thread's z window in LDS, the others in registers, plain taps
     (20 taps: the 512-thread 64 x 16 tile with two columns per thread).
@@ -723,7 +747,8 @@ def test_emulated_analysis_with_pinned_taps(emu, sizes, wnames, zchunk):
 
 
 @pytest.mark.slow
-@pytest.mark.parametrize("sizes,wname,zchunk", [((68, 36, 6, 5), "db4", 0), ((64, 32, 9, 3), "db2", 4), ((72, 33, 5, 9), "db1", 0)])
+@pytest.mark.parametrize("sizes,wname,zchunk", [((68, 36, 6, 5), "db4", 0), ((64, 32, 9, 3), "db2", 4), ((72, 33, 5, 9), "db1", 0),
+                                                ((64, 34, 26, 3), "db4", 17)])     # long march, 8 taps
 def test_emulated_4d_analysis_with_folded_t_axis(emu, sizes, wname, zchunk):
     """Fwd3<.., TPRE>: a 4-D analysis level in two launches (one per t-band) whose raw planes are the t-filtered combination of L
     frames -- no pass of its own over the data for the t axis (reference: level_1_dec of nd_dwt_4D.m:394-467)"""
@@ -746,7 +771,8 @@ def test_emulated_4d_analysis_with_folded_t_axis(emu, sizes, wname, zchunk):
 
 @pytest.mark.slow
 @pytest.mark.parametrize("sizes,wname,ychunk,shrink", [((256, 21), "db4", 0, None), ((500, 13), "db4", 5, (0.4, 0xE, 0)), ((252, 9), "db3", 0, None),
-                                                        ((248, 30), "db6", 11, (0.3, 0xE, 1)), ((40, 6), "db1", 2, None), ((260, 4), "db2", 0, None)])
+                                                        ((248, 30), "db6", 11, (0.3, 0xE, 1)), ((40, 6), "db1", 2, None), ((260, 4), "db2", 0, None),
+                                                        ((248, 38), "db6", 25, (0.3, 0xE, 0))])     # long march, 12 taps: every load slot and rotation
 @pytest.mark.parametrize("depth", [2, 4, 14])
 def test_emulated_fused2_synthesis_with_rows_in_flight(emu, sizes, wname, ychunk, shrink, depth):
     """Inv2P: 2 or 4 rows of band loads in flight per wave, the row loop unrolled in groups of L (rotation and slot of every row compile-time

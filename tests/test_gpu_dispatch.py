@@ -22,9 +22,9 @@ TOL = {"single": 2e-6, "double": 1e-12}
 
 
 def R(rid, dims, wn, prec="single", cplx=False, dil="reference", level=1, layout="packed", fwd=-1, inv=-1, path=None, dec=(), rec=(),
-      den=None, fused_level1=None):
+      den=None, fused_level1=None, chunk=None):
     return pytest.param(dict(dims=dims, wn=wn, prec=prec, cplx=cplx, dil=dil, level=level, layout=layout, fwd=fwd, inv=inv, path=path,
-                             dec=list(dec), rec=list(rec), den=den, fused_level1=fused_level1), id=rid)
+                             dec=list(dec), rec=list(rec), den=den, fused_level1=fused_level1, chunk=chunk), id=rid)
 
 
 # ---- the rows.  Each comment gives the threshold and the arithmetic that puts the row on its side of it.
@@ -218,6 +218,8 @@ def run_row(row, trace_check=True):
     pitch = vol + (1 if vol % 4 == 0 else 0) + (2 if vol % 4 in (1, 3) else 0) if row["layout"] == "pitch" else vol
     assert row["layout"] != "pitch" or pitch % 4 != 0
     plan = ndwt.Plan(dims, wl, torch.float32 if prec == "single" else torch.float64, cplx, True, dil, max_level=level)
+    if row.get("chunk"):                                     # planes (rows) every workgroup of a fused launch marches: tests/test_gpu_long_march.py
+        plan.set_tuning(0, row["chunk"])
     if row["path"]:
         plan.set_path(True)
     if row["fwd"] >= 0 or row["inv"] >= 0:
