@@ -116,7 +116,10 @@ int ndwt_plan_set_tuning(ndwt_plan* plan, int target_blocks, int force_zchunk);
  *                2-D: 9 no cascade (either direction) | 10 cascade always, kernel mode 1 | 11 cascade always
  *   variant_inv  0 default | 3-D: 2 dilated levels keep Inv3S | 3 LDS kernel Inv3 (8 taps) | 4 Inv3S | 5 Inv3Y depth 1 | 9 no shared y / z
  *                taps | 10 scatter x stage wherever it exists | 11 gather x stage everywhere | 2-D: 1 keeps Inv2S | 2 / 4 Inv2P depth 2 / 4
- *                on Inv2S's geometry | 6 depth 2, 1024 waves | 7 unpacked FMAs | cascade: 9 off | 11 always | 12 always, two rows in flight */
+ *                on Inv2S's geometry | 6 depth 2, 1024 waves | 7 unpacked FMAs | cascade: 9 off | 11 always | 12 always, two rows in flight
+ *   The 2-D cascade (two or three levels of an image in one launch) serves float and double images, real or interleaved complex, whose
+ *   rows are whole groups of 4 scalars, up to 8 taps (float real analysis: also 12): by default beyond a size per data kind, on request
+ *   (10 / 11 / 12) at any size; "two rows in flight" where that instance exists (float real, complex64), one row otherwise. */
 int ndwt_plan_set_variant(ndwt_plan* plan, int variant_fwd, int variant_inv, int zchunk_fwd, int zchunk_inv, int fp64_fused);
 /* test / tuning hook: 0 makes ndwt_denoise keep the level-1 detail bands in memory (dec, thresholding fused into the synthesis
  * loads, rec); 1 (default) = level 1 in one launch that recomputes them where that is faster (float, real, 3-D, one tap length

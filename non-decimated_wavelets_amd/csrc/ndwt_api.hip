@@ -688,34 +688,36 @@ template <class Args, class Launch> static int cascade2_launch(ndwt_plan* p, Arg
     if (rc > 0) return fail(NDWT_ERR_HIP, "cascaded 2-D %s launch failed: %s", inverse ? "synthesis" : "analysis", hipGetErrorString((hipError_t)rc));
     return rc;
 }
-static int cascade2_run(ndwt_plan* p, int Lp, int nlev, const float* in, float* const* out, hipStream_t s) {
-    Fused2CArgs<float> a;
+// (interleaved complex: rows of dims[0] * comp scalars, the x taps step over the pairs -- the kernels' EW)
+template <typename T> static int cascade2_run(ndwt_plan* p, int Lp, int nlev, const T* in, T* const* out, hipStream_t s) {
+    Fused2CArgs<T> a;
     memset(&a, 0, sizeof a);
     a.in = in;
-    a.n1 = a.rs = (int)p->dims[0];
+    a.n1 = a.rs = (int)(p->dims[0] * p->comp);
     a.n2 = (int)p->dims[1];
-    bool aligned = aligned_vec4<float>(in);
-    for (int b = 0; b < 1 + 3 * nlev; ++b) { a.out[b] = out[b]; aligned = aligned && aligned_vec4<float>(out[b]); }
+    bool aligned = aligned_vec4<T>(in);
+    for (int b = 0; b < 1 + 3 * nlev; ++b) { a.out[b] = out[b]; aligned = aligned && aligned_vec4<T>(out[b]); }
     if (!aligned) return -1;                              // not this data: one launch per level
-    a.nt = nt_store_ok<float>(a.rs, a.rs, 0, out, 1 + 3 * nlev);
+    a.nt = nt_store_ok<T>(a.rs, a.rs, 0, out, 1 + 3 * nlev);
     a.mode = p->variant_fwd == kFwdCascadeMode1 ? 1 : 0;
-    return cascade2_launch(p, a, false, fwd2c_tile_width(Lp, nlev), nlev * (Lp - 1), 8, s, [&](const void* td) { return launch_fwd2c_f32(a, Lp, nlev, td, s); });
+    const Cascade2Instance k = {false, sizeof(T) == 8, (int)p->comp, Lp, nlev, 0};
+    return cascade2_launch(p, a, false, cascade2_tile_width(k), nlev * (Lp - 1), 8, s, [&](const void* td) { return launch_cascade2(k, a, td, s); });
 }
 
 template <typename T> static int dec_impl(ndwt_plan* p, const T* x, T* y, long long bs, int level, hipStream_t s) {
     const int nb = 1 << p->ndim;
     const T* cur = x;
     int lev = 1, pp = 0;                                  // pp: the scratch volume the next launch writes (they alternate launch by launch: a
-    if constexpr (sizeof(T) == 4) {                       // launch never writes the approximation it reads)
+    {                                                     // launch never writes the approximation it reads)
         const SelPlan sp = sel(p);
         int Lp = 0;
         while (const int n = cascade2_levels(sp, false, level - lev + 1, &Lp)) {   // levels lev .. lev + n - 1 in one launch
             const int last = lev + n - 1;
-            float* out[10];
-            out[0] = (last == level) ? y : (float*)p->approx[pp];
+            T* out[10];
+            out[0] = (last == level) ? y : (T*)p->approx[pp];
             for (int l = 0; l < n; ++l)                   // cascade level l (0 = first) is transform level lev + l
                 for (int b = 1; b < nb; ++b) out[1 + 3 * (n - 1 - l) + (b - 1)] = y + (long long)(1 + (nb - 1) * (level - (lev + l)) + (b - 1)) * bs;
-            const int rc = cascade2_run(p, Lp, n, cur, out, s);
+            const int rc = cascade2_run<T>(p, Lp, n, cur, out, s);
             if (rc == -1) break;                          // not this data (alignment): one launch per level from here on
             if (rc) return rc;
             cur = out[0];
@@ -735,41 +737,41 @@ template <typename T> static int dec_impl(ndwt_plan* p, const T* x, T* y, long l
 }
 
 // the synthesis side of the cascade (Inv2C): in[0] = approximation of the coarsest level, then the detail bands coarsest level first
-static int cascade2_rec_run(ndwt_plan* p, int Lp, int nlev, const float* const* in, float* out, hipStream_t s) {
-    Fused2CIArgs<float> a;
+template <typename T> static int cascade2_rec_run(ndwt_plan* p, int Lp, int nlev, const T* const* in, T* out, hipStream_t s) {
+    Fused2CIArgs<T> a;
     memset(&a, 0, sizeof a);
     a.out = out;
-    a.n1 = a.rs = (int)p->dims[0];
+    a.n1 = a.rs = (int)(p->dims[0] * p->comp);
     a.n2 = (int)p->dims[1];
-    bool aligned = aligned_vec4<float>(out);
-    for (int b = 0; b < 1 + 3 * nlev; ++b) { a.in[b] = in[b]; aligned = aligned && aligned_vec4<float>(in[b]); }
+    bool aligned = aligned_vec4<T>(out);
+    for (int b = 0; b < 1 + 3 * nlev; ++b) { a.in[b] = in[b]; aligned = aligned && aligned_vec4<T>(in[b]); }
     if (!aligned) return -1;
-    float* outs[1] = {out};
-    a.nt = nt_store_ok<float>(a.rs, a.rs, 0, outs, 1);
+    T* outs[1] = {out};
+    a.nt = nt_store_ok<T>(a.rs, a.rs, 0, outs, 1);
     if (p->shrink_mode) {                                 // ndwt_denoise: threshold the detail bands as their rows are loaded
         a.shrink_on = 1;
-        a.shrink_thr = (float)p->shrink_thr;
+        a.shrink_thr = (T)p->shrink_thr;
         a.shrink_hard = p->shrink_mode == 2;
     }
-    const int depth = cascade2_rec_depth(p->variant_inv);
-    return cascade2_launch(p, a, true, inv2c_tile_width(Lp, nlev), nlev * (Lp - 1), 4, s, [&](const void* td) { return launch_inv2c_f32(a, Lp, nlev, depth, td, s); });
+    const Cascade2Instance k = {true, sizeof(T) == 8, (int)p->comp, Lp, nlev, cascade2_rec_depth(sel(p), Lp, nlev)};
+    return cascade2_launch(p, a, true, cascade2_tile_width(k), nlev * (Lp - 1), 4, s, [&](const void* td) { return launch_cascade2(k, a, td, s); });
 }
 
 template <typename T> static int rec_impl(ndwt_plan* p, const T* y, long long bs, T* x, int level, hipStream_t s) {
     const int nb = 1 << p->ndim;
     const T* prev = y;   // band 0
     int lev = level, pp = 0;                              // coarsest level still to be synthesised; pp: the scratch volume the next launch writes
-    if constexpr (sizeof(T) == 4) {
+    {
         const SelPlan sp = sel(p);
         int Lp = 0;
         while (const int n = cascade2_levels(sp, true, lev, &Lp)) {   // levels lev, lev - 1, .. lev - n + 1 in one launch
-            const float* in[10];
+            const T* in[10];
             in[0] = prev;
             for (int c = 0; c < n; ++c)                   // cascade level c (0 = coarsest) is transform level lev - c
                 for (int b = 1; b < nb; ++b) in[1 + 3 * c + (b - 1)] = y + (long long)(1 + (nb - 1) * (level - (lev - c)) + (b - 1)) * bs;
             const int low = lev - n + 1;
-            float* dst = (low == 1) ? x : (float*)p->approx[pp];
-            const int rc = cascade2_rec_run(p, Lp, n, in, dst, s);
+            T* dst = (low == 1) ? x : (T*)p->approx[pp];
+            const int rc = cascade2_rec_run<T>(p, Lp, n, in, dst, s);
             if (rc == -1) break;
             if (rc) return rc;
             prev = dst;

@@ -2559,7 +2559,8 @@ template <typename T, int L_, bool VEC4_, int WPE_ = 4, int EW_ = 1> struct Fwd2
 // levels live in registers only (a per-level launch writes each to memory and the next launch reads it back: 1 + 3 NLEV + 1 volumes
 // move instead of 5 NLEV).  Level l runs l RH rows behind the raw row and is valid l GL / l GR lanes inside the wave, so a wave stores
 // 4 (64 - NLEV (GL + GR)) columns of every band and starts NLEV (L/2 - 1) rows above its chunk.  Same FMAs in the same order as NLEV
-// launches of Fwd2S.  Float / double real data, rows of whole groups of 4 scalars, periodic in y.
+// launches of Fwd2S.  Float / double data, real or (EW = 2) interleaved complex with the x taps stepping over the (re, im) pairs as in
+// Fwd2S::xstage; rows of whole groups of 4 scalars, periodic in y.
 template <typename T> struct Fused2CArgs {
     const T* in;           // the image (or the approximation the cascade starts from)
     T* out[10];            // [0] the approximation of the LAST level of the cascade; level l = 1 .. NLEV (1 = first / finest of the launch):
@@ -2571,13 +2572,15 @@ template <typename T> struct Fused2CArgs {
     int mode;              // A/B (tools/bench2d_cascade.py): bit 0 = every level computes from its first input row on (no take-in-only steps)
 };
 
-template <typename T, int L_, int NLEV_, int WPE_ = 2> struct Fwd2C {
-    static constexpr int L = L_, NLEV = NLEV_, NT = 64, WPE = WPE_;
+template <typename T, int L_, int NLEV_, int WPE_ = 2, int EW_ = 1> struct Fwd2C {
+    static constexpr int L = L_, NLEV = NLEV_, NT = 64, WPE = WPE_, EW = EW_;
     static constexpr int LH = L / 2 - 1, RH = L / 2;
-    static constexpr int GL = (LH + 3) / 4, GR = (RH + 3) / 4;
-    // output columns per wave: the lanes whose values are valid at every level, rounded down to whole 128-byte lines (8 lanes) so that no
-    // line of any band is shared by two waves (a partly written line of a nontemporal stream is a read-modify-write in memory)
-    static constexpr int WX = 4 * ((64 - NLEV * (GL + GR)) / 8 * 8);
+    static constexpr int GL = (LH * EW + 3) / 4, GR = (RH * EW + 3) / 4;
+    // output columns per wave: the lanes whose values are valid at every level, rounded down to whole 128-byte lines so that no line of
+    // any band is shared by two waves (a partly written line of a nontemporal stream is a read-modify-write in memory).  A lane stores 4
+    // scalars: float 8 lanes to the line, double 4 -- LPL = 128 / (4 sizeof(T)) lanes, whatever EW (it changes the halo, not the store)
+    static constexpr int LPL = 32 / (int)sizeof(T);
+    static constexpr int WX = 4 * ((64 - NLEV * (GL + GR)) / LPL * LPL);
     static constexpr int XV = 4 * (1 + GL + GR);
     static_assert(NLEV >= 2 && NLEV <= 3 && WX > 0, "two or three levels per launch");
     typedef typename VecT<T>::v2 v2;
@@ -2621,10 +2624,13 @@ template <typename T, int L_, int NLEV_, int WPE_ = 2> struct Fwd2C {
             {
                 v2 v = {NDWT_LANE_SHIFT(ex, tid, D, s.yz[c].x), NDWT_LANE_SHIFT(ex, tid, D, s.yz[c].y)};
                 NDWT_SFOR(e, 4)
-                    constexpr int j = i - 4 * GL - e + LH;
-                    if constexpr (j >= 0 && j < L) {
-                        xlo[e] += tp.lo[0][j] * v;
-                        xhi[e] += tp.hi[0][j] * v;
+                    constexpr int dj = i - 4 * GL - e;                     // = (j - LH) * EW
+                    if constexpr (dj % EW == 0) {
+                        constexpr int j = dj / EW + LH;
+                        if constexpr (j >= 0 && j < L) {
+                            xlo[e] += tp.lo[0][j] * v;
+                            xhi[e] += tp.hi[0][j] * v;
+                        }
                     }
                 NDWT_SEND
             }
@@ -3025,7 +3031,11 @@ template <typename T, int L_, int PD_ = 2, int WPE_ = 2, bool PK_ = false> struc
 // written (one launch per level reads 4 and writes 1 each).  Arithmetic of Inv2P's packed form (pairs of adjacent x outputs per
 // v_pk_fma_f32, tap pairs pinned in SGPRs), rows in groups of L so that rotations and load slots are compile-time constants; every level
 // computes in every step (what it makes of march-in rows never reaches an output row of the chunk), so the code is straight-line and the
-// compiler counts the loads in flight exactly.  Float real data, rows of whole groups of 4 scalars, periodic in y.
+// compiler counts the loads in flight exactly.  Rows of whole groups of 4 scalars, periodic in y.
+// EW = 2 (interleaved complex): a pair of adjacent scalars is the (re, im) of one element and takes ONE x tap, so the packed x stage has
+// the form of the y stage (a tap broadcast from one half of an SGPR pair (t[2m], t[2m+1])); the sums of an output run over the taps in
+// the order of Inv2S<.., EW = 2>.  double: scalar FMAs in the expressions of Inv2P<double>::step (v_pk_fma_f32 has no double form), the
+// same groups of L with compile-time rotations and load slots.
 template <typename T> struct Fused2CIArgs {
     const T* in[10];       // [0] the approximation of the coarsest level; level l (1 = finest of the launch) detail bands b = 1 .. 3 at
                            // [1 + 3 (NLEV - l) + (b - 1)] (the order of Fused2CArgs::out)
@@ -3038,14 +3048,17 @@ template <typename T> struct Fused2CIArgs {
     int shrink_on, shrink_hard;
 };
 
-template <typename T, int L_, int NLEV_, int PD_ = 1, int WPE_ = 2> struct Inv2C {
-    static_assert(sizeof(T) == 4, "packed form: float only (v_pk_fma_f32)");
-    static constexpr int L = L_, NLEV = NLEV_, NT = 64, WPE = WPE_, PD = PD_;
+template <typename T, int L_, int NLEV_, int PD_ = 1, int WPE_ = 2, int EW_ = 1> struct Inv2C {
+    static constexpr int L = L_, NLEV = NLEV_, NT = 64, WPE = WPE_, PD = PD_, EW = EW_;
+    static constexpr bool PK = sizeof(T) == 4;            // float: packed FMAs (v_pk_fma_f32); double: scalar ones
     static_assert(L % PD == 0 && NLEV >= 2 && NLEV <= 3, "the depth divides the tap length; two or three levels per launch");
+    static_assert(EW == 1 || EW == 2, "real data or interleaved complex");
     static constexpr int LH = L / 2, RH = L / 2 - 1;
-    static constexpr int GL = (LH + 3) / 4, GR = (RH + 3) / 4;
-    static constexpr int WX = 4 * ((64 - NLEV * (GL + GR)) / 8 * 8);   // whole 128-byte lines per wave and row (see Fwd2C)
+    static constexpr int GL = (LH * EW + 3) / 4, GR = (RH * EW + 3) / 4;
+    static constexpr int LPL = 32 / (int)sizeof(T);       // lanes to a 128-byte line (see Fwd2C)
+    static constexpr int WX = 4 * ((64 - NLEV * (GL + GR)) / LPL * LPL);   // whole 128-byte lines per wave and row
     static constexpr int XV = 4 * (1 + GL + GR);
+    static_assert(WX > 0, "the halo of every level fits the wave");
     typedef typename VecT<T>::v4 v4;
     typedef typename VecT<T>::v2 v2;
     typedef Taps3Y<T, L> Taps;
@@ -3057,19 +3070,29 @@ template <typename T, int L_, int NLEV_, int PD_ = 1, int WPE_ = 2> struct Inv2C
         v4 cur[NLEV];                // cur[c]: the row level c - 1 has just completed = the approximation row of level c (c >= 1)
         int off;
     };
-    struct RegT {
-        v2 xl[L + 1], xh[L + 1];     // (t[k], t[k-1]) of the x low-pass / high-pass taps
-        v2 yl[L / 2], yh[L / 2];     // (t[2m], t[2m+1]) of the y taps
+    static constexpr int NXP = !PK ? 1 : (EW == 1 ? L + 1 : L / 2);
+    struct RegT {                    // PK: tap pairs pinned in SGPRs
+        v2 xl[NXP], xh[NXP];         // EW = 1: (t[k], t[k-1]) of the x low-pass / high-pass taps; EW = 2: (t[2m], t[2m+1])
+        v2 yl[PK ? L / 2 : 1], yh[PK ? L / 2 : 1];     // (t[2m], t[2m+1]) of the y taps
     };
     static NDWT_DEV void load_regt(RegT& rt, const Taps& tp) {
-        NDWT_SFOR(k, L + 1)
-            rt.xl[k] = PkF32::pinned(v2{tp.xplo[k][0], tp.xplo[k][1]});
-            rt.xh[k] = PkF32::pinned(v2{tp.xphi[k][0], tp.xphi[k][1]});
-        NDWT_SEND
-        NDWT_SFOR(m, L / 2)
-            rt.yl[m] = PkF32::pinned(v2{tp.lo[1][2 * m], tp.lo[1][2 * m + 1]});
-            rt.yh[m] = PkF32::pinned(v2{tp.hi[1][2 * m], tp.hi[1][2 * m + 1]});
-        NDWT_SEND
+        if constexpr (PK) {
+            if constexpr (EW == 1) {
+                NDWT_SFOR(k, L + 1)
+                    rt.xl[k] = PkF32::pinned(v2{tp.xplo[k][0], tp.xplo[k][1]});
+                    rt.xh[k] = PkF32::pinned(v2{tp.xphi[k][0], tp.xphi[k][1]});
+                NDWT_SEND
+            } else {
+                NDWT_SFOR(m, L / 2)
+                    rt.xl[m] = PkF32::pinned(v2{tp.lo[0][2 * m], tp.lo[0][2 * m + 1]});
+                    rt.xh[m] = PkF32::pinned(v2{tp.hi[0][2 * m], tp.hi[0][2 * m + 1]});
+                NDWT_SEND
+            }
+            NDWT_SFOR(m, L / 2)
+                rt.yl[m] = PkF32::pinned(v2{tp.lo[1][2 * m], tp.lo[1][2 * m + 1]});
+                rt.yh[m] = PkF32::pinned(v2{tp.hi[1][2 * m], tp.hi[1][2 * m + 1]});
+            NDWT_SEND
+        }
     }
     // band rows of level C (0 = coarsest) for march step p: level C consumes row rr0 + p - C RH (rows are periodic: any index loads)
     template <int C, int S> static NDWT_DEV void load_rows(State& st, const Args& a, int row) {
@@ -3136,21 +3159,127 @@ template <typename T, int L_, int NLEV_, int PD_ = 1, int WPE_ = 2> struct Inv2C
             stream_store(reinterpret_cast<v4*>(a.out + (long long)y * a.rs + gx), o, a.nt);
         }
     }
+    // the same on interleaved complex data (EW = 2): the pair w is the (re, im) of one element and tap j of the element at outputs (2 q, 2 q + 1)
+    // (a function of its own, not a branch inside level(): with the two x stages as `if constexpr` arms of one body and the tail in a
+    // helper, hipcc allocated the float real instances 230 instead of 176 VGPRs for 8 taps x 3 levels, and two rows in flight spilled)
+    template <int C, int K, class Exec>
+    static NDWT_DEV void level_c(Exec& ex, State& st, const RegT& rt, const Args& a, int x0, int y, bool emit, int tid) {
+        constexpr int R = (K + 1) % L, S = K % PD;
+        v2 P[2][2];                                       // [y band][x outputs (0, 1) / (2, 3)]
+        P[0][0] = P[0][1] = P[1][0] = P[1][1] = (v2)(T(0));
+        NDWT_SFOR(ii, XV / 2)
+            constexpr int i0 = 2 * ii;
+            constexpr int D = i0 / 4 - GL;
+            constexpr int c = i0 % 4;
+            v2 w[4];
+            if constexpr (C == 0) w[0] = v2{NDWT_LANE_SHIFT(ex, tid, D, s.raw[0][S][0][c]), NDWT_LANE_SHIFT(ex, tid, D, s.raw[0][S][0][c + 1])};
+            else w[0] = v2{NDWT_LANE_SHIFT(ex, tid, D, s.cur[C][c]), NDWT_LANE_SHIFT(ex, tid, D, s.cur[C][c + 1])};
+            NDWT_SFOR(b, 3)
+                w[1 + b] = v2{NDWT_LANE_SHIFT(ex, tid, D, s.raw[C][S][1 + b][c]), NDWT_LANE_SHIFT(ex, tid, D, s.raw[C][S][1 + b][c + 1])};
+            NDWT_SEND
+            NDWT_SFOR(q, 2)
+                constexpr int dj = i0 - 4 * GL - 2 * q;                   // = (j - LH) * EW, even
+                constexpr int j = dj / 2 + LH;
+                if constexpr (j >= 0 && j < L) {
+                    PkF32::fma_s<j % 2, false>(P[0][q], w[0], rt.xl[j / 2]);
+                    PkF32::fma_s<j % 2, false>(P[0][q], w[1], rt.xh[j / 2]);
+                    PkF32::fma_s<j % 2, false>(P[1][q], w[2], rt.xl[j / 2]);
+                    PkF32::fma_s<j % 2, false>(P[1][q], w[3], rt.xh[j / 2]);
+                }
+            NDWT_SEND
+        NDWT_SEND
+        NDWT_SFOR(j, L)
+            constexpr int slot = ((R - 1 - j) % L + L) % L;
+            NDWT_SFOR(q, 2)
+                v2 acc;
+                if constexpr (j == 0) acc = (v2)(T(0));
+                else acc = v2{st.yacc[C][slot][2 * q], st.yacc[C][slot][2 * q + 1]};
+                PkF32::fma_s<j % 2, false>(acc, P[0][q], rt.yl[j / 2]);
+                PkF32::fma_s<j % 2, false>(acc, P[1][q], rt.yh[j / 2]);
+                st.yacc[C][slot][2 * q] = acc.x;
+                st.yacc[C][slot][2 * q + 1] = acc.y;
+            NDWT_SEND
+        NDWT_SEND
+        constexpr int done = ((R - L) % L + L) % L;
+        const v4 o = {st.yacc[C][done][0], st.yacc[C][done][1], st.yacc[C][done][2], st.yacc[C][done][3]};
+        if constexpr (C + 1 < NLEV) {
+            st.cur[C + 1] = o;
+        } else {
+            const int gx = x0 + 4 * (tid - NLEV * GL);
+            if (!emit || tid < NLEV * GL || tid >= NLEV * GL + WX / 4 || gx >= a.n1) return;
+            stream_store(reinterpret_cast<v4*>(a.out + (long long)y * a.rs + gx), o, a.nt);
+        }
+    }
+    // the scalar form of level<C, K> (double): Inv2P::step with the approximation row of a finer level taken from cur[C]
+    template <int C, int K, class Exec>
+    static NDWT_DEV void level_s(Exec& ex, State& st, const Taps& tp, const Args& a, int x0, int y, bool emit, int tid) {
+        constexpr int R = (K + 1) % L, S = K % PD;
+        T p0[4], p1[4];
+        NDWT_SFOR(e, 4)
+            p0[e] = T(0);
+            p1[e] = T(0);
+        NDWT_SEND
+        NDWT_SFOR(i, XV)
+            constexpr int D = i / 4 - GL;
+            constexpr int c = i % 4;
+            {
+                T wa0;
+                if constexpr (C == 0) wa0 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[0][S][0][c]);
+                else wa0 = NDWT_LANE_SHIFT(ex, tid, D, s.cur[C][c]);
+                const T wd0 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[C][S][1][c]);
+                const T wa1 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[C][S][2][c]);
+                const T wd1 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[C][S][3][c]);
+                NDWT_SFOR(e, 4)
+                    constexpr int dj = i - 4 * GL - e;
+                    if constexpr (dj % EW == 0) {
+                        constexpr int j = dj / EW + LH;
+                        if constexpr (j >= 0 && j < L) {
+                            p0[e] += tp.lo[0][j] * wa0;
+                            p0[e] += tp.hi[0][j] * wd0;
+                            p1[e] += tp.lo[0][j] * wa1;
+                            p1[e] += tp.hi[0][j] * wd1;
+                        }
+                    }
+                NDWT_SEND
+            }
+        NDWT_SEND
+        NDWT_SFOR(j, L)
+            constexpr int slot = ((R - 1 - j) % L + L) % L;
+            NDWT_SFOR(e, 4)
+                const T c = tp.lo[1][j] * p0[e] + tp.hi[1][j] * p1[e];
+                if constexpr (j == 0) st.yacc[C][slot][e] = c;
+                else st.yacc[C][slot][e] += c;
+            NDWT_SEND
+        NDWT_SEND
+        constexpr int done = ((R - L) % L + L) % L;
+        const v4 o = {st.yacc[C][done][0], st.yacc[C][done][1], st.yacc[C][done][2], st.yacc[C][done][3]};
+        if constexpr (C + 1 < NLEV) {
+            st.cur[C + 1] = o;
+        } else {
+            const int gx = x0 + 4 * (tid - NLEV * GL);
+            if (!emit || tid < NLEV * GL || tid >= NLEV * GL + WX / 4 || gx >= a.n1) return;
+            stream_store(reinterpret_cast<v4*>(a.out + (long long)y * a.rs + gx), o, a.nt);
+        }
+    }
     // step p of the march (K = p % L): every level consumes its row, then the consumed load slots are refilled with the rows of step p + PD
     template <int K, class Exec>
-    static NDWT_DEV void row(Exec& ex, const RegT& rt, const Args& a, int x0, int ybeg, int yend, int rr0, int p, int nrows) {
+    static NDWT_DEV void row(Exec& ex, const Taps& tp, const RegT& rt, const Args& a, int x0, int ybeg, int yend, int rr0, int p, int nrows) {
         const int y = rr0 + p - NLEV * RH;
-        if (a.shrink_on) {                                // thresholding fused into the reconstruction (the detail rows this step consumes)
-            ex.each([&](int, State& st) __attribute__((always_inline)) {
+        if (a.shrink_on) {                                // thresholding fused into the reconstruction (the detail rows this step consumes;
+            ex.each([&](int, State& st) __attribute__((always_inline)) {   // EW = 2: the magnitude of a (re, im) pair shrinks)
                 NDWT_SFOR(c, NLEV)
                     NDWT_SFOR(b, 3)
-                        shrink4_flat<T>(st.raw[c][K % PD][1 + b], a.shrink_thr, a.shrink_hard);
+                        shrink4<T, EW>(st.raw[c][K % PD][1 + b], a.shrink_thr, a.shrink_hard);
                     NDWT_SEND
                 NDWT_SEND
             });
         }
         NDWT_SFOR(c, NLEV)
-            ex.each([&](int tid, State& st) __attribute__((always_inline)) { level<c, K>(ex, st, rt, a, x0, y, y >= ybeg && y < yend, tid); });
+            ex.each([&](int tid, State& st) __attribute__((always_inline)) {
+                if constexpr (PK && EW == 1) level<c, K>(ex, st, rt, a, x0, y, y >= ybeg && y < yend, tid);
+                else if constexpr (PK) level_c<c, K>(ex, st, rt, a, x0, y, y >= ybeg && y < yend, tid);
+                else level_s<c, K>(ex, st, tp, a, x0, y, y >= ybeg && y < yend, tid);
+            });
         NDWT_SEND
         ex.each([&](int, State& st) __attribute__((always_inline)) {
             if (p + PD < nrows) {
@@ -3188,11 +3317,11 @@ template <typename T, int L_, int NLEV_, int PD_ = 1, int WPE_ = 2> struct Inv2C
         int p = 0;
         for (; p + L <= nrows; p += L) {                  // whole groups: straight-line code, no test per row
             NDWT_SFOR(k, L)
-                row<k>(ex, rt, a, x0, ybeg, yend, rr0, p + k, nrows);
+                row<k>(ex, tp, rt, a, x0, ybeg, yend, rr0, p + k, nrows);
             NDWT_SEND
         }
         NDWT_SFOR(k, L - 1)                               // the last, partial group
-            if (p + k < nrows) row<k>(ex, rt, a, x0, ybeg, yend, rr0, p + k, nrows);
+            if (p + k < nrows) row<k>(ex, tp, rt, a, x0, ybeg, yend, rr0, p + k, nrows);
         NDWT_SEND
     }
 };

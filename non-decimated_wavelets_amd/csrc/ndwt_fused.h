@@ -30,12 +30,13 @@ int launch_fwd3_low_f32(const Fused3Args<float>& a, int Lp, bool vec4, const voi
 // x step of the query, or the Inv2P instance of the pick.  -1: no such instance.
 int launch_fused2_pick(const Fused2Pick& k, const Fused2Query& q, const Fused2Args<float>& a, const void* taps_dev, hipStream_t s);
 int launch_fused2_pick(const Fused2Pick& k, const Fused2Query& q, const Fused2Args<double>& a, const void* taps_dev, hipStream_t s);
-// two or three analysis levels of an image in one launch (Fwd2C; float real data, rows of whole groups of 4, 2 .. 8 and 12 taps)
-int fwd2c_tile_width(int Lp, int nlev);
-int launch_fwd2c_f32(const Fused2CArgs<float>& a, int Lp, int nlev, const void* taps_dev, hipStream_t s);
-// ... and the synthesis levels (Inv2C; 2 .. 8 taps; depth = rows of band loads in flight per level)
-int inv2c_tile_width(int Lp, int nlev);
-int launch_inv2c_f32(const Fused2CIArgs<float>& a, int Lp, int nlev, int depth, const void* taps_dev, hipStream_t s);
+// Two or three levels of an image in one launch (Fwd2C / Inv2C), the instance named in full (ndwt_fused_list.h: Cascade2Instance, the
+// table cascade2_levels reads; its tile: cascade2_tile_width).  Float real and interleaved complex64 take the float forms, double real and
+// complex128 the double ones; -1: no unit has the instance, -2: the launch geometry is not the instance's tile.
+int launch_cascade2(const Cascade2Instance& k, const Fused2CArgs<float>& a, const void* taps_dev, hipStream_t s);
+int launch_cascade2(const Cascade2Instance& k, const Fused2CArgs<double>& a, const void* taps_dev, hipStream_t s);
+int launch_cascade2(const Cascade2Instance& k, const Fused2CIArgs<float>& a, const void* taps_dev, hipStream_t s);
+int launch_cascade2(const Cascade2Instance& k, const Fused2CIArgs<double>& a, const void* taps_dev, hipStream_t s);
 
 // one non-contiguous axis with the window in registers (taps: kernel-form lo/hi of length L)
 int launch_march_f32(bool syn, int L, const MarchArgs<float>& a, const double* lo, const double* hi, hipStream_t s);

@@ -1,4 +1,4 @@
-// cascaded 2-D analysis, float real data: two or three levels of an image in one launch (Fwd2C), tap lengths 2 .. 8 and 12
+// cascaded 2-D analysis, interleaved complex128 (Fwd2C with the x taps stepping over the (re, im) pairs), tap lengths 2 .. 8
 #include "ndwt_fused_kernels.h"
 namespace ndwt {
 template <class K> static int go(const typename K::Args& a, const void* taps_dev, hipStream_t s) {
@@ -12,10 +12,8 @@ template <class K> static int go(const typename K::Args& a, const void* taps_dev
         static_assert(Fwd2C<T, LL, NLEV, WPE, EWV>::WX == cascade2_tile_width({false, sizeof(T) == 8, EWV, LL, NLEV, 0}), "tile width"); \
         return go<Fwd2C<T, LL, NLEV, WPE, EWV>>(a, taps_dev, s);                                      \
     }
-int launch_cascade2_c64(const Cascade2Instance& k, const Fused2CArgs<float>& a, const void* taps_dev, hipStream_t s);   // interleaved complex64
-int launch_cascade2(const Cascade2Instance& k, const Fused2CArgs<float>& a, const void* taps_dev, hipStream_t s) {
-    if (k.ew != 1) return launch_cascade2_c64(k, a, taps_dev, s);
-    NDWT_LIST_F32_FWD2C(NDWT_LAUNCH_A)
+int launch_cascade2_c128(const Cascade2Instance& k, const Fused2CArgs<double>& a, const void* taps_dev, hipStream_t s) {
+    NDWT_LIST_C128_FWD2C(NDWT_LAUNCH_A)
     return -1;
 }
 }  // namespace ndwt

@@ -1,4 +1,4 @@
-// cascaded 2-D synthesis, float real data: two or three levels of an image in one launch (Inv2C), tap lengths 2 .. 8
+// cascaded 2-D synthesis, interleaved complex64 (Inv2C, packed FMAs on (re, im) pairs), tap lengths 2 .. 8
 #include "ndwt_fused_kernels.h"
 namespace ndwt {
 template <class K> static int go(const typename K::Args& a, const void* taps_dev, hipStream_t s) {
@@ -12,10 +12,8 @@ template <class K> static int go(const typename K::Args& a, const void* taps_dev
         static_assert(Inv2C<T, LL, NLEV, PD, WPE, EWV>::WX == cascade2_tile_width({true, sizeof(T) == 8, EWV, LL, NLEV, PD}), "tile width"); \
         return go<Inv2C<T, LL, NLEV, PD, WPE, EWV>>(a, taps_dev, s);                                  \
     }
-int launch_cascade2_c64(const Cascade2Instance& k, const Fused2CIArgs<float>& a, const void* taps_dev, hipStream_t s);   // interleaved complex64
-int launch_cascade2(const Cascade2Instance& k, const Fused2CIArgs<float>& a, const void* taps_dev, hipStream_t s) {
-    if (k.ew != 1) return launch_cascade2_c64(k, a, taps_dev, s);
-    NDWT_LIST_F32_INV2C(NDWT_LAUNCH_R)
+int launch_cascade2_c64(const Cascade2Instance& k, const Fused2CIArgs<float>& a, const void* taps_dev, hipStream_t s) {
+    NDWT_LIST_C64_INV2C(NDWT_LAUNCH_R)
     return -1;
 }
 }  // namespace ndwt

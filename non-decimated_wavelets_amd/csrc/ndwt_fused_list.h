@@ -35,11 +35,18 @@ struct Fused2PInstance { bool f64; int Lp, pdepth; bool packed; };   // Inv2P<T,
 constexpr bool operator==(const Fused2PInstance& a, const Fused2PInstance& b) {
     return a.f64 == b.f64 && a.Lp == b.Lp && a.pdepth == b.pdepth && a.packed == b.packed;
 }
+// Fwd2C<T, Lp, nlev, WPE, ew> (pd = 0) / Inv2C<T, Lp, nlev, pd, WPE, ew>: two or three levels of an image in one launch
+struct Cascade2Instance { bool inverse, f64; int ew, Lp, nlev, pd; };
+constexpr bool operator==(const Cascade2Instance& a, const Cascade2Instance& b) {
+    return a.inverse == b.inverse && a.f64 == b.f64 && a.ew == b.ew && a.Lp == b.Lp && a.nlev == b.nlev && a.pd == b.pd;
+}
 
 // ---- the lists.  Entries:  F(T, L, V, VEC4, EW, PIN, TPRE, WLDS)  Fwd3 on tile V
 //                            S(KIND, T, L, V, VEC4, EW)             Inv3 / Inv3S on tile V
 //                            Y(L, VEC4, EW, DEPTH, UNIYZ, XSC)      Inv3Y (float)
 //                            P(T, L, PD, PK)                        Inv2P
+//                            A(T, EW, L, NLEV, WPE)                 Fwd2C
+//                            R(T, EW, L, NLEV, PD, WPE)             Inv2C
 // NDWT_F2 / NDWT_S2 / NDWT_Y2: the plain form of an entry for rows of whole groups of 4 scalars and for the rest
 #define NDWT_F2(F, T, L, V, EW) F(T, L, V, true, EW, false, false, 0) F(T, L, V, false, EW, false, false, 0)
 #define NDWT_S2(S, KIND, T, L, V, EW) S(KIND, T, L, V, true, EW) S(KIND, T, L, V, false, EW)
@@ -163,6 +170,36 @@ constexpr bool operator==(const Fused2PInstance& a, const Fused2PInstance& b) {
     P(float, 10, 2, false) P(float, 12, 2, false) P(float, 12, 4, false)
 #define NDWT_LIST_F64_INV2P(P) P(double, 2, 2, false) P(double, 4, 4, false) P(double, 6, 2, false) P(double, 8, 2, false)
 
+// The cascaded 2-D kernels (Fwd2C / Inv2C), rows of whole groups of 4 scalars: THE table of the instances that exist -- cascade2_levels
+// (ndwt_select.h) answers from it and the launch units (ndwt_fused2_{f32,c64,f64}_{fwd,inv}cas.hip) expand it.  Every instance runs
+// without scratch; WPE = 1 (one wave per SIMD, the 512-register budget) is where two waves per SIMD would spill (DESIGN.md 4.3 has the
+// register counts).  NDWT_A23 / NDWT_R23: both level counts of a tap length.
+#define NDWT_A23(A, T, EW, L, WPE) A(T, EW, L, 2, WPE) A(T, EW, L, 3, WPE)
+#define NDWT_R23(R, T, EW, L, PD, WPE) R(T, EW, L, 2, PD, WPE) R(T, EW, L, 3, PD, WPE)
+// float real: 2 .. 8 taps; analysis also 12 taps at two levels (three: 132 spilled registers); synthesis with one or two rows of band
+// loads in flight per level
+#define NDWT_LIST_F32_FWD2C(A) NDWT_A23(A, float, 1, 2, 2) NDWT_A23(A, float, 1, 4, 2) NDWT_A23(A, float, 1, 6, 2) NDWT_A23(A, float, 1, 8, 2) A(float, 1, 12, 2, 2)
+#define NDWT_LIST_F32_INV2C(R)                                                                                            \
+    NDWT_R23(R, float, 1, 2, 1, 2) NDWT_R23(R, float, 1, 4, 1, 2) NDWT_R23(R, float, 1, 6, 1, 2) NDWT_R23(R, float, 1, 8, 1, 2) \
+    NDWT_R23(R, float, 1, 2, 2, 2) NDWT_R23(R, float, 1, 4, 2, 2) NDWT_R23(R, float, 1, 6, 2, 2) NDWT_R23(R, float, 1, 8, 2, 2)
+// interleaved complex64: every tap length and level count at two waves per SIMD; two rows in flight except three levels of 8 taps
+// (40 bytes of scratch at two waves per SIMD: that launch keeps one row)
+#define NDWT_LIST_C64_FWD2C(A) NDWT_A23(A, float, 2, 2, 2) NDWT_A23(A, float, 2, 4, 2) NDWT_A23(A, float, 2, 6, 2) NDWT_A23(A, float, 2, 8, 2)
+#define NDWT_LIST_C64_INV2C(R)                                                                                            \
+    NDWT_R23(R, float, 2, 2, 1, 2) NDWT_R23(R, float, 2, 4, 1, 2) NDWT_R23(R, float, 2, 6, 1, 2) NDWT_R23(R, float, 2, 8, 1, 2) \
+    NDWT_R23(R, float, 2, 2, 2, 2) NDWT_R23(R, float, 2, 4, 2, 2) NDWT_R23(R, float, 2, 6, 2, 2) R(float, 2, 8, 2, 2, 2)
+// double real and complex128: the y windows / pending sums of every level are 8 registers per row, so from 6 taps x 3 levels (analysis)
+// and 4 taps x 3 levels (synthesis) on a wave needs the budget of one wave per SIMD; one row of band loads in flight.  Not built: the
+// complex128 synthesis of 8 taps x 3 levels (192 bytes of scratch even at one wave per SIMD) -- those three levels run as 2 + 1.
+#define NDWT_LIST_F64_FWD2C(A)                                                                                            \
+    NDWT_A23(A, double, 1, 2, 2) NDWT_A23(A, double, 1, 4, 2) A(double, 1, 6, 2, 2) A(double, 1, 6, 3, 1) NDWT_A23(A, double, 1, 8, 1)
+#define NDWT_LIST_C128_FWD2C(A)                                                                                           \
+    NDWT_A23(A, double, 2, 2, 2) NDWT_A23(A, double, 2, 4, 2) A(double, 2, 6, 2, 2) A(double, 2, 6, 3, 1) NDWT_A23(A, double, 2, 8, 1)
+#define NDWT_LIST_F64_INV2C(R)                                                                                            \
+    NDWT_R23(R, double, 1, 2, 1, 2) R(double, 1, 4, 2, 1, 2) R(double, 1, 4, 3, 1, 1) NDWT_R23(R, double, 1, 6, 1, 1) NDWT_R23(R, double, 1, 8, 1, 1)
+#define NDWT_LIST_C128_INV2C(R)                                                                                           \
+    NDWT_R23(R, double, 2, 2, 1, 2) R(double, 2, 4, 2, 1, 2) R(double, 2, 4, 3, 1, 1) NDWT_R23(R, double, 2, 6, 1, 1) R(double, 2, 8, 2, 1, 1)
+
 // ---- questions to the lists
 #define NDWT_IS_F(T, L, V, VEC4, EW, PIN, TPRE, WLDS) if (k == fwd3_instance(sizeof(T) == 8, L, V, VEC4, EW, PIN, TPRE, WLDS)) return true;
 #define NDWT_IS_S(KIND, T, L, V, VEC4, EW) if (k == inv3s_instance(k##KIND, sizeof(T) == 8, L, V, VEC4, EW)) return true;
@@ -178,6 +215,19 @@ inline bool fused3_instantiated(const Fused3Instance& k) {
     NDWT_LIST_F32_LONGB(NDWT_IS_F) NDWT_LIST_F32_INV(NDWT_IS_S) NDWT_LIST_F32_INVE(NDWT_IS_S) NDWT_LIST_F32_LONGI(NDWT_IS_S)
     NDWT_LIST_F64_FWD(NDWT_IS_F) NDWT_LIST_F64_INV(NDWT_IS_S) NDWT_LIST_F64_LONG(NDWT_IS_F, NDWT_IS_S)
     return false;
+}
+#define NDWT_IS_A(T, EW, L, NLEV, WPE) if (k == Cascade2Instance{false, sizeof(T) == 8, EW, L, NLEV, 0}) return true;
+#define NDWT_IS_R(T, EW, L, NLEV, PD, WPE) if (k == Cascade2Instance{true, sizeof(T) == 8, EW, L, NLEV, PD}) return true;
+inline bool cascade2_instantiated(const Cascade2Instance& k) {
+    NDWT_LIST_F32_FWD2C(NDWT_IS_A) NDWT_LIST_C64_FWD2C(NDWT_IS_A) NDWT_LIST_F64_FWD2C(NDWT_IS_A) NDWT_LIST_C128_FWD2C(NDWT_IS_A)
+    NDWT_LIST_F32_INV2C(NDWT_IS_R) NDWT_LIST_C64_INV2C(NDWT_IS_R) NDWT_LIST_F64_INV2C(NDWT_IS_R) NDWT_LIST_C128_INV2C(NDWT_IS_R)
+    return false;
+}
+// scalars of a row one wave of the instance stores: the lanes inside the halo of every level, in whole 128-byte lines (Fwd2C::WX, Inv2C::WX;
+// the launch units check the geometry against the kernel's own)
+constexpr int cascade2_tile_width(const Cascade2Instance& k) {
+    const int LH = k.inverse ? k.Lp / 2 : k.Lp / 2 - 1, RH = k.inverse ? k.Lp / 2 - 1 : k.Lp / 2, lpl = k.f64 ? 4 : 8;
+    return 4 * ((64 - k.nlev * ((LH * k.ew + 3) / 4 + (RH * k.ew + 3) / 4)) / lpl * lpl);
 }
 inline bool inv2p_instantiated(const Fused2PInstance& k) {
     NDWT_LIST_F32_INV2P(NDWT_IS_P) NDWT_LIST_F64_INV2P(NDWT_IS_P)

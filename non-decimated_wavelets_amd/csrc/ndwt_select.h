@@ -171,21 +171,40 @@ inline bool fused_shrink_capable(const SelPlan& p) {
     return r.kind == kRouteFused2 || (route_fused3(r.kind) && !(p.variant_inv == kInvLds && r.Lp == 8));   // the LDS synthesis kernel does not
 }
 
-// ---- two or three levels of an image in one launch (Fwd2C / Inv2C): float real data at tap stride 1, rows of whole groups of 4
-// scalars, up to 8 taps (analysis: or 12, two levels -- three do not fit the 256 registers).  Images beyond 2048^2 (below, the rows a
-// wave reads before its chunk produces anything outweigh the volumes saved), or on request.  `left` = levels still to do; returns how
-// many the next launch takes (and the padded tap length), 0 = one launch per level.
+// ---- two or three levels of an image in one launch (Fwd2C / Inv2C) at tap stride 1: rows of whole groups of 4 SCALARS (interleaved
+// complex: two per element), the tap lengths and level counts of the instance table (ndwt_fused_list.h: NDWT_LIST_*2C -- float real up to
+// 8 taps, analysis also 12 at two levels; which double and complex forms fit the registers is written there).  By default for images
+// from a size per data kind and direction on, in BYTES (cascade2_min_bytes: below it the rows a wave reads before its chunk produces
+// anything outweigh the volumes saved), or on request.  `left` = levels still to do; returns how many the next launch takes (and the padded tap length),
+// 0 = one launch per level.
+// The smallest image, in bytes, that takes the cascade unasked (db4, 3 levels, against the build before these kinds had
+// the cascade, at 2048^2 / 4096^2 / 8192^2; a kind and direction takes it from the smallest measured size on at which it won by more than
+// the 5 % spread between boxes).  float real: beyond 2048 x 3072 (equal at 2048^2, -33 % / -22 % at 4096^2), as ever; complex64 from
+// 2048^2 = 32 MiB (-20 % / -28 %); double real: the analysis from 2048^2 = 32 MiB (-17 %), the synthesis from 4096^2 = 128 MiB (-14 %;
+// at 2048^2 its one wave per SIMD is 24 % SLOWER than three launches); complex128 from 2048^2 = 64 MiB (-37 % / -10 %)
+constexpr long long cascade2_min_bytes(bool f64, int comp, bool inverse) {
+    return !f64 ? (comp == 1 ? (24LL << 20) + 1 : (32LL << 20)) : comp == 1 ? (inverse ? (128LL << 20) : (32LL << 20)) : (64LL << 20);
+}
 inline int cascade2_levels(const SelPlan& p, bool inverse, int left, int* Lp_out) {
     int& Lp = *Lp_out;
-    if (left < 2 || p.f64 || !p.real || p.atrous || p.variant_fwd == kFwdNoCascade || !fused2_eligible(p, 1, &Lp)) return 0;
-    if ((Lp > 8 && (Lp != 12 || inverse)) || p.dims[0] % 4 != 0 || p.dims[1] < 3 * (Lp - 1)) return 0;
-    if (p.dims[0] * p.dims[1] >= (1LL << 31)) return 0;   // the kernel's row * row-stride products are formed in 64 bits, offsets in int
-    const bool big = p.dims[0] * p.dims[1] > (6LL << 20);
+    if (left < 2 || p.atrous || p.variant_fwd == kFwdNoCascade || (p.comp != 1 && p.comp != 2) || !fused2_eligible(p, 1, &Lp)) return 0;
+    const long long n1 = p.dims[0] * p.comp;              // scalars along x
+    if (n1 % 4 != 0 || p.dims[1] < 3 * (Lp - 1)) return 0;
+    if (n1 * p.dims[1] >= (1LL << 31)) return 0;          // the kernel's row * row-stride products are formed in 64 bits, offsets in int
+    const auto exists = [&](int nlev) { return cascade2_instantiated({inverse, p.f64, p.comp, Lp, nlev, inverse ? 1 : 0}); };
+    const int n = (left >= 3 && exists(3)) ? 3 : exists(2) ? 2 : 0;
+    if (!n) return 0;
+    const bool big = n1 * p.dims[1] * (p.f64 ? 8 : 4) >= cascade2_min_bytes(p.f64, p.comp, inverse);
     if (inverse ? (p.variant_inv == kInvCascadeOff || !(big || p.variant_inv == kInvCascadeAlways || p.variant_inv == kInvCascadeDepth2))
                 : !(big || p.variant_fwd == kFwdCascadeAlways || p.variant_fwd == kFwdCascadeMode1)) return 0;
-    return (left >= 3 && Lp <= 8) ? 3 : 2;
+    return n;
 }
 constexpr int cascade2_rec_depth(int variant_inv) { return variant_inv == kInvCascadeDepth2 ? 2 : 1; }   // Inv2C: rows of band loads in flight per level
+// ... of the launch of `nlev` levels: the depth asked for where the instance exists, one row otherwise
+inline int cascade2_rec_depth(const SelPlan& p, int Lp, int nlev) {
+    const int want = cascade2_rec_depth(p.variant_inv);
+    return cascade2_instantiated({true, p.f64, p.comp, Lp, nlev, want}) ? want : 1;
+}
 
 // ---- one fused 3-D launch
 struct Fused3Query {

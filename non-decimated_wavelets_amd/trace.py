@@ -25,10 +25,10 @@ FAMILY_PARAMS = {
               ("ZLDS", 0), ("XH", 0), ("UNIYZ", False), ("XSC", False)],
     "Den3": [("T", None), ("L", None), ("NT", 1024), ("WPE", 4), ("ZLDS", 0), ("TX", 64), ("TY", 32)],
     "Fwd2S": [("T", None), ("L", None), ("VEC4", None), ("WPE", 4), ("EW", 1)],
-    "Fwd2C": [("T", None), ("L", None), ("NLEV", None), ("WPE", 2)],
+    "Fwd2C": [("T", None), ("L", None), ("NLEV", None), ("WPE", 2), ("EW", 1)],
     "Inv2S": [("T", None), ("L", None), ("VEC4", None), ("WPE", 4), ("EW", 1)],
     "Inv2P": [("T", None), ("L", None), ("PD", 2), ("WPE", 2), ("PK", False)],
-    "Inv2C": [("T", None), ("L", None), ("NLEV", None), ("PD", 1), ("WPE", 2)],
+    "Inv2C": [("T", None), ("L", None), ("NLEV", None), ("PD", 1), ("WPE", 2), ("EW", 1)],
     "AxisMarch": [("T", None), ("L", None), ("SYN", None)],
     "AxisX": [("T", None), ("L", None), ("SYN", None), ("EW", None), ("VEC4", None)],
 }
