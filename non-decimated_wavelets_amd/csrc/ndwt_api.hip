@@ -501,9 +501,10 @@ template <typename T> static int fused2_run(const ndwt_plan* p, const Fused2Laun
     const void* td = p->taps_dev[inverse ? 1 : 0];
     if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
     prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
-    const int rc = launch_fused2_pick(k, q, a, td, s);
+    const int rc = launch_fused2_pick(k, a, td, s);   // (-1, -2: after a pick, internal errors -- see fused3_run)
     prof_end(p, s, rc);
-    if (rc == -1) return fail(NDWT_ERR_UNSUPPORTED, "no fused 2-D kernel instantiated for tap length %d", Lp);
+    if (rc == -1) return fail(NDWT_ERR_UNSUPPORTED, "internal: no fused 2-D kernel instantiated for the pick (family %d, tap length %d)", (int)k.family, Lp);
+    if (rc == -2) return fail(NDWT_ERR_UNSUPPORTED, "internal: launch geometry does not match the 2-D kernel's tile width %d", fused2_tile_width(inverse, Lp, q.ew));
     if (rc != 0) return fail(NDWT_ERR_HIP, "fused 2-D kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     return NDWT_OK;
 }
@@ -1685,10 +1686,10 @@ static int den3_launch(ndwt_plan* p, int kind, int Lp, const float* x, const flo
     a.nt = nt_store_ok<float>(a.rs, a.plane, p->vol, outs, 1);
     prof_begin(p, kind == 1 ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
     const bool vec4 = aligned_vec4<float>(x) && aligned_vec4<float>(out);
-    int rc = kind == 1 ? launch_den3_f32(a, Lp, p->taps_den, s) : launch_fwd3_low_f32(a, Lp, vec4, p->taps_dev[0], s);
+    int rc = kind == 1 ? launch_den3_f32(a, Lp, p->taps_den, s) : launch_fwd3_low_f32(a, Lp, vec4, small_tile ? 0 : 2, p->taps_dev[0], s);
     prof_end(p, s, rc);
     if (rc == -1) return fail(NDWT_ERR_UNSUPPORTED, "fused level-1 kernel not instantiated for tap length %d", Lp);
-    if (rc == -2) return fail(NDWT_ERR_UNSUPPORTED, "internal: launch geometry does not match the 64 x 32 tile");
+    if (rc == -2) return fail(NDWT_ERR_UNSUPPORTED, "internal: launch geometry does not match the level-1 kernel's tile");
     if (rc != 0) return fail(NDWT_ERR_HIP, "fused level-1 kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     return NDWT_OK;
 }

@@ -1,6 +1,7 @@
 // ndwt_fused.h -- host-callable launchers of the fused level kernels (their instances are spread over translation
-// units so the build parallelises).  Returns 0 on success, -1 if no instance is the one asked for, else a
-// hipError_t.
+// units so the build parallelises).  Every fused launch takes a pick that names its instance in full (ndwt_select.h, ndwt_fused_list.h)
+// and asks the units in turn.  Returns 0 on success, -1 if no unit has the instance, -2 if the launch geometry is not the instance's
+// tile, else a hipError_t.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,12 +25,14 @@ int launch_fused3_pick(const Fused3Pick& k, const Fused3Args<double>& a, const v
 // level 1 of a denoising step in one launch (Den3: in[0] = x, in[1] = approximation band) and the approximation-only analysis
 // that goes with it (tall 64 x 32 tile); float, real data, tap lengths 2 .. 8: ndwt_fused3_f32_den.hip.  ndwt_denoise chooses these.
 int launch_den3_f32(const Fused3Args<float>& a, int Lp, const void* taps_dev, hipStream_t s);
-int launch_fwd3_low_f32(const Fused3Args<float>& a, int Lp, bool vec4, const void* taps_dev, hipStream_t s);
+// (tile: the index into Fused3Tile the caller laid the launch out for -- 2 = 64 x 32, 0 = 64 x 16)
+int launch_fwd3_low_f32(const Fused3Args<float>& a, int Lp, bool vec4, int tile, const void* taps_dev, hipStream_t s);
 
-// The fused 2-D launch a pick names (fused2_select; register-only kernels, one wave per tile): Fwd2S / Inv2S by direction, tap length and
-// x step of the query, or the Inv2P instance of the pick.  -1: no such instance.
-int launch_fused2_pick(const Fused2Pick& k, const Fused2Query& q, const Fused2Args<float>& a, const void* taps_dev, hipStream_t s);
-int launch_fused2_pick(const Fused2Pick& k, const Fused2Query& q, const Fused2Args<double>& a, const void* taps_dev, hipStream_t s);
+// The fused 2-D launch a pick names (fused2_select; register-only kernels, one wave per tile): the Fwd2S / Inv2S instance or the Inv2P
+// instance of the pick, the launch units asked in turn as for 3-D.  -1: no unit has the instance, -2: the launch geometry is not the
+// instance's tile (fused2_tile_width).
+int launch_fused2_pick(const Fused2Pick& k, const Fused2Args<float>& a, const void* taps_dev, hipStream_t s);
+int launch_fused2_pick(const Fused2Pick& k, const Fused2Args<double>& a, const void* taps_dev, hipStream_t s);
 // Two or three levels of an image in one launch (Fwd2C / Inv2C), the instance named in full (ndwt_fused_list.h: Cascade2Instance, the
 // table cascade2_levels reads; its tile: cascade2_tile_width).  Float real and interleaved complex64 take the float forms, double real and
 // complex128 the double ones; -1: no unit has the instance, -2: the launch geometry is not the instance's tile.

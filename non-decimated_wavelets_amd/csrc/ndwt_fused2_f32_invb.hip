@@ -1,7 +1,8 @@
 // fused 2-D synthesis (Inv2S), float, 8 .. 12 taps
 #include "ndwt_fused_kernels.h"
 namespace ndwt {
-int launch_inv2_f32_long(const Fused2Args<float>& a, int Lp, bool vec4, int ew, const void* taps_dev, hipStream_t s) {
-    NDWT_FUSED2_SWITCH_LONG(Inv2S, float)
+int launch2_f32_invb(const Fused2SInstance& k, const Fused2Args<float>& a, const void* taps_dev, hipStream_t s) {
+    NDWT_LIST_F32_2S_MID(NDWT_LAUNCH_W, Inv2S)
+    return -1;
 }
 }  // namespace ndwt

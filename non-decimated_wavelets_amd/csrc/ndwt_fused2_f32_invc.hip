@@ -1,16 +1,8 @@
-// fused 2-D synthesis, interleaved complex64 data, 10 .. 16 taps (db5 .. db8): Inv2S with the x taps stepping over (re, im) pairs on the
-// 256-register budget (2 waves per SIMD), no spills
+// fused 2-D synthesis (Inv2S), interleaved complex64 data, 10 .. 16 taps (db5 .. db8)
 #include "ndwt_fused_kernels.h"
 namespace ndwt {
-#define NDWT_C2_CASE(LL) \
-    case LL: return vec4 ? launch_fused2<Inv2S<float, LL, true, 2, 2>>(a, taps_dev, s) : launch_fused2<Inv2S<float, LL, false, 2, 2>>(a, taps_dev, s);
-int launch_inv2_c64_10to16(const Fused2Args<float>& a, int Lp, bool vec4, const void* taps_dev, hipStream_t s) {
-    switch (Lp) {
-        NDWT_C2_CASE(10)
-        NDWT_C2_CASE(12)
-        NDWT_C2_CASE(14)
-        NDWT_C2_CASE(16)
-        default: return -1;
-    }
+int launch2_f32_invc(const Fused2SInstance& k, const Fused2Args<float>& a, const void* taps_dev, hipStream_t s) {
+    NDWT_LIST_C64_2S_LONG(NDWT_LAUNCH_W, Inv2S)
+    return -1;
 }
 }  // namespace ndwt

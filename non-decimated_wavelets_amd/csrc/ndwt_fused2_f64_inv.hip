@@ -1,8 +1,8 @@
-// fused 2-D synthesis (Inv2S), double
+// fused 2-D synthesis (Inv2S), double, 2 .. 12 taps
 #include "ndwt_fused_kernels.h"
 namespace ndwt {
-int launch_inv2_f64(const Fused2Args<double>& a, int Lp, bool vec4, int ew, const void* taps_dev, hipStream_t s) {
-    if (Lp > 6) { NDWT_FUSED2_SWITCH_LONG(Inv2S, double) }
-    NDWT_FUSED2_SWITCH_SHORT(Inv2S, double)
+int launch2_f64_inv(const Fused2SInstance& k, const Fused2Args<double>& a, const void* taps_dev, hipStream_t s) {
+    NDWT_LIST_F64_2S(NDWT_LAUNCH_W, Inv2S)
+    return -1;
 }
 }  // namespace ndwt

@@ -19,30 +19,15 @@ int launch_den3_f32(const Fused3Args<float>& a, int Lp, const void* taps_dev, hi
     }
 }
 
-// band 0 only: TILE 2 = the tall 64 x 32 tile of the float analysis (1024 threads, one workgroup per CU), 0 = 64 x 16 (256 threads)
-template <int LL, bool V, int TILE = 2> static int go_low(const Fused3Args<float>& a, const void* taps_dev, hipStream_t s) {
-    typedef Fused3Tile<float, false, TILE> TL;
-    typedef Fwd3<float, LL, TL::TX, TL::TY, TL::NT, TL::RY, V, TL::WPE, 1, true> K;
-    return launch_fused3<K>(a, taps_dev, s);
-}
-
-int launch_fwd3_low_f32(const Fused3Args<float>& a, int Lp, bool vec4, const void* taps_dev, hipStream_t s) {
-    if (a.nty == (a.n2 + 15) / 16 && a.nty != (a.n2 + 31) / 32) {     // the caller laid out 64 x 16 tiles
-        switch (Lp) {
-            case 2: return vec4 ? go_low<2, true, 0>(a, taps_dev, s) : go_low<2, false, 0>(a, taps_dev, s);
-            case 4: return vec4 ? go_low<4, true, 0>(a, taps_dev, s) : go_low<4, false, 0>(a, taps_dev, s);
-            case 6: return vec4 ? go_low<6, true, 0>(a, taps_dev, s) : go_low<6, false, 0>(a, taps_dev, s);
-            case 8: return vec4 ? go_low<8, true, 0>(a, taps_dev, s) : go_low<8, false, 0>(a, taps_dev, s);
-            default: return -1;
-        }
-    }
-    switch (Lp) {
-        case 2: return vec4 ? go_low<2, true>(a, taps_dev, s) : go_low<2, false>(a, taps_dev, s);
-        case 4: return vec4 ? go_low<4, true>(a, taps_dev, s) : go_low<4, false>(a, taps_dev, s);
-        case 6: return vec4 ? go_low<6, true>(a, taps_dev, s) : go_low<6, false>(a, taps_dev, s);
-        case 8: return vec4 ? go_low<8, true>(a, taps_dev, s) : go_low<8, false>(a, taps_dev, s);
-        default: return -1;
-    }
+// band 0 only, on the tile the caller laid out: TILE 2 = the tall 64 x 32 tile of the float analysis (1024 threads, one workgroup per
+// CU), 0 = 64 x 16 (256 threads)
+#define NDWT_LAUNCH_LOW(LL, TILE, V)                                                                           \
+    if (Lp == LL && tile == TILE && vec4 == V) return launch_fused3<NDWT_FUSED_K(Fwd3, false, float, LL, TILE, V, 1, true)>(a, taps_dev, s);
+#define NDWT_LOW2(LL, TILE) NDWT_LAUNCH_LOW(LL, TILE, true) NDWT_LAUNCH_LOW(LL, TILE, false)
+#define NDWT_LOW8(TILE) NDWT_LOW2(2, TILE) NDWT_LOW2(4, TILE) NDWT_LOW2(6, TILE) NDWT_LOW2(8, TILE)
+int launch_fwd3_low_f32(const Fused3Args<float>& a, int Lp, bool vec4, int tile, const void* taps_dev, hipStream_t s) {
+    NDWT_LOW8(0) NDWT_LOW8(2)
+    return -1;
 }
 
 // 4-D analysis with the t axis folded in (Fwd3<.., TPRE>): chosen by the pick, as every instance of the other units

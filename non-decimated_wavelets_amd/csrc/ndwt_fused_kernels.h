@@ -40,42 +40,21 @@ template <class K> int launch_fused3(const typename K::Args& a, const void* taps
     return (int)hipGetLastError();
 }
 
-template <class K> int launch_fused2(const typename K::Args& a, const void* taps_dev, hipStream_t s) {
-    const int nblocks = a.ntx * a.nyc * a.nbatch;
+// The 2-D kernels: one wave per tile of K::WX scalars and chunk of rows, times the batch items.  The same check of the host's tiling
+// (fused2_geometry, cascade2_launch) against the tile this kernel was compiled for.
+template <class K> int launch_wave_tiles(const typename K::Args& a, int nbatch, const void* taps_dev, hipStream_t s) {
+    if (a.ntx != (a.n1 + K::WX - 1) / K::WX || a.ychunk < 1 || (long long)a.nyc * a.ychunk < a.n2) return -2;
+    const int nblocks = a.ntx * a.nyc * nbatch;
     trace_kernel<K>(dim3(nblocks), dim3(K::NT));
     hipLaunchKernelGGL(fused3_kernel<K>, dim3(nblocks), dim3(K::NT), 0, s, a, (const typename K::Taps*)taps_dev);
     return (int)hipGetLastError();
 }
-
-#define NDWT_FUSED2_CASE(KIND, T, LL)                                                        \
-    case LL:                                                                                 \
-        if constexpr (sizeof(T) == 4 && LL <= 8) {   /* a level dilated by 4: x taps over 4 scalars (float, db1..db4) */ \
-            if (ew == 4)                                                                     \
-                return vec4 ? launch_fused2<KIND<T, LL, true, 4, 4>>(a, taps_dev, s) : launch_fused2<KIND<T, LL, false, 4, 4>>(a, taps_dev, s); \
-        }                                                                                    \
-        if (ew == 4) return -1;                                                              \
-        if constexpr (LL <= 8) {   /* interleaved complex: up to 8 taps here (complex64 10 .. 16: ndwt_fused2_f32_{fwdc,invc}.hip) */ \
-            if (ew == 2)                                                                     \
-                return vec4 ? launch_fused2<KIND<T, LL, true, (sizeof(T) == 8 ? 2 : 4), 2>>(a, taps_dev, s)   \
-                            : launch_fused2<KIND<T, LL, false, (sizeof(T) == 8 ? 2 : 4), 2>>(a, taps_dev, s); \
-        }                                                                                    \
-        if (ew == 2) return -1;                                                              \
-        return vec4 ? launch_fused2<KIND<T, LL, true, (sizeof(T) == 8 ? 2 : 4)>>(a, taps_dev, s) : launch_fused2<KIND<T, LL, false, (sizeof(T) == 8 ? 2 : 4)>>(a, taps_dev, s);
-// (the tap lengths are split over two translation units per kernel family: one unit with all of them is the long pole of the build)
-#define NDWT_FUSED2_SWITCH_SHORT(KIND, T) \
-    switch (Lp) {                     \
-        NDWT_FUSED2_CASE(KIND, T, 2)  \
-        NDWT_FUSED2_CASE(KIND, T, 4)  \
-        NDWT_FUSED2_CASE(KIND, T, 6)  \
-        default: return -1;           \
-    }
-#define NDWT_FUSED2_SWITCH_LONG(KIND, T) \
-    switch (Lp) {                     \
-        NDWT_FUSED2_CASE(KIND, T, 8)  \
-        NDWT_FUSED2_CASE(KIND, T, 10) \
-        NDWT_FUSED2_CASE(KIND, T, 12) \
-        default: return -1;           \
-    }
+template <class K> int launch_fused2(const typename K::Args& a, const void* taps_dev, hipStream_t s) {      // Fwd2S / Inv2S / Inv2P
+    return launch_wave_tiles<K>(a, a.nbatch, taps_dev, s);
+}
+template <class K> int launch_cascade2_k(const typename K::Args& a, const void* taps_dev, hipStream_t s) {  // Fwd2C / Inv2C
+    return launch_wave_tiles<K>(a, 1, taps_dev, s);
+}
 
 // One entry of an instance list (ndwt_fused_list.h) as an exact-match launch: the pick is this instance, or the next entry is asked.  A
 // launch unit is its list expanded with these and a final "not mine" (-1).
@@ -90,7 +69,23 @@ template <class K> int launch_fused2(const typename K::Args& a, const void* taps
 #define NDWT_LAUNCH_Y(LL, VEC, EWV, DEPTH, UNI, XSC)                                                         \
     if (k == inv3y_instance(LL, VEC, EWV, DEPTH, UNI, XSC))                                                  \
         return launch_fused3<Inv3Y<float, LL, inv3y_tx(LL, EWV), inv3y_ty(LL, EWV), 1024, VEC, 4, DEPTH, EWV, inv3y_zlds(LL, DEPTH, EWV), 0, UNI, XSC>>(a, taps_dev, s);
+// (the host lays a one-level 2-D launch out for fused2_tile_width, a cascade for cascade2_tile_width: they are the kernels' own WX)
+#define NDWT_LAUNCH_W(KIND, T, LL, VEC, WPE, EWV)                                                            \
+    if (k == Fused2SInstance{k##KIND == kInv2S, sizeof(T) == 8, VEC, LL, EWV, WPE}) {                        \
+        static_assert(KIND<T, LL, VEC, WPE, EWV>::WX == fused2_tile_width(k##KIND == kInv2S, LL, EWV), "tile width"); \
+        return launch_fused2<KIND<T, LL, VEC, WPE, EWV>>(a, taps_dev, s);                                    \
+    }
 #define NDWT_LAUNCH_P(T, LL, PD, PK) \
     if (k == Fused2PInstance{sizeof(T) == 8, LL, PD, PK}) return launch_fused2<Inv2P<T, LL, PD, 2, PK>>(a, taps_dev, s);
+#define NDWT_LAUNCH_A(T, EWV, LL, NLEV, WPE)                                                                 \
+    if (k == Cascade2Instance{false, sizeof(T) == 8, EWV, LL, NLEV, 0}) {                                    \
+        static_assert(Fwd2C<T, LL, NLEV, WPE, EWV>::WX == cascade2_tile_width({false, sizeof(T) == 8, EWV, LL, NLEV, 0}), "tile width"); \
+        return launch_cascade2_k<Fwd2C<T, LL, NLEV, WPE, EWV>>(a, taps_dev, s);                              \
+    }
+#define NDWT_LAUNCH_R(T, EWV, LL, NLEV, PD, WPE)                                                             \
+    if (k == Cascade2Instance{true, sizeof(T) == 8, EWV, LL, NLEV, PD}) {                                    \
+        static_assert(Inv2C<T, LL, NLEV, PD, WPE, EWV>::WX == cascade2_tile_width({true, sizeof(T) == 8, EWV, LL, NLEV, PD}), "tile width"); \
+        return launch_cascade2_k<Inv2C<T, LL, NLEV, PD, WPE, EWV>>(a, taps_dev, s);                          \
+    }
 
 }  // namespace ndwt

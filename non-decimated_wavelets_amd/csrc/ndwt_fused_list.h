@@ -1,6 +1,7 @@
 // ndwt_fused_list.h -- the instances of the fused kernels that kernel selection can name, one list per launch unit (no HIP header: the
 // launch units expand a list into launches, ndwt_select.h and the host tests into questions).  An instance lives in exactly one list: the
-// unit decides how its device code is compiled (csrc/Makefile: NOSLP), and the split over units is what keeps the build parallel.
+// unit decides how its device code is compiled (csrc/Makefile: NOSLP), and the split over units is what keeps the build parallel.  Every
+// fused family is here: the 3-D kernels, the one-level 2-D ones (Fwd2S / Inv2S, Inv2P) and the 2-D cascade.
 #pragma once
 #include "ndwt_fused_tile.h"
 
@@ -31,6 +32,15 @@ constexpr Fused3Instance inv3s_instance(Fused3Kernel kernel, bool f64, int L, in
 constexpr Fused3Instance inv3y_instance(int L, bool vec4, int ew, int depth, bool uniyz, bool scatter) {
     return {kInv3Y, false, vec4, L, ew, 0, false, false, 0, depth, uniyz, scatter};
 }
+// Fwd2S / Inv2S<T, Lp, VEC4, WPE, EW>: one level of an image, one wave per tile, registers only
+enum Fused2SKind { kFwd2S, kInv2S };
+struct Fused2SInstance { bool inverse, f64, vec4; int Lp, ew, wpe; };
+constexpr bool operator==(const Fused2SInstance& a, const Fused2SInstance& b) {
+    return a.inverse == b.inverse && a.f64 == b.f64 && a.vec4 == b.vec4 && a.Lp == b.Lp && a.ew == b.ew && a.wpe == b.wpe;
+}
+// waves per SIMD an instance is compiled for (its register budget: 4 -> 128, 2 -> 256): the y window / the pending sums of a wave grow
+// with the tap length, twice as fast in double and with the x taps stepping over pairs; the 128-register forms of these would spill
+constexpr int fused2s_wpe(bool f64, int Lp, int ew) { return (f64 || (ew == 1 ? Lp >= 14 : (ew == 2 && Lp >= 10))) ? 2 : 4; }
 struct Fused2PInstance { bool f64; int Lp, pdepth; bool packed; };   // Inv2P<T, Lp, PD, 2, PK>
 constexpr bool operator==(const Fused2PInstance& a, const Fused2PInstance& b) {
     return a.f64 == b.f64 && a.Lp == b.Lp && a.pdepth == b.pdepth && a.packed == b.packed;
@@ -44,13 +54,15 @@ constexpr bool operator==(const Cascade2Instance& a, const Cascade2Instance& b) 
 // ---- the lists.  Entries:  F(T, L, V, VEC4, EW, PIN, TPRE, WLDS)  Fwd3 on tile V
 //                            S(KIND, T, L, V, VEC4, EW)             Inv3 / Inv3S on tile V
 //                            Y(L, VEC4, EW, DEPTH, UNIYZ, XSC)      Inv3Y (float)
+//                            W(KIND, T, L, VEC4, WPE, EW)           Fwd2S / Inv2S
 //                            P(T, L, PD, PK)                        Inv2P
 //                            A(T, EW, L, NLEV, WPE)                 Fwd2C
 //                            R(T, EW, L, NLEV, PD, WPE)             Inv2C
-// NDWT_F2 / NDWT_S2 / NDWT_Y2: the plain form of an entry for rows of whole groups of 4 scalars and for the rest
+// NDWT_F2 / NDWT_S2 / NDWT_Y2 / NDWT_W2: the plain form of an entry for rows of whole groups of 4 scalars and for the rest
 #define NDWT_F2(F, T, L, V, EW) F(T, L, V, true, EW, false, false, 0) F(T, L, V, false, EW, false, false, 0)
 #define NDWT_S2(S, KIND, T, L, V, EW) S(KIND, T, L, V, true, EW) S(KIND, T, L, V, false, EW)
 #define NDWT_Y2(Y, L, EW, DEPTH) Y(L, true, EW, DEPTH, false, false) Y(L, false, EW, DEPTH, false, false)
+#define NDWT_W2(W, KIND, T, L, WPE, EW) W(KIND, T, L, true, WPE, EW) W(KIND, T, L, false, WPE, EW)
 
 // float analysis: 256-thread kernel for tap lengths <= 8, the tall 64x32 tile with 1024 threads for 10 and 12 (and 14, 16:
 // ndwt_fused3_f32_long.hip); tile 1 = 512 threads, one column per thread (A/B; the kernel of interleaved complex data with 10 .. 16 taps)
@@ -161,6 +173,39 @@ constexpr bool operator==(const Cascade2Instance& a, const Cascade2Instance& b) 
     F(double, 16, 5, true, 1, false, false, 2) NDWT_F2(F, double, 14, 5, 1) NDWT_F2(F, double, 16, 5, 1)                  \
     NDWT_S2(S, Inv3S, double, 14, 5, 1) NDWT_S2(S, Inv3S, double, 16, 5, 1)
 
+// One level of an image (Fwd2S / Inv2S): a list serves the analysis unit and the synthesis unit of its tap lengths (KIND = Fwd2S / Inv2S).
+// The tap lengths of a kind are split over units because one unit with all of them is the long pole of the build.
+// float up to 12 taps at 4 waves per SIMD: real data; up to 8 taps also with the x taps stepping over 2 scalars (interleaved complex64,
+// a level dilated by 2) and over 4 (a level dilated by 4).  2 .. 6 taps: ndwt_fused2_f32.hip, ndwt_fused2_f32_inva.hip
+#define NDWT_LIST_F32_2S_SHORT(W, KIND)                                                                                   \
+    NDWT_W2(W, KIND, float, 2, 4, 4) NDWT_W2(W, KIND, float, 2, 4, 2) NDWT_W2(W, KIND, float, 2, 4, 1)                    \
+    NDWT_W2(W, KIND, float, 4, 4, 4) NDWT_W2(W, KIND, float, 4, 4, 2) NDWT_W2(W, KIND, float, 4, 4, 1)                    \
+    NDWT_W2(W, KIND, float, 6, 4, 4) NDWT_W2(W, KIND, float, 6, 4, 2) NDWT_W2(W, KIND, float, 6, 4, 1)
+// ... 8 .. 12 taps: ndwt_fused2_f32_fwdb.hip, ndwt_fused2_f32_invb.hip
+#define NDWT_LIST_F32_2S_MID(W, KIND)                                                                                     \
+    NDWT_W2(W, KIND, float, 8, 4, 4) NDWT_W2(W, KIND, float, 8, 4, 2) NDWT_W2(W, KIND, float, 8, 4, 1)                    \
+    NDWT_W2(W, KIND, float, 10, 4, 1) NDWT_W2(W, KIND, float, 12, 4, 1)
+// float real, 14 .. 20 taps (db7 .. db10): the 256-register budget (2 waves per SIMD), no spills.  Analysis: ndwt_fused2_f32_fwdl.hip;
+// synthesis: 14 / 16 in ndwt_fused2_f32_invl.hip, 18 / 20 in ndwt_fused2_f32_invm.hip
+#define NDWT_LIST_F32_2S_14_16(W, KIND) NDWT_W2(W, KIND, float, 14, 2, 1) NDWT_W2(W, KIND, float, 16, 2, 1)
+#define NDWT_LIST_F32_2S_18_20(W, KIND) NDWT_W2(W, KIND, float, 18, 2, 1) NDWT_W2(W, KIND, float, 20, 2, 1)
+// interleaved complex64, 10 .. 16 taps (db5 .. db8): the x taps stepping over (re, im) pairs on the 256-register budget, no spills
+// (ndwt_fused2_f32_fwdc.hip, ndwt_fused2_f32_invc.hip)
+#define NDWT_LIST_C64_2S_LONG(W, KIND) \
+    NDWT_W2(W, KIND, float, 10, 2, 2) NDWT_W2(W, KIND, float, 12, 2, 2) NDWT_W2(W, KIND, float, 14, 2, 2) NDWT_W2(W, KIND, float, 16, 2, 2)
+// double on the 256-register budget: real up to 12 taps; complex128 / a level dilated by 2 up to 8 (ndwt_fused2_f64.hip, ndwt_fused2_f64_inv.hip)
+#define NDWT_LIST_F64_2S(W, KIND)                                                                                         \
+    NDWT_W2(W, KIND, double, 8, 2, 2) NDWT_W2(W, KIND, double, 8, 2, 1) NDWT_W2(W, KIND, double, 10, 2, 1) NDWT_W2(W, KIND, double, 12, 2, 1) \
+    NDWT_W2(W, KIND, double, 2, 2, 2) NDWT_W2(W, KIND, double, 2, 2, 1) NDWT_W2(W, KIND, double, 4, 2, 2) NDWT_W2(W, KIND, double, 4, 2, 1) \
+    NDWT_W2(W, KIND, double, 6, 2, 2) NDWT_W2(W, KIND, double, 6, 2, 1)
+// double real, 14 and 16 taps (db7, db8), both directions in ndwt_fused2_f64_long.hip: the analysis fits the 256-register budget, the
+// synthesis spills 22 .. 70 registers (still 3x the per-axis path)
+#define NDWT_LIST_F64_2S_LONG(W, KIND) NDWT_W2(W, KIND, double, 14, 2, 1) NDWT_W2(W, KIND, double, 16, 2, 1)
+// every list of one direction
+#define NDWT_LIST_2S(W, KIND)                                                                                             \
+    NDWT_LIST_F32_2S_MID(W, KIND) NDWT_LIST_F32_2S_SHORT(W, KIND) NDWT_LIST_F32_2S_14_16(W, KIND) NDWT_LIST_F32_2S_18_20(W, KIND) \
+    NDWT_LIST_C64_2S_LONG(W, KIND) NDWT_LIST_F64_2S(W, KIND) NDWT_LIST_F64_2S_LONG(W, KIND)
+
 // 2-D synthesis with rows of band loads in flight (Inv2P), real data in rows of whole groups of 4 scalars.  float: PD rows in flight per
 // wave; packed FMAs on pairs of adjacent x outputs with the tap pairs pinned in SGPRs for 4 / 8 / 12 taps at depth 4.  double: up to 8
 // taps fit the 256-register budget without spills (4 rows in flight with 4 taps, 2 otherwise)
@@ -228,6 +273,18 @@ inline bool cascade2_instantiated(const Cascade2Instance& k) {
 constexpr int cascade2_tile_width(const Cascade2Instance& k) {
     const int LH = k.inverse ? k.Lp / 2 : k.Lp / 2 - 1, RH = k.inverse ? k.Lp / 2 - 1 : k.Lp / 2, lpl = k.f64 ? 4 : 8;
     return 4 * ((64 - k.nlev * ((LH * k.ew + 3) / 4 + (RH * k.ew + 3) / 4)) / lpl * lpl);
+}
+#define NDWT_IS_W(KIND, T, L, VEC4, WPE, EW) if (k == Fused2SInstance{k##KIND == kInv2S, sizeof(T) == 8, VEC4, L, EW, WPE}) return true;
+inline bool fused2s_instantiated(const Fused2SInstance& k) {
+    NDWT_LIST_2S(NDWT_IS_W, Fwd2S) NDWT_LIST_2S(NDWT_IS_W, Inv2S)
+    return false;
+}
+// a level of tap length Lp with the x taps stepping over ew scalars can run both ways: analysis and synthesis, rows in whole groups of 4
+// scalars or not, at the register budget of fused2s_wpe
+inline bool fused2s_both_ways(bool f64, int Lp, int ew) {
+    for (int i = 0; i < 4; ++i)
+        if (!fused2s_instantiated({i / 2 != 0, f64, i % 2 != 0, Lp, ew, fused2s_wpe(f64, Lp, ew)})) return false;
+    return true;
 }
 inline bool inv2p_instantiated(const Fused2PInstance& k) {
     NDWT_LIST_F32_INV2P(NDWT_IS_P) NDWT_LIST_F64_INV2P(NDWT_IS_P)

@@ -102,22 +102,26 @@ inline bool fused3_dilated_eligible(const SelPlan& p, long long stride, int* Lp_
     return true;
 }
 
-// the 2-D analogue: x through EW = stride, the `stride` row sub-lattices as batch items
+// the 2-D analogue: x through EW = stride, the `stride` row sub-lattices as batch items.  Which strides and scalar types have the
+// instances is the table's answer (ndwt_fused_list.h); the float lists of EW = 2 go on to 16 taps for complex64, and a dilated level
+// has only ever run, and been checked, up to kFused2DilatedMaxTaps
+constexpr int kFused2DilatedMaxTaps = 8;
 inline bool fused2_dilated_eligible(const SelPlan& p, long long stride, int* Lp_out) {
-    if (!p.path_auto || p.ndim != 2 || !p.real) return false;
-    if (stride != 2 && !(stride == 4 && !p.f64)) return false;
+    if (!p.path_auto || p.ndim != 2 || !p.real || stride < 2) return false;
     const int Lp = p.len[0] > p.len[1] ? p.len[0] : p.len[1];
-    if (Lp > 8 || p.dims[0] % stride != 0 || p.dims[1] % stride != 0 || p.dims[0] % 4 != 0) return false;
+    if (p.dims[0] % stride != 0 || p.dims[1] % stride != 0 || p.dims[0] % 4 != 0) return false;
     if (p.dims[0] >= (1LL << 30) || p.dims[1] >= (1LL << 30)) return false;
+    if (Lp > kFused2DilatedMaxTaps || !fused2s_both_ways(p.f64, Lp, (int)stride)) return false;
     *Lp_out = Lp;
     return true;
 }
 
+// one level at tap stride 1: the tap lengths the table has both ways for the plan's scalar type and x step (float real up to db10,
+// complex64 and double real up to db8, complex128 up to db4)
 inline bool fused2_eligible(const SelPlan& p, long long stride, int* Lp_out) {
     if (!p.path_auto || stride != 1 || p.ndim != 2) return false;
     const int Lp = p.len[0] > p.len[1] ? p.len[0] : p.len[1];
-    // float real: up to db10, complex64 and double real: up to db8 (256-register budget), complex128: up to db4
-    if (Lp > (!p.f64 ? (p.real ? 20 : 16) : (p.real ? 16 : 8))) return false;
+    if (!fused2s_both_ways(p.f64, Lp, p.real ? 1 : 2)) return false;
     if (p.dims[0] >= (1LL << 30) || p.dims[1] >= (1LL << 30)) return false;
     *Lp_out = Lp;
     return true;
@@ -318,9 +322,18 @@ struct Fused2Query {
     int variant_inv;
 };
 enum Fused2Family { kFused2S, kInv2P };   // Fwd2S / Inv2S by direction, or the synthesis with rows of band loads in flight
+// what a launch runs: the instance by its full name (ndwt_fused_list.h), flat as Fused3Pick is -- every template argument of Fwd2S /
+// Inv2S (family kFused2S) or of Inv2P (kInv2P: synthesis of real data, rows of whole groups of 4) -- and the waves fused2_geometry aims at
 struct Fused2Pick {
     Fused2Family family;
-    int pdepth, packed, waves;         // Inv2P: rows in flight, packed FMAs; target waves of fused2_geometry
+    bool inverse, f64, vec4;
+    int Lp, ew;
+    int wpe;                           // Fwd2S / Inv2S: waves per SIMD (fused2s_wpe)
+    int pdepth;                        // Inv2P: rows of band loads in flight
+    bool packed;                       // Inv2P: packed FMAs
+    int waves;
+    constexpr Fused2SInstance fused2s() const { return {inverse, f64, vec4, Lp, ew, wpe}; }
+    constexpr Fused2PInstance inv2p() const { return {f64, Lp, pdepth, packed}; }
 };
 // synthesis of real data in rows of whole groups of 4 scalars, images whose 70-row chunks fit one round of 1024 waves (up to 4096^2): Inv2P,
 // 4 rows of band loads in flight per wave, packed FMAs where that form exists (float 4 / 8 / 12 taps); double up to 8 taps, depth 4 for 4 taps
@@ -328,13 +341,10 @@ inline Fused2Pick fused2_select(const Fused2Query& q) {
     const int vi = q.variant_inv, WX = fused2_tile_width(q.inverse, q.Lp, q.ew), L = q.Lp;
     const bool deep = q.inverse && L <= 12 && (!q.f64 || L <= 8) && q.ew == 1 && q.dil == 1 && q.vec4 && vi != kInv2Keep2S && q.n2 >= 64 &&
                       ((long long)((q.n1 + WX - 1) / WX) * ((q.n2 + 69) / 70) <= 1280 || vi != kInvDefault);
-    Fused2Pick k = {deep ? kInv2P : kFused2S, 0, 0, (deep && vi != kInv2Depth2Geom && vi != kInv2Depth4Geom) ? 1024 : 2048};
-    if (deep) {
-        const bool d4 = q.f64 ? L == 4 : (vi != kInv2Depth2Geom && vi != kInv2Depth2Round && (L == 4 || L == 8 || L == 12));
-        k.pdepth = d4 ? 4 : 2;
-        k.packed = !q.f64 && d4 && vi != kInv2Unpacked;
-    }
-    return k;
+    const int waves = (deep && vi != kInv2Depth2Geom && vi != kInv2Depth4Geom) ? 1024 : 2048;
+    if (!deep) return {kFused2S, q.inverse, q.f64, q.vec4, L, q.ew, fused2s_wpe(q.f64, L, q.ew), 0, false, waves};
+    const bool d4 = q.f64 ? L == 4 : (vi != kInv2Depth2Geom && vi != kInv2Depth2Round && (L == 4 || L == 8 || L == 12));
+    return {kInv2P, true, q.f64, true, L, 1, 0, d4 ? 4 : 2, !q.f64 && d4 && vi != kInv2Unpacked, waves};
 }
 
 }  // namespace ndwt

@@ -36,11 +36,17 @@ extern "C" const char* sel_fused3(const int* v, int* out) {
     }
 }
 
-// v: f64, inverse, vec4, Lp, ew, dil, n1, n2, variant_inv;  out: family, pdepth, packed, waves, and (Inv2P) whether the lists hold the instance
+// v: f64, inverse, vec4, Lp, ew, dil, n1, n2, variant_inv
+// out: the pick in full -- family, inverse, f64, vec4, Lp, ew, WPE (Fwd2S / Inv2S) or pdepth (Inv2P), packed (Inv2P), waves, and whether
+// the instance lists (ndwt_fused_list.h) hold it
 extern "C" void sel_fused2(const int* v, int* out) {
     const Fused2Query q = {v[0] != 0, v[1] != 0, v[2] != 0, v[3], v[4], v[5], v[6], v[7], v[8]};
     const Fused2Pick k = fused2_select(q);
-    out[0] = (int)k.family; out[1] = k.pdepth; out[2] = k.packed; out[3] = k.waves;
-    out[4] = k.family == kInv2P && inv2p_instantiated({q.f64, q.Lp, k.pdepth, k.packed != 0});
+    const bool deep = k.family == kInv2P;
+    const int r[10] = {(int)k.family, k.inverse, k.f64, k.vec4, k.Lp, k.ew, deep ? k.pdepth : k.wpe, k.packed, k.waves,
+                       deep ? inv2p_instantiated(k.inv2p()) : fused2s_instantiated(k.fused2s())};
+    for (int i = 0; i < 10; ++i) out[i] = r[i];
 }
+// whether the lists hold the Fwd2S / Inv2S instance v: inverse, f64, vec4, Lp, ew, wpe
+extern "C" int sel_fused2s_listed(const int* v) { return fused2s_instantiated({v[0] != 0, v[1] != 0, v[2] != 0, v[3], v[4], v[5]}); }
 extern "C" int sel_cascade2_rec_depth(int variant_inv) { return cascade2_rec_depth(variant_inv); }

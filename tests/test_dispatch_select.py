@@ -1,7 +1,8 @@
 """The dispatch pins of tests/test_gpu_dispatch.py, checked without a device: kernel selection is a function of integers
 (csrc/ndwt_select.h), so every row whose level-1 launch is a fused 2-D / 3-D kernel is replayed against that header through a small
 host shim (tests/select/select_shim.cpp, compiled with g++).  The GPU test reads what ran from the launch trace; this one asks the
-same code what it would run."""
+same code what it would run.  Every pick -- 3-D, one-level 2-D, Inv2P -- is an instance's full name, so every template parameter a row
+pins (WPE of Fwd2S / Inv2S included) is compared, and every pick is looked up in the instance lists (csrc/ndwt_fused_list.h)."""
 import ctypes
 import os
 import shutil
@@ -16,8 +17,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 NUM_CUS = 256
 # template parameters of a pinned kernel that the pick does not name: none -- the pick is the instance's full name
 NOT_IN_PICK = ()
-# rows without a fused level-1 launch in either direction (1-D signals, the per-axis path on request, double with 18 taps)
-LEFT_OUT = ["1d-vec4", "1d-ragged", "1d-c64", "1d-db7-plain", "generic-path", "f64-db9-per-axis"]
+# rows without a fused level-1 launch in either direction (1-D signals, the per-axis path on request, double with 18 taps, complex128
+# images with 10)
+LEFT_OUT = ["1d-vec4", "1d-ragged", "1d-c64", "1d-db7-plain", "generic-path", "f64-db9-per-axis", "2d-c128-db5-per-axis"]
 # LevelRouteKind of csrc/ndwt_select.h
 FUSED3_DILATED, FUSED3, FUSED3_T, FUSED3_FOLD_T, FUSED2_DILATED, FUSED2, PER_AXIS = range(7)
 WHOLE_ARRAY, SLAB_OUTER, SLAB_Z = range(3)                      # SlabMode
@@ -54,6 +56,21 @@ def _fused3(shim, q):
 
 def _ints(v):
     return (ctypes.c_int * len(v))(*[int(x) for x in v])
+
+
+def _fused2(shim, q):
+    """fused2_select for the query [f64, inverse, vec4, Lp, ew, dil, n1, n2, variant_inv]: (kernel name, the trace parameters of the
+    instance it names, the raw answer by field)"""
+    r = (ctypes.c_int * 10)()
+    shim.sel_fused2(_ints(q), r)
+    f = dict(zip(("family", "inverse", "f64", "VEC4", "L", "EW", "WPE_or_PD", "PK", "waves", "listed"), r))
+    assert (bool(f["f64"]), bool(f["inverse"]), f["L"]) == (bool(q[0]), bool(q[1]), q[3]), (q, f)
+    T = "double" if f["f64"] else "float"
+    if f["family"] == 1:
+        assert f["inverse"] and f["VEC4"] and f["EW"] == 1, (q, f)
+        return "Inv2P", {"T": T, "L": f["L"], "PD": f["WPE_or_PD"], "PK": bool(f["PK"])}, f
+    assert (bool(f["VEC4"]), f["EW"]) == (bool(q[2]), q[4]), (q, f)
+    return "Inv2S" if f["inverse"] else "Fwd2S", {"T": T, "L": f["L"], "VEC4": bool(f["VEC4"]), "WPE": f["WPE_or_PD"], "EW": f["EW"]}, f
 
 
 def _plan(dims, lens, f64=False, cplx=False, generic=False, atrous=False, vf=0, vi=0):
@@ -102,12 +119,9 @@ def _picks(shim, row, inverse):
             out.append(("Inv2C" if inverse else "Fwd2C", p))
             left -= n
         if left > 0:
-            r = (ctypes.c_int * 5)()
-            shim.sel_fused2(_ints([f64, inverse, vec4, L, comp, 1, n1, dims[1], vi]), r)
-            if r[0] == 1:
-                out.append(("Inv2P", {"T": T, "L": L, "PD": r[1], "PK": bool(r[2])}))
-            else:
-                out.append(("Inv2S" if inverse else "Fwd2S", {"T": T, "L": L, "EW": comp, "VEC4": vec4}))
+            name, p, f = _fused2(shim, [f64, inverse, vec4, L, comp, 1, n1, dims[1], vi])
+            assert f["listed"], (row, name, p)
+            out.append((name, p))
     return out
 
 
@@ -190,10 +204,9 @@ def test_slab_rows_pick_their_pinned_kernels(shim):
                         assert f["listed"], (prm.id, name, p)
                         picks.append((name, p))
                 elif kind == FUSED2:
-                    r = (ctypes.c_int * 5)()
-                    shim.sel_fused2(_ints([f64, inverse, vec4, L, comp, 1, n1, local[1], max(row["inv"], 0)]), r)
-                    picks.append(("Inv2P", {"T": T, "L": L, "PD": r[1], "PK": bool(r[2])}) if r[0] == 1 else
-                                 ("Inv2S" if inverse else "Fwd2S", {"T": T, "L": L, "EW": comp, "VEC4": vec4}))
+                    name, p, f = _fused2(shim, [f64, inverse, vec4, L, comp, 1, n1, local[1], max(row["inv"], 0)])
+                    assert f["listed"], (prm.id, name, p)
+                    picks.append((name, p))
                 else:
                     assert kind == PER_AXIS and not any(fam in fused for fam, _ in specs), (prm.id, kind, specs)
                 both, _ = _route_dir(shim, plan, 1, -1, mode)      # ndwt_plan_slab_fast: slab_fused3 for both directions at once, tap stride 1
@@ -271,9 +284,52 @@ def test_every_inv2p_pick_names_an_instance(shim):
             for vec4 in (False, True):
                 for n1, n2 in ((256, 63), (256, 64), (4096, 5250), (4096, 5251)):
                     for vi in INV_NUMBERS:
-                        r = (ctypes.c_int * 5)()
-                        shim.sel_fused2(_ints([f64, True, vec4, L, 1, 1, n1, n2, vi]), r)
-                        if r[0] == 1:
-                            assert r[4], (f64, L, vec4, n1, n2, vi, list(r))
-                            seen.add((f64, L, r[1], r[2]))
+                        name, p, f = _fused2(shim, [f64, True, vec4, L, 1, 1, n1, n2, vi])
+                        if name == "Inv2P":
+                            assert f["listed"], (f64, L, vec4, n1, n2, vi, f)
+                            seen.add((f64, L, p["PD"], p["PK"]))
     assert len(seen) == 12 + 4                                  # every entry of the two lists is some pick
+
+
+# The route of a 2-D level by data kind, tap stride and tap length, written out (not computed from csrc/ndwt_fused_list.h): the longest
+# fused tap length per (double, complex, stride); everything longer, and every kind and stride not named, takes the per-axis passes.
+FUSED2_MAX_TAPS = {(False, False, 1): 20, (False, True, 1): 16, (True, False, 1): 16, (True, True, 1): 8,     # FUSED2
+                   (False, False, 2): 8, (True, False, 2): 8, (False, False, 4): 8}                             # FUSED2_DILATED
+N_FUSED2S = 136                                                 # Fwd2S / Inv2S kernels in the built library (nm -C libndwt_hip.so)
+
+
+def test_every_fused2_pick_names_an_instance(shim):
+    """level_route and fused2_select over the 2-D plans: both scalar types, real and interleaved complex, tap strides 1 / 2 / 4, tap lengths
+    2 .. 20, both directions, rows in whole groups of 4 scalars or not, every variant number of the synthesis, images on both sides of
+    n2 >= 64 and of the one-round budget.  The route is the literal table above; wherever it is fused, the pick is an entry of the
+    instance lists; and the Fwd2S / Inv2S picks are the whole table, every kernel the library was built with (a pick with another
+    WPE, or an instance no plan reaches, would break the count)"""
+    reached = set()
+    for f64 in (False, True):
+        for cplx in (False, True):
+            comp = 2 if cplx else 1
+            for stride in (1, 2, 4):
+                for L in range(2, 21, 2):
+                    want = PER_AXIS if L > FUSED2_MAX_TAPS.get((f64, cplx, stride), 0) else FUSED2 if stride == 1 else FUSED2_DILATED
+                    for n1, n2 in ((256, 63), (256, 64), (4096, 5250), (4096, 5251)):
+                        dims = [n1, n2 if stride == 1 else n2 // 4 * 4]      # (a dilated level: both dims divisible by the stride)
+                        for inverse in (False, True):
+                            for vi in (INV_NUMBERS if inverse else (0,)):
+                                plan = _plan(dims, [L, L], f64, cplx, False, stride > 1, 0, vi)
+                                kind, Lp = _route(shim, plan, stride, inverse)
+                                assert (kind, Lp) == (want, 0 if want == PER_AXIS else L), (f64, cplx, stride, L, dims, inverse, vi)
+                                if kind == PER_AXIS:
+                                    continue
+                                ew = comp if stride == 1 else stride
+                                for vec4 in (False, True):
+                                    name, p, f = _fused2(shim, [f64, inverse, vec4, L, ew, stride, n1 * comp, dims[1], vi])
+                                    assert f["listed"], (name, p, f)
+                                    assert name == "Inv2P" or name == ("Inv2S" if inverse else "Fwd2S")
+                                    if name != "Inv2P":
+                                        reached.add((inverse, f64, vec4, L, ew, p["WPE"]))
+    assert all(shim.sel_fused2s_listed(_ints(k)) for k in reached)
+    assert len(reached) == N_FUSED2S, len(reached)
+    # ... and no instance beside them: the lists over every name a pick could take
+    listed = sum(shim.sel_fused2s_listed(_ints([inverse, f64, vec4, L, ew, wpe])) for inverse in (0, 1) for f64 in (0, 1) for vec4 in (0, 1)
+                 for L in range(1, 25) for ew in (1, 2, 3, 4, 8) for wpe in (1, 2, 4, 8))
+    assert listed == N_FUSED2S, listed

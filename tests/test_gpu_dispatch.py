@@ -93,6 +93,8 @@ ROWS = [
       rec=["Inv3Y L=4 EW=1", "Inv3Y L=4 EW=2", "AxisMarch L=4 SYN=true", "axis_synthesis_kernel T=float"]),   # 18 % 4 != 0
     R("atrous-2d-l3", [72, 40], ["db4", "db2"], dil="atrous", level=3, dec=["Fwd2S L=8 EW=1", "Fwd2S L=8 EW=2", "Fwd2S L=8 EW=4"],
       rec=["Inv2S L=8 EW=1", "Inv2S L=8 EW=2", "Inv2S L=8 EW=4"]),
+    R("atrous-2d-f64", [72, 40], ["db4", "db2"], prec="double", dil="atrous", level=2,                # double: EW = 2 is its only dilated form
+      dec=["Fwd2S T=double L=8 EW=1 WPE=2", "Fwd2S T=double L=8 EW=2 WPE=2"], rec=["Inv2S T=double L=8 EW=1 WPE=2", "Inv2S T=double L=8 EW=2 WPE=2"]),
     # fp64 3-D
     R("f64-db3", [64, 40, 36], "db3", prec="double", dec=["Fwd3 T=double L=6 TY=16 NT=512"], rec=["Inv3S T=double L=6 TY=16 NT=512"]),
     R("f64-db4", [64, 40, 36], "db4", prec="double", level=2, dec=["Fwd3 T=double L=8 TY=16 NT=512"],
@@ -106,18 +108,25 @@ ROWS = [
       rec=["axis_synthesis_kernel T=double", "AxisMarch T=double L=18 SYN=true"]),
     # 2-D synthesis: Inv2P (depth 4, packed) for n2 >= 64 and tiles2 * ceil(n2 / 70) <= 1280, else Inv2S
     R("inv2p-n2-64", [256, 64], "db4", dec=["Fwd2S L=8 VEC4=true"], rec=["Inv2P L=8 PD=4 PK=true"], den=["Fwd2S L=8", "Inv2P L=8"]),
-    R("inv2s-n2-63", [256, 63], "db4", dec=["Fwd2S L=8 VEC4=true"], rec=["Inv2S L=8 VEC4=true"], den=["Fwd2S L=8", "Inv2S L=8"]),
+    R("inv2s-n2-63", [256, 63], "db4", dec=["Fwd2S L=8 VEC4=true"], rec=["Inv2S L=8 VEC4=true WPE=4"], den=["Fwd2S L=8", "Inv2S L=8"]),
     R("inv2p-budget-5250", [4096, 5250], "db4", dec=["Fwd2S L=8"], rec=["Inv2P L=8 PD=4 PK=true"]),   # 17 tiles * 75 chunks = 1275
     R("inv2s-budget-5251", [4096, 5251], "db4", dec=["Fwd2S L=8"], rec=["Inv2S L=8 VEC4=true"]),      # 17 * 76 = 1292
     R("2d-db3-short", [260, 96], "db3", dec=["Fwd2S L=6 VEC4=true"], rec=["Inv2P L=6 PD=2 PK=false"]),   # (packed depth 4: 4 / 8 / 12 taps)
-    R("2d-db7-long", [260, 96], "db7", dec=["Fwd2S L=14 VEC4=true"], rec=["Inv2S L=14 VEC4=true"], den=["Fwd2S L=14", "Inv2S L=14"]),
+    R("2d-db7-long", [260, 96], "db7", dec=["Fwd2S L=14 VEC4=true WPE=2"], rec=["Inv2S L=14 VEC4=true WPE=2"],
+      den=["Fwd2S L=14", "Inv2S L=14"]),                                                           # (14 .. 20 taps: the 256-register budget)
     R("2d-db10-long", [512, 70], "db10", dec=["Fwd2S L=20"], rec=["Inv2S L=20"]),
     R("2d-db9-ragged", [250, 65], "db9", dec=["Fwd2S L=18 VEC4=false"], rec=["Inv2S L=18 VEC4=false"]),
-    R("2d-c64-db5", [128, 70], "db5", cplx=True, dec=["Fwd2S L=10 EW=2"], rec=["Inv2S L=10 EW=2"], den=["Fwd2S L=10 EW=2", "Inv2S L=10 EW=2"]),
+    R("2d-c64-db5", [128, 70], "db5", cplx=True, dec=["Fwd2S L=10 EW=2 WPE=2"], rec=["Inv2S L=10 EW=2 WPE=2"],
+      den=["Fwd2S L=10 EW=2", "Inv2S L=10 EW=2"]),
     R("2d-c64-db8", [128, 70], "db8", cplx=True, dec=["Fwd2S L=16 EW=2"], rec=["Inv2S L=16 EW=2"]),
     R("2d-f64-db8", [260, 96], "db8", prec="double", dec=["Fwd2S T=double L=16"], rec=["Inv2S T=double L=16"]),
     R("2d-f64-db4", [260, 96], "db4", prec="double", dec=["Fwd2S T=double L=8"], rec=["Inv2P T=double L=8"],
       den=["Fwd2S T=double L=8", "Inv2P T=double L=8"]),
+    # complex128: fused up to 8 taps (one ragged wave tile of 128 scalars, 70 rows in chunks), the per-axis passes beyond
+    R("2d-c128-db4", [64, 70], "db4", prec="double", cplx=True, dec=["Fwd2S T=double L=8 EW=2 WPE=2"], rec=["Inv2S T=double L=8 EW=2 WPE=2"]),
+    R("2d-c128-db5-per-axis", [64, 70], "db5", prec="double", cplx=True,
+      dec=["AxisMarch T=double L=10 SYN=false", "AxisX T=double L=10 SYN=false EW=2"],
+      rec=["AxisMarch T=double L=10 SYN=true", "AxisX T=double L=10 SYN=true EW=2"]),
     # 2-D cascade: vol > 6 << 20 (= 2048 * 3072), level >= 2, n1 % 4 == 0, Lp <= 8 or 12
     R("cascade-off-6M", [2048, 3072], "db4", level=3, dec=["Fwd2S L=8"], rec=["Inv2P L=8 PD=4"]),
     R("cascade-db4-l3", [2048, 3073], "db4", level=3, dec=["Fwd2C L=8 NLEV=3"], rec=["Inv2C L=8 NLEV=3 PD=1"],
