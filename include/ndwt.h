@@ -72,6 +72,22 @@ int ndwt_level_from_bands(int ndim, int64_t bands); /* returns level >= 1, or -1
  * largest level dec/rec will be asked for (sizes the scratch); device = HIP device ordinal. */
 int ndwt_plan_create(ndwt_plan** plan, int ndim, const int64_t* dims, const char* const* wnames, int dtype,
                      int complexity, int pres_l2_norm, int dilation, int max_level, int device);
+/* Batched plan: `howmany` >= 1 signals of dims[0] elements transformed by one call (anything else: NDWT_ERR_INVALID_ARG).  ndim must be 1 in
+ * this version; 2 .. 4 is NDWT_ERR_UNSUPPORTED.  Both are checked before any device call.
+ * Layout: signal k at x + k * n elements; every band is a contiguous [howmany][n] block, band b at b * bs with bs = howmany * n (packed)
+ * or the caller's band_pitch >= howmany * n (ndwt_band_pitch: howmany * n plus the usual skew) -- [n, howmany, bands] in MATLAB terms.
+ * Band order and normalisation are those of a 1-D plan.
+ * At the reference's dilation two to four levels run in ONE launch wherever the rows allow it (n * comp a multiple of 4 and >= 8 taps'
+ * worth, 2 .. 8 taps, 16- / 32-byte aligned pointers): the approximations between them stay in registers, and the result equals one
+ * launch per level bit for bit.  ndwt_plan_set_variant(plan, 9, 9, ...) switches that off per direction.  Everything else (a-trous
+ * levels, longer filters, odd n) runs the per-axis kernels over all signals at once.
+ * Served: ndwt_dec, ndwt_rec, ndwt_dec_pitched, ndwt_rec_pitched, ndwt_shrink, ndwt_shrink_pitched, ndwt_denoise (dec, the shrink pass,
+ * rec), ndwt_dec_split / ndwt_rec_split, ndwt_plan_set_*, ndwt_plan_describe, profiling and the trace.
+ * Refused with NDWT_ERR_UNSUPPORTED (they size a buffer by one array's dimensions): the host-pointer forms ndwt_dec_host, ndwt_rec_host,
+ * ndwt_denoise_host, ndwt_dec_split_host, ndwt_rec_split_host; every ndwt_coef_* that takes a plan; the slab entry points
+ * ndwt_analysis_level_slab*, ndwt_synthesis_level_slab*; ndwt_slab_segments and ndwt_slab_segments_strided. */
+int ndwt_plan_create_many(ndwt_plan** plan, int ndim, const int64_t* dims, int64_t howmany, const char* const* wnames,
+                          int dtype, int complexity, int pres_l2_norm, int dilation, int max_level, int device);
 /* Plan for ONE SLAB of a volume sharded on its outermost axis (the *_slab entry points below): dims describe the local slab,
  * global_outer is the length of the sharded axis of the whole volume.  The reference's length check (nd_dwt_3D.m:277-286:
  * filter <= axis) applies to the WHOLE axis: a slab may be thinner than the filter (cfg5: 32 frames over 8 ranks = 4, db4 = 8

@@ -33,8 +33,10 @@ class Plan:
     """Thin RAII wrapper over ndwt_plan (include/ndwt.h)."""
 
     def __init__(self, dims, wnames, dtype, complex_interleaved=False, pres_l2_norm=False, dilation="reference",
-                 max_level=1, device=0, global_outer=None, shard_axis=None):
-        """global_outer: length of the sharded axis of the WHOLE volume when `dims` describe one slab of it (multi-GPU):
+                 max_level=1, device=0, global_outer=None, shard_axis=None, howmany=None):
+        """howmany: None = one array (ndwt_plan_create); a number = a batched plan of that many 1-D signals (ndwt_plan_create_many):
+        signal k at k * dims[0] elements, every band a contiguous (howmany, n) block.
+        global_outer: length of the sharded axis of the WHOLE volume when `dims` describe one slab of it (multi-GPU):
         the reference's filter-length check then applies to the whole axis, a slab may be thinner than the filter.
         shard_axis: the sharded axis, counted from the fastest (0 = x); None = the outermost (ndwt_plan_create_slab), 2 of a 4-D
         volume = z-slabs (ndwt_plan_create_slab_axis)"""
@@ -51,7 +53,13 @@ class Plan:
         dil = {"reference": L.NDWT_DILATION_REFERENCE, "atrous": L.NDWT_DILATION_ATROUS}[dilation]
         cplx = L.NDWT_COMPLEX_INTERLEAVED if complex_interleaved else L.NDWT_REAL
         self.shard_axis = self.ndim - 1 if shard_axis is None else int(shard_axis)
-        if shard_axis is not None:
+        self.howmany = None if howmany is None else int(howmany)
+        if howmany is not None:
+            if shard_axis is not None or global_outer is not None:
+                raise ValueError("a batched plan is not a slab plan")
+            L.check(L.lib().ndwt_plan_create_many(ctypes.byref(self._h), self.ndim, dims_c, self.howmany, names_c, dt, cplx,
+                                                  int(bool(pres_l2_norm)), dil, self.max_level, self.device))
+        elif shard_axis is not None:
             L.check(L.lib().ndwt_plan_create_slab_axis(ctypes.byref(self._h), self.ndim, dims_c, self.shard_axis,
                                                        int(global_outer if global_outer is not None else self.dims[self.shard_axis]),
                                                        names_c, dt, cplx, int(bool(pres_l2_norm)), dil, self.max_level, self.device))
@@ -416,6 +424,7 @@ class _NdDwtBase:
         self.device = None
         self.devices = None
         self.band_pitch = "packed"
+        self.batch = None
         # name/value pairs as in MATLAB (nd_dwt_3D.m:105-120); keyword arguments are accepted too
         if len(varargin) % 2:
             raise ValueError("Optional inputs must come in pairs")
@@ -434,6 +443,8 @@ class _NdDwtBase:
                 self.device = val
             elif k == "band_pitch":                # 'packed' (reference layout) | 'auto' | elements between bands of dec()'s result
                 self.band_pitch = val if isinstance(val, str) else int(val)
+            elif k == "batch":                     # nd_dwt_1D only: this many signals per call, x = [n, batch] (column k = signal k)
+                self.batch = int(val)
             elif k == "devices":                   # shard the outermost axis over these devices (host arrays, one process)
                 self.devices = [int(v) for v in np.atleast_1d(val)]
             else:   # unknown keys only warn (nd_dwt_3D.m:118)
@@ -457,6 +468,15 @@ class _NdDwtBase:
             raise ValueError("'band_pitch' lays out device tensors: use compute='hip'")
         if self.devices is not None and (not self._offload or d < 2):
             raise ValueError("'devices' shards host arrays of 2-D .. 4-D transforms: use compute='hip_off'")
+        if self.batch is not None:
+            if d != 1:
+                raise ValueError("'batch' is an option of nd_dwt_1D: the other classes transform one array per call")
+            if self.devices is not None:
+                raise ValueError("'batch' and 'devices' do not combine: a batched plan lives on one device")
+            if self.batch < 1:
+                raise ValueError("'batch' must be a number of signals >= 1")
+        # the shape of x in MATLAB terms: `sizes`, for a batched 1-D object [n, batch]
+        self._shape = sizes + ([self.batch] if self.batch is not None else [])
         # get_filters (nd_dwt_3D.m:263-342): per-axis taps instead of N-D FFT-domain kernels
         self.f_dec = [L.wave_filters(w) for w in self.wname[:d]]
         self.f_size = {f"s{a + 1}": len(self.f_dec[a][0]) for a in range(d)}
@@ -501,7 +521,7 @@ class _NdDwtBase:
             if p is not None:
                 torch.cuda.synchronize(idx)                           # the plan being replaced may still be running
             p = Plan(self.sizes, self.wname[: self.NDIM], real_dt, is_complex, self.pres_l2_norm, self.dilation,
-                     max_level=max(level, 3), device=idx)
+                     max_level=max(level, 3), device=idx, howmany=self.batch)
             p._last_stream = None
             self._plans[key] = p
         cur = torch.cuda.current_stream(torch.device("cuda", idx))
@@ -541,8 +561,8 @@ class _NdDwtBase:
             raise ValueError("level must be >= 1")
         like_numpy = isinstance(x, np.ndarray)
         x = self._prep_dec_input(x)
-        if list(x.shape) != self.sizes:
-            raise ValueError(f"input size {list(x.shape)} does not match the object's sizes {self.sizes}")
+        if list(x.shape) != self._shape:
+            raise ValueError(f"input size {list(x.shape)} does not match the object's sizes {self._shape}")
         if self.devices is not None:
             return self._multi(x, level, None)
         dev = self._dev(x if isinstance(x, torch.Tensor) else None)
@@ -587,8 +607,8 @@ class _NdDwtBase:
     # -- nd_dwt_3D.m:202-256 --
     def rec(self, y):
         like_numpy = isinstance(y, np.ndarray)
-        if y.ndim != self.NDIM + 1 or list(y.shape[:-1]) != self.sizes:
-            raise ValueError(f"coefficient array must have shape {self.sizes + ['bands']}")
+        if y.ndim != len(self._shape) + 1 or list(y.shape[:-1]) != self._shape:
+            raise ValueError(f"coefficient array must have shape {self._shape + ['bands']}")
         level = self._level_from_bands(int(y.shape[-1]))
         if num_bands(self.NDIM, level) != int(y.shape[-1]):
             raise ValueError(f"{int(y.shape[-1])} bands is not a valid {self.NDIM}-D coefficient count")
@@ -609,8 +629,8 @@ class _NdDwtBase:
         if mode not in ("soft", "hard"):
             raise ValueError("mode must be 'soft' or 'hard'")
         like_numpy = isinstance(y, np.ndarray)
-        if y.ndim != self.NDIM + 1 or list(y.shape[:-1]) != self.sizes:
-            raise ValueError(f"coefficient array must have shape {self.sizes + ['bands']}")
+        if y.ndim != len(self._shape) + 1 or list(y.shape[:-1]) != self._shape:
+            raise ValueError(f"coefficient array must have shape {self._shape + ['bands']}")
         level = self._level_from_bands(int(y.shape[-1]))
         dev = self._dev(y if isinstance(y, torch.Tensor) else None)
         yk, pitch = self._coef_kernel_order(y, dev)
@@ -636,8 +656,8 @@ class _NdDwtBase:
             raise ValueError("level must be >= 1")
         like_numpy = isinstance(x, np.ndarray)
         x = self._prep_dec_input(x)
-        if list(x.shape) != self.sizes:
-            raise ValueError(f"input size {list(x.shape)} does not match the object's sizes {self.sizes}")
+        if list(x.shape) != self._shape:
+            raise ValueError(f"input size {list(x.shape)} does not match the object's sizes {self._shape}")
         dev = self._dev(x if isinstance(x, torch.Tensor) else None)
         xk = self._to_device_kernel_order(x, dev, self.NDIM)
         plan = self._plan(xk.is_complex(), level, dev)
@@ -668,7 +688,9 @@ class _NdDwtBase:
 
 
 class nd_dwt_1D(_NdDwtBase):
-    """Functions/nd_dwt_1D.m -- 1-D signal of length n; coefficients [n, 1+level]."""
+    """Functions/nd_dwt_1D.m -- 1-D signal of length n; coefficients [n, 1+level].
+    nd_dwt_1D(wname, n, 'batch', K): K signals per call -- dec takes [n, K] (column k = signal k) and returns [n, K, 1+level]; rec, shrink
+    and denoise likewise.  In memory that is (K, n) contiguous: a device tensor laid out so is used where it lies."""
     NDIM = 1
 
     def _check_sizes(self, sizes):
@@ -684,8 +706,8 @@ class nd_dwt_1D(_NdDwtBase):
         return int(np.ceil(n - 1))                                        # nd_dwt_1D.m:213
 
     def _prep_dec_input(self, x):
-        # row vectors are transposed (nd_dwt_1D.m:151-153); accept [n], [n,1] and [1,n]
-        if x.ndim == 2 and 1 in x.shape:
+        # row vectors are transposed (nd_dwt_1D.m:151-153); accept [n], [n,1] and [1,n]; a batched object takes [n, batch] as it is
+        if self.batch is None and x.ndim == 2 and 1 in x.shape:
             x = x.reshape(-1)
         return x
 

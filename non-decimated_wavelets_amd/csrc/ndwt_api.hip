@@ -104,7 +104,8 @@ struct ndwt_plan {
     int dtype, complexity, l2, dilation, max_level, device, path;
     size_t esize;                      // bytes per scalar
     long long comp;                    // scalars per element (2 for interleaved complex)
-    long long vol;                     // scalars per band
+    long long vol;                     // scalars per band (a batched plan: of all its signals)
+    long long howmany;                 // ndwt_plan_create_many: signals of a batched 1-D plan, signal k at k * dims[0] elements; 0 = not batched
     void* approx[2];                   // approximation ping-pong between levels: approx_base[i] + kApproxSkew bytes
     void* approx_base[2];
     void* tmp;                         // temporaries of the per-axis path / 4-D split
@@ -203,7 +204,7 @@ static int axis_pass(const ndwt_plan* p, bool synthesis, int axis, const long lo
     AxisArgs<T> a;
     a.inner = p->comp;
     for (int k = 0; k < axis; ++k) a.inner *= dims_cur[k];
-    a.outer = 1;
+    a.outer = p->howmany > 0 ? p->howmany : 1;            // (a batched 1-D plan: its signals are the rows)
     for (int k = axis + 1; k < p->ndim; ++k) a.outer *= dims_cur[k];
     a.n = dims_cur[axis];
     a.stride = stride;
@@ -705,12 +706,50 @@ template <typename T> static int cascade2_run(ndwt_plan* p, int Lp, int nlev, co
     return cascade2_launch(p, a, false, cascade2_tile_width(k), nlev * (Lp - 1), 8, s, [&](const void* td) { return launch_cascade2(k, a, td, s); });
 }
 
+// ---- two to four levels of the signals of a batched 1-D plan in one launch (Fwd1C / Inv1C, ndwt_device_1d.h; when: cascade1_levels).
+// in / out as Fused1CArgs documents them.  Returns 0, or -1: not this data (a pointer off the 16- / 32-byte groups), no instance, or a
+// launch the kernel's tiling cannot express -- the caller takes one launch per level
+template <typename T> static int cascade1_run(ndwt_plan* p, bool inverse, int L, int nlev, const T* const* in, T* const* out, hipStream_t s) {
+    Fused1CArgs<T> a;
+    memset(&a, 0, sizeof a);
+    bool aligned = true;
+    for (int b = 0; b < (inverse ? 1 + nlev : 1); ++b) { a.in[b] = in[b]; aligned = aligned && aligned_vec4<T>(in[b]); }
+    for (int b = 0; b < (inverse ? 1 : 1 + nlev); ++b) { a.out[b] = out[b]; aligned = aligned && aligned_vec4<T>(out[b]); }
+    if (!aligned) return -1;
+    const Cascade1Instance k = {inverse, sizeof(T) == 8, (int)p->comp, L, nlev};
+    const int WX = cascade1_tile_width(k);
+    a.row = p->dims[0] * p->comp;
+    a.outer = p->howmany;
+    a.nseg = (a.row + WX - 1) / WX;
+    const void* td = p->taps_dev[inverse ? 1 : 0];
+    if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
+    prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
+    const int rc = launch_cascade1(k, a, td, s);
+    prof_end(p, s, rc);
+    if (rc > 0) return fail(NDWT_ERR_HIP, "cascaded 1-D %s launch failed: %s", inverse ? "synthesis" : "analysis", hipGetErrorString((hipError_t)rc));
+    return rc < 0 ? -1 : 0;
+}
+
 template <typename T> static int dec_impl(ndwt_plan* p, const T* x, T* y, long long bs, int level, hipStream_t s) {
     const int nb = 1 << p->ndim;
     const T* cur = x;
     int lev = 1, pp = 0;                                  // pp: the scratch volume the next launch writes (they alternate launch by launch: a
     {                                                     // launch never writes the approximation it reads)
         const SelPlan sp = sel(p);
+        int L1 = 0;
+        while (const int n = cascade1_levels(sp, p->howmany, false, level - lev + 1, &L1)) {   // a batched 1-D plan: levels lev .. lev + n - 1
+            const int last = lev + n - 1;
+            const T* in[5] = {cur};
+            T* out[5];
+            out[0] = (last == level) ? y : (T*)p->approx[pp];
+            for (int l = 0; l < n; ++l) out[1 + l] = y + (long long)(1 + (level - (lev + l))) * bs;
+            const int rc = cascade1_run<T>(p, false, L1, n, in, out, s);
+            if (rc == -1) break;                          // not this data: one launch per level from here on
+            if (rc) return rc;
+            cur = out[0];
+            pp ^= 1;
+            lev = last + 1;
+        }
         int Lp = 0;
         while (const int n = cascade2_levels(sp, false, level - lev + 1, &Lp)) {   // levels lev .. lev + n - 1 in one launch
             const int last = lev + n - 1;
@@ -764,6 +803,20 @@ template <typename T> static int rec_impl(ndwt_plan* p, const T* y, long long bs
     int lev = level, pp = 0;                              // coarsest level still to be synthesised; pp: the scratch volume the next launch writes
     {
         const SelPlan sp = sel(p);
+        int L1 = 0;
+        while (const int n = cascade1_levels(sp, p->howmany, true, lev, &L1)) {   // a batched 1-D plan: levels lev, lev - 1, .. lev - n + 1
+            const T* in[5];
+            in[0] = prev;
+            for (int c = 0; c < n; ++c) in[1 + c] = y + (long long)(1 + (level - (lev - c))) * bs;
+            const int low = lev - n + 1;
+            T* dst[5] = {(low == 1) ? x : (T*)p->approx[pp]};
+            const int rc = cascade1_run<T>(p, true, L1, n, in, dst, s);
+            if (rc == -1) break;
+            if (rc) return rc;
+            prev = dst[0];
+            pp ^= 1;
+            lev = low - 1;
+        }
         int Lp = 0;
         while (const int n = cascade2_levels(sp, true, lev, &Lp)) {   // levels lev, lev - 1, .. lev - n + 1 in one launch
             const T* in[10];
@@ -792,6 +845,14 @@ template <typename T> static int rec_impl(ndwt_plan* p, const T* y, long long bs
     return NDWT_OK;
 }
 
+// What sizes a host buffer, a handle or a slab by the dimensions of ONE array does not know the signals of a batched plan
+// (ndwt_plan_create_many): those entry points refuse it (include/ndwt.h lists them)
+static int refuse_batched(const ndwt_plan* p, const char* what) {
+    if (p && p->howmany > 0)
+        return fail(NDWT_ERR_UNSUPPORTED, "%s is not available on a batched plan (ndwt_plan_create_many): use the device-pointer entry points", what);
+    return NDWT_OK;
+}
+
 static int check_level(const ndwt_plan* p, int level) {
     if (!p) return fail(NDWT_ERR_INVALID_ARG, "null plan");
     if (level < 1 || level > p->max_level)
@@ -804,6 +865,7 @@ static int check_level(const ndwt_plan* p, int level) {
 // fused 3-D slab forms that avoid haloed copies (multi-GPU fast path)
 static int slab_fast_ok(const ndwt_plan* p, int stride, int* Lp) {
     if (!p) return fail(NDWT_ERR_INVALID_ARG, "null plan");
+    if (const int rc = refuse_batched(p, "a slab entry point")) return rc;
     if (p->ndim != 3 || !(*Lp = slab_fused3(sel(p), stride, -1, kSlabOuter)))
         return fail(NDWT_ERR_UNSUPPORTED, "split/extended slab entry points need a fused 3-D plan whose outer-axis filter is the longest");
     return NDWT_OK;
@@ -1105,7 +1167,7 @@ int ndwt_level_from_bands(int ndim, int64_t bands) {
 static bool den3_eligible(const ndwt_plan* p, int* Lp_out);
 static int den3_taps(ndwt_plan* p, int Lp);
 static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, long long global_outer, const char* const* wnames, int dtype,
-                            int complexity, int pres_l2_norm, int dilation, int max_level, int device, int shard = -1) {
+                            int complexity, int pres_l2_norm, int dilation, int max_level, int device, int shard = -1, long long howmany = 0) {
     if (!plan) return fail(NDWT_ERR_INVALID_ARG, "null plan pointer");
     *plan = nullptr;
     if (ndim < 1 || ndim > NDWT_MAX_DIMS) return fail(NDWT_ERR_INVALID_ARG, "ndim must be 1..4");
@@ -1133,7 +1195,8 @@ static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, lon
     p->shard = shard >= 0 ? shard : ndim - 1;
     p->fp64_fused = 1;   // measured: 256^3 fp64 db4 L3 2.5 ms fused (LDS analysis + lane-shift synthesis) vs 4.1 ms per-axis
     static const char* ordn[4] = {"First", "Second", "Third", "Fourth"};
-    p->vol = p->comp;
+    p->howmany = howmany;
+    p->vol = p->comp * (howmany > 0 ? howmany : 1);
     for (int a = 0; a < ndim; ++a) {
         if (dims[a] < 1) { delete p->prof; delete p->ev_pool; delete p; return fail(NDWT_ERR_INVALID_ARG, "dims[%d] must be >= 1", a); }
         const int K = parse_wavelet(wnames[a]);
@@ -1176,7 +1239,10 @@ static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, lon
             return fail(NDWT_ERR_ALLOC, "hipMalloc of the approximation scratch failed: %s", hipGetErrorString(e));
         }
     }
-    if (const int Lp = level_route(sel(p), 1, 0, kWholeArray).Lp) {   // a plan with fused levels (the analysis side admits the most tap lengths)
+    int Lp = level_route(sel(p), 1, 0, kWholeArray).Lp;
+    // a batched 1-D plan whose levels can cascade (Fwd1C / Inv1C read Taps3<T, L>, axis 0): the table of its own tap length
+    if (!Lp && howmany > 0 && p->filt[0].len <= 8 && (cascade1_instantiated({false, dtype == NDWT_F64, (int)p->comp, p->filt[0].len, 2}))) Lp = p->filt[0].len;
+    if (Lp) {   // a plan with fused levels (the analysis side admits the most tap lengths)
         for (int inv = 0; inv < 2; ++inv) {
             FusedTapsD t = fused_taps(p, Lp, inv != 0);
             // synthesis table: Taps3Y = Taps3 followed by the x tap pairs (lo[0][k], lo[0][k-1]), k = 0..Lp, of the pair-packed kernel
@@ -1228,6 +1294,15 @@ static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, lon
 int ndwt_plan_create(ndwt_plan** plan, int ndim, const int64_t* dims, const char* const* wnames, int dtype, int complexity,
                      int pres_l2_norm, int dilation, int max_level, int device) {
     return plan_create_impl(plan, ndim, dims, -1, wnames, dtype, complexity, pres_l2_norm, dilation, max_level, device);
+}
+
+int ndwt_plan_create_many(ndwt_plan** plan, int ndim, const int64_t* dims, int64_t howmany, const char* const* wnames, int dtype,
+                          int complexity, int pres_l2_norm, int dilation, int max_level, int device) {
+    if (plan) *plan = nullptr;
+    if (howmany < 1) return fail(NDWT_ERR_INVALID_ARG, "howmany must be >= 1 (got %lld)", (long long)howmany);
+    if (ndim >= 2 && ndim <= NDWT_MAX_DIMS)
+        return fail(NDWT_ERR_UNSUPPORTED, "batched plans are 1-D in this version: ndim = %d is not supported (loop over ndwt_plan_create plans)", ndim);
+    return plan_create_impl(plan, ndim, dims, -1, wnames, dtype, complexity, pres_l2_norm, dilation, max_level, device, -1, howmany);
 }
 
 int ndwt_plan_create_slab(ndwt_plan** plan, int ndim, const int64_t* dims_local, int64_t global_outer, const char* const* wnames,
@@ -1351,6 +1426,8 @@ int ndwt_plan_describe(const ndwt_plan* p, char* buf, int buflen) {
     if (f3a && f3s) s = p->ndim == 3 ? "fused3d" : "axis+fused3d";
     else if (f3a) s = p->ndim == 3 ? "fused3d analysis, axis synthesis" : "axis+fused3d analysis, axis synthesis";
     else if (ra == kRouteFused2) s = "fused2d";
+    int L1 = 0;
+    if (p->howmany > 0) s = cascade1_levels(sel(p), p->howmany, false, 2, &L1) ? "batched1d cascade" : "batched1d axis";
     snprintf(buf, (size_t)buflen, "%s", s);
     return NDWT_OK;
 }
@@ -1414,7 +1491,9 @@ static int ensure_stage(ndwt_plan* p, int which, size_t bytes) {
 }
 
 static int host_roundtrip(ndwt_plan* p, bool inverse, const void* src, void* dst, int level) {
-    int rc = check_level(p, level);
+    int rc = refuse_batched(p, "a host-pointer transform");
+    if (rc) return rc;
+    rc = check_level(p, level);
     if (rc) return rc;
     if (!src || !dst) return fail(NDWT_ERR_INVALID_ARG, "null data pointer");
     HIP_TRY(hipSetDevice(p->device));
@@ -1457,13 +1536,16 @@ struct ndwt_coef {
 };
 
 static int coef_check(const ndwt_plan* p, const ndwt_coef* c) {
+    if (const int rc = refuse_batched(p, "a coefficient handle")) return rc;
     if (!p || !c) return fail(NDWT_ERR_INVALID_ARG, "null plan / coefficient handle");
     if (c->plan != p) return fail(NDWT_ERR_INVALID_ARG, "this coefficient handle belongs to another plan");
     return NDWT_OK;
 }
 
 int ndwt_coef_create(ndwt_plan* p, int level, ndwt_coef** out) {
-    int rc = check_level(p, level);
+    int rc = refuse_batched(p, "a coefficient handle");
+    if (rc) return rc;
+    rc = check_level(p, level);
     if (rc) return rc;
     if (!out) return fail(NDWT_ERR_INVALID_ARG, "null output pointer");
     HIP_TRY(hipSetDevice(p->device));
@@ -1504,7 +1586,9 @@ int ndwt_coef_info(const ndwt_coef* c, int* level, int64_t* bands, int64_t* band
 
 // x (host) -> coefficients that STAY on the device: only the signal crosses PCIe (0.5 GB instead of 12.3 GB at 512^3, 3 levels)
 int ndwt_coef_dec_host(ndwt_plan* p, const void* x_host, int level, ndwt_coef** coef) {
-    int rc = check_level(p, level);
+    int rc = refuse_batched(p, "a coefficient handle");
+    if (rc) return rc;
+    rc = check_level(p, level);
     if (rc) return rc;
     if (!x_host || !coef) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
     HIP_TRY(hipSetDevice(p->device));
@@ -1564,7 +1648,9 @@ int ndwt_coef_get_host(ndwt_plan* p, const ndwt_coef* c, void* y_host) {
 }
 
 int ndwt_coef_put_host(ndwt_plan* p, int level, const void* y_host, ndwt_coef** coef) {
-    int rc = check_level(p, level);
+    int rc = refuse_batched(p, "a coefficient handle");
+    if (rc) return rc;
+    rc = check_level(p, level);
     if (rc) return rc;
     if (!y_host || !coef) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
     HIP_TRY(hipSetDevice(p->device));
@@ -1769,7 +1855,9 @@ int ndwt_denoise(ndwt_plan* p, const void* x, void* out, int level, double thres
 }
 
 int ndwt_denoise_host(ndwt_plan* p, const void* x, void* out, int level, double threshold, int mode) {
-    int rc = shrink_check(p, level, threshold, mode);
+    int rc = refuse_batched(p, "a host-pointer transform");
+    if (rc) return rc;
+    rc = shrink_check(p, level, threshold, mode);
     if (rc) return rc;
     if (!x || !out) return fail(NDWT_ERR_INVALID_ARG, "null data pointer");
     HIP_TRY(hipSetDevice(p->device));
@@ -1846,6 +1934,7 @@ int ndwt_slab_halo(const ndwt_plan* p, int stride, int64_t* ab, int64_t* aa, int
 }
 
 int ndwt_analysis_level_slab(ndwt_plan* p, const void* in, void* const* out, int stride, void* stream) {
+    if (const int rb = refuse_batched(p, "a slab entry point")) return rb;
     if (!p || !in || !out || stride < 1) return fail(NDWT_ERR_INVALID_ARG, "bad arguments");
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1854,6 +1943,7 @@ int ndwt_analysis_level_slab(ndwt_plan* p, const void* in, void* const* out, int
 }
 
 int ndwt_synthesis_level_slab(ndwt_plan* p, const void* const* in, void* out, int stride, void* stream) {
+    if (const int rb = refuse_batched(p, "a slab entry point")) return rb;
     if (!p || !in || !out || stride < 1) return fail(NDWT_ERR_INVALID_ARG, "bad arguments");
     HIP_TRY(hipSetDevice(p->device));
     hipStream_t s = (hipStream_t)stream;
@@ -1968,6 +2058,7 @@ int ndwt_plan_set_stamps(ndwt_plan* p, void* dev_buffer) {
 const char* ndwt_last_error(void) { return g_last_error.c_str(); }
 int ndwt_slab_segments(ndwt_plan* p, int op, int nseg, void* const* dst, const void* const* src, const int64_t* count, void* stream) {
     if (!p) return fail(NDWT_ERR_INVALID_ARG, "null plan");
+    if (const int rb = refuse_batched(p, "ndwt_slab_segments")) return rb;
     if (op != NDWT_SEG_COPY && op != NDWT_SEG_ADD) return fail(NDWT_ERR_INVALID_ARG, "op must be NDWT_SEG_COPY or NDWT_SEG_ADD");
     if (nseg < 0 || nseg > NDWT_MAX_SEGMENTS) return fail(NDWT_ERR_INVALID_ARG, "at most %d runs per call", NDWT_MAX_SEGMENTS);
     if (nseg == 0) return NDWT_OK;
@@ -1984,6 +2075,7 @@ int ndwt_slab_segments(ndwt_plan* p, int op, int nseg, void* const* dst, const v
 int ndwt_slab_segments_strided(ndwt_plan* p, int op, int nseg, void* const* dst, const void* const* src, const int64_t* count, int64_t nrep,
                                const int64_t* dst_stride, const int64_t* src_stride, void* stream) {
     if (!p) return fail(NDWT_ERR_INVALID_ARG, "null plan");
+    if (const int rb = refuse_batched(p, "ndwt_slab_segments")) return rb;
     if (op != NDWT_SEG_COPY && op != NDWT_SEG_ADD) return fail(NDWT_ERR_INVALID_ARG, "op must be NDWT_SEG_COPY or NDWT_SEG_ADD");
     if (nseg < 0 || nseg > NDWT_MAX_SEGMENTS) return fail(NDWT_ERR_INVALID_ARG, "at most %d runs per call", NDWT_MAX_SEGMENTS);
     if (nrep < 0) return fail(NDWT_ERR_INVALID_ARG, "negative repetition count");

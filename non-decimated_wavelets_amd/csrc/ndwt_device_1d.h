@@ -1,0 +1,157 @@
+// ndwt_device_1d.h -- several levels of many 1-D signals in one launch (Fwd1C / Inv1C): AxisX (ndwt_device.h) grown by a level loop.
+//
+// At the reference's dilation every level applies the same filter pair to the approximation of the level before, so the 4 scalars of
+// level l's approximation a lane holds ARE the input of level l + 1: they stay in the lane, and only the detail band of every level
+// (analysis) or of every level's input (synthesis) goes through memory -- (NLEV + 2) signal volumes instead of 3 NLEV.  Rows are
+// [outer][row] scalars, row = n * EW (EW = 2: interleaved complex, the taps step over the pairs) in whole groups of 4, periodic.
+//
+// One wave per (row, segment) item, as AxisX: lane l holds the 4 scalars at xg = seg0 + 4 (l - NLEV GL) of the row (wrapped), its
+// neighbours come from the adjacent lanes by DPP wave shifts.  Every level costs GL lanes on the left and GR on the right, so level k
+// (1 = first computed) is valid in lanes [k GL, 64 - k GR); a wave stores the lanes valid at every level, rounded down to whole
+// 128-byte lines (the rule of Fwd2C), and every band from that same window.  The FMAs of a level are those of AxisX::compute in the
+// same order, so the result equals NLEV launches of AxisX<T, L, SYN, EW, true> bit for bit.
+//
+// Written like the fused kernels: per-lane stages driven through an executor, so the same source runs under the host emulator.
+#pragma once
+#include "ndwt_device.h"
+
+namespace ndwt {
+
+// A level's sums are written as explicit fused multiply-adds: AxisX's `acc += tap * v` compiles to FMA chains in every instance, and so
+// must these for the bits to agree -- left to the compiler, the SLP vectorizer splits some chains of the longer bodies here into a
+// packed multiply and separate adds (two roundings instead of one).
+NDWT_DEV float fma1(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+NDWT_DEV double fma1(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+template <typename T> struct Fused1CArgs {
+    const T* in[5];        // analysis: in[0] the signals; synthesis: [0] the approximation of the coarsest level, [1 + c] the detail band of
+                           // cascade level c (0 = coarsest: the one synthesised first)
+    T* out[5];             // analysis: [0] the approximation of the last level, [1 + l] the detail band of cascade level l (0 = first /
+                           // finest); synthesis: out[0]
+    long long row;         // scalars per row = n * EW, a multiple of 4
+    long long outer;       // rows (signals)
+    long long nseg;        // wave segments per row: ceil(row / WX)
+};
+
+// what both directions share: the geometry of a wave and the (row, segment) item of a lane
+template <typename T, int L_, int NLEV_, int EW_, bool SYN> struct Cascade1Geom {
+    static constexpr int L = L_, NLEV = NLEV_, EW = EW_, NT = 256;
+    static constexpr int LH = SYN ? L / 2 : L / 2 - 1, RH = SYN ? L / 2 - 1 : L / 2;
+    static constexpr int GL = (LH * EW + 3) / 4, GR = (RH * EW + 3) / 4;
+    static constexpr int LPL = 32 / (int)sizeof(T);      // lanes to the 128-byte line (a lane stores 4 scalars)
+    static constexpr int WX = 4 * ((64 - NLEV * (GL + GR)) / LPL * LPL);   // output scalars per wave segment
+    static_assert(NLEV >= 2 && NLEV <= 4, "two to four levels per launch");
+    static_assert(WX > 0, "no lane is valid at every level");
+    // fills the lane's place in its row; returns the offset of its 4 scalars (wrapped) from the band pointers
+    template <class State> static NDWT_DEV long long place(State& st, const Fused1CArgs<T>& a, int bid, int tid) {
+        const long long item = (long long)bid * (NT / 64) + tid / 64;           // one wave per (row, segment)
+        const long long nitems = a.outer * a.nseg;
+        st.valid = item < nitems;
+        const long long it = st.valid ? item : nitems - 1;
+        const long long o = it / a.nseg, sg = it % a.nseg;
+        st.base = o * a.row;
+        st.xg = (int)(sg * WX) + 4 * (tid % 64 - NLEV * GL);
+        return st.base + modn64(st.xg, a.row);            // (rows are whole groups of 4: a group never straddles the wrap)
+    }
+    // this lane stores: inside the window valid at every level, and inside the row (the last segment may reach past its end)
+    template <class State> static NDWT_DEV bool stores(const State& st, const Fused1CArgs<T>& a, int tid) {
+        const int lane = tid % 64;
+        return st.valid && lane >= NLEV * GL && lane < NLEV * GL + WX / 4 && st.xg < a.row;
+    }
+};
+
+template <typename T, int L_, int NLEV_, int EW_ = 1, int WPE_ = 4> struct Fwd1C {
+    typedef Cascade1Geom<T, L_, NLEV_, EW_, false> G;
+    static constexpr int L = L_, NLEV = NLEV_, EW = EW_, NT = G::NT, WPE = WPE_;
+    static constexpr int LH = G::LH, RH = G::RH, GL = G::GL, GR = G::GR, WX = G::WX;
+    typedef typename VecT<T>::v4 v4;
+    typedef Taps3<T, L> Taps;                            // axis 0 is used
+    typedef Fused1CArgs<T> Args;
+    struct Shared { int unused; };
+    struct State {
+        v4 cur;            // this lane's 4 scalars of the level's input: the raw row, then the approximations
+        v4 nxt;            // the approximation being computed (the neighbours still read cur)
+        long long base;
+        int xg;            // first scalar of this lane inside the row (outside [0, row) for halo lanes)
+        int valid;
+    };
+    // one level: AxisX::compute on st.cur; the detail band to memory, the approximation to st.nxt
+    template <int LEV, class Exec> static NDWT_DEV void level(Exec& ex, State& st, const Args& a, const Taps& tp, int tid) {
+        v4 o0 = (v4)(T(0)), o1 = (v4)(T(0));
+        NDWT_SFOR(e, 4)
+            NDWT_SFOR(j, L)
+                constexpr int idx = e + (j - LH) * EW + 4 * GL;      // scalar index in the wave-local window, >= 0
+                constexpr int D = idx / 4 - GL;
+                constexpr int c = idx % 4;
+                const T v = NDWT_LANE_SHIFT(ex, tid, D, s.cur[c]);
+                o0[e] = fma1(tp.lo[0][j], v, o0[e]);
+                o1[e] = fma1(tp.hi[0][j], v, o1[e]);
+            NDWT_SEND
+        NDWT_SEND
+        st.nxt = o0;
+        if (!G::stores(st, a, tid)) return;
+        const long long off = st.base + st.xg;
+        *reinterpret_cast<v4*>(a.out[1 + LEV] + off) = o1;
+        if constexpr (LEV == NLEV - 1) *reinterpret_cast<v4*>(a.out[0] + off) = o0;
+    }
+    template <class Exec> static NDWT_DEV void block(Exec& ex, Shared&, const Args& a, const Taps& tp, int bid) {
+        ex.each([&](int tid, State& st) __attribute__((always_inline)) {
+            const long long off = G::place(st, a, bid, tid);
+            st.cur = *reinterpret_cast<const v4*>(a.in[0] + off);
+        });
+        NDWT_SFOR(lev, NLEV)
+            ex.each([&](int tid, State& st) __attribute__((always_inline)) { level<lev>(ex, st, a, tp, tid); });
+            if constexpr (lev + 1 < NLEV) ex.each([&](int, State& st) __attribute__((always_inline)) { st.cur = st.nxt; });
+        NDWT_SEND
+    }
+};
+
+template <typename T, int L_, int NLEV_, int EW_ = 1, int WPE_ = 4> struct Inv1C {
+    typedef Cascade1Geom<T, L_, NLEV_, EW_, true> G;
+    static constexpr int L = L_, NLEV = NLEV_, EW = EW_, NT = G::NT, WPE = WPE_;
+    static constexpr int LH = G::LH, RH = G::RH, GL = G::GL, GR = G::GR, WX = G::WX;
+    typedef typename VecT<T>::v4 v4;
+    typedef Taps3<T, L> Taps;                            // axis 0 is used
+    typedef Fused1CArgs<T> Args;
+    struct Shared { int unused; };
+    struct State {
+        v4 cur;            // the approximation entering the level: the coarsest one, then every level's output
+        v4 nxt;
+        v4 det[NLEV_];     // the detail band of every level, all loaded up front
+        long long base;
+        int xg;
+        int valid;
+    };
+    // one level: AxisX::compute (synthesis) on st.cur and st.det[LEV]; its output is the approximation of the next finer level
+    template <int LEV, class Exec> static NDWT_DEV void level(Exec& ex, State& st, const Args& a, const Taps& tp, int tid) {
+        v4 o0 = (v4)(T(0));
+        NDWT_SFOR(e, 4)
+            NDWT_SFOR(j, L)
+                constexpr int idx = e + (j - LH) * EW + 4 * GL;
+                constexpr int D = idx / 4 - GL;
+                constexpr int c = idx % 4;
+                o0[e] = fma1(tp.lo[0][j], NDWT_LANE_SHIFT(ex, tid, D, s.cur[c]), o0[e]);
+                o0[e] = fma1(tp.hi[0][j], NDWT_LANE_SHIFT(ex, tid, D, s.det[LEV][c]), o0[e]);
+            NDWT_SEND
+        NDWT_SEND
+        st.nxt = o0;
+        if constexpr (LEV == NLEV - 1) {
+            if (G::stores(st, a, tid)) *reinterpret_cast<v4*>(a.out[0] + st.base + st.xg) = o0;
+        }
+    }
+    template <class Exec> static NDWT_DEV void block(Exec& ex, Shared&, const Args& a, const Taps& tp, int bid) {
+        ex.each([&](int tid, State& st) __attribute__((always_inline)) {
+            const long long off = G::place(st, a, bid, tid);
+            st.cur = *reinterpret_cast<const v4*>(a.in[0] + off);
+            NDWT_SFOR(lev, NLEV)
+                st.det[lev] = *reinterpret_cast<const v4*>(a.in[1 + lev] + off);
+            NDWT_SEND
+        });
+        NDWT_SFOR(lev, NLEV)
+            ex.each([&](int tid, State& st) __attribute__((always_inline)) { level<lev>(ex, st, a, tp, tid); });
+            if constexpr (lev + 1 < NLEV) ex.each([&](int, State& st) __attribute__((always_inline)) { st.cur = st.nxt; });
+        NDWT_SEND
+    }
+};
+
+}  // namespace ndwt

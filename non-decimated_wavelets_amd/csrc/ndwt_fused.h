@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ndwt_device.h"
+#include "ndwt_device_1d.h"
 #include "ndwt_select.h"
 
 namespace ndwt {
@@ -40,6 +41,12 @@ int launch_cascade2(const Cascade2Instance& k, const Fused2CArgs<float>& a, cons
 int launch_cascade2(const Cascade2Instance& k, const Fused2CArgs<double>& a, const void* taps_dev, hipStream_t s);
 int launch_cascade2(const Cascade2Instance& k, const Fused2CIArgs<float>& a, const void* taps_dev, hipStream_t s);
 int launch_cascade2(const Cascade2Instance& k, const Fused2CIArgs<double>& a, const void* taps_dev, hipStream_t s);
+
+// Two to four levels of the signals of a batched 1-D plan in one launch (Fwd1C / Inv1C), the instance named in full (ndwt_fused_list.h:
+// Cascade1Instance, the table cascade1_levels reads; its tile: cascade1_tile_width).  -1: no unit has the instance, -2: the launch
+// geometry is not the instance's tile, or the grid is too large.
+int launch_cascade1(const Cascade1Instance& k, const Fused1CArgs<float>& a, const void* taps_dev, hipStream_t s);
+int launch_cascade1(const Cascade1Instance& k, const Fused1CArgs<double>& a, const void* taps_dev, hipStream_t s);
 
 // one non-contiguous axis with the window in registers (taps: kernel-form lo/hi of length L)
 int launch_march_f32(bool syn, int L, const MarchArgs<float>& a, const double* lo, const double* hi, hipStream_t s);

@@ -56,6 +56,17 @@ template <class K> int launch_cascade2_k(const typename K::Args& a, const void* 
     return launch_wave_tiles<K>(a, 1, taps_dev, s);
 }
 
+// The 1-D cascade of a batched plan: one wave per (signal, segment of K::WX scalars), four to the workgroup.  The host's segments
+// (cascade1_tile_width) against the kernel's own, and a grid the launch can express, or -2: the caller takes one launch per level.
+template <class K> int launch_cascade1_k(const typename K::Args& a, const void* taps_dev, hipStream_t s) {
+    if (a.row < 4 || a.row % 4 != 0 || a.row >= (1LL << 30) || a.outer < 1 || a.nseg != (a.row + K::WX - 1) / K::WX) return -2;
+    const long long nblocks = (a.outer * a.nseg + K::NT / 64 - 1) / (K::NT / 64);
+    if (nblocks > 0x7fffffffLL) return -2;
+    trace_kernel<K>(dim3((unsigned)nblocks), dim3(K::NT));
+    hipLaunchKernelGGL(fused3_kernel<K>, dim3((unsigned)nblocks), dim3(K::NT), 0, s, a, (const typename K::Taps*)taps_dev);
+    return (int)hipGetLastError();
+}
+
 // One entry of an instance list (ndwt_fused_list.h) as an exact-match launch: the pick is this instance, or the next entry is asked.  A
 // launch unit is its list expanded with these and a final "not mine" (-1).
 #define NDWT_FUSED_K(KIND, INV, T, LL, V, VEC, ...)                                                          \
@@ -86,6 +97,11 @@ template <class K> int launch_cascade2_k(const typename K::Args& a, const void* 
     if (k == Cascade2Instance{true, sizeof(T) == 8, EWV, LL, NLEV, PD}) {                                    \
         static_assert(Inv2C<T, LL, NLEV, PD, WPE, EWV>::WX == cascade2_tile_width({true, sizeof(T) == 8, EWV, LL, NLEV, PD}), "tile width"); \
         return launch_cascade2_k<Inv2C<T, LL, NLEV, PD, WPE, EWV>>(a, taps_dev, s);                          \
+    }
+#define NDWT_LAUNCH_C(KIND, T, EWV, LL, NLEV)                                                                \
+    if (k == Cascade1Instance{k##KIND == kInv1C, sizeof(T) == 8, EWV, LL, NLEV}) {                            \
+        static_assert(KIND<T, LL, NLEV, EWV>::WX == cascade1_tile_width({k##KIND == kInv1C, sizeof(T) == 8, EWV, LL, NLEV}), "tile width"); \
+        return launch_cascade1_k<KIND<T, LL, NLEV, EWV>>(a, taps_dev, s);                                    \
     }
 
 }  // namespace ndwt

@@ -50,6 +50,11 @@ struct Cascade2Instance { bool inverse, f64; int ew, Lp, nlev, pd; };
 constexpr bool operator==(const Cascade2Instance& a, const Cascade2Instance& b) {
     return a.inverse == b.inverse && a.f64 == b.f64 && a.ew == b.ew && a.Lp == b.Lp && a.nlev == b.nlev && a.pd == b.pd;
 }
+// Fwd1C / Inv1C<T, Lp, nlev, ew> (ndwt_device_1d.h): two to four levels of many 1-D signals in one launch
+struct Cascade1Instance { bool inverse, f64; int ew, Lp, nlev; };
+constexpr bool operator==(const Cascade1Instance& a, const Cascade1Instance& b) {
+    return a.inverse == b.inverse && a.f64 == b.f64 && a.ew == b.ew && a.Lp == b.Lp && a.nlev == b.nlev;
+}
 
 // ---- the lists.  Entries:  F(T, L, V, VEC4, EW, PIN, TPRE, WLDS)  Fwd3 on tile V
 //                            S(KIND, T, L, V, VEC4, EW)             Inv3 / Inv3S on tile V
@@ -58,6 +63,7 @@ constexpr bool operator==(const Cascade2Instance& a, const Cascade2Instance& b) 
 //                            P(T, L, PD, PK)                        Inv2P
 //                            A(T, EW, L, NLEV, WPE)                 Fwd2C
 //                            R(T, EW, L, NLEV, PD, WPE)             Inv2C
+//                            C(KIND, T, EW, L, NLEV)                Fwd1C / Inv1C
 // NDWT_F2 / NDWT_S2 / NDWT_Y2 / NDWT_W2: the plain form of an entry for rows of whole groups of 4 scalars and for the rest
 #define NDWT_F2(F, T, L, V, EW) F(T, L, V, true, EW, false, false, 0) F(T, L, V, false, EW, false, false, 0)
 #define NDWT_S2(S, KIND, T, L, V, EW) S(KIND, T, L, V, true, EW) S(KIND, T, L, V, false, EW)
@@ -245,6 +251,18 @@ constexpr bool operator==(const Cascade2Instance& a, const Cascade2Instance& b) 
 #define NDWT_LIST_C128_INV2C(R)                                                                                           \
     NDWT_R23(R, double, 2, 2, 1, 2) R(double, 2, 4, 2, 1, 2) R(double, 2, 4, 3, 1, 1) NDWT_R23(R, double, 2, 6, 1, 1) R(double, 2, 8, 2, 1, 1)
 
+// The cascaded 1-D kernels of a batched plan (Fwd1C / Inv1C, ndwt_device_1d.h), rows of whole groups of 4 scalars: THE table of the
+// instances that exist -- cascade1_levels (ndwt_select.h) answers from it, the launch units (ndwt_cascade1_{f32,c64,f64,c128}.hip)
+// expand it.  {float, double} x EW {1, 2} x 2 .. 8 taps x 2 .. 4 levels x both directions: 96 instances, a list per data kind serving
+// both directions (KIND = Fwd1C / Inv1C).  A lane holds a handful of 4-vectors: every instance fits 4 waves per SIMD without scratch.
+#define NDWT_C234(C, KIND, T, EW, L) C(KIND, T, EW, L, 2) C(KIND, T, EW, L, 3) C(KIND, T, EW, L, 4)
+#define NDWT_C1_KIND(C, KIND, T, EW) NDWT_C234(C, KIND, T, EW, 2) NDWT_C234(C, KIND, T, EW, 4) NDWT_C234(C, KIND, T, EW, 6) NDWT_C234(C, KIND, T, EW, 8)
+#define NDWT_LIST_F32_1C(C, KIND) NDWT_C1_KIND(C, KIND, float, 1)
+#define NDWT_LIST_C64_1C(C, KIND) NDWT_C1_KIND(C, KIND, float, 2)
+#define NDWT_LIST_F64_1C(C, KIND) NDWT_C1_KIND(C, KIND, double, 1)
+#define NDWT_LIST_C128_1C(C, KIND) NDWT_C1_KIND(C, KIND, double, 2)
+#define NDWT_LIST_1C(C, KIND) NDWT_LIST_F32_1C(C, KIND) NDWT_LIST_C64_1C(C, KIND) NDWT_LIST_F64_1C(C, KIND) NDWT_LIST_C128_1C(C, KIND)
+
 // ---- questions to the lists
 #define NDWT_IS_F(T, L, V, VEC4, EW, PIN, TPRE, WLDS) if (k == fwd3_instance(sizeof(T) == 8, L, V, VEC4, EW, PIN, TPRE, WLDS)) return true;
 #define NDWT_IS_S(KIND, T, L, V, VEC4, EW) if (k == inv3s_instance(k##KIND, sizeof(T) == 8, L, V, VEC4, EW)) return true;
@@ -271,6 +289,17 @@ inline bool cascade2_instantiated(const Cascade2Instance& k) {
 // scalars of a row one wave of the instance stores: the lanes inside the halo of every level, in whole 128-byte lines (Fwd2C::WX, Inv2C::WX;
 // the launch units check the geometry against the kernel's own)
 constexpr int cascade2_tile_width(const Cascade2Instance& k) {
+    const int LH = k.inverse ? k.Lp / 2 : k.Lp / 2 - 1, RH = k.inverse ? k.Lp / 2 - 1 : k.Lp / 2, lpl = k.f64 ? 4 : 8;
+    return 4 * ((64 - k.nlev * ((LH * k.ew + 3) / 4 + (RH * k.ew + 3) / 4)) / lpl * lpl);
+}
+enum Cascade1Kind { kFwd1C, kInv1C };
+#define NDWT_IS_C(KIND, T, EW, L, NLEV) if (k == Cascade1Instance{k##KIND == kInv1C, sizeof(T) == 8, EW, L, NLEV}) return true;
+inline bool cascade1_instantiated(const Cascade1Instance& k) {
+    NDWT_LIST_1C(NDWT_IS_C, Fwd1C) NDWT_LIST_1C(NDWT_IS_C, Inv1C)
+    return false;
+}
+// scalars of a row one wave of the instance stores (Fwd1C::WX, Inv1C::WX: the same rule as the 2-D cascade's)
+constexpr int cascade1_tile_width(const Cascade1Instance& k) {
     const int LH = k.inverse ? k.Lp / 2 : k.Lp / 2 - 1, RH = k.inverse ? k.Lp / 2 - 1 : k.Lp / 2, lpl = k.f64 ? 4 : 8;
     return 4 * ((64 - k.nlev * ((LH * k.ew + 3) / 4 + (RH * k.ew + 3) / 4)) / lpl * lpl);
 }

@@ -18,6 +18,7 @@ namespace ndwt {
 //   9  |                                                                     | no cascade (analysis AND synthesis): one launch per level
 //  10  |                                                                     | cascade whatever the image size, kernel mode 1 (no take-in-only steps)
 //  11  |                                                                     | cascade whatever the image size
+//      (a batched 1-D plan, cascade1_levels: fwd 9 = one launch per level in the analysis, inv 9 = in the synthesis; nothing else applies)
 //  inv | 3-D synthesis (fused3_select)                                       | 2-D (fused2_select)                | 2-D cascade (cascade2_levels)
 //   0  | default: Inv3Y (gather <= 8 taps, scatter from 10), else Inv3S      | Inv2P depth 4 packed, 1024 waves, where the image fits one round
 //   1  |                                                                     | keeps Inv2S
@@ -208,6 +209,22 @@ constexpr int cascade2_rec_depth(int variant_inv) { return variant_inv == kInvCa
 inline int cascade2_rec_depth(const SelPlan& p, int Lp, int nlev) {
     const int want = cascade2_rec_depth(p.variant_inv);
     return cascade2_instantiated({true, p.f64, p.comp, Lp, nlev, want}) ? want : 1;
+}
+
+// ---- two to four levels of the signals of a batched 1-D plan in one launch (Fwd1C / Inv1C, ndwt_device_1d.h) at the reference's
+// dilation: rows of whole groups of 4 scalars, at least 8 L of them (AxisX's own floor: whichever way a level goes, it runs the lane-shift
+// kernel), tap lengths 2 .. 8.  `howmany` = signals of the plan (0: not a batched plan); `left` = levels still to do.  Returns how many
+// the next launch takes -- the largest instantiated count <= left -- and the tap length; 0 = one launch per level.  kFwdNoCascade takes
+// the analysis off, kInvCascadeOff the synthesis (A/B runs: tools/bench1d_batch.py).
+inline int cascade1_levels(const SelPlan& p, long long howmany, bool inverse, int left, int* L_out) {
+    if (howmany < 1 || p.ndim != 1 || p.atrous || !p.path_auto || (p.comp != 1 && p.comp != 2)) return 0;
+    if (inverse ? p.variant_inv == kInvCascadeOff : p.variant_fwd == kFwdNoCascade) return 0;
+    const int L = p.len[0];
+    const long long n1 = p.dims[0] * p.comp;              // scalars per row
+    if (L < 2 || L > 8 || n1 % 4 != 0 || n1 < 8LL * L || n1 >= (1LL << 30)) return 0;
+    for (int n = left < 4 ? left : 4; n >= 2; --n)
+        if (cascade1_instantiated({inverse, p.f64, p.comp, L, n})) { *L_out = L; return n; }
+    return 0;
 }
 
 // ---- one fused 3-D launch

@@ -33,6 +33,13 @@ FAMILY_PARAMS = {
     "AxisX": [("T", None), ("L", None), ("SYN", None), ("EW", None), ("VEC4", None)],
 }
 
+# the families of csrc/ndwt_device_1d.h (the cascade of a batched 1-D plan), in a table of their own: FAMILY_PARAMS is kept equal to
+# the declarations of ndwt_device.h
+FAMILY_PARAMS_1D = {
+    "Fwd1C": [("T", None), ("L", None), ("NLEV", None), ("EW", 1), ("WPE", 4)],
+    "Inv1C": [("T", None), ("L", None), ("NLEV", None), ("EW", 1), ("WPE", 4)],
+}
+
 # the plain __global__ templates (csrc/ndwt_api.hip, csrc/ndwt_multi.hip), as their launch sites spell them
 PLAIN_PARAMS = {
     "axis_analysis_kernel": [("T", None)],
@@ -95,7 +102,7 @@ def parse_record(line: str) -> KernelLaunch:
     if not t:
         raise ValueError(f"unparsed kernel type: {text!r}")
     fam = t.group(1)
-    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam)
+    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam) or FAMILY_PARAMS_1D.get(fam)
     if table is None:
         raise ValueError(f"unknown kernel family {fam!r} in {text!r}")
     args = [_value(a) for a in _split_args(t.group(2) or "")]
