@@ -2385,6 +2385,10 @@ template <typename T, int L_, int NT_ = 1024, int WPE_ = 4, int ZLDS_ = 0, int T
     }
 };
 
+}  // namespace ndwt
+#include "ndwt_wave_row.h"   // the stages the wave-per-row kernels below (and those of ndwt_device_1d.h) share
+namespace ndwt {
+
 // ------------------------------------------------------------------------------------------------
 // Fused 2-D level, register-only.  Axis 0 = x (contiguous, n1), axis 1 = y (n2, marched).  One WAVE is one tile:
 // lane l owns 4 consecutive x (64 lanes = 256 columns, GL+GR of them halo groups), the y filter runs on a rotating
@@ -2422,13 +2426,12 @@ template <typename T> NDWT_DEV Tile2Coord decode_tile2(const Fused2Args<T>& a, i
 }
 
 template <typename T, int L_, bool VEC4_, int WPE_ = 4, int EW_ = 1> struct Fwd2S {
+    typedef WaveRowGeom<T, L_, EW_, false> G;
     static constexpr int L = L_, NT = 64, WPE = WPE_, EW = EW_;
     static constexpr bool VEC4 = VEC4_;
     static constexpr int NE = VEC4 ? 1 : 4;
-    static constexpr int LH = L / 2 - 1, RH = L / 2;
-    static constexpr int GL = (LH * EW + 3) / 4, GR = (RH * EW + 3) / 4;
-    static constexpr int WX = 4 * (64 - GL - GR);        // output columns per wave
-    static constexpr int XV = 4 * (1 + GL + GR);
+    static constexpr int LH = G::LH, RH = G::RH, GL = G::GL, GR = G::GR, XV = G::XV;
+    static constexpr int WX = G::WX;                     // output columns per wave
     typedef typename VecT<T>::v2 v2;
     typedef typename VecT<T>::v4 v4;
     typedef Taps3<T, L> Taps;                            // axes 0 (x) and 1 (y) are used
@@ -2441,41 +2444,11 @@ template <typename T, int L_, bool VEC4_, int WPE_ = 4, int EW_ = 1> struct Fwd2
         int off[NE];
     };
 
-    static NDWT_DEV void setup(State& st, const Args& a, const Tile2Coord& tc, int tid) {
-        int xb = tc.x0 - 4 * GL + 4 * tid;
-        NDWT_SFOR(e, NE)
-            st.off[e] = modn(xb + e, a.n1);
-        NDWT_SEND
-    }
+    static NDWT_DEV void setup(State& st, const Args& a, const Tile2Coord& tc, int tid) { lane_offsets(st.off, tc.x0 - 4 * GL + 4 * tid, a.n1); }
     static NDWT_DEV void load_row(State& st, const Args& a, const T* inb, int yraw) {
         long long ym = a.y_wrap ? (long long)modn(yraw, a.n2) : (long long)(yraw + LH);
         const T* p = inb + ym * a.rs;
-        if constexpr (VEC4) {
-            st.nxt = *reinterpret_cast<const v4*>(p + st.off[0]);
-        } else if (st.off[NE - 1] == st.off[0] + 3) {           // 4 contiguous x: one access (VecT::v4u)
-            st.nxt = *reinterpret_cast<const typename VecT<T>::v4u*>(p + st.off[0]);
-        } else {
-            NDWT_SFOR(e, NE)
-                st.nxt[e] = p[st.off[e]];
-            NDWT_SEND
-        }
-    }
-    template <int R> static NDWT_DEV void ystage(State& st, const Taps& tp) {
-        st.win[(R + L - 1) % L] = st.nxt;
-        v2 acc[4];
-        acc[0] = acc[1] = acc[2] = acc[3] = (v2)(T(0));
-        NDWT_SFOR(j, L)
-            v4 w = st.win[(R + j) % L];
-            v2 t = {tp.lo[1][j], tp.hi[1][j]};
-            acc[0] += t * w[0]; acc[1] += t * w[1]; acc[2] += t * w[2]; acc[3] += t * w[3];
-        NDWT_SEND
-        st.yz[0] = acc[0]; st.yz[1] = acc[1]; st.yz[2] = acc[2]; st.yz[3] = acc[3];
-    }
-    template <int R> static NDWT_DEV void ydispatch(int r, State& st, const Taps& tp) {
-        if constexpr (R < L) {
-            if (r == R) ystage<R>(st, tp);
-            else ydispatch<R + 1>(r, st, tp);
-        }
+        load_lane_rows<VEC4, 1>(&st.nxt, [&](int) __attribute__((always_inline)) { return p; }, st.off);
     }
     static NDWT_DEV void prologue(State& st, const Args& a, const T* inb, int ybeg) {
         NDWT_SFOR(j, L - 1)
@@ -2487,48 +2460,12 @@ template <typename T, int L_, bool VEC4_, int WPE_ = 4, int EW_ = 1> struct Fwd2
     template <class Exec> static NDWT_DEV void xstage(Exec& ex, State& st, const Taps& tp, const Args& a, const Tile2Coord& tc,
                                                       long long obase, int y, int tid) {
         v2 xlo[4], xhi[4];
-        NDWT_SFOR(e, 4)
-            xlo[e] = (v2)(T(0));
-            xhi[e] = (v2)(T(0));
-        NDWT_SEND
-        NDWT_SFOR(i, XV)
-            constexpr int D = i / 4 - GL;
-            constexpr int c = i % 4;
-            {
-                v2 v = {NDWT_LANE_SHIFT(ex, tid, D, s.yz[c].x), NDWT_LANE_SHIFT(ex, tid, D, s.yz[c].y)};
-                NDWT_SFOR(e, 4)
-                    constexpr int dj = i - 4 * GL - e;                     // = (j - LH) * EW
-                    if constexpr (dj % EW == 0) {
-                        constexpr int j = dj / EW + LH;
-                        if constexpr (j >= 0 && j < L) {
-                            xlo[e] += tp.lo[0][j] * v;
-                            xhi[e] += tp.hi[0][j] * v;
-                        }
-                    }
-                NDWT_SEND
-            }
-        NDWT_SEND
+        xstage_pairs<G>(ex, st, tid, tp, NDWT_ROW(s.yz), xlo, xhi);
         int gx = tc.x0 + 4 * (tid - GL);
         if (tid < GL || tid >= 64 - GR || gx >= a.n1) return;
-        long long off = obase + (long long)y * a.rs + gx;
-        v4 o0 = {xlo[0].x, xlo[1].x, xlo[2].x, xlo[3].x}, o1 = {xhi[0].x, xhi[1].x, xhi[2].x, xhi[3].x};
-        v4 o2 = {xlo[0].y, xlo[1].y, xlo[2].y, xlo[3].y}, o3 = {xhi[0].y, xhi[1].y, xhi[2].y, xhi[3].y};
-        if constexpr (VEC4) {
-            stream_store(reinterpret_cast<v4*>(a.out[0] + off), o0, a.nt);
-            stream_store(reinterpret_cast<v4*>(a.out[1] + off), o1, a.nt);
-            stream_store(reinterpret_cast<v4*>(a.out[2] + off), o2, a.nt);
-            stream_store(reinterpret_cast<v4*>(a.out[3] + off), o3, a.nt);
-        } else if (gx + 3 < a.n1) {
-            typedef typename VecT<T>::v4u v4u;
-            *reinterpret_cast<v4u*>(a.out[0] + off) = o0;
-            *reinterpret_cast<v4u*>(a.out[1] + off) = o1;
-            *reinterpret_cast<v4u*>(a.out[2] + off) = o2;
-            *reinterpret_cast<v4u*>(a.out[3] + off) = o3;
-        } else {
-            NDWT_SFOR(e, 4)
-                if (gx + e < a.n1) { a.out[0][off + e] = o0[e]; a.out[1][off + e] = o1[e]; a.out[2][off + e] = o2[e]; a.out[3][off + e] = o3[e]; }
-            NDWT_SEND
-        }
+        v4 o[4];
+        band_vectors(xlo, xhi, o[0], o[1], o[2], o[3]);
+        store_lane_rows<VEC4>(a.out, obase + (long long)y * a.rs + gx, o, gx, a.n1, a.nt);
     }
 
     template <class Exec> static NDWT_DEV void block(Exec& ex, Shared&, const Args& a, const Taps& tp, int bid) {
@@ -2544,7 +2481,7 @@ template <typename T, int L_, bool VEC4_, int WPE_ = 4, int EW_ = 1> struct Fwd2
         for (int s = 0; s < nsteps; ++s) {
             const int y = tc.ybeg + s;
             ex.each([&](int, State& st) __attribute__((always_inline)) {
-                ydispatch<0>(s % L, st, tp);
+                rot_dispatch<L>(s % L, [&](auto R) __attribute__((always_inline)) { ystage_pairs<decltype(R)::value>(st.win, st.nxt, tp, st.yz); });
                 if (s + 1 < nsteps) load_row(st, a, inb, y + 1 + RH);
             });
             ex.each([&](int tid, State& st) __attribute__((always_inline)) { xstage(ex, st, tp, a, tc, obase, y, tid); });
@@ -2558,9 +2495,9 @@ template <typename T, int L_, bool VEC4_, int WPE_ = 4, int EW_ = 1> struct Fwd2
 // approximation row level 1 completes enters the y window of level 2 in the same step, and so on -- the approximations between the
 // levels live in registers only (a per-level launch writes each to memory and the next launch reads it back: 1 + 3 NLEV + 1 volumes
 // move instead of 5 NLEV).  Level l runs l RH rows behind the raw row and is valid l GL / l GR lanes inside the wave, so a wave stores
-// 4 (64 - NLEV (GL + GR)) columns of every band and starts NLEV (L/2 - 1) rows above its chunk.  Same FMAs in the same order as NLEV
-// launches of Fwd2S.  Float / double data, real or (EW = 2) interleaved complex with the x taps stepping over the (re, im) pairs as in
-// Fwd2S::xstage; rows of whole groups of 4 scalars, periodic in y.
+// 4 (64 - NLEV (GL + GR)) columns of every band and starts NLEV (L/2 - 1) rows above its chunk.  A level is the y and x stage of
+// Fwd2S (ystage_pairs, xstage_pairs), so the bands equal those of NLEV launches of Fwd2S bit for bit.  Float / double data, real or
+// (EW = 2) interleaved complex with the x taps stepping over the (re, im) pairs; rows of whole groups of 4 scalars, periodic in y.
 template <typename T> struct Fused2CArgs {
     const T* in;           // the image (or the approximation the cascade starts from)
     T* out[10];            // [0] the approximation of the LAST level of the cascade; level l = 1 .. NLEV (1 = first / finest of the launch):
@@ -2573,15 +2510,13 @@ template <typename T> struct Fused2CArgs {
 };
 
 template <typename T, int L_, int NLEV_, int WPE_ = 2, int EW_ = 1> struct Fwd2C {
+    typedef WaveRowGeom<T, L_, EW_, false, NLEV_> G;
     static constexpr int L = L_, NLEV = NLEV_, NT = 64, WPE = WPE_, EW = EW_;
-    static constexpr int LH = L / 2 - 1, RH = L / 2;
-    static constexpr int GL = (LH * EW + 3) / 4, GR = (RH * EW + 3) / 4;
+    static constexpr int LH = G::LH, RH = G::RH, GL = G::GL, GR = G::GR, XV = G::XV;
     // output columns per wave: the lanes whose values are valid at every level, rounded down to whole 128-byte lines so that no line of
     // any band is shared by two waves (a partly written line of a nontemporal stream is a read-modify-write in memory).  A lane stores 4
     // scalars: float 8 lanes to the line, double 4 -- LPL = 128 / (4 sizeof(T)) lanes, whatever EW (it changes the halo, not the store)
-    static constexpr int LPL = 32 / (int)sizeof(T);
-    static constexpr int WX = 4 * ((64 - NLEV * (GL + GR)) / LPL * LPL);
-    static constexpr int XV = 4 * (1 + GL + GR);
+    static constexpr int LPL = G::LPL, WX = G::WX;
     static_assert(NLEV >= 2 && NLEV <= 3 && WX > 0, "two or three levels per launch");
     typedef typename VecT<T>::v2 v2;
     typedef typename VecT<T>::v4 v4;
@@ -2599,42 +2534,11 @@ template <typename T, int L_, int NLEV_, int WPE_ = 2, int EW_ = 1> struct Fwd2C
     static NDWT_DEV void load_row(State& st, const Args& a, int yraw) {
         st.nxt = *reinterpret_cast<const v4*>(a.in + (long long)modn(yraw, a.n2) * a.rs + st.off);
     }
-    template <int LEV, int R> static NDWT_DEV void ystage(State& st, const Taps& tp) {
-        st.win[LEV][(R + L - 1) % L] = st.cur;
-        v2 acc[4];
-        acc[0] = acc[1] = acc[2] = acc[3] = (v2)(T(0));
-        NDWT_SFOR(j, L)
-            v4 w = st.win[LEV][(R + j) % L];
-            v2 t = {tp.lo[1][j], tp.hi[1][j]};
-            acc[0] += t * w[0]; acc[1] += t * w[1]; acc[2] += t * w[2]; acc[3] += t * w[3];
-        NDWT_SEND
-        st.yz[0] = acc[0]; st.yz[1] = acc[1]; st.yz[2] = acc[2]; st.yz[3] = acc[3];
-    }
     // x filter of level LEV (every lane executes the shifts), stores of its bands for output row y if `emit`; its approximation row -> st.cur
     template <int LEV, class Exec> static NDWT_DEV void xstage(Exec& ex, State& st, const Taps& tp, const Args& a, int x0, int y, bool emit,
                                                                int tid) {
         v2 xlo[4], xhi[4];
-        NDWT_SFOR(e, 4)
-            xlo[e] = (v2)(T(0));
-            xhi[e] = (v2)(T(0));
-        NDWT_SEND
-        NDWT_SFOR(i, XV)
-            constexpr int D = i / 4 - GL;
-            constexpr int c = i % 4;
-            {
-                v2 v = {NDWT_LANE_SHIFT(ex, tid, D, s.yz[c].x), NDWT_LANE_SHIFT(ex, tid, D, s.yz[c].y)};
-                NDWT_SFOR(e, 4)
-                    constexpr int dj = i - 4 * GL - e;                     // = (j - LH) * EW
-                    if constexpr (dj % EW == 0) {
-                        constexpr int j = dj / EW + LH;
-                        if constexpr (j >= 0 && j < L) {
-                            xlo[e] += tp.lo[0][j] * v;
-                            xhi[e] += tp.hi[0][j] * v;
-                        }
-                    }
-                NDWT_SEND
-            }
-        NDWT_SEND
+        xstage_pairs<G>(ex, st, tid, tp, NDWT_ROW(s.yz), xlo, xhi);
         const v4 o0 = {xlo[0].x, xlo[1].x, xlo[2].x, xlo[3].x}, o1 = {xhi[0].x, xhi[1].x, xhi[2].x, xhi[3].x};
         const v4 o2 = {xlo[0].y, xlo[1].y, xlo[2].y, xlo[3].y}, o3 = {xhi[0].y, xhi[1].y, xhi[2].y, xhi[3].y};
         st.cur = o0;
@@ -2658,7 +2562,7 @@ template <typename T, int L_, int NLEV_, int WPE_ = 2, int EW_ = 1> struct Fwd2C
             // Level lev's input rows are valid from step lev (L - 1) on and its window is full L - 1 steps later: before the first it
             // has nothing to do, between the two it only takes the row in (what it would compute is march-in garbage; wave-uniform tests)
             if (lev == 0 || s >= (lev + 1) * (L - 1) || ((a.mode & 1) && s >= lev * (L - 1))) {
-                ex.each([&](int, State& st) __attribute__((always_inline)) { ystage<lev, R>(st, tp); });
+                ex.each([&](int, State& st) __attribute__((always_inline)) { ystage_pairs<R>(st.win[lev], st.cur, tp, st.yz); });
                 const int y = r - (lev + 1) * RH;
                 const bool emit = y >= ybeg && y < yend;
                 ex.each([&](int tid, State& st) __attribute__((always_inline)) { xstage<lev>(ex, st, tp, a, x0, y, emit, tid); });
@@ -2667,12 +2571,8 @@ template <typename T, int L_, int NLEV_, int WPE_ = 2, int EW_ = 1> struct Fwd2C
             }
         NDWT_SEND
     }
-    template <int R, class Exec> static NDWT_DEV void dispatch(int rot, Exec& ex, const Args& a, const Taps& tp, int x0, int ybeg, int yend, int r,
-                                                               bool more) {
-        if constexpr (R < L) {
-            if (rot == R) step<R>(ex, a, tp, x0, ybeg, yend, r, more);
-            else dispatch<R + 1>(rot, ex, a, tp, x0, ybeg, yend, r, more);
-        }
+    template <class Exec> static NDWT_DEV void dispatch(int rot, Exec& ex, const Args& a, const Taps& tp, int x0, int ybeg, int yend, int r, bool more) {
+        rot_dispatch<L>(rot, [&](auto R) __attribute__((always_inline)) { step<decltype(R)::value>(ex, a, tp, x0, ybeg, yend, r, more); });
     }
 
     template <class Exec> static NDWT_DEV void block(Exec& ex, Shared&, const Args& a, const Taps& tp, int bid) {
@@ -2701,21 +2601,19 @@ template <typename T, int L_, int NLEV_, int WPE_ = 2, int EW_ = 1> struct Fwd2C
         const int nsteps = (yend - ybeg) + NLEV * (L - 1);
         // step s >= L-1 runs with rotation (s + 1) % L: its row lands in slot L-1 at s = L-1, behind the rows of the steps before it
         if (!(a.mode & 1)) {
-            for (int s = L - 1; s < nsteps; ++s) dispatch<0>((s + 1) % L, ex, a, tp, x0, ybeg, yend, r0 + s, s + 1 < nsteps);
+            for (int s = L - 1; s < nsteps; ++s) dispatch((s + 1) % L, ex, a, tp, x0, ybeg, yend, r0 + s, s + 1 < nsteps);
         } else {
-            for (int s = 0; s < nsteps; ++s) dispatch<0>(s % L, ex, a, tp, x0, ybeg, yend, r0 + s, s + 1 < nsteps);
+            for (int s = 0; s < nsteps; ++s) dispatch(s % L, ex, a, tp, x0, ybeg, yend, r0 + s, s + 1 < nsteps);
         }
     }
 };
 
 template <typename T, int L_, bool VEC4_, int WPE_ = 4, int EW_ = 1> struct Inv2S {
+    typedef WaveRowGeom<T, L_, EW_, true> G;
     static constexpr int L = L_, NT = 64, WPE = WPE_, EW = EW_;
     static constexpr bool VEC4 = VEC4_;
     static constexpr int NE = VEC4 ? 1 : 4;
-    static constexpr int LH = L / 2, RH = L / 2 - 1;
-    static constexpr int GL = (LH * EW + 3) / 4, GR = (RH * EW + 3) / 4;
-    static constexpr int WX = 4 * (64 - GL - GR);
-    static constexpr int XV = 4 * (1 + GL + GR);
+    static constexpr int LH = G::LH, RH = G::RH, GL = G::GL, GR = G::GR, XV = G::XV, WX = G::WX;
     typedef typename VecT<T>::v2 v2;
     typedef typename VecT<T>::v4 v4;
     typedef Taps3<T, L> Taps;
@@ -2726,91 +2624,25 @@ template <typename T, int L_, bool VEC4_, int WPE_ = 4, int EW_ = 1> struct Inv2
         v4 raw[4];         // 4 x of every band of the newest row
         int off[NE];
     };
-    static NDWT_DEV void setup(State& st, const Args& a, const Tile2Coord& tc, int tid) {
-        int xb = tc.x0 - 4 * GL + 4 * tid;
-        NDWT_SFOR(e, NE)
-            st.off[e] = modn(xb + e, a.n1);
-        NDWT_SEND
-    }
+    static NDWT_DEV void setup(State& st, const Args& a, const Tile2Coord& tc, int tid) { lane_offsets(st.off, tc.x0 - 4 * GL + 4 * tid, a.n1); }
     static NDWT_DEV void load_row(State& st, const Args& a, long long ibase, int yraw) {
         long long ym = a.y_wrap ? (long long)modn(yraw, a.n2) : (long long)(yraw + LH);
-        if constexpr (VEC4) {
-            NDWT_SFOR(b, 4)
-                st.raw[b] = *reinterpret_cast<const v4*>(a.in[b] + ibase + ym * a.rs + st.off[0]);
-            NDWT_SEND
-        } else if (st.off[NE - 1] == st.off[0] + 3) {           // 4 contiguous x: one access per band (VecT::v4u)
-            NDWT_SFOR(b, 4)
-                st.raw[b] = *reinterpret_cast<const typename VecT<T>::v4u*>(a.in[b] + ibase + ym * a.rs + st.off[0]);
-            NDWT_SEND
-        } else {
-            NDWT_SFOR(b, 4)
-                NDWT_SFOR(e, NE)
-                    st.raw[b][e] = (a.in[b] + ibase + ym * a.rs)[st.off[e]];
-                NDWT_SEND
-            NDWT_SEND
-        }
+        load_lane_rows<VEC4, 4>(st.raw, [&](int b) __attribute__((always_inline)) { return a.in[b] + ibase + ym * a.rs; }, st.off);
     }
     // x-synthesis of the newest row via lane shifts, then y-synthesis (scatter); rotation R as in Inv3S
     template <int R, class Exec>
     static NDWT_DEV void step(Exec& ex, State& st, const Taps& tp, const Args& a, const Tile2Coord& tc, long long obase, int y,
                               bool emit, int tid) {
-        T p0[4], p1[4];    // x-synthesis of y-bit 0 / y-bit 1 = the (a, d) inputs of the y-synthesis; scalars, not pairs:
-        NDWT_SFOR(e, 4)    // see Inv3S::xsyn (pairs would be built right behind the prefetch loads)
-            p0[e] = T(0);
-            p1[e] = T(0);
-        NDWT_SEND
-        NDWT_SFOR(i, XV)
-            constexpr int D = i / 4 - GL;
-            constexpr int c = i % 4;
-            {
-                const T wa0 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[0][c]);   // x-bit 0, y-bit 0
-                const T wd0 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[1][c]);   // x-bit 1, y-bit 0
-                const T wa1 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[2][c]);   // x-bit 0, y-bit 1
-                const T wd1 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[3][c]);   // x-bit 1, y-bit 1
-                NDWT_SFOR(e, 4)
-                    constexpr int dj = i - 4 * GL - e;
-                    if constexpr (dj % EW == 0) {
-                        constexpr int j = dj / EW + LH;
-                        if constexpr (j >= 0 && j < L) {
-                            p0[e] += tp.lo[0][j] * wa0;
-                            p0[e] += tp.hi[0][j] * wd0;
-                            p1[e] += tp.lo[0][j] * wa1;
-                            p1[e] += tp.hi[0][j] * wd1;
-                        }
-                    }
-                NDWT_SEND
-            }
-        NDWT_SEND
-        NDWT_SFOR(j, L)
-            constexpr int slot = ((R - 1 - j) % L + L) % L;
-            NDWT_SFOR(e, 4)
-                const T c = tp.lo[1][j] * p0[e] + tp.hi[1][j] * p1[e];
-                if constexpr (j == 0) st.yacc[slot][e] = c;
-                else st.yacc[slot][e] += c;
-            NDWT_SEND
-        NDWT_SEND
+        T p0[4], p1[4];
+        xsyn_rows<G>(ex, st, tid, tp, NDWT_ROW(s.raw[0]), NDWT_ROW(s.raw[1]), NDWT_ROW(s.raw[2]), NDWT_ROW(s.raw[3]), p0, p1);
+        ysyn_scatter<R>(st.yacc, tp, p0, p1);
         if (!emit) return;
-        constexpr int done = ((R - L) % L + L) % L;
         int gx = tc.x0 + 4 * (tid - GL);
         if (tid < GL || tid >= 64 - GR || gx >= a.n1) return;
-        long long off = obase + (long long)y * a.rs + gx;
-        if constexpr (VEC4) {
-            stream_store(reinterpret_cast<v4*>(a.out[0] + off), v4{st.yacc[done][0], st.yacc[done][1], st.yacc[done][2], st.yacc[done][3]}, a.nt);
-        } else if (gx + 3 < a.n1) {
-            *reinterpret_cast<typename VecT<T>::v4u*>(a.out[0] + off) = v4{st.yacc[done][0], st.yacc[done][1], st.yacc[done][2], st.yacc[done][3]};
-        } else {
-            NDWT_SFOR(e, 4)
-                if (gx + e < a.n1) a.out[0][off + e] = st.yacc[done][e];
-            NDWT_SEND
-        }
-    }
-    template <int R, class Exec>
-    static NDWT_DEV void dispatch(int r, Exec& ex, State& st, const Taps& tp, const Args& a, const Tile2Coord& tc, long long obase,
-                                  int y, bool emit, int tid) {
-        if constexpr (R < L) {
-            if (r == R) step<R>(ex, st, tp, a, tc, obase, y, emit, tid);
-            else dispatch<R + 1>(r, ex, st, tp, a, tc, obase, y, emit, tid);
-        }
+        T* const p[1] = {a.out[0]};
+        constexpr int done = ysyn_done_slot(R, L);
+        const v4 o[1] = {v4{st.yacc[done][0], st.yacc[done][1], st.yacc[done][2], st.yacc[done][3]}};
+        store_lane_rows<VEC4>(p, obase + (long long)y * a.rs + gx, o, gx, a.n1, a.nt);
     }
     template <class Exec> static NDWT_DEV void block(Exec& ex, Shared&, const Args& a, const Taps& tp, int bid) {
         const Tile2Coord tc = decode_tile2(a, bid, WX, VEC4 ? -1 : 4 * GL, 4 * GR);
@@ -2832,7 +2664,9 @@ template <typename T, int L_, bool VEC4_, int WPE_ = 4, int EW_ = 1> struct Inv2
                 }
             });
             ex.each([&](int tid, State& st) __attribute__((always_inline)) {
-                dispatch<0>((p + 1) % L, ex, st, tp, a, tc, obase, tc.ybeg + s, s >= 0, tid);
+                const int rot = (p + 1) % L, y = tc.ybeg + s;
+                const bool emit = s >= 0;
+                rot_dispatch<L>(rot, [&](auto R) __attribute__((always_inline)) { step<decltype(R)::value>(ex, st, tp, a, tc, obase, y, emit, tid); });
             });
             ex.each([&](int, State& st) __attribute__((always_inline)) {
                 if (p + 1 < nrows) load_row(st, a, ibase, tc.ybeg - LH + p + 1);
@@ -2851,14 +2685,12 @@ template <typename T, int L_, bool VEC4_, int WPE_ = 4, int EW_ = 1> struct Inv2
 // neighbour's sample w broadcast from one half of its register pair and the tap pairs of Taps3Y pinned in SGPRs; y stage: a tap broadcast
 // from an SGPR pair.  104 packed FMAs per row and lane instead of 192 scalar ones (L = 8).
 template <typename T, int L_, int PD_ = 2, int WPE_ = 2, bool PK_ = false> struct Inv2P {
+    typedef WaveRowGeom<T, L_, 1, true> G;
     static constexpr int L = L_, NT = 64, WPE = WPE_, PD = PD_;
     static constexpr bool PK = PK_;
     static_assert(L % PD == 0, "the depth divides the tap length: a row's slot is p % PD with p = group base + k");
     static_assert(!PK_ || sizeof(T) == 4, "packed form: float only (v_pk_fma_f32)");
-    static constexpr int LH = L / 2, RH = L / 2 - 1;
-    static constexpr int GL = (LH + 3) / 4, GR = (RH + 3) / 4;
-    static constexpr int WX = 4 * (64 - GL - GR);
-    static constexpr int XV = 4 * (1 + GL + GR);
+    static constexpr int LH = G::LH, RH = G::RH, GL = G::GL, GR = G::GR, XV = G::XV, WX = G::WX;
     typedef typename VecT<T>::v4 v4;
     typedef typename VecT<T>::v2 v2;
     typedef Taps3Y<T, L> Taps;      // (its first two members are Taps3<T, L>; the x tap pairs are read by the packed form only)
@@ -2875,14 +2707,8 @@ template <typename T, int L_, int PD_ = 2, int WPE_ = 2, bool PK_ = false> struc
     };
     static NDWT_DEV void load_regt(RegT& rt, const Taps& tp) {
         if constexpr (PK) {
-            NDWT_SFOR(k, L + 1)
-                rt.xl[k] = PkF32::pinned(v2{tp.xplo[k][0], tp.xplo[k][1]});
-                rt.xh[k] = PkF32::pinned(v2{tp.xphi[k][0], tp.xphi[k][1]});
-            NDWT_SEND
-            NDWT_SFOR(m, L / 2)
-                rt.yl[m] = PkF32::pinned(v2{tp.lo[1][2 * m], tp.lo[1][2 * m + 1]});
-                rt.yh[m] = PkF32::pinned(v2{tp.hi[1][2 * m], tp.hi[1][2 * m + 1]});
-            NDWT_SEND
+            pin_x_pairs<L>(rt, tp);
+            pin_y_pairs<L>(rt, tp);
         }
     }
     template <int S> static NDWT_DEV void load_row(State& st, const Args& a, long long ibase, int yraw) {
@@ -2898,92 +2724,24 @@ template <typename T, int L_, int PD_ = 2, int WPE_ = 2, bool PK_ = false> struc
             NDWT_SEND
         }
     }
-    // row p = group base + K (rotation R = (K + 1) % L, slot K % PD): x-synthesis via lane shifts, y-synthesis in scatter form
-    // the packed form of step<K>
+    // row p = group base + K (rotation R = (K + 1) % L, slot K % PD): x-synthesis via lane shifts, y-synthesis in scatter form -- packed
+    // (PK: rt) or scalar (tp) -- and the store of the row it completes
     template <int K, class Exec>
-    static NDWT_DEV void step_pk(Exec& ex, State& st, const RegT& rt, const Args& a, const Tile2Coord& tc, long long obase, int y, bool emit, int tid) {
+    static NDWT_DEV void step(Exec& ex, State& st, const Taps& tp, const RegT& rt, const Args& a, const Tile2Coord& tc, long long obase, int y, bool emit, int tid) {
         constexpr int R = (K + 1) % L, S = K % PD;
-        v2 P[2][2];                                       // [y band][x outputs (0, 1) / (2, 3)]
-        P[0][0] = P[0][1] = P[1][0] = P[1][1] = (v2)(T(0));
-        NDWT_SFOR(ii, XV / 2)
-            constexpr int i0 = 2 * ii;
-            constexpr int D = i0 / 4 - GL;
-            constexpr int c = i0 % 4;                     // 0 or 2: the register pair (c, c + 1) of the lane D away
-            v2 w[4];
-            NDWT_SFOR(b, 4)
-                w[b] = v2{NDWT_LANE_SHIFT(ex, tid, D, s.raw[S][b][c]), NDWT_LANE_SHIFT(ex, tid, D, s.raw[S][b][c + 1])};
-            NDWT_SEND
-            NDWT_SFOR(h, 2)
-                constexpr int k0 = i0 + h - 4 * GL + LH;  // tap pair of the outputs (0, 1); (2, 3): two taps earlier
-                NDWT_SFOR(q, 2)
-                    constexpr int k = k0 - 2 * q;
-                    if constexpr (k >= 0 && k <= L) {
-                        PkF32::fma_bt<h, false, false, false>(P[0][q], w[0], rt.xl[k]);
-                        PkF32::fma_bt<h, false, false, false>(P[0][q], w[1], rt.xh[k]);
-                        PkF32::fma_bt<h, false, false, false>(P[1][q], w[2], rt.xl[k]);
-                        PkF32::fma_bt<h, false, false, false>(P[1][q], w[3], rt.xh[k]);
-                    }
-                NDWT_SEND
-            NDWT_SEND
-        NDWT_SEND
-        NDWT_SFOR(j, L)
-            constexpr int slot = ((R - 1 - j) % L + L) % L;
-            NDWT_SFOR(q, 2)
-                v2 acc;
-                if constexpr (j == 0) acc = (v2)(T(0));
-                else acc = v2{st.yacc[slot][2 * q], st.yacc[slot][2 * q + 1]};
-                PkF32::fma_s<j % 2, false>(acc, P[0][q], rt.yl[j / 2]);
-                PkF32::fma_s<j % 2, false>(acc, P[1][q], rt.yh[j / 2]);
-                st.yacc[slot][2 * q] = acc.x;
-                st.yacc[slot][2 * q + 1] = acc.y;
-            NDWT_SEND
-        NDWT_SEND
+        if constexpr (PK) {
+            v2 P[2][2];
+            xsyn_rows_pk<G>(ex, st, tid, rt, NDWT_ROW(s.raw[S][0]), NDWT_ROW(s.raw[S][1]), NDWT_ROW(s.raw[S][2]), NDWT_ROW(s.raw[S][3]), P);
+            ysyn_scatter_pk<R>(st.yacc, rt, P);
+        } else {
+            T p0[4], p1[4];
+            xsyn_rows<G>(ex, st, tid, tp, NDWT_ROW(s.raw[S][0]), NDWT_ROW(s.raw[S][1]), NDWT_ROW(s.raw[S][2]), NDWT_ROW(s.raw[S][3]), p0, p1);
+            ysyn_scatter<R>(st.yacc, tp, p0, p1);
+        }
         if (!emit) return;
-        constexpr int done = ((R - L) % L + L) % L;
         const int gx = tc.x0 + 4 * (tid - GL);
         if (tid < GL || tid >= 64 - GR || gx >= a.n1) return;
-        stream_store(reinterpret_cast<v4*>(a.out[0] + obase + (long long)y * a.rs + gx),
-                     v4{st.yacc[done][0], st.yacc[done][1], st.yacc[done][2], st.yacc[done][3]}, a.nt);
-    }
-    template <int K, class Exec>
-    static NDWT_DEV void step(Exec& ex, State& st, const Taps& tp, const Args& a, const Tile2Coord& tc, long long obase, int y, bool emit, int tid) {
-        constexpr int R = (K + 1) % L, S = K % PD;
-        T p0[4], p1[4];
-        NDWT_SFOR(e, 4)
-            p0[e] = T(0);
-            p1[e] = T(0);
-        NDWT_SEND
-        NDWT_SFOR(i, XV)
-            constexpr int D = i / 4 - GL;
-            constexpr int c = i % 4;
-            {
-                const T wa0 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[S][0][c]);
-                const T wd0 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[S][1][c]);
-                const T wa1 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[S][2][c]);
-                const T wd1 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[S][3][c]);
-                NDWT_SFOR(e, 4)
-                    constexpr int j = i - 4 * GL - e + LH;
-                    if constexpr (j >= 0 && j < L) {
-                        p0[e] += tp.lo[0][j] * wa0;
-                        p0[e] += tp.hi[0][j] * wd0;
-                        p1[e] += tp.lo[0][j] * wa1;
-                        p1[e] += tp.hi[0][j] * wd1;
-                    }
-                NDWT_SEND
-            }
-        NDWT_SEND
-        NDWT_SFOR(j, L)
-            constexpr int slot = ((R - 1 - j) % L + L) % L;
-            NDWT_SFOR(e, 4)
-                const T c = tp.lo[1][j] * p0[e] + tp.hi[1][j] * p1[e];
-                if constexpr (j == 0) st.yacc[slot][e] = c;
-                else st.yacc[slot][e] += c;
-            NDWT_SEND
-        NDWT_SEND
-        if (!emit) return;
-        constexpr int done = ((R - L) % L + L) % L;
-        const int gx = tc.x0 + 4 * (tid - GL);
-        if (tid < GL || tid >= 64 - GR || gx >= a.n1) return;
+        constexpr int done = ysyn_done_slot(R, L);
         stream_store(reinterpret_cast<v4*>(a.out[0] + obase + (long long)y * a.rs + gx),
                      v4{st.yacc[done][0], st.yacc[done][1], st.yacc[done][2], st.yacc[done][3]}, a.nt);
     }
@@ -2993,8 +2751,7 @@ template <typename T, int L_, int PD_ = 2, int WPE_ = 2, bool PK_ = false> struc
         const int s = p - (L - 1);
         ex.each([&](int, State& st) __attribute__((always_inline)) { pre<K % PD>(st, a); });
         ex.each([&](int tid, State& st) __attribute__((always_inline)) {
-            if constexpr (PK) step_pk<K>(ex, st, rt, a, tc, obase, tc.ybeg + s, s >= 0, tid);
-            else step<K>(ex, st, tp, a, tc, obase, tc.ybeg + s, s >= 0, tid);
+            step<K>(ex, st, tp, rt, a, tc, obase, tc.ybeg + s, s >= 0, tid);
         });
         ex.each([&](int, State& st) __attribute__((always_inline)) {
             if (p + PD < nrows) load_row<K % PD>(st, a, ibase, tc.ybeg - LH + p + PD);
@@ -3053,11 +2810,9 @@ template <typename T, int L_, int NLEV_, int PD_ = 1, int WPE_ = 2, int EW_ = 1>
     static constexpr bool PK = sizeof(T) == 4;            // float: packed FMAs (v_pk_fma_f32); double: scalar ones
     static_assert(L % PD == 0 && NLEV >= 2 && NLEV <= 3, "the depth divides the tap length; two or three levels per launch");
     static_assert(EW == 1 || EW == 2, "real data or interleaved complex");
-    static constexpr int LH = L / 2, RH = L / 2 - 1;
-    static constexpr int GL = (LH * EW + 3) / 4, GR = (RH * EW + 3) / 4;
-    static constexpr int LPL = 32 / (int)sizeof(T);       // lanes to a 128-byte line (see Fwd2C)
-    static constexpr int WX = 4 * ((64 - NLEV * (GL + GR)) / LPL * LPL);   // whole 128-byte lines per wave and row
-    static constexpr int XV = 4 * (1 + GL + GR);
+    typedef WaveRowGeom<T, L_, EW_, true, NLEV_> G;
+    static constexpr int LH = G::LH, RH = G::RH, GL = G::GL, GR = G::GR, XV = G::XV;
+    static constexpr int LPL = G::LPL, WX = G::WX;        // whole 128-byte lines per wave and row (see Fwd2C)
     static_assert(WX > 0, "the halo of every level fits the wave");
     typedef typename VecT<T>::v4 v4;
     typedef typename VecT<T>::v2 v2;
@@ -3078,20 +2833,14 @@ template <typename T, int L_, int NLEV_, int PD_ = 1, int WPE_ = 2, int EW_ = 1>
     static NDWT_DEV void load_regt(RegT& rt, const Taps& tp) {
         if constexpr (PK) {
             if constexpr (EW == 1) {
-                NDWT_SFOR(k, L + 1)
-                    rt.xl[k] = PkF32::pinned(v2{tp.xplo[k][0], tp.xplo[k][1]});
-                    rt.xh[k] = PkF32::pinned(v2{tp.xphi[k][0], tp.xphi[k][1]});
-                NDWT_SEND
+                pin_x_pairs<L>(rt, tp);
             } else {
                 NDWT_SFOR(m, L / 2)
                     rt.xl[m] = PkF32::pinned(v2{tp.lo[0][2 * m], tp.lo[0][2 * m + 1]});
                     rt.xh[m] = PkF32::pinned(v2{tp.hi[0][2 * m], tp.hi[0][2 * m + 1]});
                 NDWT_SEND
             }
-            NDWT_SFOR(m, L / 2)
-                rt.yl[m] = PkF32::pinned(v2{tp.lo[1][2 * m], tp.lo[1][2 * m + 1]});
-                rt.yh[m] = PkF32::pinned(v2{tp.hi[1][2 * m], tp.hi[1][2 * m + 1]});
-            NDWT_SEND
+            pin_y_pairs<L>(rt, tp);
         }
     }
     // band rows of level C (0 = coarsest) for march step p: level C consumes row rr0 + p - C RH (rows are periodic: any index loads)
@@ -3107,50 +2856,13 @@ template <typename T, int L_, int NLEV_, int PD_ = 1, int WPE_ = 2, int EW_ = 1>
             NDWT_SEND
         }
     }
-    // level C of step K of a group (rotation R = (K + 1) % L, slot K % PD): x-synthesis via lane shifts, y-synthesis in scatter form;
-    // the row it completes -> cur[C + 1], or -- the finest level -- the output row y if `emit`
-    template <int C, int K, class Exec>
-    static NDWT_DEV void level(Exec& ex, State& st, const RegT& rt, const Args& a, int x0, int y, bool emit, int tid) {
-        constexpr int R = (K + 1) % L, S = K % PD;
-        v2 P[2][2];                                       // [y band][x outputs (0, 1) / (2, 3)]
-        P[0][0] = P[0][1] = P[1][0] = P[1][1] = (v2)(T(0));
-        NDWT_SFOR(ii, XV / 2)
-            constexpr int i0 = 2 * ii;
-            constexpr int D = i0 / 4 - GL;
-            constexpr int c = i0 % 4;
-            v2 w[4];
-            if constexpr (C == 0) w[0] = v2{NDWT_LANE_SHIFT(ex, tid, D, s.raw[0][S][0][c]), NDWT_LANE_SHIFT(ex, tid, D, s.raw[0][S][0][c + 1])};
-            else w[0] = v2{NDWT_LANE_SHIFT(ex, tid, D, s.cur[C][c]), NDWT_LANE_SHIFT(ex, tid, D, s.cur[C][c + 1])};
-            NDWT_SFOR(b, 3)
-                w[1 + b] = v2{NDWT_LANE_SHIFT(ex, tid, D, s.raw[C][S][1 + b][c]), NDWT_LANE_SHIFT(ex, tid, D, s.raw[C][S][1 + b][c + 1])};
-            NDWT_SEND
-            NDWT_SFOR(h, 2)
-                constexpr int k0 = i0 + h - 4 * GL + LH;
-                NDWT_SFOR(q, 2)
-                    constexpr int k = k0 - 2 * q;
-                    if constexpr (k >= 0 && k <= L) {
-                        PkF32::fma_bt<h, false, false, false>(P[0][q], w[0], rt.xl[k]);
-                        PkF32::fma_bt<h, false, false, false>(P[0][q], w[1], rt.xh[k]);
-                        PkF32::fma_bt<h, false, false, false>(P[1][q], w[2], rt.xl[k]);
-                        PkF32::fma_bt<h, false, false, false>(P[1][q], w[3], rt.xh[k]);
-                    }
-                NDWT_SEND
-            NDWT_SEND
-        NDWT_SEND
-        NDWT_SFOR(j, L)
-            constexpr int slot = ((R - 1 - j) % L + L) % L;
-            NDWT_SFOR(q, 2)
-                v2 acc;
-                if constexpr (j == 0) acc = (v2)(T(0));
-                else acc = v2{st.yacc[C][slot][2 * q], st.yacc[C][slot][2 * q + 1]};
-                PkF32::fma_s<j % 2, false>(acc, P[0][q], rt.yl[j / 2]);
-                PkF32::fma_s<j % 2, false>(acc, P[1][q], rt.yh[j / 2]);
-                st.yacc[C][slot][2 * q] = acc.x;
-                st.yacc[C][slot][2 * q + 1] = acc.y;
-            NDWT_SEND
-        NDWT_SEND
-        constexpr int done = ((R - L) % L + L) % L;
-        const v4 o = {st.yacc[C][done][0], st.yacc[C][done][1], st.yacc[C][done][2], st.yacc[C][done][3]};
+    // the approximation row level C consumes: a band row of the coarsest level, else the row the level above has just completed
+    template <int C, int S> static NDWT_DEV const v4& apx(const State& s) {
+        if constexpr (C == 0) return s.raw[0][S][0];
+        else return s.cur[C];
+    }
+    // the row o level C has completed -> cur[C + 1], or -- the finest level -- the output row y if `emit`
+    template <int C> static NDWT_DEV void put_row(State& st, const Args& a, const v4 o, int x0, int y, bool emit, int tid) {
         if constexpr (C + 1 < NLEV) {
             st.cur[C + 1] = o;
         } else {
@@ -3159,9 +2871,20 @@ template <typename T, int L_, int NLEV_, int PD_ = 1, int WPE_ = 2, int EW_ = 1>
             stream_store(reinterpret_cast<v4*>(a.out + (long long)y * a.rs + gx), o, a.nt);
         }
     }
-    // the same on interleaved complex data (EW = 2): the pair w is the (re, im) of one element and tap j of the element at outputs (2 q, 2 q + 1)
-    // (a function of its own, not a branch inside level(): with the two x stages as `if constexpr` arms of one body and the tail in a
-    // helper, hipcc allocated the float real instances 230 instead of 176 VGPRs for 8 taps x 3 levels, and two rows in flight spilled)
+    // level C of step K of a group (rotation R = (K + 1) % L, slot K % PD): x-synthesis via lane shifts, y-synthesis in scatter form (the
+    // packed stages of Inv2P), the row it completes to put_row.
+    // Three functions, not `if constexpr` arms of one: with the two packed x stages as arms of one body hipcc allocated the float real
+    // instances 230 instead of 176 VGPRs for 8 taps x 3 levels, and two rows in flight spilled.  Sharing the y stage and put_row between
+    // them, as here, leaves every instance's code as it was with each written out (tools/isa_diff.sh).
+    template <int C, int K, class Exec>
+    static NDWT_DEV void level(Exec& ex, State& st, const RegT& rt, const Args& a, int x0, int y, bool emit, int tid) {
+        constexpr int R = (K + 1) % L, S = K % PD;
+        v2 P[2][2];
+        xsyn_rows_pk<G>(ex, st, tid, rt, NDWT_ROW((apx<C, S>(s))), NDWT_ROW(s.raw[C][S][1]), NDWT_ROW(s.raw[C][S][2]), NDWT_ROW(s.raw[C][S][3]), P);
+        put_row<C>(st, a, ysyn_scatter_pk<R>(st.yacc[C], rt, P), x0, y, emit, tid);
+    }
+    // the same on interleaved complex data (EW = 2): the pair w is the (re, im) of one element and tap j of the element at outputs
+    // (2 q, 2 q + 1), so the x stage has the form of the y stage -- this kernel's own, no other has it
     template <int C, int K, class Exec>
     static NDWT_DEV void level_c(Exec& ex, State& st, const RegT& rt, const Args& a, int x0, int y, bool emit, int tid) {
         constexpr int R = (K + 1) % L, S = K % PD;
@@ -3172,8 +2895,7 @@ template <typename T, int L_, int NLEV_, int PD_ = 1, int WPE_ = 2, int EW_ = 1>
             constexpr int D = i0 / 4 - GL;
             constexpr int c = i0 % 4;
             v2 w[4];
-            if constexpr (C == 0) w[0] = v2{NDWT_LANE_SHIFT(ex, tid, D, s.raw[0][S][0][c]), NDWT_LANE_SHIFT(ex, tid, D, s.raw[0][S][0][c + 1])};
-            else w[0] = v2{NDWT_LANE_SHIFT(ex, tid, D, s.cur[C][c]), NDWT_LANE_SHIFT(ex, tid, D, s.cur[C][c + 1])};
+            w[0] = v2{NDWT_LANE_SHIFT(ex, tid, D, (apx<C, S>(s))[c]), NDWT_LANE_SHIFT(ex, tid, D, (apx<C, S>(s))[c + 1])};
             NDWT_SFOR(b, 3)
                 w[1 + b] = v2{NDWT_LANE_SHIFT(ex, tid, D, s.raw[C][S][1 + b][c]), NDWT_LANE_SHIFT(ex, tid, D, s.raw[C][S][1 + b][c + 1])};
             NDWT_SEND
@@ -3188,78 +2910,15 @@ template <typename T, int L_, int NLEV_, int PD_ = 1, int WPE_ = 2, int EW_ = 1>
                 }
             NDWT_SEND
         NDWT_SEND
-        NDWT_SFOR(j, L)
-            constexpr int slot = ((R - 1 - j) % L + L) % L;
-            NDWT_SFOR(q, 2)
-                v2 acc;
-                if constexpr (j == 0) acc = (v2)(T(0));
-                else acc = v2{st.yacc[C][slot][2 * q], st.yacc[C][slot][2 * q + 1]};
-                PkF32::fma_s<j % 2, false>(acc, P[0][q], rt.yl[j / 2]);
-                PkF32::fma_s<j % 2, false>(acc, P[1][q], rt.yh[j / 2]);
-                st.yacc[C][slot][2 * q] = acc.x;
-                st.yacc[C][slot][2 * q + 1] = acc.y;
-            NDWT_SEND
-        NDWT_SEND
-        constexpr int done = ((R - L) % L + L) % L;
-        const v4 o = {st.yacc[C][done][0], st.yacc[C][done][1], st.yacc[C][done][2], st.yacc[C][done][3]};
-        if constexpr (C + 1 < NLEV) {
-            st.cur[C + 1] = o;
-        } else {
-            const int gx = x0 + 4 * (tid - NLEV * GL);
-            if (!emit || tid < NLEV * GL || tid >= NLEV * GL + WX / 4 || gx >= a.n1) return;
-            stream_store(reinterpret_cast<v4*>(a.out + (long long)y * a.rs + gx), o, a.nt);
-        }
+        put_row<C>(st, a, ysyn_scatter_pk<R>(st.yacc[C], rt, P), x0, y, emit, tid);
     }
-    // the scalar form of level<C, K> (double): Inv2P::step with the approximation row of a finer level taken from cur[C]
+    // the scalar form (double): the stages of Inv2S / Inv2P with the approximation row of a finer level taken from cur[C]
     template <int C, int K, class Exec>
     static NDWT_DEV void level_s(Exec& ex, State& st, const Taps& tp, const Args& a, int x0, int y, bool emit, int tid) {
         constexpr int R = (K + 1) % L, S = K % PD;
         T p0[4], p1[4];
-        NDWT_SFOR(e, 4)
-            p0[e] = T(0);
-            p1[e] = T(0);
-        NDWT_SEND
-        NDWT_SFOR(i, XV)
-            constexpr int D = i / 4 - GL;
-            constexpr int c = i % 4;
-            {
-                T wa0;
-                if constexpr (C == 0) wa0 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[0][S][0][c]);
-                else wa0 = NDWT_LANE_SHIFT(ex, tid, D, s.cur[C][c]);
-                const T wd0 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[C][S][1][c]);
-                const T wa1 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[C][S][2][c]);
-                const T wd1 = NDWT_LANE_SHIFT(ex, tid, D, s.raw[C][S][3][c]);
-                NDWT_SFOR(e, 4)
-                    constexpr int dj = i - 4 * GL - e;
-                    if constexpr (dj % EW == 0) {
-                        constexpr int j = dj / EW + LH;
-                        if constexpr (j >= 0 && j < L) {
-                            p0[e] += tp.lo[0][j] * wa0;
-                            p0[e] += tp.hi[0][j] * wd0;
-                            p1[e] += tp.lo[0][j] * wa1;
-                            p1[e] += tp.hi[0][j] * wd1;
-                        }
-                    }
-                NDWT_SEND
-            }
-        NDWT_SEND
-        NDWT_SFOR(j, L)
-            constexpr int slot = ((R - 1 - j) % L + L) % L;
-            NDWT_SFOR(e, 4)
-                const T c = tp.lo[1][j] * p0[e] + tp.hi[1][j] * p1[e];
-                if constexpr (j == 0) st.yacc[C][slot][e] = c;
-                else st.yacc[C][slot][e] += c;
-            NDWT_SEND
-        NDWT_SEND
-        constexpr int done = ((R - L) % L + L) % L;
-        const v4 o = {st.yacc[C][done][0], st.yacc[C][done][1], st.yacc[C][done][2], st.yacc[C][done][3]};
-        if constexpr (C + 1 < NLEV) {
-            st.cur[C + 1] = o;
-        } else {
-            const int gx = x0 + 4 * (tid - NLEV * GL);
-            if (!emit || tid < NLEV * GL || tid >= NLEV * GL + WX / 4 || gx >= a.n1) return;
-            stream_store(reinterpret_cast<v4*>(a.out + (long long)y * a.rs + gx), o, a.nt);
-        }
+        xsyn_rows<G>(ex, st, tid, tp, NDWT_ROW((apx<C, S>(s))), NDWT_ROW(s.raw[C][S][1]), NDWT_ROW(s.raw[C][S][2]), NDWT_ROW(s.raw[C][S][3]), p0, p1);
+        put_row<C>(st, a, ysyn_scatter_row<R>(st.yacc[C], tp, p0, p1), x0, y, emit, tid);
     }
     // step p of the march (K = p % L): every level consumes its row, then the consumed load slots are refilled with the rows of step p + PD
     template <int K, class Exec>
@@ -3394,12 +3053,6 @@ template <typename T, int L_, bool SYN> struct AxisMarch {
             if (emit) *reinterpret_cast<v4*>(a.out0 + st.base_out + z * a.inner) = st.win[((R - L) % L + L) % L];
         }
     }
-    template <int R> static NDWT_DEV void dispatch(int r, State& st, const Args& a, const Taps& tp, long long z, bool emit) {
-        if constexpr (R < L) {
-            if (r == R) step<R>(st, a, tp, z, emit);
-            else dispatch<R + 1>(r, st, a, tp, z, emit);
-        }
-    }
     template <class Exec> static NDWT_DEV void block(Exec& ex, Shared&, const Args& a, const Taps& tp, int bid) {
         // bid -> (block of 256 items, chunk); an item = (outer index, group of 4 contiguous elements), so short
         // contiguous runs (the dilated contiguous axis has inner = stride) still fill the workgroup
@@ -3425,7 +3078,10 @@ template <typename T, int L_, bool SYN> struct AxisMarch {
         for (int p = 0; p < nplanes; ++p) {
             const int s = p - (L - 1);                    // output step completed by plane p
             ex.each([&](int, State& st) __attribute__((always_inline)) {
-                dispatch<0>((p + 1) % L, st, a, tp, zbeg + s, s >= 0 && st.active);
+                const int rot = (p + 1) % L;
+                const long long z = zbeg + s;
+                const bool emit = s >= 0 && st.active;
+                rot_dispatch<L>(rot, [&](auto R) __attribute__((always_inline)) { step<decltype(R)::value>(st, a, tp, z, emit); });
                 load(st, a, zbeg - LH + (p + 1 < nplanes ? p + 1 : p));
             });
         }
@@ -3449,11 +3105,11 @@ template <typename T> struct AxisXArgs {
 };
 
 template <typename T, int L_, bool SYN, int EW_, bool VEC4_> struct AxisX {
+    typedef WaveRowGeom<T, L_, EW_, SYN> G;
     static constexpr int L = L_, EW = EW_, NT = 256, WPE = 4;
     static constexpr bool VEC4 = VEC4_;
-    static constexpr int LH = SYN ? L / 2 : L / 2 - 1, RH = SYN ? L / 2 - 1 : L / 2;
-    static constexpr int GL = (LH * EW + 3) / 4, GR = (RH * EW + 3) / 4;
-    static constexpr int WX = 4 * (64 - GL - GR);        // output scalars per wave segment
+    static constexpr int LH = G::LH, RH = G::RH, GL = G::GL, GR = G::GR;
+    static constexpr int WX = G::WX;                     // output scalars per wave segment
     static_assert(GL + GR < 32, "filter too long for one wave");
     typedef typename VecT<T>::v4 v4;
     typedef MarchTaps<T, L> Taps;
@@ -3465,6 +3121,8 @@ template <typename T, int L_, bool SYN, int EW_, bool VEC4_> struct AxisX {
         int xg;            // first scalar of this lane inside the row (may be outside [0,row) for halo lanes)
         int valid;
     };
+    // (this load and the store of compute() are AxisX's own: a row is addressed by the 64-bit xg with a wrap per access, not by the
+    // wrapped offsets of lane_offsets, and the stores are plain, not streaming -- Fwd2S / Inv2S share load_lane_rows / store_lane_rows)
     static NDWT_DEV void load(State& st, const Args& a) {
         NDWT_SFOR(b, (SYN ? 2 : 1))
             const T* p = (b == 0 ? a.in0 : a.in1) + st.ibase;
@@ -3480,22 +3138,9 @@ template <typename T, int L_, bool SYN, int EW_, bool VEC4_> struct AxisX {
         NDWT_SEND
     }
     template <class Exec> static NDWT_DEV void compute(Exec& ex, State& st, const Args& a, const Taps& tp, int tid) {
-        v4 o0 = (v4)(T(0)), o1 = (v4)(T(0));
-        NDWT_SFOR(e, 4)
-            NDWT_SFOR(j, L)
-                constexpr int idx = e + (j - LH) * EW + 4 * GL;      // scalar index in the wave-local window, >= 0
-                constexpr int D = idx / 4 - GL;
-                constexpr int c = idx % 4;
-                if constexpr (!SYN) {
-                    const T v = NDWT_LANE_SHIFT(ex, tid, D, s.raw[0][c]);
-                    o0[e] += tp.lo[j] * v;
-                    o1[e] += tp.hi[j] * v;
-                } else {
-                    o0[e] += tp.lo[j] * NDWT_LANE_SHIFT(ex, tid, D, s.raw[0][c]);
-                    o0[e] += tp.hi[j] * NDWT_LANE_SHIFT(ex, tid, D, s.raw[1][c]);
-                }
-            NDWT_SEND
-        NDWT_SEND
+        v4 o0, o1;
+        if constexpr (!SYN) row_filter_ana<G, false>(ex, st, tid, tp.lo, tp.hi, NDWT_ROW(s.raw[0]), o0, o1);
+        else row_filter_syn<G, false>(ex, st, tid, tp.lo, tp.hi, NDWT_ROW(s.raw[0]), NDWT_ROW(s.raw[1]), o0);
         const int lane = tid % 64;
         if (!st.valid || lane < GL || lane >= 64 - GR || st.xg >= a.row) return;
         if constexpr (VEC4) {

@@ -8,20 +8,14 @@
 // One wave per (row, segment) item, as AxisX: lane l holds the 4 scalars at xg = seg0 + 4 (l - NLEV GL) of the row (wrapped), its
 // neighbours come from the adjacent lanes by DPP wave shifts.  Every level costs GL lanes on the left and GR on the right, so level k
 // (1 = first computed) is valid in lanes [k GL, 64 - k GR); a wave stores the lanes valid at every level, rounded down to whole
-// 128-byte lines (the rule of Fwd2C), and every band from that same window.  The FMAs of a level are those of AxisX::compute in the
-// same order, so the result equals NLEV launches of AxisX<T, L, SYN, EW, true> bit for bit.
+// 128-byte lines (the rule of Fwd2C), and every band from that same window.  A level is the row filter AxisX::compute runs
+// (row_filter_ana / row_filter_syn, ndwt_wave_row.h), so the result equals NLEV launches of AxisX<T, L, SYN, EW, true> bit for bit.
 //
 // Written like the fused kernels: per-lane stages driven through an executor, so the same source runs under the host emulator.
 #pragma once
 #include "ndwt_device.h"
 
 namespace ndwt {
-
-// A level's sums are written as explicit fused multiply-adds: AxisX's `acc += tap * v` compiles to FMA chains in every instance, and so
-// must these for the bits to agree -- left to the compiler, the SLP vectorizer splits some chains of the longer bodies here into a
-// packed multiply and separate adds (two roundings instead of one).
-NDWT_DEV float fma1(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-NDWT_DEV double fma1(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
 template <typename T> struct Fused1CArgs {
     const T* in[5];        // analysis: in[0] the signals; synthesis: [0] the approximation of the coarsest level, [1 + c] the detail band of
@@ -35,11 +29,9 @@ template <typename T> struct Fused1CArgs {
 
 // what both directions share: the geometry of a wave and the (row, segment) item of a lane
 template <typename T, int L_, int NLEV_, int EW_, bool SYN> struct Cascade1Geom {
-    static constexpr int L = L_, NLEV = NLEV_, EW = EW_, NT = 256;
-    static constexpr int LH = SYN ? L / 2 : L / 2 - 1, RH = SYN ? L / 2 - 1 : L / 2;
-    static constexpr int GL = (LH * EW + 3) / 4, GR = (RH * EW + 3) / 4;
-    static constexpr int LPL = 32 / (int)sizeof(T);      // lanes to the 128-byte line (a lane stores 4 scalars)
-    static constexpr int WX = 4 * ((64 - NLEV * (GL + GR)) / LPL * LPL);   // output scalars per wave segment
+    typedef WaveRowGeom<T, L_, EW_, SYN, NLEV_> W;
+    static constexpr int NLEV = NLEV_, NT = 256;
+    static constexpr int LH = W::LH, RH = W::RH, GL = W::GL, GR = W::GR, WX = W::WX;   // WX: output scalars per wave segment
     static_assert(NLEV >= 2 && NLEV <= 4, "two to four levels per launch");
     static_assert(WX > 0, "no lane is valid at every level");
     // fills the lane's place in its row; returns the offset of its 4 scalars (wrapped) from the band pointers
@@ -75,19 +67,10 @@ template <typename T, int L_, int NLEV_, int EW_ = 1, int WPE_ = 4> struct Fwd1C
         int xg;            // first scalar of this lane inside the row (outside [0, row) for halo lanes)
         int valid;
     };
-    // one level: AxisX::compute on st.cur; the detail band to memory, the approximation to st.nxt
+    // one level: AxisX's row filter on st.cur; the detail band to memory, the approximation to st.nxt
     template <int LEV, class Exec> static NDWT_DEV void level(Exec& ex, State& st, const Args& a, const Taps& tp, int tid) {
-        v4 o0 = (v4)(T(0)), o1 = (v4)(T(0));
-        NDWT_SFOR(e, 4)
-            NDWT_SFOR(j, L)
-                constexpr int idx = e + (j - LH) * EW + 4 * GL;      // scalar index in the wave-local window, >= 0
-                constexpr int D = idx / 4 - GL;
-                constexpr int c = idx % 4;
-                const T v = NDWT_LANE_SHIFT(ex, tid, D, s.cur[c]);
-                o0[e] = fma1(tp.lo[0][j], v, o0[e]);
-                o1[e] = fma1(tp.hi[0][j], v, o1[e]);
-            NDWT_SEND
-        NDWT_SEND
+        v4 o0, o1;
+        row_filter_ana<typename G::W, true>(ex, st, tid, tp.lo[0], tp.hi[0], NDWT_ROW(s.cur), o0, o1);
         st.nxt = o0;
         if (!G::stores(st, a, tid)) return;
         const long long off = st.base + st.xg;
@@ -122,18 +105,10 @@ template <typename T, int L_, int NLEV_, int EW_ = 1, int WPE_ = 4> struct Inv1C
         int xg;
         int valid;
     };
-    // one level: AxisX::compute (synthesis) on st.cur and st.det[LEV]; its output is the approximation of the next finer level
+    // one level: AxisX's row filter (synthesis) on st.cur and st.det[LEV]; its output is the approximation of the next finer level
     template <int LEV, class Exec> static NDWT_DEV void level(Exec& ex, State& st, const Args& a, const Taps& tp, int tid) {
-        v4 o0 = (v4)(T(0));
-        NDWT_SFOR(e, 4)
-            NDWT_SFOR(j, L)
-                constexpr int idx = e + (j - LH) * EW + 4 * GL;
-                constexpr int D = idx / 4 - GL;
-                constexpr int c = idx % 4;
-                o0[e] = fma1(tp.lo[0][j], NDWT_LANE_SHIFT(ex, tid, D, s.cur[c]), o0[e]);
-                o0[e] = fma1(tp.hi[0][j], NDWT_LANE_SHIFT(ex, tid, D, s.det[LEV][c]), o0[e]);
-            NDWT_SEND
-        NDWT_SEND
+        v4 o0;
+        row_filter_syn<typename G::W, true>(ex, st, tid, tp.lo[0], tp.hi[0], NDWT_ROW(s.cur), NDWT_ROW(s.det[LEV]), o0);
         st.nxt = o0;
         if constexpr (LEV == NLEV - 1) {
             if (G::stores(st, a, tid)) *reinterpret_cast<v4*>(a.out[0] + st.base + st.xg) = o0;

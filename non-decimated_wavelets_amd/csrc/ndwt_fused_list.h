@@ -288,10 +288,7 @@ inline bool cascade2_instantiated(const Cascade2Instance& k) {
 }
 // scalars of a row one wave of the instance stores: the lanes inside the halo of every level, in whole 128-byte lines (Fwd2C::WX, Inv2C::WX;
 // the launch units check the geometry against the kernel's own)
-constexpr int cascade2_tile_width(const Cascade2Instance& k) {
-    const int LH = k.inverse ? k.Lp / 2 : k.Lp / 2 - 1, RH = k.inverse ? k.Lp / 2 - 1 : k.Lp / 2, lpl = k.f64 ? 4 : 8;
-    return 4 * ((64 - k.nlev * ((LH * k.ew + 3) / 4 + (RH * k.ew + 3) / 4)) / lpl * lpl);
-}
+constexpr int cascade2_tile_width(const Cascade2Instance& k) { return wave_row_width(k.inverse, k.Lp, k.ew, k.f64, k.nlev); }
 enum Cascade1Kind { kFwd1C, kInv1C };
 #define NDWT_IS_C(KIND, T, EW, L, NLEV) if (k == Cascade1Instance{k##KIND == kInv1C, sizeof(T) == 8, EW, L, NLEV}) return true;
 inline bool cascade1_instantiated(const Cascade1Instance& k) {
@@ -299,10 +296,7 @@ inline bool cascade1_instantiated(const Cascade1Instance& k) {
     return false;
 }
 // scalars of a row one wave of the instance stores (Fwd1C::WX, Inv1C::WX: the same rule as the 2-D cascade's)
-constexpr int cascade1_tile_width(const Cascade1Instance& k) {
-    const int LH = k.inverse ? k.Lp / 2 : k.Lp / 2 - 1, RH = k.inverse ? k.Lp / 2 - 1 : k.Lp / 2, lpl = k.f64 ? 4 : 8;
-    return 4 * ((64 - k.nlev * ((LH * k.ew + 3) / 4 + (RH * k.ew + 3) / 4)) / lpl * lpl);
-}
+constexpr int cascade1_tile_width(const Cascade1Instance& k) { return wave_row_width(k.inverse, k.Lp, k.ew, k.f64, k.nlev); }
 #define NDWT_IS_W(KIND, T, L, VEC4, WPE, EW) if (k == Fused2SInstance{k##KIND == kInv2S, sizeof(T) == 8, VEC4, L, EW, WPE}) return true;
 inline bool fused2s_instantiated(const Fused2SInstance& k) {
     NDWT_LIST_2S(NDWT_IS_W, Fwd2S) NDWT_LIST_2S(NDWT_IS_W, Inv2S)

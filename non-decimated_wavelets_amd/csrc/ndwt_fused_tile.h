@@ -42,4 +42,13 @@ constexpr int inv3y_zlds(int L, int depth, int ew = 1) { return ew != 1 ? 0 : (d
 // wave, 32 haloed rows -> 64 x 24.
 constexpr int inv3y_ty(int L, int ew = 1) { return ew == 4 ? (L <= 6 ? kInv3YTY : 24) : ew == 2 ? kInv3YTY : (L <= 16 ? kInv3YTY : (L <= 18 ? 24 : 28)); }
 constexpr int inv3y_tx(int L, int ew = 1) { return ew == 4 ? kInv3YTX : ew == 2 ? (L <= 10 ? kInv3YTX : 48) : (L <= 18 ? kInv3YTX : 48); }
+// THE width rule of the wave-per-row kernels (ndwt_wave_row.h: WaveRowGeom::WX) and of the host that lays their launches out: scalars of
+// a row one wave stores.  A lane holds 4 scalars; a level of Lp taps stepping over ew scalars costs GL halo lanes on the left and GR on
+// the right.  One level per launch (nlev = 1): every lane inside the halo.  A cascade of nlev levels: the lanes valid at every level,
+// rounded down to whole 128-byte lines (float 8 lanes to the line, double 4) so that no line of a band is shared by two waves.
+constexpr int wave_row_width(bool syn, int Lp, int ew, bool f64, int nlev) {
+    const int LH = syn ? Lp / 2 : Lp / 2 - 1, RH = syn ? Lp / 2 - 1 : Lp / 2, lpl = f64 ? 4 : 8;
+    const int GL = (LH * ew + 3) / 4, GR = (RH * ew + 3) / 4;
+    return nlev == 1 ? 4 * (64 - GL - GR) : 4 * ((64 - nlev * (GL + GR)) / lpl * lpl);
+}
 }  // namespace ndwt

@@ -329,10 +329,7 @@ inline Fused3Pick fused3_select(const Fused3Query& q) {
 }
 
 // ---- one fused 2-D launch
-constexpr int fused2_tile_width(bool inverse, int Lp, int ew) {
-    const int LH = inverse ? Lp / 2 : Lp / 2 - 1, RH = inverse ? Lp / 2 - 1 : Lp / 2;
-    return 4 * (64 - (LH * ew + 3) / 4 - (RH * ew + 3) / 4);
-}
+constexpr int fused2_tile_width(bool inverse, int Lp, int ew) { return wave_row_width(inverse, Lp, ew, false, 1); }
 struct Fused2Query {
     bool f64, inverse, vec4;
     int Lp, ew, dil, n1, n2;           // n1: scalars along x; n2: rows of the whole (undilated) image

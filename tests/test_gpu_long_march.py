@@ -1,7 +1,7 @@
 """Every fused kernel over full turns of its plane window.
 
 The fused kernels of csrc/ndwt_device.h keep a window of L planes (rows) and pick, at every step of their march, one of L compile-time
-specialisations of the step body (zdispatch / yzdispatch / ydispatch, the load slots of Inv2P / Inv2C): separate code with its own slot
+specialisations of the step body (zdispatch / yzdispatch / rot_dispatch, the load slots of Inv2P / Inv2C): separate code with its own slot
 indices, LDS slots (WLDS), register sets (DEPTH) and pending sums (ZLDS).  On the small shapes of tests/test_gpu_dispatch.py the launch
 geometry (csrc/ndwt_geom.h) fills the chip with chunks of 2 planes, so only the first few of the L specialisations ever store anything.
 
