@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <climits>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <type_traits>
@@ -21,6 +22,7 @@
 #include "ndwt_fused.h"
 #include "ndwt_geom.h"
 #include "ndwt_select.h"
+#include "ndwt_taps_host.h"
 #include "ndwt_trace.h"
 
 using namespace ndwt;
@@ -96,69 +98,113 @@ static constexpr size_t kApproxSkew = 0;
 #else
 static constexpr size_t kApproxSkew = 256;
 #endif
-struct ndwt_plan {
-    int ndim;
-    long long dims[NDWT_MAX_DIMS];
-    int order[NDWT_MAX_DIMS];          // K of dbK per axis
-    AxisFilter filt[NDWT_MAX_DIMS];
-    int dtype, complexity, l2, dilation, max_level, device, path;
-    size_t esize;                      // bytes per scalar
-    long long comp;                    // scalars per element (2 for interleaved complex)
-    long long vol;                     // scalars per band (a batched plan: of all its signals)
-    long long howmany;                 // ndwt_plan_create_many: signals of a batched 1-D plan, signal k at k * dims[0] elements; 0 = not batched
-    void* approx[2];                   // approximation ping-pong between levels: approx_base[i] + kApproxSkew bytes
-    void* approx_base[2];
-    void* tmp;                         // temporaries of the per-axis path / 4-D split
-    size_t tmp_bytes;
-    int target_blocks;                 // fused-kernel grid sizing: 0 = one round of resident workgroups (per kernel), else as given
-    int force_zchunk;
-    int zchunk_dir[2];                 // per-direction override of the marched chunk: [0] analysis, [1] synthesis (0 = auto)
-    int variant_fwd, variant_inv;      // fused-kernel variants (tuning experiments; same results: ndwt_select.h)
-    bool uniform_yz;                   // the y and z axes carry the same synthesis taps: Inv3Y then keeps one set of tap pairs for both
-    int num_cus;
-    int fp64_fused;                    // fp64: fused 3-D kernels (1) or the per-axis march kernels (0)
-    void* taps_dev[2];                 // device tap tables of the fused kernels: [0] analysis, [1] synthesis (Taps3<T, Lp>)
-    int shrink_mode;                   // ndwt_denoise, during its rec: 0 none, 1 soft, 2 hard -- fused into the synthesis kernels' loads
-    double shrink_thr;
-    void* coef;                        // coefficient scratch of ndwt_denoise (all bands of the last level used), lazily allocated
-    size_t coef_bytes;
-    void* taps_den;                    // device tap table of the fused level-1 denoising kernel (TapsDen<float, L>), built at plan creation where it applies
-    void* den_a1;                      // ndwt_denoise, fused level 1: the level-1 approximation / its reconstruction -- a scratch of its own (lazily
-                                       // allocated), not `tmp`: dec_impl / rec_impl run in between and may re-allocate that one
-    int fused_level1;                  // ndwt_denoise: 1 (default) level 1 in one launch where that is faster (tap lengths <= 6), 2 wherever the
-                                       // kernel exists (8 taps too: compute-bound there, +3 %), 0 never (the level-1 detail bands stay in memory)
-    // optional per-kernel timing with HIP events on the launch stream (bench.py's roofline figures)
-    int profiling;
-    std::vector<ProfRec>* prof;
-    long long* stamps;                 // diagnostic builds (-DNDWT_STAMPS): device buffer for the per-wave phase cycle sums
-    void* stage[2];                    // device staging of the host-pointer forms: [0] one band (x / the result), [1] all bands; lazily grown,
-    size_t stage_bytes[2];             // kept across calls (ndwt_plan_release_staging frees them)
-    int live_coefs;                    // ndwt_coef handles bound to this plan
-    int thin_slab;                     // slab plan whose outer axis is shorter than its filter: slab entry points only
-    int shard;                         // slab plans: the sharded axis (ndim-1, or 2 for a 4-D volume sharded on z); halos live on it
-    void* zin;                         // z-slabs, split-halo analysis: the slab assembled with its halo planes (lazily allocated)
-    size_t zin_bytes;
-    std::vector<hipEvent_t>* ev_pool;  // profiling events, reused
+// A device allocation owned by value: move-only, freed by its destructor (on the device that is current then).  It only ever grows, and
+// growing does not keep the contents: every user fills the buffer before reading it.
+struct DevBuf {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(ptr, o.ptr); std::swap(bytes, o.bytes); return *this; }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        bytes = 0;
+    }
+    // at least `need` bytes.  Large enough: nothing happens.  Else the device is synchronised (work in flight may still read the old
+    // block), the block freed and a new one allocated; on failure the buffer is empty.  what: "for temporaries", "of the staging buffer"
+    int grow(size_t need, const char* what, bool say_bytes = true) {
+        if (need <= bytes) return NDWT_OK;
+        if (ptr) {
+            HIP_TRY(hipDeviceSynchronize());
+            HIP_TRY(hipFree(ptr));
+            ptr = nullptr;
+            bytes = 0;
+        }
+        const hipError_t e = hipMalloc(&ptr, need);
+        if (e != hipSuccess) {
+            ptr = nullptr;
+            return say_bytes ? fail(NDWT_ERR_ALLOC, "hipMalloc(%zu bytes) %s failed: %s", need, what, hipGetErrorString(e))
+                             : fail(NDWT_ERR_ALLOC, "hipMalloc %s failed: %s", what, hipGetErrorString(e));
+        }
+        bytes = need;
+        return NDWT_OK;
+    }
+    // a table the kernels read: allocated and filled from host memory (synchronously)
+    int upload(const void* host, size_t n, const char* what) {
+        reset();
+        hipError_t e = hipMalloc(&ptr, n);
+        if (e == hipSuccess) { bytes = n; e = hipMemcpy(ptr, host, n, hipMemcpyHostToDevice); }
+        if (e == hipSuccess) return NDWT_OK;
+        reset();
+        return fail(NDWT_ERR_ALLOC, "uploading %s failed: %s", what, hipGetErrorString(e));
+    }
 };
 
-static int ensure_tmp(ndwt_plan* p, size_t bytes) {
-    if (bytes <= p->tmp_bytes) return NDWT_OK;
-    if (p->tmp) {
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipFree(p->tmp));
-        p->tmp = nullptr;
-        p->tmp_bytes = 0;
+struct ndwt_plan {
+    int ndim = 0;
+    long long dims[NDWT_MAX_DIMS] = {};
+    int order[NDWT_MAX_DIMS] = {};     // K of dbK per axis
+    AxisFilter filt[NDWT_MAX_DIMS] = {};
+    int dtype = 0, complexity = 0, l2 = 0, dilation = 0, max_level = 0, device = 0, path = NDWT_PATH_AUTO;
+    size_t esize = 0;                  // bytes per scalar
+    long long comp = 1;                // scalars per element (2 for interleaved complex)
+    long long vol = 0;                 // scalars per band (a batched plan: of all its signals)
+    long long howmany = 0;             // ndwt_plan_create_many: signals of a batched 1-D plan, signal k at k * dims[0] elements; 0 = not batched
+    DevBuf approx_base[2];             // approximation ping-pong between levels, each kApproxSkew bytes larger than a band: approx(i) is the band
+    DevBuf tmp;                        // temporaries of the per-axis path / 4-D split
+    int target_blocks = 0;             // fused-kernel grid sizing: 0 = one round of resident workgroups (per kernel), else as given
+    int force_zchunk = 0;
+    int zchunk_dir[2] = {0, 0};        // per-direction override of the marched chunk: [0] analysis, [1] synthesis (0 = auto)
+    int variant_fwd = 0, variant_inv = 0;   // fused-kernel variants (tuning experiments; same results: ndwt_select.h)
+    bool uniform_yz = false;           // the y and z axes carry the same synthesis taps: Inv3Y then keeps one set of tap pairs for both
+    int num_cus = 0;
+    int fp64_fused = 1;                // fp64: fused 3-D kernels (1) or the per-axis march kernels (0) -- measured: 256^3 fp64 db4 L3 2.5 ms
+                                       // fused (LDS analysis + lane-shift synthesis) vs 4.1 ms per-axis
+    DevBuf taps_dev[2];                // device tap tables of the fused kernels: [0] analysis (Taps3<T, Lp>), [1] synthesis (Taps3Y<T, Lp>)
+    int shrink_mode = 0;               // ndwt_denoise, during its rec: 0 none, 1 soft, 2 hard -- fused into the synthesis kernels' loads
+    double shrink_thr = 0;
+    DevBuf coef;                       // coefficient scratch of ndwt_denoise (all bands of the last level used), lazily allocated
+    DevBuf taps_den;                   // device tap table of the fused level-1 denoising kernel (TapsDen<float, L>), built at plan creation where it applies
+    DevBuf den_a1;                     // ndwt_denoise, fused level 1: the level-1 approximation / its reconstruction -- a scratch of its own (lazily
+                                       // allocated), not `tmp`: dec_impl / rec_impl run in between and may re-allocate that one
+    int fused_level1 = 1;              // ndwt_denoise: 1 (default) level 1 in one launch where that is faster (tap lengths <= 6), 2 wherever the
+                                       // kernel exists (8 taps too: compute-bound there, +3 %), 0 never (the level-1 detail bands stay in memory)
+    // optional per-kernel timing with HIP events on the launch stream (bench.py's roofline figures); a launch records through the
+    // const plan it is given
+    int profiling = 0;
+    mutable std::vector<ProfRec> prof;
+    mutable std::vector<hipEvent_t> ev_pool;   // profiling events, reused
+    long long* stamps = nullptr;       // diagnostic builds (-DNDWT_STAMPS): device buffer for the per-wave phase cycle sums
+    DevBuf stage[2];                   // device staging of the host-pointer forms: [0] one band (x / the result), [1] all bands; lazily grown,
+                                       // kept across calls (ndwt_plan_release_staging frees them)
+    int live_coefs = 0;                // ndwt_coef handles bound to this plan
+    int thin_slab = 0;                 // slab plan whose outer axis is shorter than its filter: slab entry points only
+    int shard = 0;                     // slab plans: the sharded axis (ndim-1, or 2 for a 4-D volume sharded on z); halos live on it
+    DevBuf zin;                        // z-slabs, split-halo analysis: the slab assembled with its halo planes (lazily allocated)
+
+    // 256 B off the allocation's (power-of-two) alignment: the approximation is then the one band of a level that does not share the
+    // address bits below 1 KiB with the packed detail bands (about a quarter of the pitched gain)
+    void* approx(int i) const { return (char*)approx_base[i].ptr + kApproxSkew; }
+    ~ndwt_plan() {                     // (the buffers free themselves; the caller has made the plan's device current)
+        for (auto& r : prof) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
+        for (auto e : ev_pool) (void)hipEventDestroy(e);
     }
-    hipError_t e = hipMalloc(&p->tmp, bytes);
-    if (e != hipSuccess) return fail(NDWT_ERR_ALLOC, "hipMalloc(%zu bytes) for temporaries failed: %s", bytes, hipGetErrorString(e));
-    p->tmp_bytes = bytes;
-    return NDWT_OK;
+};
+
+// The plan's scalar type as a type: f is a generic lambda, called with a float or a double (only its type matters).
+template <class F> static int with_scalar(const ndwt_plan* p, F&& f) { return p->dtype == NDWT_F32 ? f(float()) : f(double()); }
+// What an entry point does once its arguments are checked: make the plan's device current, then run f for the plan's scalar type.
+template <class F> static int on_device(const ndwt_plan* p, F&& f) {
+    HIP_TRY(hipSetDevice(p->device));
+    return with_scalar(p, f);
 }
 
 // Events come from a pool owned by the plan (get_profile returns them to it), and a launch that did not happen
 // (no instantiation: rc < 0, the caller falls through to another kernel) leaves no record.
 static bool prof_event(const ndwt_plan* p, hipEvent_t* e) {
-    if (!p->ev_pool->empty()) { *e = p->ev_pool->back(); p->ev_pool->pop_back(); return true; }
+    if (!p->ev_pool.empty()) { *e = p->ev_pool.back(); p->ev_pool.pop_back(); return true; }
     return hipEventCreate(e) == hipSuccess;
 }
 static void prof_begin(const ndwt_plan* p, int kind, hipStream_t s) {
@@ -166,19 +212,19 @@ static void prof_begin(const ndwt_plan* p, int kind, hipStream_t s) {
     ProfRec r;
     r.kind = kind;
     if (!prof_event(p, &r.start)) return;
-    if (!prof_event(p, &r.stop)) { p->ev_pool->push_back(r.start); return; }
+    if (!prof_event(p, &r.stop)) { p->ev_pool.push_back(r.start); return; }
     (void)hipEventRecord(r.start, s);
-    p->prof->push_back(r);
+    p->prof.push_back(r);
 }
 static void prof_end(const ndwt_plan* p, hipStream_t s, int rc = 0) {
-    if (!p->profiling || p->prof->empty()) return;
+    if (!p->profiling || p->prof.empty()) return;
     if (rc != 0) {                                        // nothing was launched: drop the record
-        p->ev_pool->push_back(p->prof->back().start);
-        p->ev_pool->push_back(p->prof->back().stop);
-        p->prof->pop_back();
+        p->ev_pool.push_back(p->prof.back().start);
+        p->ev_pool.push_back(p->prof.back().stop);
+        p->prof.pop_back();
         return;
     }
-    (void)hipEventRecord(p->prof->back().stop, s);
+    (void)hipEventRecord(p->prof.back().stop, s);
 }
 
 static long long level_stride(const ndwt_plan* p, int lev) { return p->dilation == NDWT_DILATION_ATROUS ? (1LL << (lev - 1)) : 1LL; }
@@ -334,9 +380,9 @@ template <typename T> static int per_axis_level(ndwt_plan* p, bool synthesis, co
     c.n_in = p->dims[sh] + (slab ? (long long)(p->filt[sh].len - 1) * stride : 0);
     // the temporaries hold haloed slabs, except in the analysis of an outer-axis slab: its first pass trims the halo
     c.vol_tmp = (synthesis || sh != d - 1) ? p->vol / p->dims[sh] * c.n_in : p->vol;
-    int rc = ensure_tmp(p, (size_t)(2 * (d - 1)) * (size_t)c.vol_tmp * sizeof(T));
+    int rc = p->tmp.grow((size_t)(2 * (d - 1)) * (size_t)c.vol_tmp * sizeof(T), "for temporaries");
     if (rc) return rc;
-    c.tmp = (T*)p->tmp;
+    c.tmp = (T*)p->tmp.ptr;
     return synthesis ? generic_synthesis<T>(c, d - 1, 0, in, out[0]) : generic_analysis<T>(c, d - 1, in[0], 0, out);
 }
 
@@ -449,7 +495,7 @@ template <typename T> static int fused3_run(const ndwt_plan* p, const Fused3Laun
     // (a tile narrower than whole lines -- the 48-wide pair-packed tiles of 20 taps / complex 12 taps -- would put tile edges inside
     // a line: two workgroups' partial nontemporal stores of one line, the read-modify-write case again)
     a.nt = ((long long)k.TX * (long long)sizeof(T)) % 128 == 0 ? nt_store_ok<T>(a.rs, a.plane, out_bstride, out, nout) : 0;
-    const void* td = p->taps_dev[inverse ? 1 : 0];
+    const void* td = p->taps_dev[inverse ? 1 : 0].ptr;
     if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
     prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
     const int rc = launch_fused3_pick(k, a, td, s);   // (-1: no unit has the instance -- after a pick that is an internal error)
@@ -499,7 +545,7 @@ template <typename T> static int fused2_run(const ndwt_plan* p, const Fused2Laun
     fused2_geometry(a, fused2_tile_width(inverse, Lp, q.ew), Lp, p->target_blocks > 0 ? p->target_blocks * 2 : k.waves, p->force_zchunk);
     if (dil > 1) a.rs = (int)(dil * p->dims[0]);   // 8 waves per CU: one round (measured optimum 1024^2 .. 4096^2)
     a.nt = nt_store_ok<T>(a.rs, a.rs, out_bstride, out, nout);
-    const void* td = p->taps_dev[inverse ? 1 : 0];
+    const void* td = p->taps_dev[inverse ? 1 : 0].ptr;
     if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
     prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
     const int rc = launch_fused2_pick(k, a, td, s);   // (-1, -2: after a pick, internal errors -- see fused3_run)
@@ -522,9 +568,9 @@ static long long slab_planes(const ndwt_plan* p, long long stride, bool slab) {
 template <typename T>
 static int analysis_4d(ndwt_plan* p, int Lp, const T* in, T* const* out, long long stride, long long nz_in, ZMode z, bool t_wrap, hipStream_t s) {
     const long long plane = p->comp * p->dims[0] * p->dims[1], band = plane * nz_in * p->dims[3], skew = 256 / (long long)sizeof(T);
-    int rc = ensure_tmp(p, (size_t)(2 * band + skew) * sizeof(T));
+    int rc = p->tmp.grow((size_t)(2 * band + skew) * sizeof(T), "for temporaries");
     if (rc) return rc;
-    T* lo = (T*)p->tmp;
+    T* lo = (T*)p->tmp.ptr;
     T* hi = lo + band + skew;
     const long long dims_t[NDWT_MAX_DIMS] = {p->dims[0], p->dims[1], nz_in, p->dims[3]};
     rc = axis_pass<T>(p, false, 3, dims_t, stride, t_wrap, in, nullptr, lo, hi, s);
@@ -549,9 +595,9 @@ template <typename T>
 static int synthesis_4d(ndwt_plan* p, int Lp, const T* const* in, T* out, long long stride, const Syn4& f, hipStream_t s) {
     const long long plane = p->comp * p->dims[0] * p->dims[1], vol3_out = plane * f.nz_out, pad = f.t_pad * vol3_out;
     const long long band = (f.frames + 2 * f.t_pad) * vol3_out, skew = f.t_pad ? 0 : 256 / (long long)sizeof(T);
-    int rc = ensure_tmp(p, (size_t)(2 * band + skew) * sizeof(T));
+    int rc = p->tmp.grow((size_t)(2 * band + skew) * sizeof(T), "for temporaries");
     if (rc) return rc;
-    T* bands[2] = {(T*)p->tmp, (T*)p->tmp + band + skew};
+    T* bands[2] = {(T*)p->tmp.ptr, (T*)p->tmp.ptr + band + skew};
     for (int h = 0; h < 2 && pad; ++h) {
         HIP_TRY(hipMemsetAsync(bands[h], 0, (size_t)pad * sizeof(T), s));
         HIP_TRY(hipMemsetAsync(bands[h] + band - pad, 0, (size_t)pad * sizeof(T), s));
@@ -681,7 +727,7 @@ template <class Args, class Launch> static int cascade2_launch(ndwt_plan* p, Arg
     a.nyc = (a.n2 + yc - 1) / yc;
     a.ychunk = (a.n2 + a.nyc - 1) / a.nyc;
     a.nyc = (a.n2 + a.ychunk - 1) / a.ychunk;
-    const void* td = p->taps_dev[inverse ? 1 : 0];
+    const void* td = p->taps_dev[inverse ? 1 : 0].ptr;
     if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
     prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
     const int rc = launch(td);
@@ -721,13 +767,18 @@ template <typename T> static int cascade1_run(ndwt_plan* p, bool inverse, int L,
     a.row = p->dims[0] * p->comp;
     a.outer = p->howmany;
     a.nseg = (a.row + WX - 1) / WX;
-    const void* td = p->taps_dev[inverse ? 1 : 0];
+    const void* td = p->taps_dev[inverse ? 1 : 0].ptr;
     if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
     prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
     const int rc = launch_cascade1(k, a, td, s);
     prof_end(p, s, rc);
     if (rc > 0) return fail(NDWT_ERR_HIP, "cascaded 1-D %s launch failed: %s", inverse ? "synthesis" : "analysis", hipGetErrorString((hipError_t)rc));
     return rc < 0 ? -1 : 0;
+}
+
+// detail band b (1 .. 2^d - 1) of level `lev` in the coefficients y of a `level`-level transform (the bookkeeping above)
+template <typename T> static T* detail_band(const ndwt_plan* p, T* y, long long bs, int level, int lev, int b) {
+    return y + (long long)(1 + ((1 << p->ndim) - 1) * (level - lev) + (b - 1)) * bs;
 }
 
 template <typename T> static int dec_impl(ndwt_plan* p, const T* x, T* y, long long bs, int level, hipStream_t s) {
@@ -741,8 +792,8 @@ template <typename T> static int dec_impl(ndwt_plan* p, const T* x, T* y, long l
             const int last = lev + n - 1;
             const T* in[5] = {cur};
             T* out[5];
-            out[0] = (last == level) ? y : (T*)p->approx[pp];
-            for (int l = 0; l < n; ++l) out[1 + l] = y + (long long)(1 + (level - (lev + l))) * bs;
+            out[0] = (last == level) ? y : (T*)p->approx(pp);
+            for (int l = 0; l < n; ++l) out[1 + l] = detail_band(p, y, bs, level, lev + l, 1);
             const int rc = cascade1_run<T>(p, false, L1, n, in, out, s);
             if (rc == -1) break;                          // not this data: one launch per level from here on
             if (rc) return rc;
@@ -754,9 +805,9 @@ template <typename T> static int dec_impl(ndwt_plan* p, const T* x, T* y, long l
         while (const int n = cascade2_levels(sp, false, level - lev + 1, &Lp)) {   // levels lev .. lev + n - 1 in one launch
             const int last = lev + n - 1;
             T* out[10];
-            out[0] = (last == level) ? y : (T*)p->approx[pp];
+            out[0] = (last == level) ? y : (T*)p->approx(pp);
             for (int l = 0; l < n; ++l)                   // cascade level l (0 = first) is transform level lev + l
-                for (int b = 1; b < nb; ++b) out[1 + 3 * (n - 1 - l) + (b - 1)] = y + (long long)(1 + (nb - 1) * (level - (lev + l)) + (b - 1)) * bs;
+                for (int b = 1; b < nb; ++b) out[1 + 3 * (n - 1 - l) + (b - 1)] = detail_band(p, y, bs, level, lev + l, b);
             const int rc = cascade2_run<T>(p, Lp, n, cur, out, s);
             if (rc == -1) break;                          // not this data (alignment): one launch per level from here on
             if (rc) return rc;
@@ -767,8 +818,8 @@ template <typename T> static int dec_impl(ndwt_plan* p, const T* x, T* y, long l
     }
     for (; lev <= level; ++lev, pp ^= 1) {
         T* out[16];
-        out[0] = (lev == level) ? y : (T*)p->approx[pp];
-        for (int b = 1; b < nb; ++b) out[b] = y + (long long)(1 + (nb - 1) * (level - lev) + (b - 1)) * bs;
+        out[0] = (lev == level) ? y : (T*)p->approx(pp);
+        for (int b = 1; b < nb; ++b) out[b] = detail_band(p, y, bs, level, lev, b);
         int rc = analysis_level<T>(p, cur, out, level_stride(p, lev), false, s);
         if (rc) return rc;
         cur = out[0];
@@ -807,9 +858,9 @@ template <typename T> static int rec_impl(ndwt_plan* p, const T* y, long long bs
         while (const int n = cascade1_levels(sp, p->howmany, true, lev, &L1)) {   // a batched 1-D plan: levels lev, lev - 1, .. lev - n + 1
             const T* in[5];
             in[0] = prev;
-            for (int c = 0; c < n; ++c) in[1 + c] = y + (long long)(1 + (level - (lev - c))) * bs;
+            for (int c = 0; c < n; ++c) in[1 + c] = detail_band(p, y, bs, level, lev - c, 1);
             const int low = lev - n + 1;
-            T* dst[5] = {(low == 1) ? x : (T*)p->approx[pp]};
+            T* dst[5] = {(low == 1) ? x : (T*)p->approx(pp)};
             const int rc = cascade1_run<T>(p, true, L1, n, in, dst, s);
             if (rc == -1) break;
             if (rc) return rc;
@@ -822,9 +873,9 @@ template <typename T> static int rec_impl(ndwt_plan* p, const T* y, long long bs
             const T* in[10];
             in[0] = prev;
             for (int c = 0; c < n; ++c)                   // cascade level c (0 = coarsest) is transform level lev - c
-                for (int b = 1; b < nb; ++b) in[1 + 3 * c + (b - 1)] = y + (long long)(1 + (nb - 1) * (level - (lev - c)) + (b - 1)) * bs;
+                for (int b = 1; b < nb; ++b) in[1 + 3 * c + (b - 1)] = detail_band(p, y, bs, level, lev - c, b);
             const int low = lev - n + 1;
-            T* dst = (low == 1) ? x : (T*)p->approx[pp];
+            T* dst = (low == 1) ? x : (T*)p->approx(pp);
             const int rc = cascade2_rec_run<T>(p, Lp, n, in, dst, s);
             if (rc == -1) break;
             if (rc) return rc;
@@ -836,8 +887,8 @@ template <typename T> static int rec_impl(ndwt_plan* p, const T* y, long long bs
     for (; lev >= 1; --lev, pp ^= 1) {
         const T* in[16];
         in[0] = prev;
-        for (int b = 1; b < nb; ++b) in[b] = y + (long long)(1 + (nb - 1) * (level - lev) + (b - 1)) * bs;
-        T* dst = (lev == 1) ? x : (T*)p->approx[pp];
+        for (int b = 1; b < nb; ++b) in[b] = detail_band(p, y, bs, level, lev, b);
+        T* dst = (lev == 1) ? x : (T*)p->approx(pp);
         int rc = synthesis_level<T>(p, in, dst, level_stride(p, lev), false, s);
         if (rc) return rc;
         prev = dst;
@@ -1108,19 +1159,8 @@ template <typename T>
 static int slab_split_z_impl(ndwt_plan* p, const void* in, const void* hb, const void* ha, void* const* out, long long stride, hipStream_t s) {
     const long long ab = (long long)(p->filt[2].len / 2 - 1) * stride, aa = (long long)(p->filt[2].len / 2) * stride, n = p->dims[2];
     const long long P = p->comp * p->dims[0] * p->dims[1], nin = ab + n + aa;
-    const size_t bytes = (size_t)(P * nin * p->dims[3]) * sizeof(T);
-    if (bytes > p->zin_bytes) {
-        if (p->zin) {
-            HIP_TRY(hipDeviceSynchronize());
-            HIP_TRY(hipFree(p->zin));
-            p->zin = nullptr;
-            p->zin_bytes = 0;
-        }
-        hipError_t e = hipMalloc(&p->zin, bytes);
-        if (e != hipSuccess) return fail(NDWT_ERR_ALLOC, "hipMalloc(%zu bytes) for the z-extended slab failed: %s", bytes, hipGetErrorString(e));
-        p->zin_bytes = bytes;
-    }
-    T* z = (T*)p->zin;
+    if (const int rc = p->zin.grow((size_t)(P * nin * p->dims[3]) * sizeof(T), "for the z-extended slab")) return rc;
+    T* z = (T*)p->zin.ptr;
     void* dst[3];
     const void* src[3];
     int64_t cnt[3], dstr[3], sstr[3];
@@ -1164,7 +1204,7 @@ int ndwt_level_from_bands(int ndim, int64_t bands) {
     return (int)(1 + (bands - nb) / (nb - 1));
 }
 
-static bool den3_eligible(const ndwt_plan* p, int* Lp_out);
+static bool den3_eligible(const ndwt_plan* p, int fused_level1, int* Lp_out);
 static int den3_taps(ndwt_plan* p, int Lp);
 static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, long long global_outer, const char* const* wnames, int dtype,
                             int complexity, int pres_l2_norm, int dilation, int max_level, int device, int shard = -1, long long howmany = 0) {
@@ -1176,8 +1216,8 @@ static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, lon
     if (complexity != NDWT_REAL && complexity != NDWT_COMPLEX_INTERLEAVED) return fail(NDWT_ERR_INVALID_ARG, "bad complexity");
     if (dilation != NDWT_DILATION_REFERENCE && dilation != NDWT_DILATION_ATROUS) return fail(NDWT_ERR_INVALID_ARG, "bad dilation mode");
     if (max_level < 1 || max_level > 30) return fail(NDWT_ERR_INVALID_ARG, "max_level must be 1..30");
-    ndwt_plan* p = new ndwt_plan();
-    memset(p, 0, sizeof *p);
+    std::unique_ptr<ndwt_plan> owner(new ndwt_plan());    // a plan that fails below frees what it holds on the way out
+    ndwt_plan* const p = owner.get();
     p->ndim = ndim;
     p->dtype = dtype;
     p->complexity = complexity;
@@ -1185,109 +1225,56 @@ static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, lon
     p->dilation = dilation;
     p->max_level = max_level;
     p->device = device;
-    p->path = NDWT_PATH_AUTO;
     p->esize = dtype == NDWT_F32 ? 4 : 8;
     p->comp = complexity == NDWT_COMPLEX_INTERLEAVED ? 2 : 1;
-    p->target_blocks = 0;
-    p->prof = new std::vector<ProfRec>();
-    p->ev_pool = new std::vector<hipEvent_t>();
-    p->fused_level1 = 1;
     p->shard = shard >= 0 ? shard : ndim - 1;
-    p->fp64_fused = 1;   // measured: 256^3 fp64 db4 L3 2.5 ms fused (LDS analysis + lane-shift synthesis) vs 4.1 ms per-axis
     static const char* ordn[4] = {"First", "Second", "Third", "Fourth"};
     p->howmany = howmany;
     p->vol = p->comp * (howmany > 0 ? howmany : 1);
     for (int a = 0; a < ndim; ++a) {
-        if (dims[a] < 1) { delete p->prof; delete p->ev_pool; delete p; return fail(NDWT_ERR_INVALID_ARG, "dims[%d] must be >= 1", a); }
+        if (dims[a] < 1) return fail(NDWT_ERR_INVALID_ARG, "dims[%d] must be >= 1", a);
         const int K = parse_wavelet(wnames[a]);
-        if (!K) { delete p->prof; delete p->ev_pool; delete p; return fail(NDWT_ERR_UNKNOWN_WAVELET, "Unknown Wavelet Name"); }
+        if (!K) return fail(NDWT_ERR_UNKNOWN_WAVELET, "Unknown Wavelet Name");
         p->dims[a] = dims[a];
         p->order[a] = K;
         p->filt[a] = make_axis_filter(K, p->l2 != 0);
         // nd_dwt_3D.m:277-286; for a slab plan the check is on the whole sharded axis, not on the local planes
         const long long axis_len = (a == p->shard && global_outer > 0) ? global_outer : dims[a];
         if (a == p->shard && global_outer > 0 && p->filt[a].len > dims[a]) p->thin_slab = 1;
-        if (p->filt[a].len > axis_len) {
-            delete p->prof;
-            delete p->ev_pool;
-            delete p;
+        if (p->filt[a].len > axis_len)
             return fail(NDWT_ERR_FILTER_TOO_LONG, "%s Dimension of Data is shorter than the wavelet filter being used", ordn[a]);
-        }
         p->vol *= dims[a];
     }
     p->uniform_yz = ndim >= 3 && p->order[1] == p->order[2];   // (the same wavelet: the same taps)
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        delete p->prof;
-        delete p->ev_pool;
-        delete p;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev)
         return fail(NDWT_ERR_NO_DEVICE, "no usable HIP device (requested %d of %d): this engine has no CPU path", device, ndev);
-    }
-    if (hipSetDevice(device) != hipSuccess) { delete p->prof; delete p->ev_pool; delete p; return fail(NDWT_ERR_NO_DEVICE, "hipSetDevice(%d) failed", device); }
+    if (hipSetDevice(device) != hipSuccess) return fail(NDWT_ERR_NO_DEVICE, "hipSetDevice(%d) failed", device);
     {
         hipDeviceProp_t prop;
         p->num_cus = (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
     }
     const int napprox = max_level >= 3 ? 2 : (max_level == 2 ? 1 : 0);
-    for (int i = 0; i < napprox; ++i) {
-        // 256 B off the allocation's (power-of-two) alignment: the approximation is then the one band of a level that does not
-        // share the address bits below 1 KiB with the packed detail bands (about a quarter of the pitched gain)
-        hipError_t e = hipMalloc(&p->approx_base[i], (size_t)p->vol * p->esize + kApproxSkew);
-        if (e == hipSuccess) p->approx[i] = (char*)p->approx_base[i] + kApproxSkew;
-        if (e != hipSuccess) {
-            ndwt_plan_destroy(p);
-            return fail(NDWT_ERR_ALLOC, "hipMalloc of the approximation scratch failed: %s", hipGetErrorString(e));
-        }
-    }
+    for (int i = 0; i < napprox; ++i)
+        if (const int rc = p->approx_base[i].grow((size_t)p->vol * p->esize + kApproxSkew, "of the approximation scratch", false)) return rc;
     int Lp = level_route(sel(p), 1, 0, kWholeArray).Lp;
     // a batched 1-D plan whose levels can cascade (Fwd1C / Inv1C read Taps3<T, L>, axis 0): the table of its own tap length
     if (!Lp && howmany > 0 && p->filt[0].len <= 8 && (cascade1_instantiated({false, dtype == NDWT_F64, (int)p->comp, p->filt[0].len, 2}))) Lp = p->filt[0].len;
-    if (Lp) {   // a plan with fused levels (the analysis side admits the most tap lengths)
-        for (int inv = 0; inv < 2; ++inv) {
-            FusedTapsD t = fused_taps(p, Lp, inv != 0);
-            // synthesis table: Taps3Y = Taps3 followed by the x tap pairs (lo[0][k], lo[0][k-1]), k = 0..Lp, of the pair-packed kernel
-            std::vector<char> host((size_t)(6 * Lp + (inv ? 4 * (Lp + 1) : 0)) * p->esize);
-            for (int ax = 0; ax < 3; ++ax)
-                for (int j = 0; j < Lp; ++j) {
-                    if (dtype == NDWT_F32) {
-                        ((float*)host.data())[ax * Lp + j] = (float)t.lo[ax][j];
-                        ((float*)host.data())[3 * Lp + ax * Lp + j] = (float)t.hi[ax][j];
-                    } else {
-                        ((double*)host.data())[ax * Lp + j] = t.lo[ax][j];
-                        ((double*)host.data())[3 * Lp + ax * Lp + j] = t.hi[ax][j];
-                    }
-                }
-            if (inv) {
-                for (int k = 0; k <= Lp; ++k)
-                    for (int h = 0; h < 2; ++h) {
-                        const int j = k - h;                                  // (t[k], t[k-1])
-                        const double vlo = (j >= 0 && j < Lp) ? t.lo[0][j] : 0.0, vhi = (j >= 0 && j < Lp) ? t.hi[0][j] : 0.0;
-                        const size_t ilo = (size_t)6 * Lp + 2 * k + h, ihi = ilo + 2 * (Lp + 1);
-                        if (dtype == NDWT_F32) { ((float*)host.data())[ilo] = (float)vlo; ((float*)host.data())[ihi] = (float)vhi; }
-                        else { ((double*)host.data())[ilo] = vlo; ((double*)host.data())[ihi] = vhi; }
-                    }
-            }
-            hipError_t e = hipMalloc(&p->taps_dev[inv], host.size());
-            if (e == hipSuccess) e = hipMemcpy(p->taps_dev[inv], host.data(), host.size(), hipMemcpyHostToDevice);
-            if (e != hipSuccess) {
-                ndwt_plan_destroy(p);
-                return fail(NDWT_ERR_ALLOC, "uploading the tap table failed: %s", hipGetErrorString(e));
-            }
-        }
+    // a plan with fused levels (the analysis side admits the most tap lengths): Taps3, and for the synthesis Taps3Y -- the same, then the
+    // x tap pairs of the pair-packed kernel
+    for (int inv = 0; inv < 2 && Lp; ++inv) {
+        const int rc = with_scalar(p, [&](auto t) {
+            std::vector<decltype(t)> host;
+            append_taps3(host, fused_taps(p, Lp, inv != 0), inv != 0);
+            return p->taps_dev[inv].upload(host.data(), host.size() * sizeof(t), "the tap table");
+        });
+        if (rc) return rc;
     }
-    {   // the tap table of the fused level-1 denoising kernel, where that kernel can serve this plan: ndwt_denoise then only enqueues
-        // (den3_eligible is defined further down; the default fused_level1 = 1 admits up to 6 taps, 2 admits 8: build for 8)
-        int Lden = 0;
-        const int keep = p->fused_level1;
-        p->fused_level1 = 2;
-        const bool den = den3_eligible(p, &Lden);
-        p->fused_level1 = keep;
-        if (den && den3_taps(p, Lden) != NDWT_OK) {
-            ndwt_plan_destroy(p);
-            return NDWT_ERR_ALLOC;
-        }
-    }
-    *plan = p;
+    // the tap table of the fused level-1 denoising kernel, where that kernel can serve this plan: ndwt_denoise then only enqueues
+    // (the default fused_level1 = 1 admits up to 6 taps, 2 admits 8: build for 8)
+    int Lden = 0;
+    if (den3_eligible(p, 2, &Lden) && den3_taps(p, Lden) != NDWT_OK) return NDWT_ERR_ALLOC;
+    *plan = owner.release();
     return NDWT_OK;
 }
 
@@ -1333,25 +1320,6 @@ int ndwt_plan_destroy(ndwt_plan* p) {
     if (p->live_coefs > 0)                                // (a handle points back at its plan: release the handles first)
         return fail(NDWT_ERR_INVALID_ARG, "%d coefficient handle(s) of this plan are still alive: ndwt_coef_release them first", p->live_coefs);
     (void)hipSetDevice(p->device);
-    for (int i = 0; i < 2; ++i)
-        if (p->approx_base[i]) (void)hipFree(p->approx_base[i]);
-    if (p->tmp) (void)hipFree(p->tmp);
-    if (p->zin) (void)hipFree(p->zin);
-    if (p->coef) (void)hipFree(p->coef);
-    if (p->taps_den) (void)hipFree(p->taps_den);
-    if (p->den_a1) (void)hipFree(p->den_a1);
-    for (int i = 0; i < 2; ++i)
-        if (p->stage[i]) (void)hipFree(p->stage[i]);
-    for (int i = 0; i < 2; ++i)
-        if (p->taps_dev[i]) (void)hipFree(p->taps_dev[i]);
-    if (p->prof) {
-        for (auto& r : *p->prof) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
-        delete p->prof;
-    }
-    if (p->ev_pool) {
-        for (auto e : *p->ev_pool) (void)hipEventDestroy(e);
-        delete p->ev_pool;
-    }
     delete p;
     return NDWT_OK;
 }
@@ -1370,14 +1338,14 @@ int ndwt_plan_get_profile(ndwt_plan* p, int kind, double* total_ms, int64_t* lau
     double tot = 0;
     int64_t n = 0;
     std::vector<ProfRec> keep;
-    for (auto& r : *p->prof) {
+    for (auto& r : p->prof) {
         if (r.kind != kind) { keep.push_back(r); continue; }
         float ms = 0;
         if (hipEventElapsedTime(&ms, r.start, r.stop) == hipSuccess) { tot += ms; ++n; }
-        p->ev_pool->push_back(r.start);
-        p->ev_pool->push_back(r.stop);
+        p->ev_pool.push_back(r.start);
+        p->ev_pool.push_back(r.stop);
     }
-    p->prof->swap(keep);
+    p->prof.swap(keep);
     *total_ms = tot;
     *launches = n;
     return NDWT_OK;
@@ -1446,10 +1414,7 @@ int ndwt_dec_pitched(ndwt_plan* p, const void* x, void* y, int64_t band_pitch, i
     long long bs = 0;
     rc = pitch_scalars(p, band_pitch, &bs);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(p->device));
-    hipStream_t s = (hipStream_t)stream;
-    return p->dtype == NDWT_F32 ? dec_impl<float>(p, (const float*)x, (float*)y, bs, level, s)
-                                : dec_impl<double>(p, (const double*)x, (double*)y, bs, level, s);
+    return on_device(p, [&](auto t) { return dec_impl(p, (const decltype(t)*)x, (decltype(t)*)y, bs, level, (hipStream_t)stream); });
 }
 
 int ndwt_rec_pitched(ndwt_plan* p, const void* y, int64_t band_pitch, void* x, int level, void* stream) {
@@ -1459,10 +1424,7 @@ int ndwt_rec_pitched(ndwt_plan* p, const void* y, int64_t band_pitch, void* x, i
     long long bs = 0;
     rc = pitch_scalars(p, band_pitch, &bs);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(p->device));
-    hipStream_t s = (hipStream_t)stream;
-    return p->dtype == NDWT_F32 ? rec_impl<float>(p, (const float*)y, bs, (float*)x, level, s)
-                                : rec_impl<double>(p, (const double*)y, bs, (double*)x, level, s);
+    return on_device(p, [&](auto t) { return rec_impl(p, (const decltype(t)*)y, bs, (decltype(t)*)x, level, (hipStream_t)stream); });
 }
 
 int ndwt_dec(ndwt_plan* p, const void* x, void* y, int level, void* stream) { return ndwt_dec_pitched(p, x, y, 0, level, stream); }
@@ -1476,19 +1438,7 @@ int64_t ndwt_band_pitch(const ndwt_plan* p) {
 
 // Device staging of the host-pointer forms, owned by the plan and grown on demand: the gateway calls dec / rec with one configuration
 // thousands of times (README.md:2), and a hipMalloc + hipFree of the 12 GB a 512^3 3-level transform stages costs milliseconds per call.
-static int ensure_stage(ndwt_plan* p, int which, size_t bytes) {
-    if (bytes <= p->stage_bytes[which]) return NDWT_OK;
-    if (p->stage[which]) {
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipFree(p->stage[which]));
-        p->stage[which] = nullptr;
-        p->stage_bytes[which] = 0;
-    }
-    hipError_t e = hipMalloc(&p->stage[which], bytes);
-    if (e != hipSuccess) return fail(NDWT_ERR_ALLOC, "hipMalloc(%zu bytes) of the staging buffer failed: %s", bytes, hipGetErrorString(e));
-    p->stage_bytes[which] = bytes;
-    return NDWT_OK;
-}
+static int ensure_stage(ndwt_plan* p, int which, size_t bytes) { return p->stage[which].grow(bytes, "of the staging buffer"); }
 
 static int host_roundtrip(ndwt_plan* p, bool inverse, const void* src, void* dst, int level) {
     int rc = refuse_batched(p, "a host-pointer transform");
@@ -1502,7 +1452,7 @@ static int host_roundtrip(ndwt_plan* p, bool inverse, const void* src, void* dst
     rc = ensure_stage(p, 0, bx);
     if (rc == NDWT_OK) rc = ensure_stage(p, 1, by);
     if (rc) return rc;
-    void *dx = p->stage[0], *dy = p->stage[1];
+    void *dx = p->stage[0].ptr, *dy = p->stage[1].ptr;
     hipError_t e = hipMemcpy(inverse ? dy : dx, src, inverse ? by : bx, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         rc = inverse ? ndwt_rec(p, dy, dx, level, nullptr) : ndwt_dec(p, dx, dy, level, nullptr);
@@ -1517,11 +1467,8 @@ int ndwt_plan_release_staging(ndwt_plan* p) {
     if (!p) return fail(NDWT_ERR_INVALID_ARG, "null plan");
     HIP_TRY(hipSetDevice(p->device));
     HIP_TRY(hipDeviceSynchronize());
-    for (int i = 0; i < 2; ++i) {
-        if (p->stage[i]) (void)hipFree(p->stage[i]);
-        p->stage[i] = nullptr;
-        p->stage_bytes[i] = 0;
-    }
+    p->stage[0].reset();
+    p->stage[1].reset();
     return NDWT_OK;
 }
 
@@ -1531,8 +1478,7 @@ struct ndwt_coef {
     int level;
     long long bands;
     long long pitch;                   // elements between bands (ndwt_band_pitch)
-    void* dev;
-    size_t bytes;
+    DevBuf dev;
 };
 
 static int coef_check(const ndwt_plan* p, const ndwt_coef* c) {
@@ -1549,19 +1495,14 @@ int ndwt_coef_create(ndwt_plan* p, int level, ndwt_coef** out) {
     if (rc) return rc;
     if (!out) return fail(NDWT_ERR_INVALID_ARG, "null output pointer");
     HIP_TRY(hipSetDevice(p->device));
-    ndwt_coef* c = new ndwt_coef();
+    std::unique_ptr<ndwt_coef> c(new ndwt_coef());
     c->plan = p;
     c->level = level;
     c->bands = ndwt_num_bands(p->ndim, level);
     c->pitch = ndwt_band_pitch(p);
-    c->bytes = (size_t)c->bands * (size_t)c->pitch * (size_t)p->comp * p->esize;
-    hipError_t e = hipMalloc(&c->dev, c->bytes);
-    if (e != hipSuccess) {
-        delete c;
-        return fail(NDWT_ERR_ALLOC, "hipMalloc(%zu bytes) of a coefficient set failed: %s", (size_t)0 + c->bytes, hipGetErrorString(e));
-    }
+    if (const int rc = c->dev.grow((size_t)c->bands * (size_t)c->pitch * (size_t)p->comp * p->esize, "of a coefficient set")) return rc;
     p->live_coefs++;
-    *out = c;
+    *out = c.release();
     return NDWT_OK;
 }
 
@@ -1569,7 +1510,6 @@ int ndwt_coef_release(ndwt_coef* c) {
     if (!c) return NDWT_OK;
     (void)hipSetDevice(c->plan->device);
     (void)hipDeviceSynchronize();
-    if (c->dev) (void)hipFree(c->dev);
     c->plan->live_coefs--;
     delete c;
     return NDWT_OK;
@@ -1580,17 +1520,18 @@ int ndwt_coef_info(const ndwt_coef* c, int* level, int64_t* bands, int64_t* band
     if (level) *level = c->level;
     if (bands) *bands = c->bands;
     if (band_pitch) *band_pitch = c->pitch;
-    if (dev_ptr) *dev_ptr = c->dev;
+    if (dev_ptr) *dev_ptr = c->dev.ptr;
     return NDWT_OK;
 }
 
-// x (host) -> coefficients that STAY on the device: only the signal crosses PCIe (0.5 GB instead of 12.3 GB at 512^3, 3 levels)
-int ndwt_coef_dec_host(ndwt_plan* p, const void* x_host, int level, ndwt_coef** coef) {
+// The handle an upload fills, after the checks both uploads make: *coef where the caller passes one of this plan and level for reuse, else
+// a new one.  `fill` writes its coefficients; where that fails, a handle made here is released and *coef stays as it was.
+extern "C++" template <class F> static int coef_upload(ndwt_plan* p, int level, const void* host, ndwt_coef** coef, F&& fill) {
     int rc = refuse_batched(p, "a coefficient handle");
     if (rc) return rc;
     rc = check_level(p, level);
     if (rc) return rc;
-    if (!x_host || !coef) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
+    if (!host || !coef) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
     HIP_TRY(hipSetDevice(p->device));
     ndwt_coef* c = *coef;
     if (c && (c->plan != p || c->level != level)) return fail(NDWT_ERR_INVALID_ARG, "the handle passed for reuse holds another plan's / level's coefficients");
@@ -1599,18 +1540,29 @@ int ndwt_coef_dec_host(ndwt_plan* p, const void* x_host, int level, ndwt_coef** 
         rc = ndwt_coef_create(p, level, &c);
         if (rc) return rc;
     }
-    const size_t bx = (size_t)p->vol * p->esize;
-    rc = ensure_stage(p, 0, bx);
-    hipError_t e = hipSuccess;
-    if (rc == NDWT_OK) e = hipMemcpy(p->stage[0], x_host, bx, hipMemcpyHostToDevice);
-    if (rc == NDWT_OK && e == hipSuccess) rc = ndwt_dec_pitched(p, p->stage[0], c->dev, c->pitch, level, nullptr);
-    if (rc == NDWT_OK && e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (rc != NDWT_OK || e != hipSuccess) {
+    rc = fill(c);
+    if (rc) {
         if (fresh) ndwt_coef_release(c);
-        return rc ? rc : fail(NDWT_ERR_HIP, "staging copy failed: %s", hipGetErrorString(e));
+        return rc;
     }
     *coef = c;
     return NDWT_OK;
+}
+
+// x (host) -> coefficients that STAY on the device: only the signal crosses PCIe (0.5 GB instead of 12.3 GB at 512^3, 3 levels)
+int ndwt_coef_dec_host(ndwt_plan* p, const void* x_host, int level, ndwt_coef** coef) {
+    return coef_upload(p, level, x_host, coef, [&](ndwt_coef* c) {
+        const size_t bx = (size_t)p->vol * p->esize;
+        int rc = ensure_stage(p, 0, bx);
+        if (rc) return rc;
+        hipError_t e = hipMemcpy(p->stage[0].ptr, x_host, bx, hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            rc = ndwt_dec_pitched(p, p->stage[0].ptr, c->dev.ptr, c->pitch, level, nullptr);
+            if (rc) return rc;
+            e = hipStreamSynchronize(nullptr);
+        }
+        return e == hipSuccess ? NDWT_OK : fail(NDWT_ERR_HIP, "staging copy failed: %s", hipGetErrorString(e));
+    });
 }
 
 int ndwt_coef_rec_host(ndwt_plan* p, const ndwt_coef* c, void* x_host) {
@@ -1621,16 +1573,16 @@ int ndwt_coef_rec_host(ndwt_plan* p, const ndwt_coef* c, void* x_host) {
     const size_t bx = (size_t)p->vol * p->esize;
     rc = ensure_stage(p, 0, bx);
     if (rc) return rc;
-    rc = ndwt_rec_pitched(p, c->dev, c->pitch, p->stage[0], c->level, nullptr);
+    rc = ndwt_rec_pitched(p, c->dev.ptr, c->pitch, p->stage[0].ptr, c->level, nullptr);
     if (rc) return rc;
-    HIP_TRY(hipMemcpy(x_host, p->stage[0], bx, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(x_host, p->stage[0].ptr, bx, hipMemcpyDeviceToHost));
     return NDWT_OK;
 }
 
 int ndwt_coef_shrink(ndwt_plan* p, ndwt_coef* c, double threshold, int mode) {
     int rc = coef_check(p, c);
     if (rc) return rc;
-    rc = ndwt_shrink_pitched(p, c->dev, c->pitch, c->level, threshold, mode, nullptr);
+    rc = ndwt_shrink_pitched(p, c->dev.ptr, c->pitch, c->level, threshold, mode, nullptr);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return NDWT_OK;
@@ -1643,32 +1595,16 @@ int ndwt_coef_get_host(ndwt_plan* p, const ndwt_coef* c, void* y_host) {
     if (!y_host) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
     HIP_TRY(hipSetDevice(p->device));
     const size_t band = (size_t)p->vol * p->esize, pitch = (size_t)c->pitch * (size_t)p->comp * p->esize;
-    HIP_TRY(hipMemcpy2D(y_host, band, c->dev, pitch, band, (size_t)c->bands, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy2D(y_host, band, c->dev.ptr, pitch, band, (size_t)c->bands, hipMemcpyDeviceToHost));
     return NDWT_OK;
 }
 
 int ndwt_coef_put_host(ndwt_plan* p, int level, const void* y_host, ndwt_coef** coef) {
-    int rc = refuse_batched(p, "a coefficient handle");
-    if (rc) return rc;
-    rc = check_level(p, level);
-    if (rc) return rc;
-    if (!y_host || !coef) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
-    HIP_TRY(hipSetDevice(p->device));
-    ndwt_coef* c = *coef;
-    if (c && (c->plan != p || c->level != level)) return fail(NDWT_ERR_INVALID_ARG, "the handle passed for reuse holds another plan's / level's coefficients");
-    const bool fresh = c == nullptr;
-    if (fresh) {
-        rc = ndwt_coef_create(p, level, &c);
-        if (rc) return rc;
-    }
-    const size_t band = (size_t)p->vol * p->esize, pitch = (size_t)c->pitch * (size_t)p->comp * p->esize;
-    hipError_t e = hipMemcpy2D(c->dev, pitch, y_host, band, band, (size_t)c->bands, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (fresh) ndwt_coef_release(c);
-        return fail(NDWT_ERR_HIP, "upload of the coefficients failed: %s", hipGetErrorString(e));
-    }
-    *coef = c;
-    return NDWT_OK;
+    return coef_upload(p, level, y_host, coef, [&](ndwt_coef* c) {
+        const size_t band = (size_t)p->vol * p->esize, pitch = (size_t)c->pitch * (size_t)p->comp * p->esize;
+        const hipError_t e = hipMemcpy2D(c->dev.ptr, pitch, y_host, band, band, (size_t)c->bands, hipMemcpyHostToDevice);
+        return e == hipSuccess ? NDWT_OK : fail(NDWT_ERR_HIP, "upload of the coefficients failed: %s", hipGetErrorString(e));
+    });
 }
 
 int ndwt_dec_host(ndwt_plan* p, const void* x, void* y, int level) { return host_roundtrip(p, false, x, y, level); }
@@ -1690,9 +1626,7 @@ int ndwt_shrink_pitched(ndwt_plan* p, void* y, int64_t band_pitch, int level, do
     long long bs = 0;
     rc = pitch_scalars(p, band_pitch, &bs);
     if (rc) return rc;
-    HIP_TRY(hipSetDevice(p->device));
-    return p->dtype == NDWT_F32 ? shrink_impl<float>(p, (float*)y, bs, level, threshold, mode, (hipStream_t)stream)
-                                : shrink_impl<double>(p, (double*)y, bs, level, threshold, mode, (hipStream_t)stream);
+    return on_device(p, [&](auto t) { return shrink_impl(p, (decltype(t)*)y, bs, level, threshold, mode, (hipStream_t)stream); });
 }
 int ndwt_shrink(ndwt_plan* p, void* y, int level, double threshold, int mode, void* stream) {
     return ndwt_shrink_pitched(p, y, 0, level, threshold, mode, stream);
@@ -1700,15 +1634,16 @@ int ndwt_shrink(ndwt_plan* p, void* y, int level, double threshold, int mode, vo
 
 // ---- level 1 of a denoising step without its detail bands in memory (Den3, ndwt_device.h) ----
 // Float, real, 3-D, reference dilation, the same tap length L <= 8 on every axis, rows of whole 16-byte groups.
-static bool den3_eligible(const ndwt_plan* p, int* Lp_out) {
-    if (!p->fused_level1 || p->dtype != NDWT_F32 || p->complexity != NDWT_REAL || p->ndim != 3 || p->dilation != NDWT_DILATION_REFERENCE)
+// fused_level1: the setting asked about (ndwt_plan_set_fused_level1: the plan's own for a call, 2 for "does the kernel exist for this plan")
+static bool den3_eligible(const ndwt_plan* p, int fused_level1, int* Lp_out) {
+    if (!fused_level1 || p->dtype != NDWT_F32 || p->complexity != NDWT_REAL || p->ndim != 3 || p->dilation != NDWT_DILATION_REFERENCE)
         return false;
     const LevelRoute r = level_route(sel(p), 1, -1, kWholeArray);
     const int Lp = r.Lp;
     // measured, 512^3, 3 levels, ndwt_denoise with / without the fused level 1: db1 4.49 / 5.27 ms, db2 5.10 / 5.67, db3 5.72 / 6.09,
     // db4 6.30 / 6.13 -- with 8 taps the recomputation (2.3x the arithmetic of the synthesis kernel, 67 % VALU-busy) costs more than the
     // 13 volume transfers it removes, so 8 taps take the kernel only when asked to (ndwt_plan_set_fused_level1(plan, 2))
-    if (r.kind != kRouteFused3 || Lp > (p->fused_level1 >= 2 ? 8 : 6) || !inv3y_plan_ok(sel(p), Lp)) return false;
+    if (r.kind != kRouteFused3 || Lp > (fused_level1 >= 2 ? 8 : 6) || !inv3y_plan_ok(sel(p), Lp)) return false;
     for (int ax = 0; ax < 3; ++ax)
         if (p->filt[ax].len != Lp) return false;
     if (p->dims[0] % 4 != 0) return false;
@@ -1717,36 +1652,11 @@ static bool den3_eligible(const ndwt_plan* p, int* Lp_out) {
 }
 
 static int den3_taps(ndwt_plan* p, int Lp) {
-    if (p->taps_den) return NDWT_OK;
-    const FusedTapsD ts = fused_taps(p, Lp, true), ta = fused_taps(p, Lp, false);
-    std::vector<float> h;                                 // TapsDen<float, Lp>: Taps3Y (lo[3][L], hi[3][L], xplo[L+1][2], xphi[L+1][2]), alo[3][L], azp[L][2], axp[L+1][2]
-    for (int ax = 0; ax < 3; ++ax) for (int j = 0; j < Lp; ++j) h.push_back((float)ts.lo[ax][j]);
-    for (int ax = 0; ax < 3; ++ax) for (int j = 0; j < Lp; ++j) h.push_back((float)ts.hi[ax][j]);
-    for (int hi = 0; hi < 2; ++hi)
-        for (int k = 0; k <= Lp; ++k)
-            for (int hh = 0; hh < 2; ++hh) {
-                const int j = k - hh;
-                h.push_back((j >= 0 && j < Lp) ? (float)(hi ? ts.hi[0][j] : ts.lo[0][j]) : 0.0f);
-            }
-    for (int ax = 0; ax < 3; ++ax) for (int j = 0; j < Lp; ++j) h.push_back((float)ta.lo[ax][j]);
-    for (int j = 0; j < Lp; ++j) { h.push_back((float)ta.lo[2][j]); h.push_back((float)ta.hi[2][j]); }
-    for (int k = 0; k <= Lp; ++k)                         // axp[L+1][2]: (alo_x[k], alo_x[k-1])
-        for (int hh = 0; hh < 2; ++hh) {
-            const int j = k - hh;
-            h.push_back((j >= 0 && j < Lp) ? (float)ta.lo[0][j] : 0.0f);
-        }
-    // the kernel derives the analysis high-pass taps of x and y from the low-pass ones: ahi[j] = (-1)^j alo[L-1-j]
-    for (int ax = 0; ax < 2; ++ax)
-        for (int j = 0; j < Lp; ++j)
-            if ((float)ta.hi[ax][j] != ((j % 2) ? -1.0f : 1.0f) * (float)ta.lo[ax][Lp - 1 - j])
-                return fail(NDWT_ERR_UNSUPPORTED, "internal: analysis taps are not a mirrored pair");
-    hipError_t e = hipMalloc(&p->taps_den, h.size() * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(p->taps_den, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        if (p->taps_den) { (void)hipFree(p->taps_den); p->taps_den = nullptr; }
-        return fail(NDWT_ERR_ALLOC, "uploading the tap table of the fused level-1 kernel failed: %s", hipGetErrorString(e));
-    }
-    return NDWT_OK;
+    if (p->taps_den.ptr) return NDWT_OK;
+    std::vector<float> h;                                 // TapsDen<float, Lp>
+    if (!build_taps_den(h, fused_taps(p, Lp, true), fused_taps(p, Lp, false)))
+        return fail(NDWT_ERR_UNSUPPORTED, "internal: analysis taps are not a mirrored pair");
+    return p->taps_den.upload(h.data(), h.size() * sizeof(float), "the tap table of the fused level-1 kernel");
 }
 
 // kind 0: approximation band of one analysis level (x -> out);  kind 1: Den3 (x, approximation -> out)
@@ -1772,7 +1682,7 @@ static int den3_launch(ndwt_plan* p, int kind, int Lp, const float* x, const flo
     a.nt = nt_store_ok<float>(a.rs, a.plane, p->vol, outs, 1);
     prof_begin(p, kind == 1 ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
     const bool vec4 = aligned_vec4<float>(x) && aligned_vec4<float>(out);
-    int rc = kind == 1 ? launch_den3_f32(a, Lp, p->taps_den, s) : launch_fwd3_low_f32(a, Lp, vec4, small_tile ? 0 : 2, p->taps_dev[0], s);
+    int rc = kind == 1 ? launch_den3_f32(a, Lp, p->taps_den.ptr, s) : launch_fwd3_low_f32(a, Lp, vec4, small_tile ? 0 : 2, p->taps_dev[0].ptr, s);
     prof_end(p, s, rc);
     if (rc == -1) return fail(NDWT_ERR_UNSUPPORTED, "fused level-1 kernel not instantiated for tap length %d", Lp);
     if (rc == -2) return fail(NDWT_ERR_UNSUPPORTED, "internal: launch geometry does not match the level-1 kernel's tile");
@@ -1780,19 +1690,7 @@ static int den3_launch(ndwt_plan* p, int kind, int Lp, const float* x, const flo
     return NDWT_OK;
 }
 
-static int ensure_coef(ndwt_plan* p, size_t need) {
-    if (need <= p->coef_bytes) return NDWT_OK;
-    if (p->coef) {
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipFree(p->coef));
-        p->coef = nullptr;
-        p->coef_bytes = 0;
-    }
-    hipError_t e = hipMalloc(&p->coef, need);
-    if (e != hipSuccess) return fail(NDWT_ERR_ALLOC, "hipMalloc(%zu bytes) for the coefficient scratch failed: %s", need, hipGetErrorString(e));
-    p->coef_bytes = need;
-    return NDWT_OK;
-}
+static int ensure_coef(ndwt_plan* p, size_t need) { return p->coef.grow(need, "for the coefficient scratch"); }
 
 // dec -> shrink -> rec with level 1 fused: x -> approximation of level 1 (band 0 only) -> levels 2 .. `level` as a (level - 1)-level
 // transform of that band (the reference applies the same filters at every level, nd_dwt_3D.m:178-186) with the thresholding in the
@@ -1800,19 +1698,17 @@ static int ensure_coef(ndwt_plan* p, size_t need) {
 static int denoise_fused_level1(ndwt_plan* p, int Lp, const float* x, float* out, int level, double threshold, int mode, hipStream_t s) {
     int rc = den3_taps(p, Lp);
     if (rc) return rc;
-    if (!p->den_a1) {
-        hipError_t e = hipMalloc(&p->den_a1, (size_t)p->vol * sizeof(float) + kApproxSkew);
-        if (e != hipSuccess) return fail(NDWT_ERR_ALLOC, "hipMalloc of the level-1 approximation scratch failed: %s", hipGetErrorString(e));
-    }
-    float* a1 = (float*)((char*)p->den_a1 + kApproxSkew);   // level-1 approximation, then its reconstruction (256 B off the alignment, like the ping-pong scratch)
+    rc = p->den_a1.grow((size_t)p->vol * sizeof(float) + kApproxSkew, "of the level-1 approximation scratch", false);
+    if (rc) return rc;
+    float* a1 = (float*)((char*)p->den_a1.ptr + kApproxSkew);   // level-1 approximation, then its reconstruction (256 B off the alignment, like the ping-pong scratch)
     p->shrink_mode = mode == NDWT_SHRINK_HARD ? 2 : 1;
     p->shrink_thr = threshold;
     rc = den3_launch(p, 0, Lp, x, nullptr, a1, s);
     if (rc == NDWT_OK && level > 1) {
         const int64_t pitch = ndwt_band_pitch(p);
         rc = ensure_coef(p, (size_t)pitch * p->esize * (size_t)ndwt_num_bands(3, level - 1));
-        if (rc == NDWT_OK) rc = dec_impl<float>(p, a1, (float*)p->coef, pitch, level - 1, s);
-        if (rc == NDWT_OK) rc = rec_impl<float>(p, (const float*)p->coef, pitch, a1, level - 1, s);   // (thresholding in the band loads)
+        if (rc == NDWT_OK) rc = dec_impl<float>(p, a1, (float*)p->coef.ptr, pitch, level - 1, s);
+        if (rc == NDWT_OK) rc = rec_impl<float>(p, (const float*)p->coef.ptr, pitch, a1, level - 1, s);   // (thresholding in the band loads)
     }
     if (rc == NDWT_OK) rc = den3_launch(p, 1, Lp, x, a1, out, s);
     p->shrink_mode = 0;
@@ -1831,26 +1727,27 @@ int ndwt_denoise(ndwt_plan* p, const void* x, void* out, int level, double thres
         const char *xb = (const char*)x, *ob = (const char*)out;
         const size_t nbytes = (size_t)p->vol * p->esize;
         const bool disjoint = xb + nbytes <= ob || ob + nbytes <= xb;
-        if (den3_eligible(p, &Lp1) && disjoint && aligned_vec4<float>(x) && aligned_vec4<float>(out))
+        if (den3_eligible(p, p->fused_level1, &Lp1) && disjoint && aligned_vec4<float>(x) && aligned_vec4<float>(out))
             return denoise_fused_level1(p, Lp1, (const float*)x, (float*)out, level, threshold, mode, (hipStream_t)stream);
     }
     // the scratch coefficients are pitched (ndwt_band_pitch): nobody else reads them
     const int64_t pitch = ndwt_band_pitch(p);
     rc = ensure_coef(p, (size_t)pitch * p->comp * p->esize * (size_t)ndwt_num_bands(p->ndim, level));
     if (rc) return rc;
-    rc = ndwt_dec_pitched(p, x, p->coef, pitch, level, stream);
+    void* const coef = p->coef.ptr;
+    rc = ndwt_dec_pitched(p, x, coef, pitch, level, stream);
     if (rc) return rc;
     if (fused_shrink_capable(sel(p))) {
         // every level is reconstructed by a lane-shift kernel: the detail bands are thresholded in registers as that
         // kernel loads them, and the separate pass (a read and a write of every detail band) disappears
         p->shrink_mode = mode == NDWT_SHRINK_HARD ? 2 : 1;
         p->shrink_thr = threshold;
-        rc = ndwt_rec_pitched(p, p->coef, pitch, out, level, stream);
+        rc = ndwt_rec_pitched(p, coef, pitch, out, level, stream);
         p->shrink_mode = 0;
         return rc;
     }
-    rc = ndwt_shrink_pitched(p, p->coef, pitch, level, threshold, mode, stream);
-    if (rc == NDWT_OK) rc = ndwt_rec_pitched(p, p->coef, pitch, out, level, stream);
+    rc = ndwt_shrink_pitched(p, coef, pitch, level, threshold, mode, stream);
+    if (rc == NDWT_OK) rc = ndwt_rec_pitched(p, coef, pitch, out, level, stream);
     return rc;
 }
 
@@ -1864,7 +1761,7 @@ int ndwt_denoise_host(ndwt_plan* p, const void* x, void* out, int level, double 
     const size_t bx = (size_t)p->vol * p->esize;
     rc = ensure_stage(p, 0, 2 * bx);                      // the signal and the result, side by side (kept across calls)
     if (rc) return rc;
-    void *dx = p->stage[0], *dout = (char*)p->stage[0] + bx;
+    void *dx = p->stage[0].ptr, *dout = (char*)dx + bx;
     hipError_t e = hipMemcpy(dx, x, bx, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         rc = ndwt_denoise(p, dx, dout, level, threshold, mode, nullptr);
@@ -1877,46 +1774,27 @@ int ndwt_denoise_host(ndwt_plan* p, const void* x, void* out, int level, double 
 
 // Split complex (separate real / imaginary arrays: mxGetPr / mxGetPi of nd_dwt_mex.c:55-58).  The filters are
 // real, so the complex transform is the real transform of each part: a REAL plan is run once per part.
-static int split_check(const ndwt_plan* p) {
+// one(in, out): the real transform of one part
+extern "C++" template <class F> static int split_run(const ndwt_plan* p, const void* in_re, const void* in_im, void* out_re, void* out_im, F&& one) {
     if (!p) return fail(NDWT_ERR_INVALID_ARG, "null plan");
     if (p->comp != 1) return fail(NDWT_ERR_INVALID_ARG, "split-complex entry points take a plan created with NDWT_REAL");
-    return NDWT_OK;
+    if ((in_im == nullptr) != (out_im == nullptr)) return fail(NDWT_ERR_INVALID_ARG, "imaginary input and output must both be given or both be NULL");
+    int rc = one(in_re, out_re);
+    if (rc == NDWT_OK && in_im) rc = one(in_im, out_im);
+    return rc;
 }
 
 int ndwt_dec_split(ndwt_plan* p, const void* x_re, const void* x_im, void* y_re, void* y_im, int level, void* stream) {
-    int rc = split_check(p);
-    if (rc) return rc;
-    if ((x_im == nullptr) != (y_im == nullptr)) return fail(NDWT_ERR_INVALID_ARG, "imaginary input and output must both be given or both be NULL");
-    rc = ndwt_dec(p, x_re, y_re, level, stream);
-    if (rc == NDWT_OK && x_im) rc = ndwt_dec(p, x_im, y_im, level, stream);
-    return rc;
+    return split_run(p, x_re, x_im, y_re, y_im, [&](const void* x, void* y) { return ndwt_dec(p, x, y, level, stream); });
 }
-
 int ndwt_rec_split(ndwt_plan* p, const void* y_re, const void* y_im, void* x_re, void* x_im, int level, void* stream) {
-    int rc = split_check(p);
-    if (rc) return rc;
-    if ((x_im == nullptr) != (y_im == nullptr)) return fail(NDWT_ERR_INVALID_ARG, "imaginary input and output must both be given or both be NULL");
-    rc = ndwt_rec(p, y_re, x_re, level, stream);
-    if (rc == NDWT_OK && y_im) rc = ndwt_rec(p, y_im, x_im, level, stream);
-    return rc;
+    return split_run(p, y_re, y_im, x_re, x_im, [&](const void* y, void* x) { return ndwt_rec(p, y, x, level, stream); });
 }
-
 int ndwt_dec_split_host(ndwt_plan* p, const void* x_re, const void* x_im, void* y_re, void* y_im, int level) {
-    int rc = split_check(p);
-    if (rc) return rc;
-    if ((x_im == nullptr) != (y_im == nullptr)) return fail(NDWT_ERR_INVALID_ARG, "imaginary input and output must both be given or both be NULL");
-    rc = host_roundtrip(p, false, x_re, y_re, level);
-    if (rc == NDWT_OK && x_im) rc = host_roundtrip(p, false, x_im, y_im, level);
-    return rc;
+    return split_run(p, x_re, x_im, y_re, y_im, [&](const void* x, void* y) { return host_roundtrip(p, false, x, y, level); });
 }
-
 int ndwt_rec_split_host(ndwt_plan* p, const void* y_re, const void* y_im, void* x_re, void* x_im, int level) {
-    int rc = split_check(p);
-    if (rc) return rc;
-    if ((x_im == nullptr) != (y_im == nullptr)) return fail(NDWT_ERR_INVALID_ARG, "imaginary input and output must both be given or both be NULL");
-    rc = host_roundtrip(p, true, y_re, x_re, level);
-    if (rc == NDWT_OK && y_im) rc = host_roundtrip(p, true, y_im, x_im, level);
-    return rc;
+    return split_run(p, y_re, y_im, x_re, x_im, [&](const void* y, void* x) { return host_roundtrip(p, true, y, x, level); });
 }
 
 int ndwt_plan_slab_fast(const ndwt_plan* p) {
@@ -1936,38 +1814,31 @@ int ndwt_slab_halo(const ndwt_plan* p, int stride, int64_t* ab, int64_t* aa, int
 int ndwt_analysis_level_slab(ndwt_plan* p, const void* in, void* const* out, int stride, void* stream) {
     if (const int rb = refuse_batched(p, "a slab entry point")) return rb;
     if (!p || !in || !out || stride < 1) return fail(NDWT_ERR_INVALID_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(p->device));
-    hipStream_t s = (hipStream_t)stream;
-    return p->dtype == NDWT_F32 ? analysis_level<float>(p, (const float*)in, (float* const*)out, stride, true, s)
-                                : analysis_level<double>(p, (const double*)in, (double* const*)out, stride, true, s);
+    return on_device(p, [&](auto t) { return analysis_level(p, (const decltype(t)*)in, (decltype(t)* const*)out, stride, true, (hipStream_t)stream); });
 }
 
 int ndwt_synthesis_level_slab(ndwt_plan* p, const void* const* in, void* out, int stride, void* stream) {
     if (const int rb = refuse_batched(p, "a slab entry point")) return rb;
     if (!p || !in || !out || stride < 1) return fail(NDWT_ERR_INVALID_ARG, "bad arguments");
-    HIP_TRY(hipSetDevice(p->device));
-    hipStream_t s = (hipStream_t)stream;
-    return p->dtype == NDWT_F32 ? synthesis_level<float>(p, (const float* const*)in, (float*)out, stride, true, s)
-                                : synthesis_level<double>(p, (const double* const*)in, (double*)out, stride, true, s);
+    return on_device(p, [&](auto t) { return synthesis_level(p, (const decltype(t)* const*)in, (decltype(t)*)out, stride, true, (hipStream_t)stream); });
 }
 
 int ndwt_analysis_level_slab_split(ndwt_plan* p, const void* in_local, const void* halo_before, const void* halo_after,
                                    void* const* out, int stride, void* stream) {
-    int Lp = 0;
     if (p && p->shard != p->ndim - 1) {                  // z-slab: assembled with its halo planes, then the level (any plan kind)
         if (stride < 1) return fail(NDWT_ERR_INVALID_ARG, "bad stride");
         if (!in_local || !out || (p->filt[2].len > 2 && !halo_before) || !halo_after) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
-        HIP_TRY(hipSetDevice(p->device));
-        return p->dtype == NDWT_F32 ? slab_split_z_impl<float>(p, in_local, halo_before, halo_after, out, stride, (hipStream_t)stream)
-                                    : slab_split_z_impl<double>(p, in_local, halo_before, halo_after, out, stride, (hipStream_t)stream);
+        return on_device(p, [&](auto t) { return slab_split_z_impl<decltype(t)>(p, in_local, halo_before, halo_after, out, stride, (hipStream_t)stream); });
     }
-    int rc = slab_fast_ok(p, stride, &Lp);
-    if (rc) return rc;
-    if (!in_local || !out || (Lp > 2 && !halo_before) || !halo_after) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
-    HIP_TRY(hipSetDevice(p->device));
-    if (!halo_before) halo_before = halo_after;   // db1: no plane before the slab is needed
-    return p->dtype == NDWT_F32 ? slab_analysis_part_impl<float>(p, Lp, in_local, halo_before, halo_after, out, p->dims[2], (hipStream_t)stream)
-                                : slab_analysis_part_impl<double>(p, Lp, in_local, halo_before, halo_after, out, p->dims[2], (hipStream_t)stream);
+    // an outer-axis slab: every plane of it, as one part (a plan always has 1 <= dims[2] <= INT32_MAX planes)
+    return ndwt_analysis_level_slab_part(p, in_local, halo_before, halo_after, out, stride, p ? p->dims[2] : 0, stream);
+}
+
+// what the split / extended forms of a fused 3-D slab plan check first: the plan (slab_fast_ok), then the two pointers each of them needs
+static int slab_fast_begin(const ndwt_plan* p, int stride, int* Lp, const void* in, const void* out) {
+    if (const int rc = slab_fast_ok(p, stride, Lp)) return rc;
+    if (!in || !out) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
+    return NDWT_OK;
 }
 
 int ndwt_synthesis_level_slab_ext(ndwt_plan* p, const void* const* in_local, void* out_ext, int stride, void* stream) {
@@ -1976,9 +1847,7 @@ int ndwt_synthesis_level_slab_ext(ndwt_plan* p, const void* const* in_local, voi
         if (stride != 1 || !(Lp = slab_fused3(sel(p), 1, 1, kSlabZ)))
             return fail(NDWT_ERR_UNSUPPORTED, "the zero-extended z-slab synthesis needs a plan on the fused 3-D kernels whose z filter is the longest (stride 1)");
         if (!in_local || !out_ext) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
-        HIP_TRY(hipSetDevice(p->device));
-        return p->dtype == NDWT_F32 ? slab_ext_z_impl<float>(p, Lp, in_local, out_ext, (hipStream_t)stream)
-                                    : slab_ext_z_impl<double>(p, Lp, in_local, out_ext, (hipStream_t)stream);
+        return on_device(p, [&](auto t) { return slab_ext_z_impl<decltype(t)>(p, Lp, in_local, out_ext, (hipStream_t)stream); });
     }
     if (p && p->ndim == 4) {                             // t-sharded 4-D: 3-D part per frame, zero-extended t-axis pass
         const LevelRoute r = level_route(sel(p), 1, -1, kSlabOuter);
@@ -1986,16 +1855,10 @@ int ndwt_synthesis_level_slab_ext(ndwt_plan* p, const void* const* in_local, voi
         if (stride != 1 || r.kind != kRouteFused3T)
             return fail(NDWT_ERR_UNSUPPORTED, "the zero-extended 4-D slab synthesis needs a plan on the fused 3-D kernels (stride 1)");
         if (!in_local || !out_ext) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
-        HIP_TRY(hipSetDevice(p->device));
-        return p->dtype == NDWT_F32 ? slab_ext4_impl<float>(p, Lp, in_local, out_ext, (hipStream_t)stream)
-                                    : slab_ext4_impl<double>(p, Lp, in_local, out_ext, (hipStream_t)stream);
+        return on_device(p, [&](auto t) { return slab_ext4_impl<decltype(t)>(p, Lp, in_local, out_ext, (hipStream_t)stream); });
     }
-    int rc = slab_fast_ok(p, stride, &Lp);
-    if (rc) return rc;
-    if (!in_local || !out_ext) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
-    HIP_TRY(hipSetDevice(p->device));
-    return p->dtype == NDWT_F32 ? slab_ext_impl<float>(p, Lp, in_local, out_ext, (hipStream_t)stream)
-                                : slab_ext_impl<double>(p, Lp, in_local, out_ext, (hipStream_t)stream);
+    if (const int rc = slab_fast_begin(p, stride, &Lp, in_local, out_ext)) return rc;
+    return on_device(p, [&](auto t) { return slab_ext_impl<decltype(t)>(p, Lp, in_local, out_ext, (hipStream_t)stream); });
 }
 
 int ndwt_analysis_level_slab_part(ndwt_plan* p, const void* in_local, const void* halo_before, const void* halo_after,
@@ -2005,27 +1868,23 @@ int ndwt_analysis_level_slab_part(ndwt_plan* p, const void* in_local, const void
     if (rc) return rc;
     if (!in_local || !out || (Lp > 2 && !halo_before) || !halo_after) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
     if (n_planes < 1 || n_planes > INT32_MAX) return fail(NDWT_ERR_INVALID_ARG, "n_planes must be >= 1");
-    HIP_TRY(hipSetDevice(p->device));
-    if (!halo_before) halo_before = halo_after;
-    return p->dtype == NDWT_F32
-               ? slab_analysis_part_impl<float>(p, Lp, in_local, halo_before, halo_after, out, n_planes, (hipStream_t)stream)
-               : slab_analysis_part_impl<double>(p, Lp, in_local, halo_before, halo_after, out, n_planes, (hipStream_t)stream);
+    if (!halo_before) halo_before = halo_after;          // db1: no plane before the slab is needed
+    return on_device(p, [&](auto t) {
+        return slab_analysis_part_impl<decltype(t)>(p, Lp, in_local, halo_before, halo_after, out, n_planes, (hipStream_t)stream);
+    });
 }
 
 int ndwt_synthesis_level_slab_runs(ndwt_plan* p, const void* const* in_local, int64_t n_in, int64_t e0, int64_t e_stride,
                                    int64_t n_runs, int64_t n_out, void* out, int stride, void* stream) {
     int Lp = 0;
-    int rc = slab_fast_ok(p, stride, &Lp);
-    if (rc) return rc;
-    if (!in_local || !out) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
+    if (const int rc = slab_fast_begin(p, stride, &Lp, in_local, out)) return rc;
     if (n_in < 1 || e0 < 0 || n_out < 1 || n_runs < 1 || e_stride < 0 || n_in > INT32_MAX ||
         e0 + (n_runs - 1) * e_stride + n_out > n_in + Lp - 1)
         return fail(NDWT_ERR_INVALID_ARG, "every run of output planes must lie inside the %lld planes of the zero-extended result",
                     (long long)(n_in + Lp - 1));
-    HIP_TRY(hipSetDevice(p->device));
-    return p->dtype == NDWT_F32
-               ? slab_synthesis_runs_impl<float>(p, Lp, in_local, n_in, e0, e_stride, n_runs, n_out, out, (hipStream_t)stream)
-               : slab_synthesis_runs_impl<double>(p, Lp, in_local, n_in, e0, e_stride, n_runs, n_out, out, (hipStream_t)stream);
+    return on_device(p, [&](auto t) {
+        return slab_synthesis_runs_impl<decltype(t)>(p, Lp, in_local, n_in, e0, e_stride, n_runs, n_out, out, (hipStream_t)stream);
+    });
 }
 
 int ndwt_synthesis_level_slab_part(ndwt_plan* p, const void* const* in_local, int64_t n_in, int64_t e0, int64_t n_out,
@@ -2036,14 +1895,11 @@ int ndwt_synthesis_level_slab_part(ndwt_plan* p, const void* const* in_local, in
 int ndwt_analysis_level_slab_runs(ndwt_plan* p, const void* in_with_halo, void* const* out, int stride, int64_t n_planes,
                                   int64_t n_runs, int64_t run_stride, void* stream) {
     int Lp = 0;
-    int rc = slab_fast_ok(p, stride, &Lp);
-    if (rc) return rc;
-    if (!in_with_halo || !out) return fail(NDWT_ERR_INVALID_ARG, "null pointer");
+    if (const int rc = slab_fast_begin(p, stride, &Lp, in_with_halo, out)) return rc;
     if (n_planes < 1 || n_planes > INT32_MAX || n_runs < 1 || run_stride < 0) return fail(NDWT_ERR_INVALID_ARG, "bad run geometry");
-    HIP_TRY(hipSetDevice(p->device));
-    return p->dtype == NDWT_F32
-               ? slab_analysis_runs_impl<float>(p, Lp, in_with_halo, out, n_planes, n_runs, run_stride, (hipStream_t)stream)
-               : slab_analysis_runs_impl<double>(p, Lp, in_with_halo, out, n_planes, n_runs, run_stride, (hipStream_t)stream);
+    return on_device(p, [&](auto t) {
+        return slab_analysis_runs_impl<decltype(t)>(p, Lp, in_with_halo, out, n_planes, n_runs, run_stride, (hipStream_t)stream);
+    });
 }
 
 #ifdef NDWT_STAMPS
@@ -2056,28 +1912,30 @@ int ndwt_plan_set_stamps(ndwt_plan* p, void* dev_buffer) {
 #endif
 
 const char* ndwt_last_error(void) { return g_last_error.c_str(); }
-int ndwt_slab_segments(ndwt_plan* p, int op, int nseg, void* const* dst, const void* const* src, const int64_t* count, void* stream) {
+// what both segment forms check first
+static int segments_check(const ndwt_plan* p, int op, int nseg) {
     if (!p) return fail(NDWT_ERR_INVALID_ARG, "null plan");
     if (const int rb = refuse_batched(p, "ndwt_slab_segments")) return rb;
     if (op != NDWT_SEG_COPY && op != NDWT_SEG_ADD) return fail(NDWT_ERR_INVALID_ARG, "op must be NDWT_SEG_COPY or NDWT_SEG_ADD");
     if (nseg < 0 || nseg > NDWT_MAX_SEGMENTS) return fail(NDWT_ERR_INVALID_ARG, "at most %d runs per call", NDWT_MAX_SEGMENTS);
+    return NDWT_OK;
+}
+static int segments_launched(int rc) {
+    return rc == 0 ? NDWT_OK : fail(NDWT_ERR_HIP, "segment kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+}
+
+int ndwt_slab_segments(ndwt_plan* p, int op, int nseg, void* const* dst, const void* const* src, const int64_t* count, void* stream) {
+    if (const int rc = segments_check(p, op, nseg)) return rc;
     if (nseg == 0) return NDWT_OK;
     if (!dst || !src || !count) return fail(NDWT_ERR_INVALID_ARG, "null argument");
     for (int i = 0; i < nseg; ++i)
         if (!dst[i] || !src[i] || count[i] < 0) return fail(NDWT_ERR_INVALID_ARG, "run %d: null pointer or negative count", i);
-    HIP_TRY(hipSetDevice(p->device));
-    const int rc = p->dtype == NDWT_F32 ? segments_launch<float>(op, nseg, dst, src, count, (hipStream_t)stream)
-                                        : segments_launch<double>(op, nseg, dst, src, count, (hipStream_t)stream);
-    if (rc != 0) return fail(NDWT_ERR_HIP, "segment kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return NDWT_OK;
+    return on_device(p, [&](auto t) { return segments_launched(segments_launch<decltype(t)>(op, nseg, dst, src, count, (hipStream_t)stream)); });
 }
 
 int ndwt_slab_segments_strided(ndwt_plan* p, int op, int nseg, void* const* dst, const void* const* src, const int64_t* count, int64_t nrep,
                                const int64_t* dst_stride, const int64_t* src_stride, void* stream) {
-    if (!p) return fail(NDWT_ERR_INVALID_ARG, "null plan");
-    if (const int rb = refuse_batched(p, "ndwt_slab_segments")) return rb;
-    if (op != NDWT_SEG_COPY && op != NDWT_SEG_ADD) return fail(NDWT_ERR_INVALID_ARG, "op must be NDWT_SEG_COPY or NDWT_SEG_ADD");
-    if (nseg < 0 || nseg > NDWT_MAX_SEGMENTS) return fail(NDWT_ERR_INVALID_ARG, "at most %d runs per call", NDWT_MAX_SEGMENTS);
+    if (const int rc = segments_check(p, op, nseg)) return rc;
     if (nrep < 0) return fail(NDWT_ERR_INVALID_ARG, "negative repetition count");
     if (nseg == 0 || nrep == 0) return NDWT_OK;
     if (!dst || !src || !count || !dst_stride || !src_stride) return fail(NDWT_ERR_INVALID_ARG, "null argument");
@@ -2088,11 +1946,9 @@ int ndwt_slab_segments_strided(ndwt_plan* p, int op, int nseg, void* const* dst,
             return fail(NDWT_ERR_INVALID_ARG, "run %d: destination stride %lld is shorter than the run (%lld)", i, (long long)dst_stride[i],
                         (long long)count[i]);
     }
-    HIP_TRY(hipSetDevice(p->device));
-    const int rc = p->dtype == NDWT_F32 ? segments_strided_launch<float>(op, nseg, dst, src, count, nrep, dst_stride, src_stride, (hipStream_t)stream)
-                                        : segments_strided_launch<double>(op, nseg, dst, src, count, nrep, dst_stride, src_stride, (hipStream_t)stream);
-    if (rc != 0) return fail(NDWT_ERR_HIP, "segment kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    return NDWT_OK;
+    return on_device(p, [&](auto t) {
+        return segments_launched(segments_strided_launch<decltype(t)>(op, nseg, dst, src, count, nrep, dst_stride, src_stride, (hipStream_t)stream));
+    });
 }
 
 const char* ndwt_version(void) { return "ndwt-hip 0.1 (gfx950)"; }

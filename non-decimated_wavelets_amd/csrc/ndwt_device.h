@@ -201,6 +201,11 @@ template <typename T, int L> struct Taps3 {
     T lo[3][L];
     T hi[3][L];
 };
+// scalars of the tap tables (this one, Taps3Y and TapsDen further down), as the host writes them one after the other: ndwt_taps_host.h.
+// The static_asserts after TapsDen hold the structs to these counts.
+constexpr int taps3_scalars(int L) { return 6 * L; }
+constexpr int taps3y_scalars(int L) { return taps3_scalars(L) + 4 * (L + 1); }
+constexpr int tapsden_scalars(int L) { return taps3y_scalars(L) + 3 * L + 2 * L + 2 * (L + 1); }
 
 template <typename T> struct Fused3Args {
     const T* in[8];        // analysis: in[0] only; synthesis: the 2^3 bands
@@ -2146,6 +2151,25 @@ template <typename T, int L> struct TapsDen {
     T azp[L][2];             // (alo_z[j], ahi_z[j]): the z stage produces (lo, hi) pairs from one broadcast sample
     T axp[L + 1][2];         // (alo_x[k], alo_x[k-1]), k = 0..L, taps outside [0, L) = 0: the x stage works on pairs of adjacent x
 };
+
+// The host writes the tables as flat runs of scalars (ndwt_taps_host.h): the structs have exactly those scalars, without padding, their
+// members in the order written, and Taps3Y begins with Taps3 (a kernel that takes Taps3 reads the head of a Taps3Y table).
+template <typename T, int L> constexpr bool taps_layout_ok() {
+    typedef Taps3<T, L> A;
+    typedef Taps3Y<T, L> Y;
+    typedef TapsDen<T, L> D;
+    static_assert(sizeof(A) == taps3_scalars(L) * sizeof(T) && sizeof(Y) == taps3y_scalars(L) * sizeof(T) && sizeof(D) == tapsden_scalars(L) * sizeof(T),
+                  "a tap table is not the scalars the host writes");
+    static_assert(__builtin_offsetof(A, lo) == 0 && __builtin_offsetof(Y, lo) == 0 && __builtin_offsetof(Y, hi) == __builtin_offsetof(A, hi) &&
+                      __builtin_offsetof(Y, xplo) == sizeof(A) && __builtin_offsetof(Y, xphi) == sizeof(A) + 2 * (L + 1) * sizeof(T),
+                  "Taps3Y does not begin with Taps3");
+    static_assert(__builtin_offsetof(D, syn) == 0 && __builtin_offsetof(D, alo) == sizeof(Y) && __builtin_offsetof(D, azp) == sizeof(Y) + 3 * L * sizeof(T) &&
+                      __builtin_offsetof(D, axp) == sizeof(Y) + 5 * L * sizeof(T),
+                  "TapsDen is not in the order the host writes it");
+    return true;
+}
+template <typename T, int... Ls> constexpr bool taps_layouts_ok() { return (taps_layout_ok<T, Ls>() && ...); }
+static_assert(taps_layouts_ok<float, 2, 4, 6, 8, 10, 12, 14, 16, 18, 20>() && taps_layouts_ok<double, 2, 4, 6, 8, 10, 12, 14, 16, 18, 20>(), "");
 
 template <typename T, int L_, int NT_ = 1024, int WPE_ = 4, int ZLDS_ = 0, int TX_ = 64, int TY_ = 32> struct Den3 {
     static_assert(sizeof(T) == 4, "float only");

@@ -11,12 +11,6 @@
 
 namespace ndwt {
 
-struct FusedTapsD {       // per axis (0 = x, 1 = y, 2 = z), zero-padded to Lp, double precision: what the plan's device tap tables are filled from
-    int Lp;
-    double lo[3][kMaxTaps];
-    double hi[3][kMaxTaps];
-};
-
 // The fused 3-D launch a pick names (ndwt_select.h: fused3_select).  The launch units are asked in turn; each runs the instance of its list
 // (ndwt_fused_list.h) that the pick equals, or answers "not mine".  -1: no unit has the instance, -2: the launch geometry is not the
 // instance's tile.

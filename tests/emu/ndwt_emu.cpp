@@ -12,6 +12,7 @@
 #include "ndwt_device.h"
 #include "ndwt_geom.h"
 #include "ndwt_fused_tile.h"
+#include "ndwt_taps_host.h"
 
 // The pair-packed synthesis instantiations (10 tap lengths x 2 access widths x 2 depths x tiles) live in translation units of their
 // own (EMU_PART 9 .. 12): as part of emu3<float, true> they made that one unit compile for 6.5 minutes.
@@ -42,14 +43,34 @@ template <class State, int NT> struct EmuExec {
     void barrier() {}
 };
 
+// lo / hi ([naxes][kMaxTaps], the first L of each axis read) as the library holds the taps of a plan
+inline ndwt::FusedTapsD emu_taps_d(const double* lo, const double* hi, int L, int naxes = 3) {
+    ndwt::FusedTapsD t = {};
+    t.Lp = L;
+    for (int ax = 0; ax < naxes; ++ax)
+        for (int j = 0; j < L; ++j) {
+            t.lo[ax][j] = lo[ax * ndwt::kMaxTaps + j];
+            t.hi[ax][j] = hi[ax * ndwt::kMaxTaps + j];
+        }
+    return t;
+}
+// the table the library would upload (ndwt_taps_host.h), copied into the kernel's struct: they must be the same size
+template <class TP, typename T> void emu_load_taps(TP& tp, const std::vector<T>& table) {
+    if (table.size() * sizeof(T) != sizeof(TP)) std::abort();
+    std::memcpy(&tp, table.data(), sizeof(TP));
+}
+// K::Taps = Taps3<T, L>, or Taps3Y<T, L> (the x tap pairs after it): what a plan uploads for the analysis / for the synthesis
+template <class K, typename T> typename K::Taps emu_taps3(const double* lo, const double* hi, int naxes = 3) {
+    std::vector<T> table;
+    ndwt::append_taps3(table, emu_taps_d(lo, hi, K::L, naxes), sizeof(typename K::Taps) != sizeof(ndwt::Taps3<T, K::L>));
+    typename K::Taps tp;
+    emu_load_taps(tp, table);
+    return tp;
+}
+
 template <class K, typename T>
 int run(ndwt::Fused3Args<T>& a, const double* lo, const double* hi) {
-    typename K::Taps tp;
-    for (int ax = 0; ax < 3; ++ax)
-        for (int j = 0; j < K::L; ++j) {
-            tp.lo[ax][j] = (T)lo[ax * ndwt::kMaxTaps + j];
-            tp.hi[ax][j] = (T)hi[ax * ndwt::kMaxTaps + j];
-        }
+    const typename K::Taps tp = emu_taps3<K, T>(lo, hi);
     const int nblocks = a.ntx * a.nty * a.nzc * a.nbatch;
     // LDS image on the heap with exact size so ASan sees overruns
     for (int b = 0; b < nblocks; ++b) {
@@ -63,18 +84,7 @@ int run(ndwt::Fused3Args<T>& a, const double* lo, const double* hi) {
 // the pair-packed float synthesis kernel (Inv3Y): extended tap table
 template <class K, typename T>
 int runY(ndwt::Fused3Args<T>& a, const double* lo, const double* hi) {
-    typename K::Taps tp;
-    for (int ax = 0; ax < 3; ++ax)
-        for (int j = 0; j < K::L; ++j) {
-            tp.lo[ax][j] = (T)lo[ax * ndwt::kMaxTaps + j];
-            tp.hi[ax][j] = (T)hi[ax * ndwt::kMaxTaps + j];
-        }
-    for (int k = 0; k <= K::L; ++k)
-        for (int h = 0; h < 2; ++h) {
-            const int j = k - h;
-            tp.xplo[k][h] = (j >= 0 && j < K::L) ? (T)lo[j] : T(0);
-            tp.xphi[k][h] = (j >= 0 && j < K::L) ? (T)hi[j] : T(0);
-        }
+    const typename K::Taps tp = emu_taps3<K, T>(lo, hi);
     const int nblocks = a.ntx * a.nty * a.nzc * a.nbatch;
     for (int b = 0; b < nblocks; ++b) {
         std::unique_ptr<typename K::Shared> sh(new typename K::Shared);
@@ -274,24 +284,8 @@ int emu3(int Lp, int vec4, const T* in, T* out, int n1, int n2, int n3, int nbat
     }
 }
 
-template <class TP> static auto fill_x_pairs(TP& tp, const double* lo, const double* hi, int L, int) -> decltype((void)tp.xplo) {
-    for (int k = 0; k <= L; ++k)
-        for (int h = 0; h < 2; ++h) {
-            const int j = k - h;
-            typedef typename std::remove_reference<decltype(tp.xplo[0][0])>::type E;
-            tp.xplo[k][h] = (j >= 0 && j < L) ? (E)lo[j] : E(0);
-            tp.xphi[k][h] = (j >= 0 && j < L) ? (E)hi[j] : E(0);
-        }
-}
-template <class TP> static void fill_x_pairs(TP&, const double*, const double*, int, long) {}
 template <class K, typename T> int run2(ndwt::Fused2Args<T>& a, const double* lo, const double* hi) {
-    typename K::Taps tp;
-    for (int ax = 0; ax < 3; ++ax)
-        for (int j = 0; j < K::L; ++j) {
-            tp.lo[ax][j] = (T)lo[ax * ndwt::kMaxTaps + j];
-            tp.hi[ax][j] = (T)hi[ax * ndwt::kMaxTaps + j];
-        }
-    fill_x_pairs(tp, lo, hi, K::L, 0);
+    const typename K::Taps tp = emu_taps3<K, T>(lo, hi);
     const int nblocks = a.ntx * a.nyc * a.nbatch;
     for (int b = 0; b < nblocks; ++b) {
         typename K::Shared sh;
@@ -559,27 +553,9 @@ template <int LL>
 static int run_den3(ndwt::Fused3Args<float>& a, const double* slo, const double* shi, const double* alo, const double* ahi) {
     typedef ndwt::Den3<float, LL, 1024, 4, (LL == 8 ? 6 : 0)> K;
     std::unique_ptr<typename K::Taps> tp(new typename K::Taps);
-    for (int ax = 0; ax < 3; ++ax)
-        for (int j = 0; j < LL; ++j) {
-            tp->syn.lo[ax][j] = (float)slo[ax * ndwt::kMaxTaps + j];
-            tp->syn.hi[ax][j] = (float)shi[ax * ndwt::kMaxTaps + j];
-            tp->alo[ax][j] = (float)alo[ax * ndwt::kMaxTaps + j];
-        }
-    for (int k = 0; k <= LL; ++k)
-        for (int h = 0; h < 2; ++h) {
-            const int j = k - h;
-            tp->syn.xplo[k][h] = (j >= 0 && j < LL) ? (float)slo[j] : 0.0f;
-            tp->syn.xphi[k][h] = (j >= 0 && j < LL) ? (float)shi[j] : 0.0f;
-        }
-    for (int j = 0; j < LL; ++j) {
-        tp->azp[j][0] = (float)alo[2 * ndwt::kMaxTaps + j];
-        tp->azp[j][1] = (float)ahi[2 * ndwt::kMaxTaps + j];
-    }
-    for (int k = 0; k <= LL; ++k)
-        for (int h = 0; h < 2; ++h) {
-            const int j = k - h;
-            tp->axp[k][h] = (j >= 0 && j < LL) ? (float)alo[j] : 0.0f;
-        }
+    std::vector<float> table;
+    if (!ndwt::build_taps_den(table, emu_taps_d(slo, shi, LL), emu_taps_d(alo, ahi, LL))) return -3;   // (as the library: no table for such taps)
+    emu_load_taps(*tp, table);
     const int nblocks = a.ntx * a.nty * a.nzc * a.nbatch;
     for (int b = 0; b < nblocks; ++b) {
         std::unique_ptr<typename K::Shared> sh(new typename K::Shared);
@@ -723,13 +699,7 @@ template <int LL, int NLEV, int PD> static int run_inv2c(ndwt::Fused2CIArgs<floa
     a.ntx = (a.n1 + K::WX - 1) / K::WX;
     a.ychunk = ychunk > 0 ? (ychunk < a.n2 ? ychunk : a.n2) : a.n2;
     a.nyc = (a.n2 + a.ychunk - 1) / a.ychunk;
-    typename K::Taps tp;
-    for (int ax = 0; ax < 3; ++ax)
-        for (int j = 0; j < LL; ++j) {
-            tp.lo[ax][j] = (float)lo[ax * ndwt::kMaxTaps + j];
-            tp.hi[ax][j] = (float)hi[ax * ndwt::kMaxTaps + j];
-        }
-    fill_x_pairs(tp, lo, hi, LL, 0);
+    const typename K::Taps tp = emu_taps3<K, float>(lo, hi);
     for (int b = 0; b < a.ntx * a.nyc; ++b) {
         typename K::Shared sh;
         EmuExec<typename K::State, K::NT> ex;
@@ -743,12 +713,7 @@ template <int LL, int NLEV> static int run_fwd2c(ndwt::Fused2CArgs<float>& a, co
     a.ntx = (a.n1 + K::WX - 1) / K::WX;
     a.ychunk = ychunk > 0 ? (ychunk < a.n2 ? ychunk : a.n2) : a.n2;
     a.nyc = (a.n2 + a.ychunk - 1) / a.ychunk;
-    typename K::Taps tp;
-    for (int ax = 0; ax < 3; ++ax)
-        for (int j = 0; j < LL; ++j) {
-            tp.lo[ax][j] = (float)lo[ax * ndwt::kMaxTaps + j];
-            tp.hi[ax][j] = (float)hi[ax * ndwt::kMaxTaps + j];
-        }
+    const typename K::Taps tp = emu_taps3<K, float>(lo, hi);
     for (int b = 0; b < a.ntx * a.nyc; ++b) {
         typename K::Shared sh;
         EmuExec<typename K::State, K::NT> ex;

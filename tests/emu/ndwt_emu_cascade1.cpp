@@ -10,12 +10,7 @@ namespace {
 
 template <class K, typename T> int run_cascade1(ndwt::Fused1CArgs<T>& a, const double* lo, const double* hi) {
     a.nseg = (a.row + K::WX - 1) / K::WX;
-    typename K::Taps tp;
-    std::memset(&tp, 0, sizeof tp);
-    for (int j = 0; j < K::L; ++j) {                      // converted from double as the plan's device table is
-        tp.lo[0][j] = (T)lo[j];
-        tp.hi[0][j] = (T)hi[j];
-    }
+    const typename K::Taps tp = emu_taps3<K, T>(lo, hi, 1);   // the table of a 1-D plan: axis 0, the other axes zero
     const long long nblocks = (a.outer * a.nseg + K::NT / 64 - 1) / (K::NT / 64);
     for (long long b = 0; b < nblocks; ++b) {
         typename K::Shared sh;

@@ -12,13 +12,7 @@ template <class K, class A> int run_cascade(A& a, const double* lo, const double
     a.ntx = (a.n1 + K::WX - 1) / K::WX;
     a.ychunk = ychunk > 0 ? (ychunk < a.n2 ? ychunk : a.n2) : a.n2;
     a.nyc = (a.n2 + a.ychunk - 1) / a.ychunk;
-    typename K::Taps tp;
-    for (int ax = 0; ax < 3; ++ax)
-        for (int j = 0; j < K::L; ++j) {
-            tp.lo[ax][j] = (T)lo[ax * ndwt::kMaxTaps + j];
-            tp.hi[ax][j] = (T)hi[ax * ndwt::kMaxTaps + j];
-        }
-    fill_x_pairs(tp, lo, hi, K::L, 0);
+    const typename K::Taps tp = emu_taps3<K, T>(lo, hi);
     for (int b = 0; b < a.ntx * a.nyc; ++b) {
         typename K::Shared sh;
         EmuExec<typename K::State, K::NT> ex;

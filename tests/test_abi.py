@@ -73,6 +73,53 @@ def test_plan_validation_messages_follow_the_reference():
     assert rc == 1
 
 
+def _create(fn, ndim, dims, names, *between, tail=(0, 0, 0, 0, 1, 0), handle=True):
+    """one of the ndwt_plan_create* calls: (plan, ndim, dims, <between>, wnames, dtype, complexity, l2, dilation, max_level, device);
+    dims / names None = a null pointer, handle False = a null plan pointer.  -> (code, message, handle)"""
+    lib = ndwt.lib()
+    h = ctypes.c_void_p(None)
+    d = None if dims is None else (ctypes.c_int64 * len(dims))(*dims)
+    w = None if names is None else (ctypes.c_char_p * len(names))(*[n.encode() for n in names])
+    rc = getattr(lib, fn)(ctypes.byref(h) if handle else None, ndim, d, *between, w, *tail)
+    return rc, lib.ndwt_last_error().decode(), h
+
+
+INVALID, UNSUPPORTED = 1, 7       # NDWT_ERR_INVALID_ARG, NDWT_ERR_UNSUPPORTED (include/ndwt.h)
+# every one of these returns before the device is asked for: (id, entry point, ndim, dims, names, arguments between dims and wnames,
+# (dtype, complexity, l2, dilation, max_level, device), code, message)
+CREATION_REFUSALS = [
+    ("dims-below-1", "ndwt_plan_create", 2, [16, 0], ["db1", "db1"], (), (0, 0, 0, 0, 1, 0), INVALID, "dims[1] must be >= 1"),
+    ("dims-negative", "ndwt_plan_create", 3, [-4, 16, 16], ["db1"] * 3, (), (0, 0, 0, 0, 1, 0), INVALID, "dims[0] must be >= 1"),
+    ("bad-complexity", "ndwt_plan_create", 1, [64], ["db2"], (), (0, 2, 0, 0, 1, 0), INVALID, "bad complexity"),
+    ("bad-dilation", "ndwt_plan_create", 1, [64], ["db2"], (), (0, 0, 0, 2, 1, 0), INVALID, "bad dilation mode"),
+    ("max-level-0", "ndwt_plan_create", 1, [64], ["db2"], (), (0, 0, 0, 0, 0, 0), INVALID, "max_level must be 1..30"),
+    ("max-level-31", "ndwt_plan_create", 1, [64], ["db2"], (), (0, 0, 0, 0, 31, 0), INVALID, "max_level must be 1..30"),
+    ("null-dims", "ndwt_plan_create", 1, None, ["db2"], (), (0, 0, 0, 0, 1, 0), INVALID, "null dims/wnames"),
+    ("null-wnames", "ndwt_plan_create", 1, [64], None, (), (0, 0, 0, 0, 1, 0), INVALID, "null dims/wnames"),
+    ("many-howmany-0", "ndwt_plan_create_many", 1, [64], ["db2"], (0,), (0, 0, 0, 0, 1, 0), INVALID, "howmany must be >= 1 (got 0)"),
+    ("many-2d", "ndwt_plan_create_many", 2, [64, 64], ["db2"] * 2, (3,), (0, 0, 0, 0, 1, 0), UNSUPPORTED,
+     "batched plans are 1-D in this version: ndim = 2 is not supported (loop over ndwt_plan_create plans)"),
+    ("slab-global-shorter", "ndwt_plan_create_slab", 3, [16, 16, 8], ["db2"] * 3, (7,), (0, 0, 0, 0, 1, 0), INVALID,
+     "global_outer (7) is shorter than the local slab (8)"),
+    ("slab-axis-unsupported", "ndwt_plan_create_slab_axis", 3, [16, 16, 8], ["db2"] * 3, (0, 32), (0, 0, 0, 0, 1, 0), UNSUPPORTED,
+     "shard_axis 0 of a 3-D volume: slab plans shard the outermost axis (2), or z (2) of a 4-D volume"),
+    ("slab-axis-z-global-shorter", "ndwt_plan_create_slab_axis", 4, [8, 8, 6, 6], ["db2"] * 4, (2, 5), (0, 0, 0, 0, 1, 0), INVALID,
+     "global_len (5) is shorter than the local slab (6)"),
+]
+
+
+@pytest.mark.parametrize("fn,ndim,dims,names,between,tail,code,text", [c[1:] for c in CREATION_REFUSALS], ids=[c[0] for c in CREATION_REFUSALS])
+def test_plan_creation_refusals_keep_their_code_and_text(fn, ndim, dims, names, between, tail, code, text):
+    rc, msg, h = _create(fn, ndim, dims, names, *between, tail=tail)
+    assert (rc, msg) == (code, text)
+    assert not h.value                                        # no handle comes back
+
+
+def test_plan_creation_refuses_a_null_plan_pointer():
+    rc, msg, _ = _create("ndwt_plan_create", 1, [64], ["db2"], handle=False)
+    assert (rc, msg) == (INVALID, "null plan pointer")
+
+
 def test_no_gpu_means_a_loud_failure_not_a_fallback():
     import torch
     if torch.cuda.is_available():

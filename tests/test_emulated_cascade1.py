@@ -52,7 +52,8 @@ CASES = [(f"{kind}-{sid}", kind, wn, nlev, K, row) for kind in KINDS for sid, wn
 
 def _sources():
     return [os.path.join(EMU, "ndwt_emu_cascade1.cpp"), os.path.join(EMU, "ndwt_emu.cpp"), os.path.join(CSRC, "ndwt_device_1d.h"),
-            os.path.join(CSRC, "ndwt_device.h"), os.path.join(CSRC, "ndwt_wave_row.h"), os.path.join(CSRC, "ndwt_geom.h"), os.path.join(CSRC, "ndwt_fused_tile.h")]
+            os.path.join(CSRC, "ndwt_device.h"), os.path.join(CSRC, "ndwt_wave_row.h"), os.path.join(CSRC, "ndwt_geom.h"), os.path.join(CSRC, "ndwt_fused_tile.h"),
+            os.path.join(CSRC, "ndwt_taps_host.h")]
 
 
 def _build(tag, flags, link_flags, out, extra=()):

@@ -45,7 +45,8 @@ CASES = [(f"{kind}-{sid}", kind, sizes[kind], wn, nlev, ychunk, depth if kind ==
 
 def _sources():
     return [os.path.join(EMU, "ndwt_emu_cascade2_kinds.cpp"), os.path.join(EMU, "ndwt_emu.cpp"), os.path.join(CSRC, "ndwt_device.h"),
-            os.path.join(CSRC, "ndwt_wave_row.h"), os.path.join(CSRC, "ndwt_geom.h"), os.path.join(CSRC, "ndwt_fused_tile.h")]
+            os.path.join(CSRC, "ndwt_wave_row.h"), os.path.join(CSRC, "ndwt_geom.h"), os.path.join(CSRC, "ndwt_fused_tile.h"),
+            os.path.join(CSRC, "ndwt_taps_host.h")]
 
 
 def _build(tag, flags, link_flags, out, extra=()):

@@ -12,7 +12,7 @@ sig() {
   $B/clang-offload-bundler --unbundle --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=$T/x.fat --output=$T/x.elf 2>/dev/null || return 1
   $B/llvm-objdump -d $T/x.elf | sed -E 's#// [0-9A-F]+:#//#' | awk -v dir=$T/k '
     /^[0-9a-f]+ <.*>:$/ { if (f) close(f); name = $2; gsub(/[<>:]/, "", name); f = dir "/" (++n); print name > (dir "/names"); next }
-    f { print > f }'
+    f && !/^[ \t]*(\.\.\.)?$/ { print > f }'   # (without the "..." that stands for the padding behind the last kernel of a unit: the kernels may come in another order)
   n=0
   while read -r name; do n=$((n + 1)); echo "$name code $(md5sum < $T/k/$n | cut -d" " -f1)"; done < $T/k/names
   $B/llvm-readelf --notes $T/x.elf | awk '
