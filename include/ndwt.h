@@ -88,6 +88,26 @@ int ndwt_plan_create(ndwt_plan** plan, int ndim, const int64_t* dims, const char
  * ndwt_analysis_level_slab*, ndwt_synthesis_level_slab*; ndwt_slab_segments and ndwt_slab_segments_strided. */
 int ndwt_plan_create_many(ndwt_plan** plan, int ndim, const int64_t* dims, int64_t howmany, const char* const* wnames,
                           int dtype, int complexity, int pres_l2_norm, int dilation, int max_level, int device);
+/* Plan that filters SOME axes of an array: dims[0 .. ndim) is the whole array (ndim 1 .. 4), bit a of `axes` set = axis a is filtered --
+ * swtn(..., axes=...) of other wavelet packages.  Served in this version: the k lowest bits, 1 <= k <= ndim (the leading axes).
+ * axes == 0, a bit at or above ndim, ndim outside 1 .. 4: NDWT_ERR_INVALID_ARG; any other mask (0x5, 0x2, ...): NDWT_ERR_UNSUPPORTED, the
+ * message names the mask.  All of it is checked before any device call.
+ * k == ndim is exactly ndwt_plan_create.  k < ndim is a STACK: the K = prod(dims[k .. ndim)) items of prod(dims[0 .. k)) elements lie back
+ * to back and each gets the periodic k-D transform on its own (k == 1: the batched plan of ndwt_plan_create_many with howmany = K).
+ * wnames has ndim entries; those of the axes left alone are ignored and may be NULL.  The reference's length check (filter <= axis, the
+ * same messages) applies to the filtered axes only; an axis left alone needs length >= 1.
+ * Layout: ndwt_num_bands(k, level) bands, each a whole array [dims]; band b at b * bs with bs = prod(dims) (packed) or the caller's
+ * band_pitch (ndwt_band_pitch: prod(dims) plus the usual skew); item j of a band at j * prod(dims[0 .. k)) -- [n1, n2, K, bands] in MATLAB
+ * terms.  Band order and normalisation are those of a k-D plan.
+ * Kernels: a level at tap stride 1 is ONE fused 2-D / 3-D launch with the items in its batch slot; a-trous levels and whatever the fused
+ * kernels refuse run the per-axis kernels over all items at once.  Two or three levels of a stack of images can run in one launch
+ * (Fwd2C / Inv2C with the item taken from the block id) under the per-item conditions of a single image: unasked from the
+ * item height and total size at which that was measured to win (float: items of 128 rows (dec) / 256 rows (rec) in 64 MiB; the other
+ * kinds 512 rows in 128 MiB: DESIGN.md 4.3b), else on request (ndwt_plan_set_variant(plan, 11, 11, ...)); 9 / 9 switches it off.  ndwt_plan_describe: "stack2d cascade",
+ * "stack2d fused", "stack3d fused" or "stack axis".
+ * Served and refused entry points: the lists of ndwt_plan_create_many, with the same message. */
+int ndwt_plan_create_axes(ndwt_plan** plan, int ndim, const int64_t* dims, unsigned axes, const char* const* wnames, int dtype,
+                          int complexity, int pres_l2_norm, int dilation, int max_level, int device);
 /* Plan for ONE SLAB of a volume sharded on its outermost axis (the *_slab entry points below): dims describe the local slab,
  * global_outer is the length of the sharded axis of the whole volume.  The reference's length check (nd_dwt_3D.m:277-286:
  * filter <= axis) applies to the WHOLE axis: a slab may be thinner than the filter (cfg5: 32 frames over 8 ranks = 4, db4 = 8

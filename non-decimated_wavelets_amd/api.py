@@ -33,9 +33,12 @@ class Plan:
     """Thin RAII wrapper over ndwt_plan (include/ndwt.h)."""
 
     def __init__(self, dims, wnames, dtype, complex_interleaved=False, pres_l2_norm=False, dilation="reference",
-                 max_level=1, device=0, global_outer=None, shard_axis=None, howmany=None):
+                 max_level=1, device=0, global_outer=None, shard_axis=None, howmany=None, axes=None):
         """howmany: None = one array (ndwt_plan_create); a number = a batched plan of that many 1-D signals (ndwt_plan_create_many):
         signal k at k * dims[0] elements, every band a contiguous (howmany, n) block.
+        axes: a tuple of axis numbers (0 = the fastest) = only these axes of `dims`, the WHOLE array, are filtered
+        (ndwt_plan_create_axes; served: the leading axes (0, .., k-1)).  With k < len(dims) the plan is a stack: the prod(dims[k:]) items
+        lie back to back and each gets the k-D transform; every band is a whole array.  Not together with `howmany`.
         global_outer: length of the sharded axis of the WHOLE volume when `dims` describe one slab of it (multi-GPU):
         the reference's filter-length check then applies to the whole axis, a slab may be thinner than the filter.
         shard_axis: the sharded axis, counted from the fastest (0 = x); None = the outermost (ndwt_plan_create_slab), 2 of a 4-D
@@ -48,13 +51,26 @@ class Plan:
         self.device = int(device)
         self._h = ctypes.c_void_p(None)
         dims_c = (ctypes.c_int64 * self.ndim)(*self.dims)
-        names_c = (ctypes.c_char_p * self.ndim)(*[w.encode() for w in self.wnames])
+        names_c = (ctypes.c_char_p * self.ndim)(*[None if w is None else w.encode() for w in self.wnames])
         dt = L.NDWT_F32 if dtype in (torch.float32, np.float32, "single") else L.NDWT_F64
         dil = {"reference": L.NDWT_DILATION_REFERENCE, "atrous": L.NDWT_DILATION_ATROUS}[dilation]
         cplx = L.NDWT_COMPLEX_INTERLEAVED if complex_interleaved else L.NDWT_REAL
         self.shard_axis = self.ndim - 1 if shard_axis is None else int(shard_axis)
         self.howmany = None if howmany is None else int(howmany)
-        if howmany is not None:
+        self.axes = None if axes is None else tuple(int(a) for a in axes)
+        if axes is not None:
+            if howmany is not None:
+                raise ValueError("'axes' and 'howmany' are two ways to say the same thing: give one of them")
+            if shard_axis is not None or global_outer is not None:
+                raise ValueError("a plan over some axes is not a slab plan")
+            if any(a < 0 or a > 31 for a in self.axes) or len(set(self.axes)) != len(self.axes):
+                raise ValueError(f"axes must be distinct axis numbers >= 0 (got {self.axes})")
+            mask = 0
+            for a in self.axes:
+                mask |= 1 << a
+            L.check(L.lib().ndwt_plan_create_axes(ctypes.byref(self._h), self.ndim, dims_c, mask, names_c, dt, cplx,
+                                                  int(bool(pres_l2_norm)), dil, self.max_level, self.device))
+        elif howmany is not None:
             if shard_axis is not None or global_outer is not None:
                 raise ValueError("a batched plan is not a slab plan")
             L.check(L.lib().ndwt_plan_create_many(ctypes.byref(self._h), self.ndim, dims_c, self.howmany, names_c, dt, cplx,
@@ -425,6 +441,7 @@ class _NdDwtBase:
         self.devices = None
         self.band_pitch = "packed"
         self.batch = None
+        self.stack = None
         # name/value pairs as in MATLAB (nd_dwt_3D.m:105-120); keyword arguments are accepted too
         if len(varargin) % 2:
             raise ValueError("Optional inputs must come in pairs")
@@ -445,6 +462,8 @@ class _NdDwtBase:
                 self.band_pitch = val if isinstance(val, str) else int(val)
             elif k == "batch":                     # nd_dwt_1D only: this many signals per call, x = [n, batch] (column k = signal k)
                 self.batch = int(val)
+            elif k == "stack":                     # nd_dwt_2D / nd_dwt_3D: this many images / volumes per call, x = [sizes, stack]
+                self.stack = int(val)
             elif k == "devices":                   # shard the outermost axis over these devices (host arrays, one process)
                 self.devices = [int(v) for v in np.atleast_1d(val)]
             else:   # unknown keys only warn (nd_dwt_3D.m:118)
@@ -475,8 +494,17 @@ class _NdDwtBase:
                 raise ValueError("'batch' and 'devices' do not combine: a batched plan lives on one device")
             if self.batch < 1:
                 raise ValueError("'batch' must be a number of signals >= 1")
-        # the shape of x in MATLAB terms: `sizes`, for a batched 1-D object [n, batch]
-        self._shape = sizes + ([self.batch] if self.batch is not None else [])
+        if self.stack is not None:
+            if d == 1:
+                raise ValueError("'stack' is an option of nd_dwt_2D and nd_dwt_3D: many signals per call are nd_dwt_1D's 'batch'")
+            if d == 4:
+                raise ValueError("'stack' is an option of nd_dwt_2D and nd_dwt_3D: a stack of 4-D arrays is not supported")
+            if self.devices is not None:
+                raise ValueError("'stack' and 'devices' do not combine: a stack plan lives on one device")
+            if self.stack < 1:
+                raise ValueError("'stack' must be a number of items >= 1")
+        # the shape of x in MATLAB terms: `sizes`, for a batched 1-D object [n, batch], for a stack [sizes, stack]
+        self._shape = sizes + ([self.batch] if self.batch is not None else []) + ([self.stack] if self.stack is not None else [])
         # get_filters (nd_dwt_3D.m:263-342): per-axis taps instead of N-D FFT-domain kernels
         self.f_dec = [L.wave_filters(w) for w in self.wname[:d]]
         self.f_size = {f"s{a + 1}": len(self.f_dec[a][0]) for a in range(d)}
@@ -520,8 +548,12 @@ class _NdDwtBase:
             real_dt = torch.float32 if self.precision.lower() == "single" else torch.float64
             if p is not None:
                 torch.cuda.synchronize(idx)                           # the plan being replaced may still be running
-            p = Plan(self.sizes, self.wname[: self.NDIM], real_dt, is_complex, self.pres_l2_norm, self.dilation,
-                     max_level=max(level, 3), device=idx, howmany=self.batch)
+            if self.stack is not None:                                # the whole array, its leading axes filtered
+                p = Plan(self.sizes + [self.stack], self.wname[: self.NDIM] + [None], real_dt, is_complex, self.pres_l2_norm,
+                         self.dilation, max_level=max(level, 3), device=idx, axes=tuple(range(self.NDIM)))
+            else:
+                p = Plan(self.sizes, self.wname[: self.NDIM], real_dt, is_complex, self.pres_l2_norm, self.dilation,
+                         max_level=max(level, 3), device=idx, howmany=self.batch)
             p._last_stream = None
             self._plans[key] = p
         cur = torch.cuda.current_stream(torch.device("cuda", idx))
@@ -713,7 +745,9 @@ class nd_dwt_1D(_NdDwtBase):
 
 
 class nd_dwt_2D(_NdDwtBase):
-    """Functions/nd_dwt_2D.m -- coefficients [n1, n2, 4+3(level-1)]."""
+    """Functions/nd_dwt_2D.m -- coefficients [n1, n2, 4+3(level-1)].
+    nd_dwt_2D(wname, [n1, n2], 'stack', K): K images per call -- dec takes [n1, n2, K] and returns [n1, n2, K, bands], image j transformed
+    on its own; rec, shrink and denoise likewise.  In memory that is (K, n2, n1) contiguous."""
     NDIM = 2
 
     def _check_sizes(self, sizes):
@@ -733,7 +767,8 @@ class nd_dwt_2D(_NdDwtBase):
 
 
 class nd_dwt_3D(_NdDwtBase):
-    """Functions/nd_dwt_3D.m -- coefficients [n1, n2, n3, 8+7(level-1)]."""
+    """Functions/nd_dwt_3D.m -- coefficients [n1, n2, n3, 8+7(level-1)].
+    nd_dwt_3D(wname, [n1, n2, n3], 'stack', K): K volumes per call -- dec takes [n1, n2, n3, K] and returns [n1, n2, n3, K, bands]."""
     NDIM = 3
 
     def _check_sizes(self, sizes):

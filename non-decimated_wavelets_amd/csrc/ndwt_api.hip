@@ -150,8 +150,10 @@ struct ndwt_plan {
     int dtype = 0, complexity = 0, l2 = 0, dilation = 0, max_level = 0, device = 0, path = NDWT_PATH_AUTO;
     size_t esize = 0;                  // bytes per scalar
     long long comp = 1;                // scalars per element (2 for interleaved complex)
-    long long vol = 0;                 // scalars per band (a batched plan: of all its signals)
-    long long howmany = 0;             // ndwt_plan_create_many: signals of a batched 1-D plan, signal k at k * dims[0] elements; 0 = not batched
+    long long vol = 0;                 // scalars per band (a batched plan: of all its signals / items)
+    long long howmany = 0;             // ndwt_plan_create_many: signals of a batched 1-D plan, signal k at k * dims[0] elements; 0 = not batched.
+                                       // ndwt_plan_create_axes: the items of a stack -- ndim and dims are those of ONE item (an image or a
+                                       // volume), item j at j * item_vol() scalars of the input and of every band
     DevBuf approx_base[2];             // approximation ping-pong between levels, each kApproxSkew bytes larger than a band: approx(i) is the band
     DevBuf tmp;                        // temporaries of the per-axis path / 4-D split
     int target_blocks = 0;             // fused-kernel grid sizing: 0 = one round of resident workgroups (per kernel), else as given
@@ -187,6 +189,8 @@ struct ndwt_plan {
     // 256 B off the allocation's (power-of-two) alignment: the approximation is then the one band of a level that does not share the
     // address bits below 1 KiB with the packed detail bands (about a quarter of the pitched gain)
     void* approx(int i) const { return (char*)approx_base[i].ptr + kApproxSkew; }
+    long long items() const { return howmany > 0 ? howmany : 1; }
+    long long item_vol() const { return vol / items(); }   // scalars of one item of a band (an unbatched plan: the band)
     ~ndwt_plan() {                     // (the buffers free themselves; the caller has made the plan's device current)
         for (auto& r : prof) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
         for (auto e : ev_pool) (void)hipEventDestroy(e);
@@ -390,7 +394,7 @@ template <typename T> static int per_axis_level(ndwt_plan* p, bool synthesis, co
 // The eligibility predicates and the choice of kernel are plain functions of integers (ndwt_select.h); this is what they see of a plan.
 static SelPlan sel(const ndwt_plan* p) {
     SelPlan q = {p->ndim, (int)p->comp, p->dtype == NDWT_F64, p->complexity == NDWT_REAL, p->path == NDWT_PATH_AUTO,
-                 p->dilation != NDWT_DILATION_REFERENCE, p->fp64_fused != 0, {1, 1, 1, 1}, {2, 2, 2, 2}, p->variant_fwd, p->variant_inv};
+                 p->dilation != NDWT_DILATION_REFERENCE, p->fp64_fused != 0, {1, 1, 1, 1}, {2, 2, 2, 2}, p->variant_fwd, p->variant_inv, p->howmany};
     for (int k = 0; k < p->ndim; ++k) { q.dims[k] = p->dims[k]; q.len[k] = p->filt[k].len; }
     return q;
 }
@@ -516,6 +520,7 @@ template <typename T> struct Fused2Launch {
     long long in_bstride = 0, out_bstride = 0;
     bool y_wrap = true;                // false: the inputs carry the y halo (slab mode)
     int dil = 1;                       // tap stride of a dilated level on its row sub-lattices
+    long long nbatch = 1;              // images of the launch (a stack: its items, in_bstride / out_bstride apart)
 };
 template <typename T> static int fused2_run(const ndwt_plan* p, const Fused2Launch<T>& l, hipStream_t s) {
     const bool inverse = l.inverse;
@@ -527,7 +532,7 @@ template <typename T> static int fused2_run(const ndwt_plan* p, const Fused2Laun
     memset(&a, 0, sizeof a);
     a.n1 = (int)(p->dims[0] * p->comp);
     a.n2 = (int)(n2 / dil);                               // dil > 1: the dil row sub-lattices are the batch items
-    a.nbatch = dil;
+    a.nbatch = dil > 1 ? dil : (int)l.nbatch;
     a.in_bstride = dil > 1 ? p->dims[0] : l.in_bstride;
     a.out_bstride = dil > 1 ? p->dims[0] : out_bstride;
     a.y_wrap = l.y_wrap ? 1 : 0;
@@ -540,7 +545,7 @@ template <typename T> static int fused2_run(const ndwt_plan* p, const Fused2Laun
     const int nin = inverse ? 4 : 1, nout = inverse ? 1 : 4;
     for (int b = 0; b < nin; ++b) { a.in[b] = in[b]; vec4 = vec4 && aligned_vec4<T>(in[b]); }
     for (int b = 0; b < nout; ++b) { a.out[b] = out[b]; vec4 = vec4 && aligned_vec4<T>(out[b]); }
-    const Fused2Query q = {sizeof(T) == 8, inverse, vec4, Lp, dil > 1 ? dil : (int)p->comp, dil, a.n1, (int)n2, p->variant_inv};
+    const Fused2Query q = {sizeof(T) == 8, inverse, vec4, Lp, dil > 1 ? dil : (int)p->comp, dil, a.n1, (int)n2, p->variant_inv, a.nbatch};
     const Fused2Pick k = fused2_select(q);
     fused2_geometry(a, fused2_tile_width(inverse, Lp, q.ew), Lp, p->target_blocks > 0 ? p->target_blocks * 2 : k.waves, p->force_zchunk);
     if (dil > 1) a.rs = (int)(dil * p->dims[0]);   // 8 waves per CU: one round (measured optimum 1024^2 .. 4096^2)
@@ -551,7 +556,7 @@ template <typename T> static int fused2_run(const ndwt_plan* p, const Fused2Laun
     const int rc = launch_fused2_pick(k, a, td, s);   // (-1, -2: after a pick, internal errors -- see fused3_run)
     prof_end(p, s, rc);
     if (rc == -1) return fail(NDWT_ERR_UNSUPPORTED, "internal: no fused 2-D kernel instantiated for the pick (family %d, tap length %d)", (int)k.family, Lp);
-    if (rc == -2) return fail(NDWT_ERR_UNSUPPORTED, "internal: launch geometry does not match the 2-D kernel's tile width %d", fused2_tile_width(inverse, Lp, q.ew));
+    if (rc == -2) return fail(NDWT_ERR_UNSUPPORTED, "internal: launch geometry does not match the 2-D kernel's tile width %d, or its grid is beyond 2^31 - 1 waves", fused2_tile_width(inverse, Lp, q.ew));
     if (rc != 0) return fail(NDWT_ERR_HIP, "fused 2-D kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     return NDWT_OK;
 }
@@ -617,7 +622,8 @@ static int synthesis_4d(ndwt_plan* p, int Lp, const T* const* in, T* out, long l
 // analysis of one level: in (vol scalars, + halo planes in slab mode) -> 2^d bands
 template <typename T>
 static int analysis_level(ndwt_plan* p, const T* in, T* const* out, long long stride, bool slab, hipStream_t s) {
-    const long long n_sh = slab_planes(p, stride, slab), vol_in = p->vol / p->dims[p->shard] * n_sh;
+    // (a stack is never a slab: vol_in and vol_out are then the scalars of ONE item, the launch's batch stride both ways)
+    const long long n_sh = slab_planes(p, stride, slab), vol_out = p->item_vol(), vol_in = vol_out / p->dims[p->shard] * n_sh;
     const bool on_z = p->shard == 2;                       // (of a 4-D level: the sharded axis is z, else t)
     const T* ins[8] = {in};
     LevelRoute r = level_route(sel(p), stride, 0, slab_mode(p, slab));
@@ -634,7 +640,7 @@ static int analysis_level(ndwt_plan* p, const T* in, T* const* out, long long st
         }
         case kRouteFused3: {
             Fused3Launch<T> l = {false, r.Lp, ins, out, p->dims[2]};
-            l.in_bstride = vol_in; l.out_bstride = p->vol; l.z = slab ? kZHalo : kZPeriodic;
+            l.nbatch = p->items(); l.in_bstride = vol_in; l.out_bstride = vol_out; l.z = slab ? kZHalo : kZPeriodic;
             return fused3_run<T>(p, l, s);
         }
         // A/B variant 7 (Plan.set_variant(fwd=7)) -- MEASURED AND NOT THE DEFAULT: the t axis folded into the fused launches, each raw plane a
@@ -664,7 +670,7 @@ static int analysis_level(ndwt_plan* p, const T* in, T* const* out, long long st
         }
         case kRouteFused2: {
             Fused2Launch<T> l = {false, r.Lp, ins, out, p->dims[1]};
-            l.in_bstride = vol_in; l.out_bstride = p->vol; l.y_wrap = !slab;
+            l.nbatch = p->items(); l.in_bstride = vol_in; l.out_bstride = vol_out; l.y_wrap = !slab;
             return fused2_run<T>(p, l, s);
         }
         default: return per_axis_level<T>(p, false, ins, out, stride, slab, s);   // kRoutePerAxis
@@ -673,7 +679,7 @@ static int analysis_level(ndwt_plan* p, const T* in, T* const* out, long long st
 
 template <typename T>
 static int synthesis_level(ndwt_plan* p, const T* const* in, T* out, long long stride, bool slab, hipStream_t s) {
-    const long long n_sh = slab_planes(p, stride, slab), vol_in = p->vol / p->dims[p->shard] * n_sh;
+    const long long n_sh = slab_planes(p, stride, slab), vol_out = p->item_vol(), vol_in = vol_out / p->dims[p->shard] * n_sh;
     const bool on_z = p->shard == 2;
     T* outs[8] = {out};
     const LevelRoute r = level_route(sel(p), stride, 1, slab_mode(p, slab));
@@ -685,7 +691,7 @@ static int synthesis_level(ndwt_plan* p, const T* const* in, T* out, long long s
         }
         case kRouteFused3: {
             Fused3Launch<T> l = {true, r.Lp, in, outs, p->dims[2]};
-            l.in_bstride = vol_in; l.out_bstride = p->vol; l.z = slab ? kZHalo : kZPeriodic; l.shrink_mask = kShrinkTLowDetails;
+            l.nbatch = p->items(); l.in_bstride = vol_in; l.out_bstride = vol_out; l.z = slab ? kZHalo : kZPeriodic; l.shrink_mask = kShrinkTLowDetails;
             return fused3_run<T>(p, l, s);
         }
         case kRouteFused3T: {                              // (a slab on t: the 3-D part runs on the halo frames too)
@@ -700,7 +706,7 @@ static int synthesis_level(ndwt_plan* p, const T* const* in, T* out, long long s
         }
         case kRouteFused2: {
             Fused2Launch<T> l = {true, r.Lp, in, outs, p->dims[1]};
-            l.in_bstride = vol_in; l.out_bstride = p->vol; l.y_wrap = !slab;
+            l.nbatch = p->items(); l.in_bstride = vol_in; l.out_bstride = vol_out; l.y_wrap = !slab;
             return fused2_run<T>(p, l, s);
         }
         default: return per_axis_level<T>(p, true, in, outs, stride, slab, s);   // kRoutePerAxis
@@ -715,11 +721,13 @@ static int synthesis_level(ndwt_plan* p, const T* const* in, T* out, long long s
 // ---- two or three levels of an image in one launch (Fwd2C / Inv2C, ndwt_device.h; when: cascade2_levels).  Shared by both directions:
 // the tiling (one round of `per_cu` waves per CU -- analysis 8, synthesis 4: DESIGN.md 4 -- in equal chunks of at least nlev (Lp - 1) rows:
 // the march-in is at most half of a wave's steps; force_zchunk = rows per wave), profiling, the launch and its error mapping.
-// Returns 0, or -1: no instance (the caller takes one launch per level)
+// A stack: the items share the round -- chunks per item = waves / (ntx * items), at least 1 -- and the grid is ntx * nyc * items waves.
+// Returns 0, or -1: no instance, or a stack whose grid the launch cannot express (the caller takes one launch per level)
 template <class Args, class Launch> static int cascade2_launch(ndwt_plan* p, Args& a, bool inverse, int WX, int min_chunk, int per_cu, hipStream_t s, Launch&& launch) {
     a.ntx = (a.n1 + WX - 1) / WX;
     const int waves = p->target_blocks > 0 ? p->target_blocks : p->num_cus * per_cu;
-    const int chunks = waves / a.ntx > 1 ? waves / a.ntx : 1;
+    const long long items = p->items(), per_chunk = a.ntx * items;
+    const int chunks = waves / per_chunk > 1 ? (int)(waves / per_chunk) : 1;
     int yc = (a.n2 + chunks - 1) / chunks;
     if (yc < min_chunk) yc = min_chunk;
     if (p->force_zchunk > 0) yc = p->force_zchunk;
@@ -727,6 +735,9 @@ template <class Args, class Launch> static int cascade2_launch(ndwt_plan* p, Arg
     a.nyc = (a.n2 + yc - 1) / yc;
     a.ychunk = (a.n2 + a.nyc - 1) / a.nyc;
     a.nyc = (a.n2 + a.ychunk - 1) / a.ychunk;
+    a.nbatch = (int)items;
+    a.bstride = p->item_vol();
+    if ((long long)a.ntx * a.nyc * items > 0x7fffffffLL) return -1;
     const void* td = p->taps_dev[inverse ? 1 : 0].ptr;
     if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
     prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
@@ -746,7 +757,7 @@ template <typename T> static int cascade2_run(ndwt_plan* p, int Lp, int nlev, co
     bool aligned = aligned_vec4<T>(in);
     for (int b = 0; b < 1 + 3 * nlev; ++b) { a.out[b] = out[b]; aligned = aligned && aligned_vec4<T>(out[b]); }
     if (!aligned) return -1;                              // not this data: one launch per level
-    a.nt = nt_store_ok<T>(a.rs, a.rs, 0, out, 1 + 3 * nlev);
+    a.nt = nt_store_ok<T>(a.rs, a.rs, 0, out, 1 + 3 * nlev);   // (the item stride is rows of rs scalars: whole lines wherever rs is)
     a.mode = p->variant_fwd == kFwdCascadeMode1 ? 1 : 0;
     const Cascade2Instance k = {false, sizeof(T) == 8, (int)p->comp, Lp, nlev, 0};
     return cascade2_launch(p, a, false, cascade2_tile_width(k), nlev * (Lp - 1), 8, s, [&](const void* td) { return launch_cascade2(k, a, td, s); });
@@ -900,7 +911,7 @@ template <typename T> static int rec_impl(ndwt_plan* p, const T* y, long long bs
 // (ndwt_plan_create_many): those entry points refuse it (include/ndwt.h lists them)
 static int refuse_batched(const ndwt_plan* p, const char* what) {
     if (p && p->howmany > 0)
-        return fail(NDWT_ERR_UNSUPPORTED, "%s is not available on a batched plan (ndwt_plan_create_many): use the device-pointer entry points", what);
+        return fail(NDWT_ERR_UNSUPPORTED, "%s is not available on a batched plan (ndwt_plan_create_many): use the device-pointer entry points", what);   // (a stack too)
     return NDWT_OK;
 }
 
@@ -1292,6 +1303,30 @@ int ndwt_plan_create_many(ndwt_plan** plan, int ndim, const int64_t* dims, int64
     return plan_create_impl(plan, ndim, dims, -1, wnames, dtype, complexity, pres_l2_norm, dilation, max_level, device, -1, howmany);
 }
 
+// A transform of the leading axes only.  Everything is checked before any device call.  k filtered axes of ndim: k == ndim is
+// ndwt_plan_create itself; k < ndim is the batched plan generalised -- ndim = k, howmany = the product of the axes left alone (k == 1: the
+// batched 1-D plan of ndwt_plan_create_many, kernels and all).
+int ndwt_plan_create_axes(ndwt_plan** plan, int ndim, const int64_t* dims, unsigned axes, const char* const* wnames, int dtype, int complexity,
+                          int pres_l2_norm, int dilation, int max_level, int device) {
+    if (plan) *plan = nullptr;
+    if (ndim < 1 || ndim > NDWT_MAX_DIMS) return fail(NDWT_ERR_INVALID_ARG, "ndim must be 1..4");
+    if (axes == 0 || (axes >> ndim) != 0)
+        return fail(NDWT_ERR_INVALID_ARG, "axes mask 0x%x: it must name at least one of the %d axes and none beyond them", axes, ndim);
+    int k = 0;
+    while ((axes >> k) & 1u) ++k;
+    if ((axes >> k) != 0)
+        return fail(NDWT_ERR_UNSUPPORTED, "axes mask 0x%x is not supported: this version filters leading axes only (masks 0x1, 0x3, 0x7, 0xf)", axes);
+    if (k == ndim) return plan_create_impl(plan, ndim, dims, -1, wnames, dtype, complexity, pres_l2_norm, dilation, max_level, device);
+    if (!dims || !wnames) return fail(NDWT_ERR_INVALID_ARG, "null dims/wnames");
+    long long items = 1;
+    for (int a = k; a < ndim; ++a) {
+        if (dims[a] < 1) return fail(NDWT_ERR_INVALID_ARG, "dims[%d] must be >= 1", a);
+        if (dims[a] > (1LL << 40) / items) return fail(NDWT_ERR_INVALID_ARG, "the axes left alone hold more than 2^40 items");
+        items *= dims[a];
+    }
+    return plan_create_impl(plan, k, dims, -1, wnames, dtype, complexity, pres_l2_norm, dilation, max_level, device, -1, items);
+}
+
 int ndwt_plan_create_slab(ndwt_plan** plan, int ndim, const int64_t* dims_local, int64_t global_outer, const char* const* wnames,
                           int dtype, int complexity, int pres_l2_norm, int dilation, int max_level, int device) {
     if (ndim >= 1 && ndim <= NDWT_MAX_DIMS && dims_local && global_outer < dims_local[ndim - 1])
@@ -1396,6 +1431,10 @@ int ndwt_plan_describe(const ndwt_plan* p, char* buf, int buflen) {
     else if (ra == kRouteFused2) s = "fused2d";
     int L1 = 0;
     if (p->howmany > 0) s = cascade1_levels(sel(p), p->howmany, false, 2, &L1) ? "batched1d cascade" : "batched1d axis";
+    if (p->howmany > 0 && p->ndim >= 2) {                 // a stack (ndwt_plan_create_axes): what two levels of it run today
+        int Lp = 0;
+        s = cascade2_levels(sel(p), false, 2, &Lp) ? "stack2d cascade" : ra == kRouteFused2 ? "stack2d fused" : f3a ? "stack3d fused" : "stack axis";
+    }
     snprintf(buf, (size_t)buflen, "%s", s);
     return NDWT_OK;
 }
@@ -1638,6 +1677,7 @@ int ndwt_shrink(ndwt_plan* p, void* y, int level, double threshold, int mode, vo
 static bool den3_eligible(const ndwt_plan* p, int fused_level1, int* Lp_out) {
     if (!fused_level1 || p->dtype != NDWT_F32 || p->complexity != NDWT_REAL || p->ndim != 3 || p->dilation != NDWT_DILATION_REFERENCE)
         return false;
+    if (p->howmany > 0) return false;                     // a stack: Den3 knows one volume (its level 1 materialises like the others)
     const LevelRoute r = level_route(sel(p), 1, -1, kWholeArray);
     const int Lp = r.Lp;
     // measured, 512^3, 3 levels, ndwt_denoise with / without the fused level 1: db1 4.49 / 5.27 ms, db2 5.10 / 5.67, db3 5.72 / 6.09,

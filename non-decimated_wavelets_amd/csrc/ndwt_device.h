@@ -2531,6 +2531,8 @@ template <typename T> struct Fused2CArgs {
     int rs;                // elements between rows
     int nt;                // nontemporal stores
     int mode;              // A/B (tools/bench2d_cascade.py): bit 0 = every level computes from its first input row on (no take-in-only steps)
+    int nbatch;            // a stack of images (ndwt_plan_create_axes): items of the launch, 0 or 1 = one image ...
+    long long bstride;     // ... and the scalars between them: the input, every band and the approximation hold their items back to back
 };
 
 template <typename T, int L_, int NLEV_, int WPE_ = 2, int EW_ = 1> struct Fwd2C {
@@ -2599,7 +2601,18 @@ template <typename T, int L_, int NLEV_, int WPE_ = 2, int EW_ = 1> struct Fwd2C
         rot_dispatch<L>(rot, [&](auto R) __attribute__((always_inline)) { step<decltype(R)::value>(ex, a, tp, x0, ybeg, yend, r, more); });
     }
 
-    template <class Exec> static NDWT_DEV void block(Exec& ex, Shared&, const Args& a, const Taps& tp, int bid) {
+    template <class Exec> static NDWT_DEV void block(Exec& ex, Shared&, const Args& a0, const Taps& tp, int bid) {
+        // A stack: the item is the slowest part of the block id (the order of decode_tile2).  Its offset goes into the base pointers once,
+        // in 64 bits; from here on the wave sees one image -- offsets stay 32-bit and y wraps modulo the item's own n2, so that no row
+        // of a neighbouring item is ever read.  (One image: the launch has ntx * nyc waves and the item is 0.)
+        const int per_item = a0.ntx * a0.nyc, item = bid / per_item;
+        bid -= item * per_item;
+        Args a = a0;
+        const long long ioff = (long long)item * a0.bstride;
+        a.in += ioff;
+        NDWT_SFOR(b, 1 + 3 * NLEV)
+            a.out[b] += ioff;
+        NDWT_SEND
         const int tx = bid % a.ntx, yc = bid / a.ntx;
         const int x0 = tx * WX;
         const int ybeg = yc * a.ychunk;
@@ -2827,6 +2840,8 @@ template <typename T> struct Fused2CIArgs {
     int nt;
     T shrink_thr;          // ndwt_denoise: soft (or, shrink_hard, hard) thresholding of every detail band as its rows are loaded; 0 = off
     int shrink_on, shrink_hard;
+    int nbatch;            // items of a stack and the scalars between them (Fused2CArgs)
+    long long bstride;
 };
 
 template <typename T, int L_, int NLEV_, int PD_ = 1, int WPE_ = 2, int EW_ = 1> struct Inv2C {
@@ -2972,7 +2987,16 @@ template <typename T, int L_, int NLEV_, int PD_ = 1, int WPE_ = 2, int EW_ = 1>
             }
         });
     }
-    template <class Exec> static NDWT_DEV void block(Exec& ex, Shared&, const Args& a, const Taps& tp, int bid) {
+    template <class Exec> static NDWT_DEV void block(Exec& ex, Shared&, const Args& a0, const Taps& tp, int bid) {
+        // a stack: the item from the block id, its offset into the base pointers once (see Fwd2C::block)
+        const int per_item = a0.ntx * a0.nyc, item = bid / per_item;
+        bid -= item * per_item;
+        Args a = a0;
+        const long long ioff = (long long)item * a0.bstride;
+        a.out += ioff;
+        NDWT_SFOR(b, 1 + 3 * NLEV)
+            a.in[b] += ioff;
+        NDWT_SEND
         const int tx = bid % a.ntx, yc = bid / a.ntx;
         const int x0 = tx * WX;
         const int ybeg = yc * a.ychunk;

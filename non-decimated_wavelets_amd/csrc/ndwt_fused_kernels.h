@@ -44,6 +44,7 @@ template <class K> int launch_fused3(const typename K::Args& a, const void* taps
 // (fused2_geometry, cascade2_launch) against the tile this kernel was compiled for.
 template <class K> int launch_wave_tiles(const typename K::Args& a, int nbatch, const void* taps_dev, hipStream_t s) {
     if (a.ntx != (a.n1 + K::WX - 1) / K::WX || a.ychunk < 1 || (long long)a.nyc * a.ychunk < a.n2) return -2;
+    if (nbatch < 1 || (long long)a.ntx * a.nyc * nbatch > 0x7fffffffLL) return -2;   // (a stack: up to 2^20 - 1 items times the tiles of one)
     const int nblocks = a.ntx * a.nyc * nbatch;
     trace_kernel<K>(dim3(nblocks), dim3(K::NT));
     hipLaunchKernelGGL(fused3_kernel<K>, dim3(nblocks), dim3(K::NT), 0, s, a, (const typename K::Taps*)taps_dev);
@@ -53,7 +54,7 @@ template <class K> int launch_fused2(const typename K::Args& a, const void* taps
     return launch_wave_tiles<K>(a, a.nbatch, taps_dev, s);
 }
 template <class K> int launch_cascade2_k(const typename K::Args& a, const void* taps_dev, hipStream_t s) {  // Fwd2C / Inv2C
-    return launch_wave_tiles<K>(a, 1, taps_dev, s);
+    return launch_wave_tiles<K>(a, a.nbatch > 1 ? a.nbatch : 1, taps_dev, s);   // a stack: its items (a zeroed field: one image)
 }
 
 // The 1-D cascade of a batched plan: one wave per (signal, segment of K::WX scalars), four to the workgroup.  The host's segments

@@ -46,7 +46,10 @@ struct SelPlan {
     long long dims[4];
     int len[4];                        // tap length per axis
     int variant_fwd, variant_inv;
+    long long howmany = 0;             // items of a batched plan: the signals of ndwt_plan_create_many, or the images / volumes of a stack
+                                       // (ndwt_plan_create_axes: ndim and dims are those of ONE item); 0 = not batched
 };
+constexpr bool is_stack(const SelPlan& p) { return p.howmany > 0 && p.ndim >= 2; }
 
 inline int padded_len(const int* len) { int Lp = 2; for (int a = 0; a < 3; ++a) Lp = len[a] > Lp ? len[a] : Lp; return Lp; }
 // the zero padding (Lp - len) / 2 of every axis' taps is even: the kernels that derive the high-pass taps from the low-pass ones
@@ -84,7 +87,7 @@ inline bool fused3_eligible(const SelPlan& p, long long stride, int* Lp_out, int
     // (complex128: 10 taps both ways, 12 taps analysis only -- its synthesis spills 500+ registers on every tile)
     // (complex64: 14 / 16 taps in the analysis, and in the synthesis through the pair-packed kernel -- the Lp > lmax clause above)
     if (!p.real && Lp > (!p.f64 ? 16 : (dir == 0 ? 12 : 10))) return false;
-    if (!fused3_fits(p.dims[0] * p.comp, p.dims[1], p.dims[2] + 64, p.ndim == 4 ? p.dims[3] + 64 : 1)) return false;
+    if (!fused3_fits(p.dims[0] * p.comp, p.dims[1], p.dims[2] + 64, p.ndim == 4 ? p.dims[3] + 64 : is_stack(p) ? p.howmany : 1)) return false;
     *Lp_out = Lp;
     return true;
 }
@@ -149,9 +152,17 @@ enum SlabMode { kWholeArray, kSlabOuter, kSlabZ };
 // Slabs have no sub-lattice form, and a fused kernel marches exactly Lp - 1 halo planes: where the halo is on the kernel's own outer axis
 // (z of a 3-D slab or of a 4-D volume sharded on z, y of an image) that axis' filter has to be the longest.  (A 4-D slab on t: t is the
 // per-axis pass.)
+// A stack (ndwt_plan_create_axes) takes the one-launch forms with its items in the batch slot of the launch.  The sub-lattice forms of a
+// dilated level use that slot themselves: they are not offered, and a dilated level of a stack runs the per-axis passes.
 inline LevelRoute level_route(const SelPlan& p, long long stride, int dir, SlabMode mode) {
     const bool slab = mode != kWholeArray, halo_on_z = mode == kSlabZ || (mode == kSlabOuter && p.ndim == 3);
     int Lp = 0;
+    if (is_stack(p)) {
+        if (slab || stride != 1 || p.howmany >= (1LL << 20)) return {kRoutePerAxis, 0};
+        if (p.ndim == 3 && fused3_eligible(p, stride, &Lp, dir)) return {kRouteFused3, Lp};
+        if (p.ndim == 2 && fused2_eligible(p, stride, &Lp)) return {kRouteFused2, Lp};
+        return {kRoutePerAxis, 0};
+    }
     if (!slab && fused3_dilated_eligible(p, stride, &Lp)) return {kRouteFused3Dilated, Lp};
     if (fused3_eligible(p, stride, &Lp, dir) && !(halo_on_z && p.len[2] != Lp)) {
         if (p.ndim == 3) return {kRouteFused3, Lp};
@@ -190,6 +201,16 @@ inline bool fused_shrink_capable(const SelPlan& p) {
 constexpr long long cascade2_min_bytes(bool f64, int comp, bool inverse) {
     return !f64 ? (comp == 1 ? (24LL << 20) + 1 : (32LL << 20)) : comp == 1 ? (inverse ? (128LL << 20) : (32LL << 20)) : (64LL << 20);
 }
+// A stack of images takes the cascade under the same conditions, which are per item (one wave marches rows of ONE item).  Whether it
+// does so unasked is measured per data kind and direction (tools/bench2d_stack.py: db4, 3 levels, forced cascade against
+// one launch per level on stack plans): from the smallest measured (item height, bytes of all items) on at which the cascade won by more
+// than the 5 % spread between boxes.  float real: the analysis from 128 rows (-30 % at 1024 x 128^2, -35 % at 256 x 256^2, -33 % at
+// 64 x 512^2), the synthesis from 256 rows (-0.3 % at 128 rows -- its march-in reads every band --, -7 % at 256, -21 % at 512), both at
+// 64 MiB; complex64 (-25 % / -7 %), double (-23 % / -18 %) and complex128 (-19 % / -24 %) from 512 rows at 128 MiB, the smallest measured.
+// Below these nothing is known and nothing is taken unasked: variants 10 / 11 / 12 force the cascade, 9 switches it off.
+constexpr bool cascade2_stack_default(bool f64, int comp, bool inverse, long long n2, long long total_bytes) {
+    return (!f64 && comp == 1) ? n2 >= (inverse ? 256 : 128) && total_bytes >= (64LL << 20) : n2 >= 512 && total_bytes >= (128LL << 20);
+}
 inline int cascade2_levels(const SelPlan& p, bool inverse, int left, int* Lp_out) {
     int& Lp = *Lp_out;
     if (left < 2 || p.atrous || p.variant_fwd == kFwdNoCascade || (p.comp != 1 && p.comp != 2) || !fused2_eligible(p, 1, &Lp)) return 0;
@@ -199,7 +220,8 @@ inline int cascade2_levels(const SelPlan& p, bool inverse, int left, int* Lp_out
     const auto exists = [&](int nlev) { return cascade2_instantiated({inverse, p.f64, p.comp, Lp, nlev, inverse ? 1 : 0}); };
     const int n = (left >= 3 && exists(3)) ? 3 : exists(2) ? 2 : 0;
     if (!n) return 0;
-    const bool big = n1 * p.dims[1] * (p.f64 ? 8 : 4) >= cascade2_min_bytes(p.f64, p.comp, inverse);
+    const long long bytes = n1 * p.dims[1] * (p.f64 ? 8 : 4);
+    const bool big = is_stack(p) ? cascade2_stack_default(p.f64, p.comp, inverse, p.dims[1], bytes * p.howmany) : bytes >= cascade2_min_bytes(p.f64, p.comp, inverse);
     if (inverse ? (p.variant_inv == kInvCascadeOff || !(big || p.variant_inv == kInvCascadeAlways || p.variant_inv == kInvCascadeDepth2))
                 : !(big || p.variant_fwd == kFwdCascadeAlways || p.variant_fwd == kFwdCascadeMode1)) return 0;
     return n;
@@ -334,6 +356,7 @@ struct Fused2Query {
     bool f64, inverse, vec4;
     int Lp, ew, dil, n1, n2;           // n1: scalars along x; n2: rows of the whole (undilated) image
     int variant_inv;
+    int nbatch = 1;                    // images of the launch (a stack: its items)
 };
 enum Fused2Family { kFused2S, kInv2P };   // Fwd2S / Inv2S by direction, or the synthesis with rows of band loads in flight
 // what a launch runs: the instance by its full name (ndwt_fused_list.h), flat as Fused3Pick is -- every template argument of Fwd2S /
@@ -350,11 +373,12 @@ struct Fused2Pick {
     constexpr Fused2PInstance inv2p() const { return {f64, Lp, pdepth, packed}; }
 };
 // synthesis of real data in rows of whole groups of 4 scalars, images whose 70-row chunks fit one round of 1024 waves (up to 4096^2): Inv2P,
-// 4 rows of band loads in flight per wave, packed FMAs where that form exists (float 4 / 8 / 12 taps); double up to 8 taps, depth 4 for 4 taps
+// 4 rows of band loads in flight per wave, packed FMAs where that form exists (float 4 / 8 / 12 taps); double up to 8 taps, depth 4 for 4 taps.
+// A stack: the waves of all its items count against the round.
 inline Fused2Pick fused2_select(const Fused2Query& q) {
     const int vi = q.variant_inv, WX = fused2_tile_width(q.inverse, q.Lp, q.ew), L = q.Lp;
     const bool deep = q.inverse && L <= 12 && (!q.f64 || L <= 8) && q.ew == 1 && q.dil == 1 && q.vec4 && vi != kInv2Keep2S && q.n2 >= 64 &&
-                      ((long long)((q.n1 + WX - 1) / WX) * ((q.n2 + 69) / 70) <= 1280 || vi != kInvDefault);
+                      ((long long)((q.n1 + WX - 1) / WX) * ((q.n2 + 69) / 70) * (q.nbatch > 1 ? q.nbatch : 1) <= 1280 || vi != kInvDefault);
     const int waves = (deep && vi != kInv2Depth2Geom && vi != kInv2Depth4Geom) ? 1024 : 2048;
     if (!deep) return {kFused2S, q.inverse, q.f64, q.vec4, L, q.ew, fused2s_wpe(q.f64, L, q.ew), 0, false, waves};
     const bool d4 = q.f64 ? L == 4 : (vi != kInv2Depth2Geom && vi != kInv2Depth2Round && (L == 4 || L == 8 || L == 12));
