@@ -108,6 +108,26 @@ int ndwt_plan_create_many(ndwt_plan** plan, int ndim, const int64_t* dims, int64
  * Served and refused entry points: the lists of ndwt_plan_create_many, with the same message. */
 int ndwt_plan_create_axes(ndwt_plan** plan, int ndim, const int64_t* dims, unsigned axes, const char* const* wnames, int dtype,
                           int complexity, int pres_l2_norm, int dilation, int max_level, int device);
+/* Plan over INTERLEAVED SAMPLES: each sample is `inner` >= 1 elements that lie together (fastest in memory), the filtered axes come next,
+ * `howmany` >= 1 items last -- the array is [inner, dims.., howmany] in MATLAB terms.  ndim 1 .. 4; dims / wnames describe ONE item.  A
+ * dynamic series [nx, ny, nt] filtered in time only is inner = nx * ny, dims = {nt}; channels-first images [C, n1, n2] are inner = C.
+ * inner < 1, howmany < 1, ndim outside 1 .. 4: NDWT_ERR_INVALID_ARG, the message names the argument; checked before any device call.
+ * Layout: element (c, i, j) at c + inner * (i + prod(dims) * j); item j of the input and of every band at j * inner * prod(dims); band b
+ * at b * bs with bs = inner * prod(dims) * howmany (packed) or the caller's band_pitch (ndwt_band_pitch: the same plus the usual skew).
+ * Interleaved complex stays innermost (2 scalars per element).  Band order, normalisation and the length checks (on dims only, the
+ * reference's messages) are those of an ndim-D plan.  inner == 1 is the plan ndwt_plan_create_axes makes for [dims.., howmany] with its
+ * leading axes filtered: the same routes, the same bits.
+ * Kernels: every filtered axis is strided, so a level runs one per-axis pass per axis (the register-window march where comp * inner is a
+ * multiple of 4 and the pointers are 16- / 32-byte aligned, the element-wise kernels otherwise: RGB, inner = 3) -- every data kind, both
+ * dilations, every tap length.  With ndim == 1, the reference's dilation, 2 .. 8 taps and comp * inner a multiple of 4, two to four
+ * levels can run inside ONE march (FwdMC / InvMC: the approximations between levels stay in registers, level + 2 volumes of traffic
+ * instead of 3 level), equal to one launch per level bit for bit: on request (ndwt_plan_set_variant(plan, 11, 11, ...)), and unasked only
+ * where it was measured to win; 9 / 9 switches it off per direction.  ndwt_plan_describe: "interleaved cascade" or
+ * "interleaved axis".  ndwt_denoise runs dec, the shrink pass, rec.
+ * Served and refused entry points: the lists of ndwt_plan_create_many, with the same message. */
+int ndwt_plan_create_interleaved(ndwt_plan** plan, int ndim, const int64_t* dims, int64_t inner, int64_t howmany,
+                                 const char* const* wnames, int dtype, int complexity, int pres_l2_norm, int dilation, int max_level,
+                                 int device);
 /* Plan for ONE SLAB of a volume sharded on its outermost axis (the *_slab entry points below): dims describe the local slab,
  * global_outer is the length of the sharded axis of the whole volume.  The reference's length check (nd_dwt_3D.m:277-286:
  * filter <= axis) applies to the WHOLE axis: a slab may be thinner than the filter (cfg5: 32 frames over 8 ranks = 4, db4 = 8

@@ -32,6 +32,7 @@ EXPORTS = [
     "ndwt_comm_last_error", "ndwt_coef_create", "ndwt_coef_release", "ndwt_coef_info", "ndwt_coef_dec_host", "ndwt_coef_rec_host",
     "ndwt_coef_shrink", "ndwt_coef_get_host", "ndwt_coef_put_host", "ndwt_plan_create_slab_axis", "ndwt_slab_segments_strided",
     "ndwt_mplan_create_axis", "ndwt_trace_enable", "ndwt_trace_get", "ndwt_plan_create_many", "ndwt_plan_create_axes",
+    "ndwt_plan_create_interleaved",
 ]
 
 
@@ -78,6 +79,9 @@ def lib() -> ctypes.CDLL:
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ndwt_plan_create_axes.argtypes = [c_void_pp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_uint, ctypes.POINTER(ctypes.c_char_p),
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.ndwt_plan_create_interleaved.argtypes = [c_void_pp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.c_int64,
+                                               ctypes.POINTER(ctypes.c_char_p), ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int]
     L.ndwt_plan_create_slab.argtypes = [c_void_pp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.POINTER(ctypes.c_char_p),
                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.ndwt_plan_create_slab_axis.argtypes = [c_void_pp, ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.c_int, ctypes.c_int64,

@@ -33,12 +33,16 @@ class Plan:
     """Thin RAII wrapper over ndwt_plan (include/ndwt.h)."""
 
     def __init__(self, dims, wnames, dtype, complex_interleaved=False, pres_l2_norm=False, dilation="reference",
-                 max_level=1, device=0, global_outer=None, shard_axis=None, howmany=None, axes=None):
+                 max_level=1, device=0, global_outer=None, shard_axis=None, howmany=None, axes=None, inner=None):
         """howmany: None = one array (ndwt_plan_create); a number = a batched plan of that many 1-D signals (ndwt_plan_create_many):
         signal k at k * dims[0] elements, every band a contiguous (howmany, n) block.
         axes: a tuple of axis numbers (0 = the fastest) = only these axes of `dims`, the WHOLE array, are filtered
         (ndwt_plan_create_axes; served: the leading axes (0, .., k-1)).  With k < len(dims) the plan is a stack: the prod(dims[k:]) items
         lie back to back and each gets the k-D transform; every band is a whole array.  Not together with `howmany`.
+        A run of adjacent axes (a, .., a+k-1) with a > 0 is a plan over interleaved samples (ndwt_plan_create_interleaved):
+        inner = prod(dims[:a]), the filtered axes dims[a:a+k], howmany = prod(dims[a+k:]); the names of the axes left alone are ignored.
+        inner: a number = each sample is that many elements lying together, the array is [inner, dims.., howmany] (howmany: None = 1) and
+        `dims` / `wnames` describe one item (ndwt_plan_create_interleaved).  Not together with `axes`.
         global_outer: length of the sharded axis of the WHOLE volume when `dims` describe one slab of it (multi-GPU):
         the reference's filter-length check then applies to the whole axis, a slab may be thinner than the filter.
         shard_axis: the sharded axis, counted from the fastest (0 = x); None = the outermost (ndwt_plan_create_slab), 2 of a 4-D
@@ -58,7 +62,25 @@ class Plan:
         self.shard_axis = self.ndim - 1 if shard_axis is None else int(shard_axis)
         self.howmany = None if howmany is None else int(howmany)
         self.axes = None if axes is None else tuple(int(a) for a in axes)
-        if axes is not None:
+        self.inner = None if inner is None else int(inner)
+        if inner is not None and axes is not None:
+            raise ValueError("'axes' and 'inner' are two ways to say the same thing: give one of them")
+        if axes is not None and howmany is None and shard_axis is None and global_outer is None:
+            ax = sorted(self.axes)
+            if (len(set(ax)) == len(ax) and ax[0] > 0 and ax[-1] < self.ndim and ax == list(range(ax[0], ax[-1] + 1))):
+                # a run of adjacent axes that does not start at 0: the axes below it are the sample, those above it the items
+                whole, names = self.dims, self.wnames
+                self.inner = int(np.prod(whole[:ax[0]], dtype=np.int64))
+                self.howmany = int(np.prod(whole[ax[-1] + 1:], dtype=np.int64))
+                item = whole[ax[0]:ax[-1] + 1]
+                self._create_interleaved(item, names[ax[0]:ax[-1] + 1], dt, cplx, pres_l2_norm, dil)
+                return
+        if inner is not None:
+            if shard_axis is not None or global_outer is not None:
+                raise ValueError("a plan over interleaved samples is not a slab plan")
+            self.howmany = 1 if howmany is None else int(howmany)
+            self._create_interleaved(self.dims, self.wnames, dt, cplx, pres_l2_norm, dil)
+        elif axes is not None:
             if howmany is not None:
                 raise ValueError("'axes' and 'howmany' are two ways to say the same thing: give one of them")
             if shard_axis is not None or global_outer is not None:
@@ -85,6 +107,13 @@ class Plan:
         else:
             L.check(L.lib().ndwt_plan_create_slab(ctypes.byref(self._h), self.ndim, dims_c, int(global_outer), names_c, dt, cplx,
                                                   int(bool(pres_l2_norm)), dil, self.max_level, self.device))
+
+    def _create_interleaved(self, item_dims, item_names, dt, cplx, pres_l2_norm, dil):
+        k = len(item_dims)
+        dims_c = (ctypes.c_int64 * max(k, 1))(*item_dims)
+        names_c = (ctypes.c_char_p * max(k, 1))(*[None if w is None else w.encode() for w in item_names])
+        L.check(L.lib().ndwt_plan_create_interleaved(ctypes.byref(self._h), k, dims_c, self.inner, self.howmany, names_c, dt, cplx,
+                                                     int(bool(pres_l2_norm)), dil, self.max_level, self.device))
 
     def __del__(self):
         try:
@@ -442,6 +471,7 @@ class _NdDwtBase:
         self.band_pitch = "packed"
         self.batch = None
         self.stack = None
+        self.inner = None
         # name/value pairs as in MATLAB (nd_dwt_3D.m:105-120); keyword arguments are accepted too
         if len(varargin) % 2:
             raise ValueError("Optional inputs must come in pairs")
@@ -464,6 +494,8 @@ class _NdDwtBase:
                 self.batch = int(val)
             elif k == "stack":                     # nd_dwt_2D / nd_dwt_3D: this many images / volumes per call, x = [sizes, stack]
                 self.stack = int(val)
+            elif k == "inner":                     # nd_dwt_1D / 2D / 3D: each sample is this many elements (a number or a list of sizes) lying
+                self.inner = [int(v) for v in np.atleast_1d(val)]   # together: x = [inner.., sizes, (batch | stack)]
             elif k == "devices":                   # shard the outermost axis over these devices (host arrays, one process)
                 self.devices = [int(v) for v in np.atleast_1d(val)]
             else:   # unknown keys only warn (nd_dwt_3D.m:118)
@@ -503,8 +535,16 @@ class _NdDwtBase:
                 raise ValueError("'stack' and 'devices' do not combine: a stack plan lives on one device")
             if self.stack < 1:
                 raise ValueError("'stack' must be a number of items >= 1")
-        # the shape of x in MATLAB terms: `sizes`, for a batched 1-D object [n, batch], for a stack [sizes, stack]
-        self._shape = sizes + ([self.batch] if self.batch is not None else []) + ([self.stack] if self.stack is not None else [])
+        if self.inner is not None:
+            if d == 4:
+                raise ValueError("'inner' is an option of nd_dwt_1D, nd_dwt_2D and nd_dwt_3D: interleaved samples of 4-D arrays are not supported")
+            if self.devices is not None:
+                raise ValueError("'inner' and 'devices' do not combine: a plan over interleaved samples lives on one device")
+            if len(self.inner) < 1 or any(v < 1 for v in self.inner):
+                raise ValueError("'inner' must be a number of elements >= 1, or a list of such sizes")
+        # the shape of x in MATLAB terms: `sizes`, for a batched 1-D object [n, batch], for a stack [sizes, stack]; with 'inner' its sizes
+        # come first: [inner.., sizes, (batch | stack)]
+        self._shape = (self.inner or []) + sizes + ([self.batch] if self.batch is not None else []) + ([self.stack] if self.stack is not None else [])
         # get_filters (nd_dwt_3D.m:263-342): per-axis taps instead of N-D FFT-domain kernels
         self.f_dec = [L.wave_filters(w) for w in self.wname[:d]]
         self.f_size = {f"s{a + 1}": len(self.f_dec[a][0]) for a in range(d)}
@@ -548,7 +588,10 @@ class _NdDwtBase:
             real_dt = torch.float32 if self.precision.lower() == "single" else torch.float64
             if p is not None:
                 torch.cuda.synchronize(idx)                           # the plan being replaced may still be running
-            if self.stack is not None:                                # the whole array, its leading axes filtered
+            if self.inner is not None:                                # interleaved samples: every filtered axis is strided
+                p = Plan(self.sizes, self.wname[: self.NDIM], real_dt, is_complex, self.pres_l2_norm, self.dilation, max_level=max(level, 3),
+                         device=idx, inner=int(np.prod(self.inner, dtype=np.int64)), howmany=self.batch or self.stack or 1)
+            elif self.stack is not None:                              # the whole array, its leading axes filtered
                 p = Plan(self.sizes + [self.stack], self.wname[: self.NDIM] + [None], real_dt, is_complex, self.pres_l2_norm,
                          self.dilation, max_level=max(level, 3), device=idx, axes=tuple(range(self.NDIM)))
             else:
@@ -739,7 +782,7 @@ class nd_dwt_1D(_NdDwtBase):
 
     def _prep_dec_input(self, x):
         # row vectors are transposed (nd_dwt_1D.m:151-153); accept [n], [n,1] and [1,n]; a batched object takes [n, batch] as it is
-        if self.batch is None and x.ndim == 2 and 1 in x.shape:
+        if self.batch is None and self.inner is None and x.ndim == 2 and 1 in x.shape:
             x = x.reshape(-1)
         return x
 

@@ -154,6 +154,8 @@ struct ndwt_plan {
     long long howmany = 0;             // ndwt_plan_create_many: signals of a batched 1-D plan, signal k at k * dims[0] elements; 0 = not batched.
                                        // ndwt_plan_create_axes: the items of a stack -- ndim and dims are those of ONE item (an image or a
                                        // volume), item j at j * item_vol() scalars of the input and of every band
+    long long inner = 1;               // ndwt_plan_create_interleaved: elements of a sample that lie together, faster in memory than dims[0]
+                                       // (the array is [inner, dims.., howmany]); 1 everywhere else
     DevBuf approx_base[2];             // approximation ping-pong between levels, each kApproxSkew bytes larger than a band: approx(i) is the band
     DevBuf tmp;                        // temporaries of the per-axis path / 4-D split
     int target_blocks = 0;             // fused-kernel grid sizing: 0 = one round of resident workgroups (per kernel), else as given
@@ -252,7 +254,7 @@ static int axis_pass(const ndwt_plan* p, bool synthesis, int axis, const long lo
         tp.hi[j] = (T)(synthesis ? f.syn_hi[j] : f.ana_hi[j]);
     }
     AxisArgs<T> a;
-    a.inner = p->comp;
+    a.inner = p->comp * p->inner;                         // (interleaved samples: axis 0 is strided too)
     for (int k = 0; k < axis; ++k) a.inner *= dims_cur[k];
     a.outer = p->howmany > 0 ? p->howmany : 1;            // (a batched 1-D plan: its signals are the rows)
     for (int k = axis + 1; k < p->ndim; ++k) a.outer *= dims_cur[k];
@@ -295,7 +297,7 @@ static int axis_pass(const ndwt_plan* p, bool synthesis, int axis, const long lo
         // rc < 0: no instantiation / grid too large -> fall through to the element-wise kernel
     }
     // the contiguous axis (1-D signals, interleaved complex): one wave per row segment, neighbours by lane shifts
-    if (p->path == NDWT_PATH_AUTO && axis == 0 && stride == 1 && wrap && f.len <= 12 && (p->comp == 1 || p->comp == 2) &&
+    if (p->path == NDWT_PATH_AUTO && axis == 0 && p->inner == 1 && stride == 1 && wrap && f.len <= 12 && (p->comp == 1 || p->comp == 2) &&
         a.n * p->comp >= 8 * f.len) {
         AxisXArgs<T> x;
         x.in0 = in0; x.in1 = in1; x.out0 = out0; x.out1 = out1;
@@ -394,7 +396,7 @@ template <typename T> static int per_axis_level(ndwt_plan* p, bool synthesis, co
 // The eligibility predicates and the choice of kernel are plain functions of integers (ndwt_select.h); this is what they see of a plan.
 static SelPlan sel(const ndwt_plan* p) {
     SelPlan q = {p->ndim, (int)p->comp, p->dtype == NDWT_F64, p->complexity == NDWT_REAL, p->path == NDWT_PATH_AUTO,
-                 p->dilation != NDWT_DILATION_REFERENCE, p->fp64_fused != 0, {1, 1, 1, 1}, {2, 2, 2, 2}, p->variant_fwd, p->variant_inv, p->howmany};
+                 p->dilation != NDWT_DILATION_REFERENCE, p->fp64_fused != 0, {1, 1, 1, 1}, {2, 2, 2, 2}, p->variant_fwd, p->variant_inv, p->howmany, p->inner};
     for (int k = 0; k < p->ndim; ++k) { q.dims[k] = p->dims[k]; q.len[k] = p->filt[k].len; }
     return q;
 }
@@ -787,6 +789,43 @@ template <typename T> static int cascade1_run(ndwt_plan* p, bool inverse, int L,
     return rc < 0 ? -1 : 0;
 }
 
+// ---- two to four levels of the one strided axis of a plan over interleaved samples in one march (FwdMC / InvMC, ndwt_device_axis.h;
+// when: cascadem_levels).  in / out as MarchCArgs documents them.  The chunking is axis_pass's own rule (about 4096 workgroups, in chunks
+// of the axis), the floor raised to 4 nlev (L - 1) planes -- the march-in is at most a quarter of a thread's planes -- and capped at the
+// axis; force_zchunk / zchunk_dir = planes per chunk.  Returns 0, or -1: not this data (a pointer off the 16- / 32-byte groups), no
+// instance, or a grid beyond 2^31 - 1 workgroups -- the caller takes one launch per level
+template <typename T> static int cascadem_run(ndwt_plan* p, bool inverse, int L, int nlev, const T* const* in, T* const* out, hipStream_t s) {
+    MarchCArgs<T> a;
+    memset(&a, 0, sizeof a);
+    bool aligned = true;
+    for (int b = 0; b < (inverse ? 1 + nlev : 1); ++b) { a.in[b] = in[b]; aligned = aligned && aligned_vec4<T>(in[b]); }
+    for (int b = 0; b < (inverse ? 1 : 1 + nlev); ++b) { a.out[b] = out[b]; aligned = aligned && aligned_vec4<T>(out[b]); }
+    a.inner = p->comp * p->inner;
+    if (!aligned || a.inner % 4 != 0) return -1;
+    a.n = p->dims[0];
+    a.outer = p->items();
+    a.ngroups = a.inner / 4;
+    const long long iblocks = (a.ngroups * a.outer + 255) / 256;
+    long long want = (4096 + iblocks - 1) / iblocks;
+    if (want < 1) want = 1;
+    long long chunk = (a.n + want - 1) / want;
+    const long long min_chunk = 4LL * nlev * (L - 1);
+    if (chunk < min_chunk) chunk = min_chunk;
+    const int zc_force = p->zchunk_dir[inverse ? 1 : 0] > 0 ? p->zchunk_dir[inverse ? 1 : 0] : p->force_zchunk;
+    if (zc_force > 0) chunk = zc_force;
+    if (chunk > a.n) chunk = a.n;
+    a.chunk = (int)chunk;
+    a.nchunks = (int)((a.n + chunk - 1) / chunk);
+    if (iblocks * a.nchunks > 0x7fffffffLL) return -1;
+    const AxisFilter& f = p->filt[0];
+    const CascadeMInstance k = {inverse, sizeof(T) == 8, L, nlev};
+    prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
+    const int rc = launch_cascadem(k, a, inverse ? f.syn_lo : f.ana_lo, inverse ? f.syn_hi : f.ana_hi, s);
+    prof_end(p, s, rc);
+    if (rc > 0) return fail(NDWT_ERR_HIP, "cascaded march %s launch failed: %s", inverse ? "synthesis" : "analysis", hipGetErrorString((hipError_t)rc));
+    return rc < 0 ? -1 : 0;
+}
+
 // detail band b (1 .. 2^d - 1) of level `lev` in the coefficients y of a `level`-level transform (the bookkeeping above)
 template <typename T> static T* detail_band(const ndwt_plan* p, T* y, long long bs, int level, int lev, int b) {
     return y + (long long)(1 + ((1 << p->ndim) - 1) * (level - lev) + (b - 1)) * bs;
@@ -806,6 +845,20 @@ template <typename T> static int dec_impl(ndwt_plan* p, const T* x, T* y, long l
             out[0] = (last == level) ? y : (T*)p->approx(pp);
             for (int l = 0; l < n; ++l) out[1 + l] = detail_band(p, y, bs, level, lev + l, 1);
             const int rc = cascade1_run<T>(p, false, L1, n, in, out, s);
+            if (rc == -1) break;                          // not this data: one launch per level from here on
+            if (rc) return rc;
+            cur = out[0];
+            pp ^= 1;
+            lev = last + 1;
+        }
+        int Lm = 0;
+        while (const int n = cascadem_levels(sp, false, level - lev + 1, &Lm)) {   // interleaved samples, one axis: levels lev .. lev + n - 1
+            const int last = lev + n - 1;
+            const T* in[5] = {cur};
+            T* out[5];
+            out[0] = (last == level) ? y : (T*)p->approx(pp);
+            for (int l = 0; l < n; ++l) out[1 + l] = detail_band(p, y, bs, level, lev + l, 1);
+            const int rc = cascadem_run<T>(p, false, Lm, n, in, out, s);
             if (rc == -1) break;                          // not this data: one launch per level from here on
             if (rc) return rc;
             cur = out[0];
@@ -873,6 +926,20 @@ template <typename T> static int rec_impl(ndwt_plan* p, const T* y, long long bs
             const int low = lev - n + 1;
             T* dst[5] = {(low == 1) ? x : (T*)p->approx(pp)};
             const int rc = cascade1_run<T>(p, true, L1, n, in, dst, s);
+            if (rc == -1) break;
+            if (rc) return rc;
+            prev = dst[0];
+            pp ^= 1;
+            lev = low - 1;
+        }
+        int Lm = 0;
+        while (const int n = cascadem_levels(sp, true, lev, &Lm)) {   // interleaved samples, one axis: levels lev, lev - 1, .. lev - n + 1
+            const T* in[5];
+            in[0] = prev;
+            for (int c = 0; c < n; ++c) in[1 + c] = detail_band(p, y, bs, level, lev - c, 1);
+            const int low = lev - n + 1;
+            T* dst[5] = {(low == 1) ? x : (T*)p->approx(pp)};
+            const int rc = cascadem_run<T>(p, true, Lm, n, in, dst, s);
             if (rc == -1) break;
             if (rc) return rc;
             prev = dst[0];
@@ -1218,7 +1285,8 @@ int ndwt_level_from_bands(int ndim, int64_t bands) {
 static bool den3_eligible(const ndwt_plan* p, int fused_level1, int* Lp_out);
 static int den3_taps(ndwt_plan* p, int Lp);
 static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, long long global_outer, const char* const* wnames, int dtype,
-                            int complexity, int pres_l2_norm, int dilation, int max_level, int device, int shard = -1, long long howmany = 0) {
+                            int complexity, int pres_l2_norm, int dilation, int max_level, int device, int shard = -1, long long howmany = 0,
+                            long long inner = 1) {
     if (!plan) return fail(NDWT_ERR_INVALID_ARG, "null plan pointer");
     *plan = nullptr;
     if (ndim < 1 || ndim > NDWT_MAX_DIMS) return fail(NDWT_ERR_INVALID_ARG, "ndim must be 1..4");
@@ -1241,7 +1309,8 @@ static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, lon
     p->shard = shard >= 0 ? shard : ndim - 1;
     static const char* ordn[4] = {"First", "Second", "Third", "Fourth"};
     p->howmany = howmany;
-    p->vol = p->comp * (howmany > 0 ? howmany : 1);
+    p->inner = inner;
+    p->vol = p->comp * inner * (howmany > 0 ? howmany : 1);
     for (int a = 0; a < ndim; ++a) {
         if (dims[a] < 1) return fail(NDWT_ERR_INVALID_ARG, "dims[%d] must be >= 1", a);
         const int K = parse_wavelet(wnames[a]);
@@ -1270,7 +1339,7 @@ static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, lon
         if (const int rc = p->approx_base[i].grow((size_t)p->vol * p->esize + kApproxSkew, "of the approximation scratch", false)) return rc;
     int Lp = level_route(sel(p), 1, 0, kWholeArray).Lp;
     // a batched 1-D plan whose levels can cascade (Fwd1C / Inv1C read Taps3<T, L>, axis 0): the table of its own tap length
-    if (!Lp && howmany > 0 && p->filt[0].len <= 8 && (cascade1_instantiated({false, dtype == NDWT_F64, (int)p->comp, p->filt[0].len, 2}))) Lp = p->filt[0].len;
+    if (!Lp && howmany > 0 && inner == 1 && p->filt[0].len <= 8 && (cascade1_instantiated({false, dtype == NDWT_F64, (int)p->comp, p->filt[0].len, 2}))) Lp = p->filt[0].len;
     // a plan with fused levels (the analysis side admits the most tap lengths): Taps3, and for the synthesis Taps3Y -- the same, then the
     // x tap pairs of the pair-packed kernel
     for (int inv = 0; inv < 2 && Lp; ++inv) {
@@ -1325,6 +1394,19 @@ int ndwt_plan_create_axes(ndwt_plan** plan, int ndim, const int64_t* dims, unsig
         items *= dims[a];
     }
     return plan_create_impl(plan, k, dims, -1, wnames, dtype, complexity, pres_l2_norm, dilation, max_level, device, -1, items);
+}
+
+// Samples of `inner` elements that lie together: the array is [inner, dims.., howmany], every filtered axis strided.  Everything is
+// checked before any device call.  inner == 1 is the plan ndwt_plan_create_axes makes for [dims.., howmany] with its leading axes filtered
+// (the same plan fields, so the same routes and the same bits); the plan is always a batched one (howmany >= 1).
+int ndwt_plan_create_interleaved(ndwt_plan** plan, int ndim, const int64_t* dims, int64_t inner, int64_t howmany, const char* const* wnames,
+                                 int dtype, int complexity, int pres_l2_norm, int dilation, int max_level, int device) {
+    if (plan) *plan = nullptr;
+    if (ndim < 1 || ndim > NDWT_MAX_DIMS) return fail(NDWT_ERR_INVALID_ARG, "ndim must be 1..4 (got %d)", ndim);
+    if (inner < 1) return fail(NDWT_ERR_INVALID_ARG, "inner must be >= 1 (got %lld)", (long long)inner);
+    if (howmany < 1) return fail(NDWT_ERR_INVALID_ARG, "howmany must be >= 1 (got %lld)", (long long)howmany);
+    if (inner > (1LL << 40) || howmany > (1LL << 40)) return fail(NDWT_ERR_INVALID_ARG, "inner and howmany are at most 2^40 each");
+    return plan_create_impl(plan, ndim, dims, -1, wnames, dtype, complexity, pres_l2_norm, dilation, max_level, device, -1, howmany, inner);
 }
 
 int ndwt_plan_create_slab(ndwt_plan** plan, int ndim, const int64_t* dims_local, int64_t global_outer, const char* const* wnames,
@@ -1434,6 +1516,10 @@ int ndwt_plan_describe(const ndwt_plan* p, char* buf, int buflen) {
     if (p->howmany > 0 && p->ndim >= 2) {                 // a stack (ndwt_plan_create_axes): what two levels of it run today
         int Lp = 0;
         s = cascade2_levels(sel(p), false, 2, &Lp) ? "stack2d cascade" : ra == kRouteFused2 ? "stack2d fused" : f3a ? "stack3d fused" : "stack axis";
+    }
+    if (p->inner > 1) {                                   // interleaved samples (ndwt_plan_create_interleaved): what two levels of it run today
+        int Lm = 0;
+        s = cascadem_levels(sel(p), false, 2, &Lm) ? "interleaved cascade" : "interleaved axis";
     }
     snprintf(buf, (size_t)buflen, "%s", s);
     return NDWT_OK;

@@ -7,6 +7,7 @@
 
 #include "ndwt_device.h"
 #include "ndwt_device_1d.h"
+#include "ndwt_device_axis.h"
 #include "ndwt_select.h"
 
 namespace ndwt {
@@ -41,6 +42,12 @@ int launch_cascade2(const Cascade2Instance& k, const Fused2CIArgs<double>& a, co
 // geometry is not the instance's tile, or the grid is too large.
 int launch_cascade1(const Cascade1Instance& k, const Fused1CArgs<float>& a, const void* taps_dev, hipStream_t s);
 int launch_cascade1(const Cascade1Instance& k, const Fused1CArgs<double>& a, const void* taps_dev, hipStream_t s);
+
+// Two to four levels of one strided axis inside one march (FwdMC / InvMC), the instance named in full (ndwt_fused_list.h:
+// CascadeMInstance, the table cascadem_levels reads); lo / hi: the kernel-form taps of the direction, length k.L.  -1: no unit has the
+// instance, -2: the grid is too large.
+int launch_cascadem(const CascadeMInstance& k, const MarchCArgs<float>& a, const double* lo, const double* hi, hipStream_t s);
+int launch_cascadem(const CascadeMInstance& k, const MarchCArgs<double>& a, const double* lo, const double* hi, hipStream_t s);
 
 // one non-contiguous axis with the window in registers (taps: kernel-form lo/hi of length L)
 int launch_march_f32(bool syn, int L, const MarchArgs<float>& a, const double* lo, const double* hi, hipStream_t s);

@@ -27,6 +27,14 @@ __global__ __launch_bounds__(K::NT) __attribute__((amdgpu_waves_per_eu(K::WPE, K
     K::block(ex, sh, a, tp, (int)blockIdx.x);
 }
 
+// The march kernels (AxisMarch, AxisX: ndwt_march.hip; FwdMC / InvMC: ndwt_marchc_*.hip): arguments and taps by value, no LDS
+template <class K>
+__global__ __launch_bounds__(K::NT) void march_kernel(const typename K::Args a, const typename K::Taps tp) {
+    typename K::Shared sh;
+    GpuExec<typename K::State> ex;
+    K::block(ex, sh, a, tp, (int)blockIdx.x);
+}
+
 // taps_dev: device buffer holding Taps3<T, Lp> (lo[3][Lp] then hi[3][Lp]) for this direction
 template <class K> int launch_fused3(const typename K::Args& a, const void* taps_dev, hipStream_t s) {
     // the host computed the tiling for a tile shape (fused3_tile_shape); this kernel was compiled for one: they must be the same,
@@ -68,6 +76,21 @@ template <class K> int launch_cascade1_k(const typename K::Args& a, const void* 
     return (int)hipGetLastError();
 }
 
+// The cascaded march of one strided axis: 256 (item, group of 4 scalars) pairs per workgroup, times the chunks of the axis
+template <class K> int launch_cascadem_k(const typename K::Args& a, const double* lo, const double* hi, hipStream_t s) {
+    typename K::Taps tp;
+    typedef std::remove_reference_t<decltype(tp.lo[0])> T;
+    for (int j = 0; j < K::L; ++j) { tp.lo[j] = (T)lo[j]; tp.hi[j] = (T)hi[j]; }
+    if (a.inner < 4 || a.inner % 4 != 0 || a.ngroups != a.inner / 4 || a.n < 1 || a.outer < 1 || a.chunk < 1 ||
+        (long long)a.nchunks * a.chunk < a.n || (long long)(a.nchunks - 1) * a.chunk >= a.n)
+        return -2;
+    const long long nblocks = (a.ngroups * a.outer + K::NT - 1) / K::NT * a.nchunks;
+    if (nblocks <= 0 || nblocks > 0x7fffffffLL) return -2;
+    trace_kernel<K>(dim3((unsigned)nblocks), dim3(K::NT));
+    hipLaunchKernelGGL(march_kernel<K>, dim3((unsigned)nblocks), dim3(K::NT), 0, s, a, tp);
+    return (int)hipGetLastError();
+}
+
 // One entry of an instance list (ndwt_fused_list.h) as an exact-match launch: the pick is this instance, or the next entry is asked.  A
 // launch unit is its list expanded with these and a final "not mine" (-1).
 #define NDWT_FUSED_K(KIND, INV, T, LL, V, VEC, ...)                                                          \
@@ -104,5 +127,7 @@ template <class K> int launch_cascade1_k(const typename K::Args& a, const void* 
         static_assert(KIND<T, LL, NLEV, EWV>::WX == cascade1_tile_width({k##KIND == kInv1C, sizeof(T) == 8, EWV, LL, NLEV}), "tile width"); \
         return launch_cascade1_k<KIND<T, LL, NLEV, EWV>>(a, taps_dev, s);                                    \
     }
+#define NDWT_LAUNCH_M(KIND, T, LL, NLEV) \
+    if (k == CascadeMInstance{k##KIND == kInvMC, sizeof(T) == 8, LL, NLEV}) return launch_cascadem_k<KIND<T, LL, NLEV>>(a, lo, hi, s);
 
 }  // namespace ndwt

@@ -55,6 +55,12 @@ struct Cascade1Instance { bool inverse, f64; int ew, Lp, nlev; };
 constexpr bool operator==(const Cascade1Instance& a, const Cascade1Instance& b) {
     return a.inverse == b.inverse && a.f64 == b.f64 && a.ew == b.ew && a.Lp == b.Lp && a.nlev == b.nlev;
 }
+// FwdMC / InvMC<T, L, nlev> (ndwt_device_axis.h): two to four levels of one strided axis inside one march (interleaved complex: the
+// factor 2 in the inner block, no instance of its own)
+struct CascadeMInstance { bool inverse, f64; int L, nlev; };
+constexpr bool operator==(const CascadeMInstance& a, const CascadeMInstance& b) {
+    return a.inverse == b.inverse && a.f64 == b.f64 && a.L == b.L && a.nlev == b.nlev;
+}
 
 // ---- the lists.  Entries:  F(T, L, V, VEC4, EW, PIN, TPRE, WLDS)  Fwd3 on tile V
 //                            S(KIND, T, L, V, VEC4, EW)             Inv3 / Inv3S on tile V
@@ -64,6 +70,7 @@ constexpr bool operator==(const Cascade1Instance& a, const Cascade1Instance& b) 
 //                            A(T, EW, L, NLEV, WPE)                 Fwd2C
 //                            R(T, EW, L, NLEV, PD, WPE)             Inv2C
 //                            C(KIND, T, EW, L, NLEV)                Fwd1C / Inv1C
+//                            M(KIND, T, L, NLEV)                    FwdMC / InvMC
 // NDWT_F2 / NDWT_S2 / NDWT_Y2 / NDWT_W2: the plain form of an entry for rows of whole groups of 4 scalars and for the rest
 #define NDWT_F2(F, T, L, V, EW) F(T, L, V, true, EW, false, false, 0) F(T, L, V, false, EW, false, false, 0)
 #define NDWT_S2(S, KIND, T, L, V, EW) S(KIND, T, L, V, true, EW) S(KIND, T, L, V, false, EW)
@@ -263,6 +270,19 @@ constexpr bool operator==(const Cascade1Instance& a, const Cascade1Instance& b) 
 #define NDWT_LIST_C128_1C(C, KIND) NDWT_C1_KIND(C, KIND, double, 2)
 #define NDWT_LIST_1C(C, KIND) NDWT_LIST_F32_1C(C, KIND) NDWT_LIST_C64_1C(C, KIND) NDWT_LIST_F64_1C(C, KIND) NDWT_LIST_C128_1C(C, KIND)
 
+// The cascaded march of one strided axis (FwdMC / InvMC, ndwt_device_axis.h): THE table of the instances that exist -- cascadem_levels
+// (ndwt_select.h) answers from it, the launch units (ndwt_marchc_{f32,f64}.hip) expand it.  {float, double} x 2 .. 8 taps x 2 .. 4 levels
+// x both directions, less the two that spill.  A lane keeps NLEV windows of L 4-vectors: 4 NLEV L registers in float, twice that in
+// double.  Every listed instance builds for gfx950 without scratch and without spilled vector registers (tools/kernel_resources.sh);
+// InvMC<double, 8, 3> (5 spilled registers, 24 B of scratch) and InvMC<double, 8, 4> (162, 644 B) do not and are left out: the double
+// 8-tap synthesis cascades two levels at a time.
+#define NDWT_M234(M, KIND, T, L) M(KIND, T, L, 2) M(KIND, T, L, 3) M(KIND, T, L, 4)
+#define NDWT_LIST_F32_FWDMC(M) NDWT_M234(M, FwdMC, float, 2) NDWT_M234(M, FwdMC, float, 4) NDWT_M234(M, FwdMC, float, 6) NDWT_M234(M, FwdMC, float, 8)
+#define NDWT_LIST_F32_INVMC(M) NDWT_M234(M, InvMC, float, 2) NDWT_M234(M, InvMC, float, 4) NDWT_M234(M, InvMC, float, 6) NDWT_M234(M, InvMC, float, 8)
+#define NDWT_LIST_F64_FWDMC(M) NDWT_M234(M, FwdMC, double, 2) NDWT_M234(M, FwdMC, double, 4) NDWT_M234(M, FwdMC, double, 6) NDWT_M234(M, FwdMC, double, 8)
+#define NDWT_LIST_F64_INVMC(M) NDWT_M234(M, InvMC, double, 2) NDWT_M234(M, InvMC, double, 4) NDWT_M234(M, InvMC, double, 6) M(InvMC, double, 8, 2)
+#define NDWT_LIST_MC(M) NDWT_LIST_F32_FWDMC(M) NDWT_LIST_F32_INVMC(M) NDWT_LIST_F64_FWDMC(M) NDWT_LIST_F64_INVMC(M)
+
 // ---- questions to the lists
 #define NDWT_IS_F(T, L, V, VEC4, EW, PIN, TPRE, WLDS) if (k == fwd3_instance(sizeof(T) == 8, L, V, VEC4, EW, PIN, TPRE, WLDS)) return true;
 #define NDWT_IS_S(KIND, T, L, V, VEC4, EW) if (k == inv3s_instance(k##KIND, sizeof(T) == 8, L, V, VEC4, EW)) return true;
@@ -297,6 +317,12 @@ inline bool cascade1_instantiated(const Cascade1Instance& k) {
 }
 // scalars of a row one wave of the instance stores (Fwd1C::WX, Inv1C::WX: the same rule as the 2-D cascade's)
 constexpr int cascade1_tile_width(const Cascade1Instance& k) { return wave_row_width(k.inverse, k.Lp, k.ew, k.f64, k.nlev); }
+enum CascadeMKind { kFwdMC, kInvMC };
+#define NDWT_IS_M(KIND, T, L, NLEV) if (k == CascadeMInstance{k##KIND == kInvMC, sizeof(T) == 8, L, NLEV}) return true;
+inline bool cascadem_instantiated(const CascadeMInstance& k) {
+    NDWT_LIST_MC(NDWT_IS_M)
+    return false;
+}
 #define NDWT_IS_W(KIND, T, L, VEC4, WPE, EW) if (k == Fused2SInstance{k##KIND == kInv2S, sizeof(T) == 8, VEC4, L, EW, WPE}) return true;
 inline bool fused2s_instantiated(const Fused2SInstance& k) {
     NDWT_LIST_2S(NDWT_IS_W, Fwd2S) NDWT_LIST_2S(NDWT_IS_W, Inv2S)

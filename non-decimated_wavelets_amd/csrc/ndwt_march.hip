@@ -3,13 +3,6 @@
 
 namespace ndwt {
 
-template <class K>
-__global__ __launch_bounds__(K::NT) void march_kernel(const typename K::Args a, const typename K::Taps tp) {
-    typename K::Shared sh;
-    GpuExec<typename K::State> ex;
-    K::block(ex, sh, a, tp, (int)blockIdx.x);
-}
-
 template <typename T, int L, bool SYN>
 static int launch_march_L(const MarchArgs<T>& a, const double* lo, const double* hi, hipStream_t s) {
     typedef AxisMarch<T, L, SYN> K;

@@ -19,6 +19,7 @@ namespace ndwt {
 //  10  |                                                                     | cascade whatever the image size, kernel mode 1 (no take-in-only steps)
 //  11  |                                                                     | cascade whatever the image size
 //      (a batched 1-D plan, cascade1_levels: fwd 9 = one launch per level in the analysis, inv 9 = in the synthesis; nothing else applies)
+//      (interleaved samples, one axis, cascadem_levels: fwd / inv 9 = one launch per level, 11 = the cascaded march wherever it exists)
 //  inv | 3-D synthesis (fused3_select)                                       | 2-D (fused2_select)                | 2-D cascade (cascade2_levels)
 //   0  | default: Inv3Y (gather <= 8 taps, scatter from 10), else Inv3S      | Inv2P depth 4 packed, 1024 waves, where the image fits one round
 //   1  |                                                                     | keeps Inv2S
@@ -48,8 +49,11 @@ struct SelPlan {
     int variant_fwd, variant_inv;
     long long howmany = 0;             // items of a batched plan: the signals of ndwt_plan_create_many, or the images / volumes of a stack
                                        // (ndwt_plan_create_axes: ndim and dims are those of ONE item); 0 = not batched
+    long long inner = 1;               // ndwt_plan_create_interleaved: elements of a sample that lie together, faster in memory than dims[0];
+                                       // every filtered axis is then strided: the per-axis kernels, and for one axis the cascaded march
 };
 constexpr bool is_stack(const SelPlan& p) { return p.howmany > 0 && p.ndim >= 2; }
+constexpr bool is_interleaved(const SelPlan& p) { return p.inner > 1; }
 
 inline int padded_len(const int* len) { int Lp = 2; for (int a = 0; a < 3; ++a) Lp = len[a] > Lp ? len[a] : Lp; return Lp; }
 // the zero padding (Lp - len) / 2 of every axis' taps is even: the kernels that derive the high-pass taps from the low-pass ones
@@ -157,6 +161,7 @@ enum SlabMode { kWholeArray, kSlabOuter, kSlabZ };
 inline LevelRoute level_route(const SelPlan& p, long long stride, int dir, SlabMode mode) {
     const bool slab = mode != kWholeArray, halo_on_z = mode == kSlabZ || (mode == kSlabOuter && p.ndim == 3);
     int Lp = 0;
+    if (is_interleaved(p)) return {kRoutePerAxis, 0};     // no fused form reads samples of `inner` elements
     if (is_stack(p)) {
         if (slab || stride != 1 || p.howmany >= (1LL << 20)) return {kRoutePerAxis, 0};
         if (p.ndim == 3 && fused3_eligible(p, stride, &Lp, dir)) return {kRouteFused3, Lp};
@@ -182,7 +187,7 @@ inline int slab_fused3(const SelPlan& p, long long stride, int dir, SlabMode mod
 
 // true when every synthesis level of this plan runs a kernel that can shrink its inputs on load (Inv3S / Inv3Y / Inv2S / Inv2P)
 inline bool fused_shrink_capable(const SelPlan& p) {
-    if (p.atrous) return false;                                       // dilated levels take the per-axis kernels
+    if (p.atrous || is_interleaved(p)) return false;                  // dilated levels, interleaved samples: the per-axis kernels
     const LevelRoute r = level_route(p, 1, -1, kWholeArray);
     return r.kind == kRouteFused2 || (route_fused3(r.kind) && !(p.variant_inv == kInvLds && r.Lp == 8));   // the LDS synthesis kernel does not
 }
@@ -213,7 +218,7 @@ constexpr bool cascade2_stack_default(bool f64, int comp, bool inverse, long lon
 }
 inline int cascade2_levels(const SelPlan& p, bool inverse, int left, int* Lp_out) {
     int& Lp = *Lp_out;
-    if (left < 2 || p.atrous || p.variant_fwd == kFwdNoCascade || (p.comp != 1 && p.comp != 2) || !fused2_eligible(p, 1, &Lp)) return 0;
+    if (left < 2 || p.atrous || is_interleaved(p) || p.variant_fwd == kFwdNoCascade || (p.comp != 1 && p.comp != 2) || !fused2_eligible(p, 1, &Lp)) return 0;
     const long long n1 = p.dims[0] * p.comp;              // scalars along x
     if (n1 % 4 != 0 || p.dims[1] < 3 * (Lp - 1)) return 0;
     if (n1 * p.dims[1] >= (1LL << 31)) return 0;          // the kernel's row * row-stride products are formed in 64 bits, offsets in int
@@ -239,13 +244,45 @@ inline int cascade2_rec_depth(const SelPlan& p, int Lp, int nlev) {
 // the next launch takes -- the largest instantiated count <= left -- and the tap length; 0 = one launch per level.  kFwdNoCascade takes
 // the analysis off, kInvCascadeOff the synthesis (A/B runs: tools/bench1d_batch.py).
 inline int cascade1_levels(const SelPlan& p, long long howmany, bool inverse, int left, int* L_out) {
-    if (howmany < 1 || p.ndim != 1 || p.atrous || !p.path_auto || (p.comp != 1 && p.comp != 2)) return 0;
+    if (howmany < 1 || p.ndim != 1 || p.atrous || is_interleaved(p) || !p.path_auto || (p.comp != 1 && p.comp != 2)) return 0;
     if (inverse ? p.variant_inv == kInvCascadeOff : p.variant_fwd == kFwdNoCascade) return 0;
     const int L = p.len[0];
     const long long n1 = p.dims[0] * p.comp;              // scalars per row
     if (L < 2 || L > 8 || n1 % 4 != 0 || n1 < 8LL * L || n1 >= (1LL << 30)) return 0;
     for (int n = left < 4 ? left : 4; n >= 2; --n)
         if (cascade1_instantiated({inverse, p.f64, p.comp, L, n})) { *L_out = L; return n; }
+    return 0;
+}
+
+// ---- two to four levels of ONE strided axis inside one march (FwdMC / InvMC, ndwt_device_axis.h): a plan over interleaved samples
+// (ndwt_plan_create_interleaved) with one filtered axis, at the reference's dilation, tap lengths 2 .. 8, sample blocks of whole groups
+// of 4 scalars.  `left` = levels still to do.  Returns how many the next launch takes -- the largest instantiated count <= left -- and
+// the tap length; 0 = one launch per level.
+// Unasked, the cascade is taken only where it has been measured to win (cascadem_default); kFwdCascadeAlways /
+// kInvCascadeAlways force it wherever it exists, kFwdNoCascade / kInvCascadeOff switch it off, each for its own direction.
+// Measured on the MI355X, db2 and db4, 3 levels, forced cascade against one launch per level on the same plan (tools/bench_interleaved.py,
+// DESIGN.md 4.3c).  The rule of 4.3b: a data kind and direction takes the cascade unasked from the smallest measured size on at which it
+// won by more than the 5 % spread between boxes, for both wavelets -- `bytes` = bytes of the whole array.  float real, both directions:
+// from 256 MiB (-41 % / -22 % dec, -34 % / -33 % rec for db2 / db4); at 64 MiB db4 is SLOWER in the analysis (+7 %, +15 %) and equal in
+// the synthesis of the channels-first shape, at 8 MiB db2 is equal (dec) and slower (rec, +23 %).  double at 16 MiB: db2 -4 % / +33 %,
+// db4 -27 % / +6 % -- no size measured to win both ways; complex64 was measured at 16 MiB only (dec -10 % / -39 %, rec +10 % / -19 %) and
+// complex128 not at all: on request only (kCascadeMNever).
+constexpr long long kCascadeMNever = 0x7fffffffffffffffLL;
+constexpr long long cascadem_min_bytes(bool f64, int comp, bool inverse) {
+    (void)inverse;
+    return (!f64 && comp == 1) ? (256LL << 20) : kCascadeMNever;
+}
+constexpr bool cascadem_default(bool f64, int comp, bool inverse, long long bytes) { return bytes >= cascadem_min_bytes(f64, comp, inverse); }
+inline int cascadem_levels(const SelPlan& p, bool inverse, int left, int* L_out) {
+    if (p.ndim != 1 || !is_interleaved(p) || p.atrous || !p.path_auto || left < 2) return 0;
+    if (inverse ? p.variant_inv == kInvCascadeOff : p.variant_fwd == kFwdNoCascade) return 0;
+    const int L = p.len[0];
+    if (L < 2 || L > 8 || (p.comp * p.inner) % 4 != 0) return 0;
+    const long long items = p.howmany > 0 ? p.howmany : 1;
+    const long long bytes = p.comp * p.inner * p.dims[0] * items * (p.f64 ? 8 : 4);
+    if (!(inverse ? p.variant_inv == kInvCascadeAlways : p.variant_fwd == kFwdCascadeAlways) && !cascadem_default(p.f64, p.comp, inverse, bytes)) return 0;
+    for (int n = left < 4 ? left : 4; n >= 2; --n)
+        if (cascadem_instantiated({inverse, p.f64, L, n})) { *L_out = L; return n; }
     return 0;
 }
 

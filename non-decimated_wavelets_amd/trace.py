@@ -40,6 +40,12 @@ FAMILY_PARAMS_1D = {
     "Inv1C": [("T", None), ("L", None), ("NLEV", None), ("EW", 1), ("WPE", 4)],
 }
 
+# the families of csrc/ndwt_device_axis.h (all levels of one strided axis inside one march: plans over interleaved samples), likewise
+FAMILY_PARAMS_AXIS = {
+    "FwdMC": [("T", None), ("L", None), ("NLEV", None)],
+    "InvMC": [("T", None), ("L", None), ("NLEV", None)],
+}
+
 # the plain __global__ templates (csrc/ndwt_api.hip, csrc/ndwt_multi.hip), as their launch sites spell them
 PLAIN_PARAMS = {
     "axis_analysis_kernel": [("T", None)],
@@ -102,7 +108,7 @@ def parse_record(line: str) -> KernelLaunch:
     if not t:
         raise ValueError(f"unparsed kernel type: {text!r}")
     fam = t.group(1)
-    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam) or FAMILY_PARAMS_1D.get(fam)
+    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam) or FAMILY_PARAMS_1D.get(fam) or FAMILY_PARAMS_AXIS.get(fam)
     if table is None:
         raise ValueError(f"unknown kernel family {fam!r} in {text!r}")
     args = [_value(a) for a in _split_args(t.group(2) or "")]
