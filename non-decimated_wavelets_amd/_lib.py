@@ -32,7 +32,7 @@ EXPORTS = [
     "ndwt_comm_last_error", "ndwt_coef_create", "ndwt_coef_release", "ndwt_coef_info", "ndwt_coef_dec_host", "ndwt_coef_rec_host",
     "ndwt_coef_shrink", "ndwt_coef_get_host", "ndwt_coef_put_host", "ndwt_plan_create_slab_axis", "ndwt_slab_segments_strided",
     "ndwt_mplan_create_axis", "ndwt_trace_enable", "ndwt_trace_get", "ndwt_plan_create_many", "ndwt_plan_create_axes",
-    "ndwt_plan_create_interleaved",
+    "ndwt_plan_create_interleaved", "ndwt_band_gains", "ndwt_shrink_bands", "ndwt_denoise_bands",
 ]
 
 
@@ -107,6 +107,12 @@ def lib() -> ctypes.CDLL:
     L.ndwt_band_pitch.restype = ctypes.c_int64
     L.ndwt_denoise.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int,
                                ctypes.c_void_p]
+    L.ndwt_band_gains.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_char_p), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                  ctypes.POINTER(ctypes.c_double)]
+    L.ndwt_shrink_bands.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+                                    ctypes.c_void_p]
+    L.ndwt_denoise_bands.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
+                                     ctypes.c_void_p]
     L.ndwt_denoise_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int]
     for f in (L.ndwt_dec_split, L.ndwt_rec_split):
         f.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p]
@@ -189,3 +195,23 @@ def wave_filters(wname: str):
     n = ctypes.c_int(0)
     check(lib().ndwt_wave_filters(wname.encode(), lo, hi, ctypes.byref(n)))
     return list(lo[: n.value]), list(hi[: n.value])
+
+
+def band_gains(dims, wnames, level, pres_l2_norm=0, dilation="reference"):
+    """Standard deviation of every band of a `level`-level transform of unit-variance white noise on an array of `dims` (the filtered
+    axes of one item), as a numpy array of ndwt_num_bands(len(dims), level) doubles -- include/ndwt.h: ndwt_band_gains.  Host only: no
+    device is needed.  wnames: one name for every axis, or a name per axis.  thresholds[b] = k * sigma * gains[b]."""
+    import numpy as np
+    dims = [int(d) for d in np.atleast_1d(dims)]
+    names = [wnames] * len(dims) if isinstance(wnames, str) else list(wnames)
+    if len(names) != len(dims):
+        raise ValueError(f"{len(dims)} axes need {len(dims)} wavelet names (or one for all), got {len(names)}")
+    if dilation not in ("reference", "atrous"):
+        raise ValueError("dilation must be 'reference' or 'atrous'")
+    nb = int(lib().ndwt_num_bands(len(dims), int(level)))
+    out = np.zeros(max(nb, 1))
+    c_dims = (ctypes.c_int64 * len(dims))(*dims)
+    c_names = (ctypes.c_char_p * len(dims))(*[None if w is None else str(w).encode() for w in names])
+    check(lib().ndwt_band_gains(len(dims), c_dims, c_names, int(bool(pres_l2_norm)), NDWT_DILATION_ATROUS if dilation == "atrous" else NDWT_DILATION_REFERENCE,
+                                int(level), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+    return out[:nb]

@@ -180,6 +180,28 @@ class Plan:
         """dec -> shrink -> rec with the coefficients in a scratch array owned by the plan"""
         L.check(L.lib().ndwt_denoise(self._h, x_ptr, out_ptr, int(level), float(threshold), int(bool(hard)), ctypes.c_void_p(stream)))
 
+    def _check_band_count(self, t, level):
+        nb = num_bands(self.ndim if self.axes is None else len(self.axes), level)   # (the filtered axes)
+        if t.size != nb:
+            raise ValueError(f"{nb} thresholds expected (one per band of a {level}-level transform), got {t.size}")
+
+    @staticmethod
+    def _thresholds(thresholds):
+        t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64).reshape(-1))
+        return t, t.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+    def shrink_bands(self, y_ptr, level, thresholds, hard=False, stream=0, band_pitch=0):
+        """in-place thresholding with one threshold per band (num_bands of them, band 0 included; 0 = leave the band alone)"""
+        t, tp = self._thresholds(thresholds)
+        self._check_band_count(t, level)
+        L.check(L.lib().ndwt_shrink_bands(self._h, y_ptr, int(band_pitch), int(level), tp, int(bool(hard)), ctypes.c_void_p(stream)))
+
+    def denoise_bands(self, x_ptr, out_ptr, level, thresholds, hard=False, stream=0):
+        """dec -> per-band shrink -> rec; a batched 1-D plan can run it in one launch (set_variant(fwd=11, inv=11))"""
+        t, tp = self._thresholds(thresholds)
+        self._check_band_count(t, level)
+        L.check(L.lib().ndwt_denoise_bands(self._h, x_ptr, out_ptr, int(level), tp, int(bool(hard)), ctypes.c_void_p(stream)))
+
     def denoise_host(self, x_ptr, out_ptr, level, threshold, hard=False):
         L.check(L.lib().ndwt_denoise_host(self._h, x_ptr, out_ptr, int(level), float(threshold), int(bool(hard))))
 
@@ -707,6 +729,7 @@ class _NdDwtBase:
         if y.ndim != len(self._shape) + 1 or list(y.shape[:-1]) != self._shape:
             raise ValueError(f"coefficient array must have shape {self._shape + ['bands']}")
         level = self._level_from_bands(int(y.shape[-1]))
+        thr = self._band_thresholds(threshold, level)
         dev = self._dev(y if isinstance(y, torch.Tensor) else None)
         yk, pitch = self._coef_kernel_order(y, dev)
         if isinstance(y, torch.Tensor) and yk.data_ptr() == y.data_ptr():
@@ -719,7 +742,10 @@ class _NdDwtBase:
                 yk = yk.clone()
         plan = self._plan(yk.is_complex(), level, dev)
         with torch.cuda.device(dev):
-            plan.shrink(yk.data_ptr(), level, threshold, mode == "hard", _current_stream(dev), band_pitch=pitch)
+            if thr is None:
+                plan.shrink(yk.data_ptr(), level, threshold, mode == "hard", _current_stream(dev), band_pitch=pitch)
+            else:
+                plan.shrink_bands(yk.data_ptr(), level, thr, mode == "hard", _current_stream(dev), band_pitch=pitch)
         return self._from_device(yk, like_numpy, dev)
 
     def denoise(self, x, level, threshold, mode="soft"):
@@ -729,6 +755,7 @@ class _NdDwtBase:
         level = int(level)
         if level < 1:
             raise ValueError("level must be >= 1")
+        thr = self._band_thresholds(threshold, level)
         like_numpy = isinstance(x, np.ndarray)
         x = self._prep_dec_input(x)
         if list(x.shape) != self._shape:
@@ -738,8 +765,26 @@ class _NdDwtBase:
         plan = self._plan(xk.is_complex(), level, dev)
         out = torch.empty_like(xk)
         with torch.cuda.device(dev):
-            plan.denoise(xk.data_ptr(), out.data_ptr(), level, threshold, mode == "hard", _current_stream(dev))
+            if thr is None:
+                plan.denoise(xk.data_ptr(), out.data_ptr(), level, threshold, mode == "hard", _current_stream(dev))
+            else:
+                plan.denoise_bands(xk.data_ptr(), out.data_ptr(), level, thr, mode == "hard", _current_stream(dev))
         return self._from_device(out, like_numpy, dev)
+
+    def _band_thresholds(self, threshold, level):
+        """None for a scalar threshold (today's call), else the sequence as an array of one threshold per band"""
+        if np.ndim(threshold) == 0:
+            return None
+        if isinstance(threshold, torch.Tensor):
+            threshold = threshold.detach().cpu().numpy()
+        thr = np.asarray(threshold, dtype=np.float64).reshape(-1)
+        if thr.size != num_bands(self.NDIM, level):
+            raise ValueError(f"threshold must be a scalar or {num_bands(self.NDIM, level)} values, one per band of a {level}-level transform (got {thr.size})")
+        return thr
+
+    def band_gains(self, level):
+        """standard deviation of every band for unit-variance white input (ndwt_band_gains): thresholds = k * sigma * band_gains(level)"""
+        return L.band_gains(self.sizes, self.wname[: self.NDIM], int(level), self.pres_l2_norm, self.dilation)
 
     def _prep_dec_input(self, x):
         return x

@@ -22,6 +22,7 @@
 #include "ndwt_fused.h"
 #include "ndwt_geom.h"
 #include "ndwt_select.h"
+#include "ndwt_shrink.h"
 #include "ndwt_taps_host.h"
 #include "ndwt_trace.h"
 
@@ -171,6 +172,7 @@ struct ndwt_plan {
     double shrink_thr = 0;
     DevBuf coef;                       // coefficient scratch of ndwt_denoise (all bands of the last level used), lazily allocated
     DevBuf taps_den;                   // device tap table of the fused level-1 denoising kernel (TapsDen<float, L>), built at plan creation where it applies
+    DevBuf taps_den1;                  // a batched 1-D plan whose levels can cascade: Taps1D<T, L>, the tables of both directions for Den1C
     DevBuf den_a1;                     // ndwt_denoise, fused level 1: the level-1 approximation / its reconstruction -- a scratch of its own (lazily
                                        // allocated), not `tmp`: dec_impl / rec_impl run in between and may re-allocate that one
     int fused_level1 = 1;              // ndwt_denoise: 1 (default) level 1 in one launch where that is faster (tap lengths <= 6), 2 wherever the
@@ -789,6 +791,37 @@ template <typename T> static int cascade1_run(ndwt_plan* p, bool inverse, int L,
     return rc < 0 ? -1 : 0;
 }
 
+// ---- dec, per-band thresholding and rec of the signals of a batched 1-D plan in one launch (Den1C, ndwt_device_1d.h; when:
+// denoise1_levels).  thr: one threshold per band of the coefficient array (band 0 the approximation, then the detail bands coarsest
+// level first), converted as shrink_run converts them.  Returns 0, or -1: not this data -- x or out off the 16- / 32-byte groups, x and
+// out overlapping (a wave reads halo scalars that another wave's store may already have replaced), no instance, no tap table, or a grid
+// beyond 2^31 - 1 workgroups -- and the caller takes the general route
+template <typename T> static int denoise1_run(ndwt_plan* p, int L, int nlev, const T* x, T* out, const double* thr, int mode, hipStream_t s) {
+    const char *xb = (const char*)x, *ob = (const char*)out;
+    const size_t nbytes = (size_t)p->vol * sizeof(T);
+    if (!aligned_vec4<T>(x) || !aligned_vec4<T>(out) || !(xb + nbytes <= ob || ob + nbytes <= xb)) return -1;
+    const void* td = p->taps_den1.ptr;
+    if (!td) return -1;
+    Den1CArgs<T> a;
+    memset(&a, 0, sizeof a);
+    a.in[0] = x;
+    a.out[0] = out;
+    a.thr[0] = (T)thr[0];
+    for (int l = 0; l < nlev; ++l) a.thr[1 + l] = (T)thr[1 + (nlev - 1 - l)];   // cascade level l (0 = finest) is transform level l + 1: band 1 + (nlev - (l + 1))
+    a.hard = mode == NDWT_SHRINK_HARD;
+    const Den1Instance k = {sizeof(T) == 8, (int)p->comp, L, nlev};
+    const int WX = den1_tile_width(k);
+    a.row = p->dims[0] * p->comp;
+    a.outer = p->howmany;
+    a.nseg = (a.row + WX - 1) / WX;
+    if ((a.outer * a.nseg + 3) / 4 > 0x7fffffffLL) return -1;
+    prof_begin(p, NDWT_KERNEL_FUSED_SYNTHESIS, s);
+    const int rc = launch_den1(k, a, td, s);
+    prof_end(p, s, rc);
+    if (rc > 0) return fail(NDWT_ERR_HIP, "one-launch denoise failed: %s", hipGetErrorString((hipError_t)rc));
+    return rc < 0 ? -1 : 0;
+}
+
 // ---- two to four levels of the one strided axis of a plan over interleaved samples in one march (FwdMC / InvMC, ndwt_device_axis.h;
 // when: cascadem_levels).  in / out as MarchCArgs documents them.  The chunking is axis_pass's own rule (about 4096 workgroups, in chunks
 // of the axis), the floor raised to 4 nlev (L - 1) planes -- the march-in is at most a quarter of a thread's planes -- and capped at the
@@ -1010,21 +1043,7 @@ template <typename T> static int slab_ext_impl(ndwt_plan* p, int Lp, const void*
 
 
 // --------------------------------------------------------------------------- shrinkage of detail bands
-// Element-wise, in place, 1 read + 1 write per coefficient (HBM-bound).  COMP = 2: interleaved complex, the magnitude
-// is shrunk and the phase kept.  mode 0 soft: c * max(|c| - t, 0) / |c|; mode 1 hard: c if |c| > t else 0.
-template <typename T, int COMP> __device__ __forceinline__ void shrink_group(T* c, T thr, int hard) {
-    if (COMP == 1) {
-        const T m = c[0] < T(0) ? -c[0] : c[0];
-        if (hard) c[0] = m > thr ? c[0] : T(0);
-        else c[0] = m > thr ? (c[0] < T(0) ? c[0] + thr : c[0] - thr) : T(0);
-    } else {
-        const T m = sqrt(c[0] * c[0] + c[1] * c[1]);
-        const T g = m > thr ? (hard ? T(1) : (m - thr) / m) : T(0);
-        c[0] *= g;
-        c[1] *= g;
-    }
-}
-
+// Element-wise, in place, 1 read + 1 write per coefficient (HBM-bound); the arithmetic is shrink_group (ndwt_shrink.h).
 // VEC: 4 scalars per thread and step (16-byte / 32-byte accesses; pointer aligned, n a multiple of 4); else one group
 template <typename T, int COMP, bool VEC>
 __global__ void __launch_bounds__(256) shrink_kernel(T* __restrict__ y, long long n_scalars, T thr, int hard) {
@@ -1339,7 +1358,17 @@ static int plan_create_impl(ndwt_plan** plan, int ndim, const int64_t* dims, lon
         if (const int rc = p->approx_base[i].grow((size_t)p->vol * p->esize + kApproxSkew, "of the approximation scratch", false)) return rc;
     int Lp = level_route(sel(p), 1, 0, kWholeArray).Lp;
     // a batched 1-D plan whose levels can cascade (Fwd1C / Inv1C read Taps3<T, L>, axis 0): the table of its own tap length
-    if (!Lp && howmany > 0 && inner == 1 && p->filt[0].len <= 8 && (cascade1_instantiated({false, dtype == NDWT_F64, (int)p->comp, p->filt[0].len, 2}))) Lp = p->filt[0].len;
+    if (!Lp && howmany > 0 && inner == 1 && p->filt[0].len <= 8 && (cascade1_instantiated({false, dtype == NDWT_F64, (int)p->comp, p->filt[0].len, 2}))) {
+        Lp = p->filt[0].len;
+        // ... and both directions in one table for the one-launch denoise (Den1C reads Taps1D<T, L>)
+        const int rc = with_scalar(p, [&](auto t) {
+            std::vector<decltype(t)> host;
+            append_taps3(host, fused_taps(p, Lp, false), false);
+            append_taps3(host, fused_taps(p, Lp, true), false);
+            return p->taps_den1.upload(host.data(), host.size() * sizeof(t), "the tap table of the one-launch denoise");
+        });
+        if (rc) return rc;
+    }
     // a plan with fused levels (the analysis side admits the most tap lengths): Taps3, and for the synthesis Taps3Y -- the same, then the
     // x tap pairs of the pair-packed kernel
     for (int inv = 0; inv < 2 && Lp; ++inv) {
@@ -1757,6 +1786,99 @@ int ndwt_shrink(ndwt_plan* p, void* y, int level, double threshold, int mode, vo
     return ndwt_shrink_pitched(p, y, 0, level, threshold, mode, stream);
 }
 
+// ---- one threshold per band (include/ndwt.h: ndwt_band_gains says what to scale them by) ----
+static int bands_check(const ndwt_plan* p, int level, const double* thr, int mode) {
+    int rc = check_level(p, level);
+    if (rc) return rc;
+    if (!thr) return fail(NDWT_ERR_INVALID_ARG, "null thresholds");
+    const long long nb = ndwt_num_bands(p->ndim, level);
+    for (long long b = 0; b < nb; ++b)
+        if (!(thr[b] >= 0.0)) return fail(NDWT_ERR_INVALID_ARG, "threshold of band %lld must be >= 0", b);
+    if (mode != NDWT_SHRINK_SOFT && mode != NDWT_SHRINK_HARD) return fail(NDWT_ERR_INVALID_ARG, "mode must be NDWT_SHRINK_SOFT or NDWT_SHRINK_HARD");
+    return NDWT_OK;
+}
+// one run of shrink_kernel per band with a non-zero threshold, band 0 like any other; a zero leaves its band untouched (no launch)
+extern "C++" template <typename T> static int shrink_bands_impl(ndwt_plan* p, T* y, long long bs, int level, const double* thr, int mode, hipStream_t s) {
+    const long long nb = ndwt_num_bands(p->ndim, level);
+    for (long long b = 0; b < nb; ++b) {
+        if (thr[b] == 0.0) continue;
+        const int rc = shrink_run<T>(p, y + b * bs, p->vol, thr[b], mode, s);
+        if (rc) return rc;
+    }
+    return NDWT_OK;
+}
+
+int ndwt_shrink_bands(ndwt_plan* p, void* y, int64_t band_pitch, int level, const double* thresholds, int mode, void* stream) {
+    int rc = bands_check(p, level, thresholds, mode);
+    if (rc) return rc;
+    if (!y) return fail(NDWT_ERR_INVALID_ARG, "null data pointer");
+    long long bs = 0;
+    rc = pitch_scalars(p, band_pitch, &bs);
+    if (rc) return rc;
+    return on_device(p, [&](auto t) { return shrink_bands_impl(p, (decltype(t)*)y, bs, level, thresholds, mode, (hipStream_t)stream); });
+}
+
+// Periodic dec of a unit impulse, axis by axis: A[l] / D[l] = the l2 norm of the approximation / detail response of level l on an axis of
+// n samples -- the periodised convolution of the levels' taps at their tap strides.  A band of a k-D transform is the outer product of
+// its axes' responses, so its norm is the product of theirs.
+static void axis_gains(const AxisFilter& f, long long n, bool atrous, int level, double* A, double* D) {
+    std::vector<double> cur((size_t)n, 0.0), lo((size_t)n), hi((size_t)n);
+    cur[0] = 1.0;
+    A[0] = 1.0;
+    D[0] = 0.0;
+    for (int lev = 1; lev <= level; ++lev) {
+        const long long stride = atrous ? (1LL << (lev - 1)) % n : 1LL;
+        double sl = 0.0, sh = 0.0;
+        for (long long i = 0; i < n; ++i) {
+            double al = 0.0, ah = 0.0;
+            long long pos = i;
+            for (int j = 0; j < f.len; ++j) {
+                al += f.ana_lo[j] * cur[(size_t)pos];
+                ah += f.ana_hi[j] * cur[(size_t)pos];
+                pos += stride;
+                if (pos >= n) pos -= n;
+            }
+            lo[(size_t)i] = al;
+            hi[(size_t)i] = ah;
+            sl += al * al;
+            sh += ah * ah;
+        }
+        A[lev] = std::sqrt(sl);
+        D[lev] = std::sqrt(sh);
+        cur.swap(lo);
+    }
+}
+
+int ndwt_band_gains(int ndim, const int64_t* dims, const char* const* wnames, int pres_l2_norm, int dilation, int level, double* gains) {
+    if (ndim < 1 || ndim > NDWT_MAX_DIMS) return fail(NDWT_ERR_INVALID_ARG, "ndim must be 1..4");
+    if (!dims || !wnames) return fail(NDWT_ERR_INVALID_ARG, "null dims/wnames");
+    if (!gains) return fail(NDWT_ERR_INVALID_ARG, "null output pointer");
+    if (dilation != NDWT_DILATION_REFERENCE && dilation != NDWT_DILATION_ATROUS) return fail(NDWT_ERR_INVALID_ARG, "bad dilation mode");
+    if (level < 1 || level > 30) return fail(NDWT_ERR_INVALID_ARG, "level must be 1..30");
+    static const char* ordn[4] = {"First", "Second", "Third", "Fourth"};
+    std::vector<double> A[NDWT_MAX_DIMS], D[NDWT_MAX_DIMS];
+    for (int a = 0; a < ndim; ++a) {
+        if (dims[a] < 1) return fail(NDWT_ERR_INVALID_ARG, "dims[%d] must be >= 1", a);
+        const int K = parse_wavelet(wnames[a]);
+        if (!K) return fail(NDWT_ERR_UNKNOWN_WAVELET, "Unknown Wavelet Name");
+        const AxisFilter f = make_axis_filter(K, pres_l2_norm != 0);
+        if (f.len > dims[a]) return fail(NDWT_ERR_FILTER_TOO_LONG, "%s Dimension of Data is shorter than the wavelet filter being used", ordn[a]);
+        A[a].resize((size_t)level + 1);
+        D[a].resize((size_t)level + 1);
+        axis_gains(f, dims[a], dilation == NDWT_DILATION_ATROUS, level, A[a].data(), D[a].data());
+    }
+    const int nb = 1 << ndim;
+    const long long bands = ndwt_num_bands(ndim, level);
+    for (long long b = 0; b < bands; ++b) {
+        const int lev = b == 0 ? level : level - (int)((b - 1) / (nb - 1));     // band 0: the approximation of the last level
+        const int bits = b == 0 ? 0 : 1 + (int)((b - 1) % (nb - 1));            // bit a: high-pass on axis a
+        double g = 1.0;
+        for (int a = 0; a < ndim; ++a) g *= ((bits >> a) & 1) ? D[a][(size_t)lev] : A[a][(size_t)lev];
+        gains[b] = g;
+    }
+    return NDWT_OK;
+}
+
 // ---- level 1 of a denoising step without its detail bands in memory (Den3, ndwt_device.h) ----
 // Float, real, 3-D, reference dilation, the same tap length L <= 8 on every axis, rows of whole 16-byte groups.
 // fused_level1: the setting asked about (ndwt_plan_set_fused_level1: the plan's own for a call, 2 for "does the kernel exist for this plan")
@@ -1873,6 +1995,33 @@ int ndwt_denoise(ndwt_plan* p, const void* x, void* out, int level, double thres
         return rc;
     }
     rc = ndwt_shrink_pitched(p, coef, pitch, level, threshold, mode, stream);
+    if (rc == NDWT_OK) rc = ndwt_rec_pitched(p, coef, pitch, out, level, stream);
+    return rc;
+}
+
+int ndwt_denoise_bands(ndwt_plan* p, const void* x, void* out, int level, const double* thresholds, int mode, void* stream) {
+    int rc = bands_check(p, level, thresholds, mode);
+    if (rc) return rc;
+    if (!x || !out) return fail(NDWT_ERR_INVALID_ARG, "null data pointer");
+    HIP_TRY(hipSetDevice(p->device));
+    {
+        // a batched 1-D plan: the whole depth in one launch, where that exists and is wanted (denoise1_levels / denoise1_wanted)
+        const SelPlan sp = sel(p);
+        const int n = denoise1_wanted(sp) ? denoise1_levels(sp, p->howmany, level) : 0;
+        if (n) {
+            rc = with_scalar(p, [&](auto t) {
+                return denoise1_run<decltype(t)>(p, p->filt[0].len, n, (const decltype(t)*)x, (decltype(t)*)out, thresholds, mode, (hipStream_t)stream);
+            });
+            if (rc != -1) return rc;                      // -1: not this data -- the general route, silently
+        }
+    }
+    // the general route: dec into the plan's pitched scratch, one shrink pass per band, rec (no thresholding in the synthesis loads)
+    const int64_t pitch = ndwt_band_pitch(p);
+    rc = ensure_coef(p, (size_t)pitch * p->comp * p->esize * (size_t)ndwt_num_bands(p->ndim, level));
+    if (rc) return rc;
+    void* const coef = p->coef.ptr;
+    rc = ndwt_dec_pitched(p, x, coef, pitch, level, stream);
+    if (rc == NDWT_OK) rc = ndwt_shrink_bands(p, coef, pitch, level, thresholds, mode, stream);
     if (rc == NDWT_OK) rc = ndwt_rec_pitched(p, coef, pitch, out, level, stream);
     return rc;
 }

@@ -14,6 +14,7 @@
 // Written like the fused kernels: per-lane stages driven through an executor, so the same source runs under the host emulator.
 #pragma once
 #include "ndwt_device.h"
+#include "ndwt_shrink.h"
 
 namespace ndwt {
 
@@ -125,6 +126,104 @@ template <typename T, int L_, int NLEV_, int EW_ = 1, int WPE_ = 4> struct Inv1C
         NDWT_SFOR(lev, NLEV)
             ex.each([&](int tid, State& st) __attribute__((always_inline)) { level<lev>(ex, st, a, tp, tid); });
             if constexpr (lev + 1 < NLEV) ex.each([&](int, State& st) __attribute__((always_inline)) { st.cur = st.nxt; });
+        NDWT_SEND
+    }
+};
+
+// ---- dec -> threshold per band -> rec of the signals of a batched plan in ONE launch (Den1C): the analysis cascade above, the
+// thresholding of shrink_kernel (shrink_group, ndwt_shrink.h) on the coefficients where they lie -- in the lane -- and the synthesis
+// cascade, without a coefficient ever reaching memory: one read of the signals (with halo) and one write.
+//
+// Geometry: a lane holds the 4 scalars at xg = seg0 + 4 (lane - HL), HL = NLEV (GLa + GLs) (a / s: the halo lanes of the analysis / of the
+// synthesis, WaveRowGeom).  Analysis level k is valid in lanes [k GLa, 64 - k GRa); the synthesis, coarsest level first, then costs GLs
+// and GRs lanes per level, so the result is valid in [HL, 64 - HR), HR = NLEV (GRa + GRs), stored in whole 128-byte lines: WX =
+// den1_tile_width.  What a lane outside its level's window computes (the wave shifts deliver 0 past the wave's ends) never reaches a
+// storing lane.  A wave reads halo scalars that lie in another wave's output segment: the input and the output must not overlap.
+template <typename T> struct Den1CArgs : Fused1CArgs<T> {   // in[0]: the signals; out[0]: the result
+    T thr[5];              // [0] the approximation of the last level, [1 + l] the detail band of cascade level l (0 = finest); 0: the band is left alone
+    int hard;
+};
+template <typename T, int L> struct Taps1D {              // both directions of a 1-D plan, as the host appends them (axis 0 is used)
+    Taps3<T, L> ana, syn;
+};
+
+template <typename T, int L_, int NLEV_, int EW_ = 1, int WPE_ = 4> struct Den1C {
+    typedef WaveRowGeom<T, L_, EW_, false> WA;
+    typedef WaveRowGeom<T, L_, EW_, true> WS;
+    static constexpr int L = L_, NLEV = NLEV_, EW = EW_, NT = 256, WPE = WPE_;
+    static constexpr int HL = NLEV * (WA::GL + WS::GL), HR = NLEV * (WA::GR + WS::GR);
+    static constexpr int WX = 4 * ((64 - HL - HR) / WA::LPL * WA::LPL);   // output scalars per wave segment
+    static_assert(NLEV >= 1 && NLEV <= 4, "one to four levels per launch");
+    static_assert(WX > 0, "no lane is valid at every level");
+    typedef typename VecT<T>::v4 v4;
+    typedef Taps1D<T, L> Taps;
+    typedef Den1CArgs<T> Args;
+    struct Shared { int unused; };
+    struct State {
+        v4 cur;            // the raw row, then the approximations on the way down, then every synthesis level's output on the way up
+        v4 nxt;
+        v4 det[NLEV_];     // the detail band of every level (0 = finest)
+        long long base;
+        int xg;            // first scalar of this lane inside the row (outside [0, row) for halo lanes)
+        int valid;
+    };
+    // fills the lane's place in its row; returns the offset of its 4 scalars (wrapped) from the signals
+    static NDWT_DEV long long place(State& st, const Args& a, int bid, int tid) {
+        const long long item = (long long)bid * (NT / 64) + tid / 64;           // one wave per (row, segment)
+        const long long nitems = a.outer * a.nseg;
+        st.valid = item < nitems;
+        const long long it = st.valid ? item : nitems - 1;
+        const long long o = it / a.nseg, sg = it % a.nseg;
+        st.base = o * a.row;
+        st.xg = (int)(sg * WX) + 4 * (tid % 64 - HL);
+        return st.base + modn64(st.xg, a.row);            // (rows are whole groups of 4: a group never straddles the wrap)
+    }
+    // this lane stores: inside the window valid after the last synthesis level, and inside the row
+    static NDWT_DEV bool stores(const State& st, const Args& a, int tid) {
+        const int lane = tid % 64;
+        return st.valid && lane >= HL && lane < HL + WX / 4 && st.xg < a.row;
+    }
+    // shrink_kernel's arithmetic on the lane's 4 scalars (EW = 2: two (re, im) pairs)
+    static NDWT_DEV void shrink4(v4& c, T thr, int hard) {
+        T e[4] = {c[0], c[1], c[2], c[3]};
+        NDWT_SFOR(k, 4 / EW)
+            shrink_group<T, EW>(e + k * EW, thr, hard);
+        NDWT_SEND
+        c = v4{e[0], e[1], e[2], e[3]};
+    }
+    template <int LEV, class Exec> static NDWT_DEV void ana_level(Exec& ex, State& st, const Taps& tp, int tid) {
+        v4 o0, o1;
+        row_filter_ana<WA, true>(ex, st, tid, tp.ana.lo[0], tp.ana.hi[0], NDWT_ROW(s.cur), o0, o1);
+        st.nxt = o0;
+        st.det[LEV] = o1;
+    }
+    // synthesis of cascade level LEV (NLEV - 1 = coarsest, first): its output is the approximation of the next finer level, or the result
+    template <int LEV, class Exec> static NDWT_DEV void syn_level(Exec& ex, State& st, const Args& a, const Taps& tp, int tid) {
+        v4 o0;
+        row_filter_syn<WS, true>(ex, st, tid, tp.syn.lo[0], tp.syn.hi[0], NDWT_ROW(s.cur), NDWT_ROW(s.det[LEV]), o0);
+        st.nxt = o0;
+        if constexpr (LEV == 0) {
+            if (stores(st, a, tid)) *reinterpret_cast<v4*>(a.out[0] + st.base + st.xg) = o0;
+        }
+    }
+    template <class Exec> static NDWT_DEV void block(Exec& ex, Shared&, const Args& a, const Taps& tp, int bid) {
+        ex.each([&](int tid, State& st) __attribute__((always_inline)) {
+            const long long off = place(st, a, bid, tid);
+            st.cur = *reinterpret_cast<const v4*>(a.in[0] + off);
+        });
+        NDWT_SFOR(lev, NLEV)
+            ex.each([&](int tid, State& st) __attribute__((always_inline)) { ana_level<lev>(ex, st, tp, tid); });
+            ex.each([&](int, State& st) __attribute__((always_inline)) { st.cur = st.nxt; });
+        NDWT_SEND
+        ex.each([&](int, State& st) __attribute__((always_inline)) {
+            if (a.thr[0] > T(0)) shrink4(st.cur, a.thr[0], a.hard);
+            NDWT_SFOR(lev, NLEV)
+                if (a.thr[1 + lev] > T(0)) shrink4(st.det[lev], a.thr[1 + lev], a.hard);
+            NDWT_SEND
+        });
+        NDWT_SFOR(c, NLEV)
+            ex.each([&](int tid, State& st) __attribute__((always_inline)) { syn_level<NLEV - 1 - c>(ex, st, a, tp, tid); });
+            if constexpr (c + 1 < NLEV) ex.each([&](int, State& st) __attribute__((always_inline)) { st.cur = st.nxt; });
         NDWT_SEND
     }
 };

@@ -43,6 +43,12 @@ int launch_cascade2(const Cascade2Instance& k, const Fused2CIArgs<double>& a, co
 int launch_cascade1(const Cascade1Instance& k, const Fused1CArgs<float>& a, const void* taps_dev, hipStream_t s);
 int launch_cascade1(const Cascade1Instance& k, const Fused1CArgs<double>& a, const void* taps_dev, hipStream_t s);
 
+// dec, per-band thresholding and rec of one to four levels of the signals of a batched 1-D plan in one launch (Den1C), the instance named
+// in full (ndwt_fused_list.h: Den1Instance, the table denoise1_levels reads; its tile: den1_tile_width); taps_dev: Taps1D<T, L>.  -1: no
+// unit has the instance, -2: the launch geometry is not the instance's tile, or the grid is too large.
+int launch_den1(const Den1Instance& k, const Den1CArgs<float>& a, const void* taps_dev, hipStream_t s);
+int launch_den1(const Den1Instance& k, const Den1CArgs<double>& a, const void* taps_dev, hipStream_t s);
+
 // Two to four levels of one strided axis inside one march (FwdMC / InvMC), the instance named in full (ndwt_fused_list.h:
 // CascadeMInstance, the table cascadem_levels reads); lo / hi: the kernel-form taps of the direction, length k.L.  -1: no unit has the
 // instance, -2: the grid is too large.

@@ -76,6 +76,16 @@ template <class K> int launch_cascade1_k(const typename K::Args& a, const void* 
     return (int)hipGetLastError();
 }
 
+// The one-launch denoise of a batched plan (Den1C): the same layout of waves; taps_dev holds Taps1D<T, L> (both directions)
+template <class K> int launch_den1_k(const typename K::Args& a, const void* taps_dev, hipStream_t s) {
+    if (a.row < 4 || a.row % 4 != 0 || a.row >= (1LL << 30) || a.outer < 1 || a.nseg != (a.row + K::WX - 1) / K::WX) return -2;
+    const long long nblocks = (a.outer * a.nseg + K::NT / 64 - 1) / (K::NT / 64);
+    if (nblocks > 0x7fffffffLL) return -2;
+    trace_kernel<K>(dim3((unsigned)nblocks), dim3(K::NT));
+    hipLaunchKernelGGL(fused3_kernel<K>, dim3((unsigned)nblocks), dim3(K::NT), 0, s, a, (const typename K::Taps*)taps_dev);
+    return (int)hipGetLastError();
+}
+
 // The cascaded march of one strided axis: 256 (item, group of 4 scalars) pairs per workgroup, times the chunks of the axis
 template <class K> int launch_cascadem_k(const typename K::Args& a, const double* lo, const double* hi, hipStream_t s) {
     typename K::Taps tp;
@@ -126,6 +136,11 @@ template <class K> int launch_cascadem_k(const typename K::Args& a, const double
     if (k == Cascade1Instance{k##KIND == kInv1C, sizeof(T) == 8, EWV, LL, NLEV}) {                            \
         static_assert(KIND<T, LL, NLEV, EWV>::WX == cascade1_tile_width({k##KIND == kInv1C, sizeof(T) == 8, EWV, LL, NLEV}), "tile width"); \
         return launch_cascade1_k<KIND<T, LL, NLEV, EWV>>(a, taps_dev, s);                                    \
+    }
+#define NDWT_LAUNCH_D(T, EWV, LL, NLEV)                                                                      \
+    if (k == Den1Instance{sizeof(T) == 8, EWV, LL, NLEV}) {                                                  \
+        static_assert(Den1C<T, LL, NLEV, EWV>::WX == den1_tile_width(LL, EWV, sizeof(T) == 8, NLEV), "tile width"); \
+        return launch_den1_k<Den1C<T, LL, NLEV, EWV>>(a, taps_dev, s);                                       \
     }
 #define NDWT_LAUNCH_M(KIND, T, LL, NLEV) \
     if (k == CascadeMInstance{k##KIND == kInvMC, sizeof(T) == 8, LL, NLEV}) return launch_cascadem_k<KIND<T, LL, NLEV>>(a, lo, hi, s);

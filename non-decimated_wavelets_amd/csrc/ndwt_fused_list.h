@@ -55,6 +55,9 @@ struct Cascade1Instance { bool inverse, f64; int ew, Lp, nlev; };
 constexpr bool operator==(const Cascade1Instance& a, const Cascade1Instance& b) {
     return a.inverse == b.inverse && a.f64 == b.f64 && a.ew == b.ew && a.Lp == b.Lp && a.nlev == b.nlev;
 }
+// Den1C<T, Lp, nlev, ew> (ndwt_device_1d.h): dec, per-band thresholding and rec of one to four levels of many 1-D signals in one launch
+struct Den1Instance { bool f64; int ew, Lp, nlev; };
+constexpr bool operator==(const Den1Instance& a, const Den1Instance& b) { return a.f64 == b.f64 && a.ew == b.ew && a.Lp == b.Lp && a.nlev == b.nlev; }
 // FwdMC / InvMC<T, L, nlev> (ndwt_device_axis.h): two to four levels of one strided axis inside one march (interleaved complex: the
 // factor 2 in the inner block, no instance of its own)
 struct CascadeMInstance { bool inverse, f64; int L, nlev; };
@@ -71,6 +74,7 @@ constexpr bool operator==(const CascadeMInstance& a, const CascadeMInstance& b) 
 //                            R(T, EW, L, NLEV, PD, WPE)             Inv2C
 //                            C(KIND, T, EW, L, NLEV)                Fwd1C / Inv1C
 //                            M(KIND, T, L, NLEV)                    FwdMC / InvMC
+//                            D(T, EW, L, NLEV)                      Den1C
 // NDWT_F2 / NDWT_S2 / NDWT_Y2 / NDWT_W2: the plain form of an entry for rows of whole groups of 4 scalars and for the rest
 #define NDWT_F2(F, T, L, V, EW) F(T, L, V, true, EW, false, false, 0) F(T, L, V, false, EW, false, false, 0)
 #define NDWT_S2(S, KIND, T, L, V, EW) S(KIND, T, L, V, true, EW) S(KIND, T, L, V, false, EW)
@@ -270,6 +274,22 @@ constexpr bool operator==(const CascadeMInstance& a, const CascadeMInstance& b) 
 #define NDWT_LIST_C128_1C(C, KIND) NDWT_C1_KIND(C, KIND, double, 2)
 #define NDWT_LIST_1C(C, KIND) NDWT_LIST_F32_1C(C, KIND) NDWT_LIST_C64_1C(C, KIND) NDWT_LIST_F64_1C(C, KIND) NDWT_LIST_C128_1C(C, KIND)
 
+// The one-launch denoise of a batched 1-D plan (Den1C, ndwt_device_1d.h), rows of whole groups of 4 scalars: THE table of the instances
+// that exist -- denoise1_levels (ndwt_select.h) answers from it, the launch units (ndwt_denoise1_{f32,c64,f64,c128}.hip) expand it.
+// {float, double} x EW {1, 2} x 2 .. 8 taps x 1 .. 4 levels, less the three that spill: 61 instances.  A lane holds 2 + NLEV 4-vectors:
+// every listed instance builds for gfx950 without LDS, scratch or spilled registers at 4 waves per SIMD (tools/kernel_resources.sh;
+// DESIGN.md 4.3d has the counts).  Left out, all complex128: 6 taps x 4 levels (20 spilled registers, 84 B of scratch), 8 taps x 3
+// levels (15, 64 B) and 8 taps x 4 levels (51, 208 B) -- ndwt_denoise_bands takes the general route there.
+#define NDWT_D1234(D, T, EW, L) D(T, EW, L, 1) D(T, EW, L, 2) D(T, EW, L, 3) D(T, EW, L, 4)
+#define NDWT_D1_KIND(D, T, EW) NDWT_D1234(D, T, EW, 2) NDWT_D1234(D, T, EW, 4) NDWT_D1234(D, T, EW, 6) NDWT_D1234(D, T, EW, 8)
+#define NDWT_LIST_F32_DEN1(D) NDWT_D1_KIND(D, float, 1)
+#define NDWT_LIST_C64_DEN1(D) NDWT_D1_KIND(D, float, 2)
+#define NDWT_LIST_F64_DEN1(D) NDWT_D1_KIND(D, double, 1)
+#define NDWT_LIST_C128_DEN1(D)                                                                                            \
+    NDWT_D1234(D, double, 2, 2) NDWT_D1234(D, double, 2, 4) D(double, 2, 6, 1) D(double, 2, 6, 2) D(double, 2, 6, 3)      \
+    D(double, 2, 8, 1) D(double, 2, 8, 2)
+#define NDWT_LIST_DEN1(D) NDWT_LIST_F32_DEN1(D) NDWT_LIST_C64_DEN1(D) NDWT_LIST_F64_DEN1(D) NDWT_LIST_C128_DEN1(D)
+
 // The cascaded march of one strided axis (FwdMC / InvMC, ndwt_device_axis.h): THE table of the instances that exist -- cascadem_levels
 // (ndwt_select.h) answers from it, the launch units (ndwt_marchc_{f32,f64}.hip) expand it.  {float, double} x 2 .. 8 taps x 2 .. 4 levels
 // x both directions, less the two that spill.  A lane keeps NLEV windows of L 4-vectors: 4 NLEV L registers in float, twice that in
@@ -317,6 +337,13 @@ inline bool cascade1_instantiated(const Cascade1Instance& k) {
 }
 // scalars of a row one wave of the instance stores (Fwd1C::WX, Inv1C::WX: the same rule as the 2-D cascade's)
 constexpr int cascade1_tile_width(const Cascade1Instance& k) { return wave_row_width(k.inverse, k.Lp, k.ew, k.f64, k.nlev); }
+#define NDWT_IS_D(T, EW, L, NLEV) if (k == Den1Instance{sizeof(T) == 8, EW, L, NLEV}) return true;
+inline bool den1_instantiated(const Den1Instance& k) {
+    NDWT_LIST_DEN1(NDWT_IS_D)
+    return false;
+}
+// scalars of a row one wave of the instance stores (Den1C::WX)
+constexpr int den1_tile_width(const Den1Instance& k) { return den1_tile_width(k.Lp, k.ew, k.f64, k.nlev); }
 enum CascadeMKind { kFwdMC, kInvMC };
 #define NDWT_IS_M(KIND, T, L, NLEV) if (k == CascadeMInstance{k##KIND == kInvMC, sizeof(T) == 8, L, NLEV}) return true;
 inline bool cascadem_instantiated(const CascadeMInstance& k) {

@@ -51,4 +51,12 @@ constexpr int wave_row_width(bool syn, int Lp, int ew, bool f64, int nlev) {
     const int GL = (LH * ew + 3) / 4, GR = (RH * ew + 3) / 4;
     return nlev == 1 ? 4 * (64 - GL - GR) : 4 * ((64 - nlev * (GL + GR)) / lpl * lpl);
 }
+// The same rule for the one-launch denoise of a batched 1-D plan (Den1C, ndwt_device_1d.h): nlev analysis levels and nlev synthesis levels
+// on the same lanes, so every level costs the halo lanes of both directions; whole 128-byte lines whatever nlev (1 .. 4).  Positive
+// for every listed instance: the narrowest, 8 taps stepping over pairs at 4 levels, keeps 32 lanes.
+constexpr int den1_tile_width(int Lp, int ew, bool f64, int nlev) {
+    const int lpl = f64 ? 4 : 8;
+    const int GLa = ((Lp / 2 - 1) * ew + 3) / 4, GRa = ((Lp / 2) * ew + 3) / 4, GLs = GRa, GRs = GLa;   // the synthesis halo is the analysis one mirrored
+    return 4 * ((64 - nlev * (GLa + GRa + GLs + GRs)) / lpl * lpl);
+}
 }  // namespace ndwt

@@ -19,6 +19,7 @@ namespace ndwt {
 //  10  |                                                                     | cascade whatever the image size, kernel mode 1 (no take-in-only steps)
 //  11  |                                                                     | cascade whatever the image size
 //      (a batched 1-D plan, cascade1_levels: fwd 9 = one launch per level in the analysis, inv 9 = in the synthesis; nothing else applies)
+//      (ndwt_denoise_bands of a batched 1-D plan, denoise1_levels: fwd 11 AND inv 11 = the one-launch Den1C wherever it exists, 9 in either slot = off)
 //      (interleaved samples, one axis, cascadem_levels: fwd / inv 9 = one launch per level, 11 = the cascaded march wherever it exists)
 //  inv | 3-D synthesis (fused3_select)                                       | 2-D (fused2_select)                | 2-D cascade (cascade2_levels)
 //   0  | default: Inv3Y (gather <= 8 taps, scatter from 10), else Inv3S      | Inv2P depth 4 packed, 1024 waves, where the image fits one round
@@ -252,6 +253,33 @@ inline int cascade1_levels(const SelPlan& p, long long howmany, bool inverse, in
     for (int n = left < 4 ? left : 4; n >= 2; --n)
         if (cascade1_instantiated({inverse, p.f64, p.comp, L, n})) { *L_out = L; return n; }
     return 0;
+}
+
+// ---- ndwt_denoise_bands of a batched 1-D plan in ONE launch (Den1C, ndwt_device_1d.h): dec, the per-band thresholding and rec of all
+// `level` levels with the coefficients in registers, under cascade1_levels' conditions, 1 <= level <= 4 (deeper transforms take the
+// general route: dec, one shrink pass per band, rec).  Returns `level` if the whole depth fits one launch, else 0.  Either A/B switch
+// (kFwdNoCascade, kInvCascadeOff) takes it off.
+inline int denoise1_levels(const SelPlan& p, long long howmany, int level) {
+    if (level < 1 || level > 4) return 0;
+    if (howmany < 1 || p.ndim != 1 || p.atrous || is_interleaved(p) || !p.path_auto || (p.comp != 1 && p.comp != 2)) return 0;
+    if (p.variant_fwd == kFwdNoCascade || p.variant_inv == kInvCascadeOff) return 0;
+    const int L = p.len[0];
+    const long long n1 = p.dims[0] * p.comp;              // scalars per row
+    if (L < 2 || L > 8 || n1 % 4 != 0 || n1 < 8LL * L || n1 >= (1LL << 30)) return 0;
+    return den1_instantiated({p.f64, p.comp, L, level}) ? level : 0;
+}
+// Whether ndwt_denoise_bands takes that launch unasked.  The rule of DESIGN.md 4.3b: a data kind takes it by default only if it was
+// measured to win by more than the 5 % spread between boxes on every measured shape of the kind.  Measured on the MI355X
+// (tools/bench1d_denoise.py, profiles/bench1d_denoise.txt; the table is in DESIGN.md 4.3d), one launch against the parent's
+// ndwt_denoise with one threshold / against the general route of ndwt_denoise_bands, db4 at 4 levels and db2 at 3:
+//   float      4096 x 4096, 65536 x 256, 16 x 2^20:  0.49 .. 0.57 / 0.31 .. 0.39 (db4),  0.36 .. 0.42 / 0.23 .. 0.30 (db2)
+//   complex64  4096 x 2048:                          0.75 / 0.48 (db4),  0.41 / 0.27 (db2)
+//   double     4096 x 4096:                          0.28 / 0.18 (db4),  0.18 / 0.12 (db2)
+// so float, complex64 and double take it unasked.  complex128 was not measured (and three of its instances are not built): on request
+// only, ndwt_plan_set_variant(plan, 11, 11, ...).
+constexpr bool denoise1_default(bool f64, int comp) { return !(f64 && comp == 2); }
+inline bool denoise1_wanted(const SelPlan& p) {
+    return (p.variant_fwd == kFwdCascadeAlways && p.variant_inv == kInvCascadeAlways) || denoise1_default(p.f64, p.comp);
 }
 
 // ---- two to four levels of ONE strided axis inside one march (FwdMC / InvMC, ndwt_device_axis.h): a plan over interleaved samples

@@ -33,11 +33,12 @@ FAMILY_PARAMS = {
     "AxisX": [("T", None), ("L", None), ("SYN", None), ("EW", None), ("VEC4", None)],
 }
 
-# the families of csrc/ndwt_device_1d.h (the cascade of a batched 1-D plan), in a table of their own: FAMILY_PARAMS is kept equal to
+# the families of csrc/ndwt_device_1d.h (the cascades and the one-launch denoise of a batched 1-D plan), in a table of their own: FAMILY_PARAMS is kept equal to
 # the declarations of ndwt_device.h
 FAMILY_PARAMS_1D = {
     "Fwd1C": [("T", None), ("L", None), ("NLEV", None), ("EW", 1), ("WPE", 4)],
     "Inv1C": [("T", None), ("L", None), ("NLEV", None), ("EW", 1), ("WPE", 4)],
+    "Den1C": [("T", None), ("L", None), ("NLEV", None), ("EW", 1), ("WPE", 4)],
 }
 
 # the families of csrc/ndwt_device_axis.h (all levels of one strided axis inside one march: plans over interleaved samples), likewise
