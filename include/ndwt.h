@@ -51,7 +51,9 @@ enum {
 enum { NDWT_F32 = 0, NDWT_F64 = 1 };                 /* 'precision' = single / double (nd_dwt_3D.m:130-132) */
 enum { NDWT_REAL = 0, NDWT_COMPLEX_INTERLEAVED = 1 }; /* split complex: call twice (re, im) -- the filters are real */
 enum { NDWT_DILATION_REFERENCE = 0, /* same un-dilated taps at every level: what the reference computes (nd_dwt_3D.m:178-186, nddwt.c:214-234) */
-       NDWT_DILATION_ATROUS = 1 };   /* tap stride 2^(level-1): textbook stationary wavelet transform */
+       NDWT_DILATION_ATROUS = 1 };   /* tap stride 2^(level-1): textbook stationary wavelet transform.  An axis only has to hold the
+                                        un-dilated filter: axes shorter than a level's dilated filter are served, the filter periodised
+                                        (it wraps round the axis, taps that land on one sample add up) */
 enum { NDWT_PATH_AUTO = 0,    /* fused kernels where they apply, per-axis kernels otherwise */
        NDWT_PATH_GENERIC = 1  /* force the per-axis kernels (used by the parity tests to cross-check the fused ones) */ };
 

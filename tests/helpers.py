@@ -52,6 +52,39 @@ def fuzz_cases(n, seed, max_order=10, p_atrous=0.2):
     return out
 
 
+def short_axis_cases(n, seed):
+    """`n` random configurations on the shortest legal axes (a generator of its own beside fuzz_cases, same dicts): every axis has
+    L .. L + 3 samples for its filter of L taps, a-trous dilation with probability 1/2 at 1 .. 4 levels -- so a dilated filter is longer
+    than its axis, wraps round it more than once, lands two taps on one sample or (tap stride a multiple of the axis) all of them --,
+    the four data kinds, both pres_l2_norm settings"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(n):
+        d = int(rng.choice([1, 2, 3, 3, 4]))
+        orders = [int(rng.integers(1, (10 if d < 4 else 4) + 1)) for _ in range(d)]
+        sizes = [2 * o + int(rng.integers(0, 4)) for o in orders]
+        out.append({"d": d, "sizes": sizes, "wn": [f"db{o}" for o in orders], "level": int(rng.integers(1, 5)),
+                    "dilation": "atrous" if rng.random() < 0.5 else "reference", "l2": int(rng.integers(0, 2)),
+                    "precision": "single" if rng.random() < 0.5 else "double", "cplx": bool(rng.random() < 0.5),
+                    "data_seed": int(seed) * 100003 + k})
+    return out
+
+
+def zero_bands(sizes, level, dilation):
+    """bands of a `level`-level transform that are identically zero in exact arithmetic: a-trous details of a level whose tap stride is
+    a multiple of an axis on which they are high-pass (every tap lands on one sample, and the high-pass taps sum to zero).  Band order
+    of the reference: 0 = approximation, then the details of the coarsest level first; bit a of a detail's number = high-pass on axis a"""
+    d = len(sizes)
+    nd = (1 << d) - 1
+    zero = np.zeros(1 + nd * level, dtype=bool)
+    if dilation == "atrous":
+        for lev in range(1, level + 1):
+            stride = 1 << (lev - 1)
+            for bits in range(1, nd + 1):
+                zero[1 + nd * (level - lev) + bits - 1] = any((bits >> a) & 1 and stride % sizes[a] == 0 for a in range(d))
+    return zero
+
+
 def fuzz_id(c):
     return (f"{c['d']}d-{'x'.join(map(str, c['sizes']))}-{'.'.join(w[2:] for w in c['wn'])}-L{c['level']}-l2{c['l2']}-"
             f"{c['precision'][0]}{'c' if c['cplx'] else 'r'}-{c['dilation'][0]}")

@@ -7,6 +7,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import helpers
 import ndwt_amd as ndwt
 import ndwt_oracle as orc
 
@@ -35,6 +36,11 @@ GAIN_CASES = [
     ("2d-32x32-db2-db3-l2", [32, 32], ["db2", "db3"], 2, 1, "reference"),
     ("3d-16-db1", [16, 16, 16], ["db1"] * 3, 2, 0, "reference"),
     ("1d-atrous-n64-db2-l3", [64], ["db2"], 3, 1, "atrous"),
+    # a-trous on axes shorter than the dilated filter: it goes round the axis more than once, two taps land on one sample
+    ("1d-atrous-n8-db4-l3-wraps", [8], ["db4"], 3, 1, "atrous"),
+    ("1d-atrous-n10-db5-l4-wraps", [10], ["db5"], 4, 0, "atrous"),
+    ("3d-atrous-8-db4-l3-wraps", [8, 8, 8], ["db4"] * 3, 3, 1, "atrous"),
+    ("2d-atrous-12x6-db3-l4-wraps", [12, 6], ["db3", "db3"], 4, 1, "atrous"),
 ]
 
 
@@ -46,6 +52,28 @@ def test_band_gains_are_the_band_norms_of_the_oracles_impulse_response(cid, dims
     err = np.abs(got - want).max() / np.abs(want).max()
     print(f"{cid}: gains {np.array2string(got, precision=4)}, relative error {err:.3g}")
     assert np.abs(got / want - 1).max() <= 1e-12
+
+
+# a tap stride that is a multiple of an axis: every tap lands on one sample, the high-pass taps sum to zero, and the bands that are
+# high-pass on that axis are identically zero in exact arithmetic (helpers.zero_bands).  Both sides return rounding noise there: those
+# bands are compared absolutely, against the largest gain, the others relatively as above
+ZERO_GAIN_CASES = [
+    ("1d-atrous-n8-db4-l5", [8], ["db4"], 5, 1, 2),                               # the details of levels 4 and 5
+    ("4d-atrous-6x4x5x4-l3", [6, 4, 5, 4], ["db3", "db2", "db2", "db1"], 3, 0, 12),   # level 3 (stride 4): high-pass on y or t
+]
+
+
+@pytest.mark.parametrize("cid,dims,wn,level,l2,nzero", ZERO_GAIN_CASES, ids=[c[0] for c in ZERO_GAIN_CASES])
+def test_band_gains_where_the_tap_stride_is_a_multiple_of_an_axis(cid, dims, wn, level, l2, nzero):
+    got = ndwt.band_gains(dims, wn, level, pres_l2_norm=l2, dilation="atrous")
+    want = _oracle_gains(dims, wn, level, l2, "atrous")
+    zero = helpers.zero_bands(dims, level, "atrous")
+    assert got.shape == want.shape == zero.shape and int(zero.sum()) == nzero
+    print(f"{cid}: zero bands: got {np.abs(got[zero]).max():.3g}, oracle {np.abs(want[zero]).max():.3g}; "
+          f"the others: relative error {np.abs(got[~zero] / want[~zero] - 1).max():.3g}")
+    assert np.abs(want[zero]).max() <= 1e-12 * want.max()                             # the oracle agrees that they are zero
+    assert np.abs(got[zero] - want[zero]).max() <= 1e-12 * want.max()
+    assert np.abs(got[~zero] / want[~zero] - 1).max() <= 1e-12
 
 
 def test_the_figures_users_are_told():

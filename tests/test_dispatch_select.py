@@ -333,3 +333,80 @@ def test_every_fused2_pick_names_an_instance(shim):
     listed = sum(shim.sel_fused2s_listed(_ints([inverse, f64, vec4, L, ew, wpe])) for inverse in (0, 1) for f64 in (0, 1) for vec4 in (0, 1)
                  for L in range(1, 25) for ew in (1, 2, 3, 4, 8) for wpe in (1, 2, 4, 8))
     assert listed == N_FUSED2S, listed
+
+
+# ---- axes shorter than the dilated filter (tests/test_gpu_short_axes.py): the route of a level does not ask how long a sub-lattice is
+def test_short_axis_levels_keep_their_routes(shim):
+    """written out: [8, 8, 8] db4 runs the fused sub-lattice kernels at tap strides 2 and 4 (sub-lattices of 4 and 2 samples under 8
+    taps) and the per-axis passes at 8; double has no stride-4 form; an axis the stride does not divide takes the per-axis passes"""
+    for inverse in (False, True):
+        f32 = _plan([8, 8, 8], [8, 8, 8], atrous=True)
+        assert _route(shim, f32, 1, inverse) == (FUSED3, 8)
+        assert _route(shim, f32, 2, inverse) == (FUSED3_DILATED, 8)
+        assert _route(shim, f32, 4, inverse) == (FUSED3_DILATED, 8)
+        assert _route(shim, f32, 8, inverse) == (PER_AXIS, 0)
+        f64 = _plan([8, 8, 8], [8, 8, 8], f64=True, atrous=True)
+        assert _route(shim, f64, 2, inverse) == (FUSED3_DILATED, 8)
+        assert _route(shim, f64, 4, inverse) == (PER_AXIS, 0)
+        assert _route(shim, _plan([8, 8, 8], [8, 8, 8], cplx=True, atrous=True), 2, inverse) == (PER_AXIS, 0)
+        assert _route(shim, _plan([8, 8, 8], [8, 8, 8], generic=True, atrous=True), 2, inverse) == (PER_AXIS, 0)
+        for dims, lens in (([16, 8, 8], [8, 8, 8]), ([12, 8, 8], [8, 8, 8]), ([8, 8, 4], [8, 8, 4]), ([8, 8, 8], [4, 8, 4]), ([8, 4, 4], [4, 4, 4]),
+                           ([16, 8, 8], [6, 6, 6]), ([4, 4, 4], [2, 2, 2])):
+            for stride in (2, 4):
+                assert _route(shim, _plan(dims, lens, atrous=True), stride, inverse) == (FUSED3_DILATED, max(lens)), (dims, lens, stride)
+        for stride in (2, 4):
+            assert _route(shim, _plan([10, 9, 7], [6, 4, 4], atrous=True), stride, inverse) == (PER_AXIS, 0)
+            assert _route(shim, _plan([16, 16, 8], [12, 12, 8], atrous=True), stride, inverse) == (PER_AXIS, 0)      # 12 taps: no sub-lattice form
+            assert _route(shim, _plan([6, 4, 5, 4], [6, 4, 4, 2], atrous=True), stride, inverse) == (PER_AXIS, 0)
+            assert _route(shim, _plan([9, 6], [4, 6], atrous=True), stride, inverse) == (PER_AXIS, 0)
+            assert _route(shim, _plan([8, 8], [8, 8], atrous=True), stride, inverse) == (FUSED2_DILATED, 8)
+            assert _route(shim, _plan([16, 4], [4, 4], atrous=True), stride, inverse) == (FUSED2_DILATED, 4)
+        assert _route(shim, _plan([8, 8], [8, 8], f64=True, atrous=True), 2, inverse) == (FUSED2_DILATED, 8)
+        assert _route(shim, _plan([8, 8], [8, 8], f64=True, atrous=True), 4, inverse) == (PER_AXIS, 0)
+
+
+def test_short_axis_rows_route_and_pick_what_the_gpu_file_expects(shim):
+    """every row of tests/test_gpu_short_axes.py on a plain plan, in every data kind it runs, level by level and both ways: the route
+    that file's restatement of the selection rule gives is level_route's, and wherever the level is fused, fused3_select / fused2_select
+    name a listed instance that one of the row's expected specs matches.  (Stacks, interleaved samples and batched plans: their own
+    select tests; their dilated levels take the per-axis passes.)"""
+    import test_gpu_short_axes as sa
+    fused, checked = 0, 0
+    for row in sa.ROWS:
+        if row["plan"] != "plain":
+            continue
+        dims, lens, d = row["dims"], row["lens"], len(row["dims"])
+        for kind in row["kinds"]:
+            prec, cplx = sa.KINDS[kind]
+            f64, comp = prec == "double", 2 if cplx else 1
+            n1 = dims[0] * comp
+            vec4 = not row["offset"] and n1 % 4 == 0 and (n1 * dims[1] if d > 1 else 4) % 4 == 0
+            plan = _plan(dims, lens, f64, cplx, row["generic"], row["dil"] == "atrous", row["vf"], row["vi"])
+            for inverse in (False, True):
+                must, may = sa.expected(row, kind, inverse)
+                specs = [helpers.spec(s) for s in must]
+                for lev in range(1, row["level"] + 1):
+                    stride = (1 << (lev - 1)) if row["dil"] == "atrous" else 1
+                    kind_, Lp = _route(shim, plan, stride, inverse)
+                    assert (kind_, Lp) == sa.level_kind(row, kind, stride, inverse), (row["id"], kind, stride, inverse, kind_, Lp)
+                    checked += 1
+                    if kind_ == PER_AXIS:
+                        assert may or row["axis"], (row["id"], kind)
+                        continue
+                    if kind_ == FUSED3_DILATED:
+                        name, p, f = _fused3(shim, [f64, inverse, vec4, lens[1] == lens[2], 0, Lp] + lens[:3] + [stride, stride, dims[0], dims[1] // stride,
+                                                    stride * stride, row["vf"], row["vi"], NUM_CUS, 0])
+                    elif kind_ in (FUSED3, FUSED3_T):
+                        name, p, f = _fused3(shim, [f64, inverse, vec4, lens[1] == lens[2], 0, Lp] + lens[:3] + [comp, 1, n1, dims[1], dims[3] if d == 4 else 1,
+                                                    row["vf"], row["vi"], NUM_CUS, 0])
+                    else:
+                        assert kind_ in (FUSED2, FUSED2_DILATED)
+                        dil = stride if kind_ == FUSED2_DILATED else 1
+                        left = row["level"] if row["dil"] == "reference" else 0
+                        assert left == 0 or row["vf"] == row["vi"] == 11 or shim.sel_cascade2_levels(plan, inverse, left) == 0   # one launch per level
+                        name, p, f = _fused2(shim, [f64, inverse, vec4, Lp, dil if dil > 1 else comp, dil, n1, dims[1], row["vi"]])
+                    assert f["listed"], (row["id"], kind, name, p)
+                    rec = helpers._trace.KernelLaunch(name, p)
+                    assert not row["trace"] or any(helpers.matches(rec, sp) for sp in specs), (row["id"], kind, stride, "rec" if inverse else "dec", rec, must)
+                    fused += 1
+    assert checked >= 1000 and fused >= 400, (checked, fused)

@@ -589,6 +589,14 @@ def test_emulated_synthesis_with_fused_shrinkage(emu, cplx, hard):
     ((24, 12, 8), ("db4", "db2", "db3"), 2, np.float64),
     ((72, 16, 6), ("db2", "db4", "db1"), 2, np.float32),
     ((72, 16, 8), ("db4", "db3", "db2"), 4, np.float32),        # stride 4: the 512-thread tiles, x taps over 4 scalars
+    # sub-lattices shorter than the padded taps (4, 2 or 1 samples under 8 taps): the filter goes round them more than once
+    ((8, 8, 8), ("db4", "db4", "db4"), 2, np.float32),
+    ((8, 8, 8), ("db4", "db4", "db4"), 2, np.float64),
+    ((8, 4, 4), ("db4", "db4", "db4"), 2, np.float32),
+    ((16, 8, 8), ("db4", "db4", "db4"), 4, np.float32),
+    ((12, 8, 8), ("db4", "db4", "db4"), 4, np.float32),
+    ((8, 8, 4), ("db4", "db4", "db4"), 4, np.float32),          # one sample per z sub-lattice
+    ((8, 8, 8), ("db2", "db4", "db2"), 4, np.float32),
 ])
 def test_emulated_dilated_level_on_sublattices(emu, sizes, wn, dil, dtype):
     """an a-trous level (tap stride = dil on every axis) as dil^3 independent stride-1 problems: x through EW = dil,
@@ -614,6 +622,13 @@ def test_emulated_dilated_level_on_sublattices(emu, sizes, wn, dil, dtype):
     ((72, 16, 8), ("db2", "db2", "db2"), 4),
     ((64, 12, 16), ("db3", "db1", "db3"), 4),
     ((80, 8, 12), ("db1", "db1", "db1"), 4),
+    # sub-lattices shorter than the padded taps
+    ((8, 8, 8), ("db4", "db4", "db4"), 2),
+    ((8, 4, 4), ("db4", "db4", "db4"), 2),
+    ((16, 8, 8), ("db4", "db4", "db4"), 4),
+    ((12, 8, 8), ("db4", "db4", "db4"), 4),
+    ((8, 8, 4), ("db4", "db4", "db4"), 4),
+    ((8, 8, 8), ("db2", "db4", "db2"), 4),
 ])
 def test_emulated_dilated_synthesis_on_the_pair_packed_kernel(emu, sizes, wn, dil):
     """float synthesis of an a-trous level through Inv3Y: tap stride 2 = its interleaved-pair form (the two x sub-lattices are the
@@ -631,7 +646,10 @@ def test_emulated_dilated_synthesis_on_the_pair_packed_kernel(emu, sizes, wn, di
 
 
 @pytest.mark.slow
-@pytest.mark.parametrize("sizes,wn,dtype", [((72, 20), ("db4", "db2"), np.float64), ((264, 14), ("db2", "db4"), np.float32)])
+@pytest.mark.parametrize("sizes,wn,dtype", [((72, 20), ("db4", "db2"), np.float64), ((264, 14), ("db2", "db4"), np.float32),
+                                            # row sub-lattices of 4 and 2 rows under 8 and 4 taps: the filter wraps
+                                            ((8, 8), ("db4", "db4"), np.float32), ((8, 8), ("db4", "db4"), np.float64),
+                                            ((16, 4), ("db2", "db2"), np.float32)])
 def test_emulated_dilated_2d_level_on_row_sublattices(emu, sizes, wn, dtype):
     """2-D a-trous level with tap stride 2: x through EW = 2, the two row sub-lattices as batch items (row stride 2*n1)"""
     rng = np.random.default_rng(23)

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Randomised parity sweep on the GPU: random dimensions (primes, sizes below one tile, non-multiples of 4), mixed
 db1..db10 wavelets, levels, precisions, real / complex, both dilations, against the CPU oracle.  Not part of the test
-suite (minutes of oracle time); run it after kernel changes:  python tools/fuzz_gpu.py [cases] [seed] [max_order] [p_atrous]   (max_order <= 4 keeps every
-case on the fused kernels)"""
+suite (minutes of oracle time); run it after kernel changes:  python tools/fuzz_gpu.py [cases] [seed] [max_order] [p_atrous] [short]
+(max_order <= 4 keeps every case on the fused kernels; a fifth argument `short` draws from helpers.short_axis_cases instead: axes of
+L .. L + 3 samples, a-trous half of the time, so the dilated filters wrap -- max_order and p_atrous are then not used)"""
 import os
 import sys
 
@@ -19,13 +20,14 @@ cases = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 0
 max_order = int(sys.argv[3]) if len(sys.argv) > 3 else 10
 p_atrous = float(sys.argv[4]) if len(sys.argv) > 4 else 0.2
+short = len(sys.argv) > 5 and sys.argv[5] == "short"
 CLS = {1: ndwt.nd_dwt_1D, 2: ndwt.nd_dwt_2D, 3: ndwt.nd_dwt_3D, 4: ndwt.nd_dwt_4D}
 TOL = {"double": 1e-12, "single": 3e-6}
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import helpers  # noqa: E402
 
 worst = 0.0
-for case in helpers.fuzz_cases(cases, seed, max_order, p_atrous):
+for case in (helpers.short_axis_cases(cases, seed) if short else helpers.fuzz_cases(cases, seed, max_order, p_atrous)):
     d, sizes, wn, level, l2 = case["d"], case["sizes"], case["wn"], case["level"], case["l2"]
     precision, cplx, dilation = case["precision"], case["cplx"], case["dilation"]
     rng = np.random.default_rng(case["data_seed"])
