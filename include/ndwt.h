@@ -275,6 +275,32 @@ int ndwt_denoise_host(ndwt_plan* plan, const void* x_host, void* out_host, int l
 int ndwt_band_gains(int ndim, const int64_t* dims, const char* const* wnames, int pres_l2_norm, int dilation, int level, double* gains);
 int ndwt_shrink_bands(ndwt_plan* plan, void* y_dev, int64_t band_pitch, int level, const double* thresholds, int mode, void* stream);
 int ndwt_denoise_bands(ndwt_plan* plan, const void* x_dev, void* out_dev, int level, const double* thresholds, int mode, void* stream);
+/* ---- the sigma of thresholds[b] = k * sigma * gains[b]: exact order statistics of a band's |c|, on the device ----
+ * ndwt_band_select: values[i] = the k[i]-th smallest (0-based) |c| of band `band` of a level-`level` coefficient array on the device
+ *   (band_pitch 0 = packed), for nk = 1 .. 4 ranks in one call; a rank may be given twice.  Real data: |c| exactly (the value's own
+ *   bits, widened to double).  Interleaved complex data: the magnitude sqrt(re^2 + im^2) in the plan's scalar type, as the shrink
+ *   computes and compares it.  A NaN orders after every number, -0 and +0 are equal.  A band is the plan's WHOLE array: all signals of
+ *   a batch and all items of a stack pooled (as ndwt_shrink_bands sees it); a statistic per item is not offered.  Every plan kind
+ *   ndwt_shrink_bands serves.  The band is read 3 times (float, complex64) or 6 times (double, complex128), whatever nk -- a radix
+ *   select on the bit pattern, no sort, no copy -- and never written; the plan keeps 32 KB of device scratch for it.  Bands of 2^32
+ *   elements or more: NDWT_ERR_UNSUPPORTED.
+ *   k and values are HOST pointers, so the call is synchronous like the other forms with host pointers: it enqueues on `stream`, copies
+ *   the nk results back, synchronises the stream and returns.  plan, y_dev, k or values null, band outside [0, ndwt_num_bands), nk
+ *   outside 1 .. 4, a k[i] outside [0, elements of the band): NDWT_ERR_INVALID_ARG, the message names the argument.
+ * ndwt_estimate_sigma_coef: the standard deviation of white noise in the SIGNAL, estimated from a level-`level` coefficient array
+ *   (Donoho and Johnstone): m = the median of |c| over the LAST band -- level 1, high-pass on every filtered axis -- (an even count:
+ *   the mean of the two middle order statistics), g = that band's gain (what ndwt_band_gains returns for the plan's filtered axes,
+ *   pres_l2_norm and dilation), and
+ *     real data     sigma = m / 0.6744897501960817 / g   (the median of |N(0, 1)|)
+ *     complex data  sigma = m / 1.1774100225154747 / g   (|c| is Rayleigh distributed; sqrt(2 ln 2) is its median for unit parts):
+ *                   the standard deviation of EACH of the real and imaginary parts, not of the complex sample (that is sqrt(2) larger).
+ *   *sigma is a HOST pointer: synchronous, as above.
+ * ndwt_estimate_sigma: the same from a signal on the device: one level-1 dec into the plan's coefficient scratch (as ndwt_denoise_bands
+ *   runs it), then the coefficient path.  x is not modified. */
+int ndwt_band_select(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, int64_t band, int nk, const int64_t* k,
+                     double* values, void* stream);
+int ndwt_estimate_sigma_coef(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double* sigma, void* stream);
+int ndwt_estimate_sigma(ndwt_plan* plan, const void* x_dev, double* sigma, void* stream);
 
 /* Split complex: separate real / imaginary arrays, the layout the reference's gateway receives from MATLAB
  * (mxGetPr / mxGetPi, nd_dwt_mex.c:55-58,90-93) and hands to nd_dwt_dec / nd_dwt_rec (outR/outI, imageR/imageI,

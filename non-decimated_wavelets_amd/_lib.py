@@ -32,7 +32,8 @@ EXPORTS = [
     "ndwt_comm_last_error", "ndwt_coef_create", "ndwt_coef_release", "ndwt_coef_info", "ndwt_coef_dec_host", "ndwt_coef_rec_host",
     "ndwt_coef_shrink", "ndwt_coef_get_host", "ndwt_coef_put_host", "ndwt_plan_create_slab_axis", "ndwt_slab_segments_strided",
     "ndwt_mplan_create_axis", "ndwt_trace_enable", "ndwt_trace_get", "ndwt_plan_create_many", "ndwt_plan_create_axes",
-    "ndwt_plan_create_interleaved", "ndwt_band_gains", "ndwt_shrink_bands", "ndwt_denoise_bands",
+    "ndwt_plan_create_interleaved", "ndwt_band_gains", "ndwt_shrink_bands", "ndwt_denoise_bands", "ndwt_band_select",
+    "ndwt_estimate_sigma_coef", "ndwt_estimate_sigma",
 ]
 
 
@@ -113,6 +114,11 @@ def lib() -> ctypes.CDLL:
                                     ctypes.c_void_p]
     L.ndwt_denoise_bands.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_int,
                                      ctypes.c_void_p]
+    L.ndwt_band_select.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                   ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
+    L.ndwt_estimate_sigma_coef.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                           ctypes.c_void_p]
+    L.ndwt_estimate_sigma.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
     L.ndwt_denoise_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int]
     for f in (L.ndwt_dec_split, L.ndwt_rec_split):
         f.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p]

@@ -202,6 +202,29 @@ class Plan:
         self._check_band_count(t, level)
         L.check(L.lib().ndwt_denoise_bands(self._h, x_ptr, out_ptr, int(level), tp, int(bool(hard)), ctypes.c_void_p(stream)))
 
+    def band_select(self, y_ptr, level, band, ks, stream=0, band_pitch=0):
+        """the ks[i]-th smallest (0-based) |c| of band `band` of a level-`level` coefficient array on the device, exactly, as a numpy array
+        of doubles (include/ndwt.h: ndwt_band_select): up to 4 ranks per call; complex data: the magnitude the shrink compares.  The band
+        is the plan's whole array (all signals of a batch, all items of a stack).  Synchronous: the results are host values."""
+        k = np.ascontiguousarray(np.asarray(ks, dtype=np.int64).reshape(-1))
+        out = np.zeros(max(k.size, 1))
+        L.check(L.lib().ndwt_band_select(self._h, y_ptr, int(band_pitch), int(level), int(band), int(k.size), k.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.c_void_p(stream)))
+        return out[:k.size]
+
+    def estimate_sigma_coef(self, y_ptr, level, stream=0, band_pitch=0):
+        """sigma of white noise in the SIGNAL from a coefficient array on the device: median |c| of the last band / 0.6745 / its gain
+        (complex data: / 1.1774, the sigma of each of the real and imaginary parts) -- include/ndwt.h: ndwt_estimate_sigma_coef"""
+        s = ctypes.c_double(0.0)
+        L.check(L.lib().ndwt_estimate_sigma_coef(self._h, y_ptr, int(band_pitch), int(level), ctypes.byref(s), ctypes.c_void_p(stream)))
+        return float(s.value)
+
+    def estimate_sigma(self, x_ptr, stream=0):
+        """the same from a signal on the device: one level-1 dec into the plan's coefficient scratch, then estimate_sigma_coef"""
+        s = ctypes.c_double(0.0)
+        L.check(L.lib().ndwt_estimate_sigma(self._h, x_ptr, ctypes.byref(s), ctypes.c_void_p(stream)))
+        return float(s.value)
+
     def denoise_host(self, x_ptr, out_ptr, level, threshold, hard=False):
         L.check(L.lib().ndwt_denoise_host(self._h, x_ptr, out_ptr, int(level), float(threshold), int(bool(hard))))
 
@@ -785,6 +808,53 @@ class _NdDwtBase:
     def band_gains(self, level):
         """standard deviation of every band for unit-variance white input (ndwt_band_gains): thresholds = k * sigma * band_gains(level)"""
         return L.band_gains(self.sizes, self.wname[: self.NDIM], int(level), self.pres_l2_norm, self.dilation)
+
+    # -- the sigma of thresholds = k * sigma * band_gains(level), estimated on the device (extension; not in the reference) --
+    def estimate_sigma(self, x):
+        """Standard deviation of white noise in the signal `x` (Donoho and Johnstone): the median of |c| over the finest all-high-pass
+        band of a level-1 dec, / 0.6745 and / that band's gain; complex x: / 1.1774, the sigma of each of the real and imaginary parts.
+        The band is the whole array (all signals of a batch, all items of a stack).  A float; the call waits for the result."""
+        x = self._prep_dec_input(x)
+        if list(x.shape) != self._shape:
+            raise ValueError(f"input size {list(x.shape)} does not match the object's sizes {self._shape}")
+        dev = self._dev(x if isinstance(x, torch.Tensor) else None)
+        xk = self._to_device_kernel_order(x, dev, self.NDIM)
+        plan = self._plan(xk.is_complex(), 1, dev)
+        with torch.cuda.device(dev):
+            return plan.estimate_sigma(xk.data_ptr(), _current_stream(dev))
+
+    def _coef_for_stats(self, y):
+        if y.ndim != len(self._shape) + 1 or list(y.shape[:-1]) != self._shape:
+            raise ValueError(f"coefficient array must have shape {self._shape + ['bands']}")
+        level = self._level_from_bands(int(y.shape[-1]))
+        dev = self._dev(y if isinstance(y, torch.Tensor) else None)
+        yk, pitch = self._coef_kernel_order(y, dev)
+        return yk, pitch, level, dev, self._plan(yk.is_complex(), level, dev)
+
+    def estimate_sigma_coef(self, y):
+        """estimate_sigma from a coefficient array (what dec returns, any level): its last band is the one the estimate reads"""
+        yk, pitch, level, dev, plan = self._coef_for_stats(y)
+        with torch.cuda.device(dev):
+            return plan.estimate_sigma_coef(yk.data_ptr(), level, _current_stream(dev), band_pitch=pitch)
+
+    def band_median(self, y, band):
+        """The median of |c| over band `band` of a coefficient array, exactly (an even count: the mean of the two middle order
+        statistics, as numpy.median); complex data: of the magnitude the shrink compares.  Computed on the device without a sort."""
+        yk, pitch, level, dev, plan = self._coef_for_stats(y)
+        n = int(np.prod(yk.shape[1:]))
+        with torch.cuda.device(dev):
+            v = plan.band_select(yk.data_ptr(), level, int(band), [(n - 1) // 2] if n % 2 else [n // 2 - 1, n // 2], _current_stream(dev), band_pitch=pitch)
+        return float(v[0]) if n % 2 else 0.5 * float(v[0] + v[1])
+
+    def universal_thresholds(self, x, level, k=None):
+        """k * estimate_sigma(x) * band_gains(level) with entry 0 (the approximation) set to 0: one threshold per band, as denoise(x, level,
+        thresholds) and shrink(y, thresholds) take them.  k defaults to the universal sqrt(2 ln N), N = the samples of one item's
+        filtered axes."""
+        if k is None:
+            k = float(np.sqrt(2.0 * np.log(float(np.prod(self.sizes, dtype=np.float64)))))
+        thr = float(k) * self.estimate_sigma(x) * self.band_gains(level)
+        thr[0] = 0.0
+        return thr
 
     def _prep_dec_input(self, x):
         return x

@@ -18,6 +18,7 @@
 
 #include "../../include/ndwt.h"
 #include "ndwt_device.h"
+#include "ndwt_device_select.h"
 #include "ndwt_filters.h"
 #include "ndwt_fused.h"
 #include "ndwt_geom.h"
@@ -172,6 +173,8 @@ struct ndwt_plan {
     double shrink_thr = 0;
     DevBuf coef;                       // coefficient scratch of ndwt_denoise (all bands of the last level used), lazily allocated
     DevBuf taps_den;                   // device tap table of the fused level-1 denoising kernel (TapsDen<float, L>), built at plan creation where it applies
+    DevBuf select_buf;                 // ndwt_band_select: the device-side state and the global histogram (SelectState, then [slot][bin]); lazily allocated
+    double sigma_gain = 0.0;           // ndwt_estimate_sigma*: the gain of the last level-1 band (last_band_gain), computed at the first call
     DevBuf taps_den1;                  // a batched 1-D plan whose levels can cascade: Taps1D<T, L>, the tables of both directions for Den1C
     DevBuf den_a1;                     // ndwt_denoise, fused level 1: the level-1 approximation / its reconstruction -- a scratch of its own (lazily
                                        // allocated), not `tmp`: dec_impl / rec_impl run in between and may re-allocate that one
@@ -2024,6 +2027,112 @@ int ndwt_denoise_bands(ndwt_plan* p, const void* x, void* out, int level, const 
     if (rc == NDWT_OK) rc = ndwt_shrink_bands(p, coef, pitch, level, thresholds, mode, stream);
     if (rc == NDWT_OK) rc = ndwt_rec_pitched(p, coef, pitch, out, level, stream);
     return rc;
+}
+
+// ---- order statistics of a band's |c|, and the noise estimate on top of them (include/ndwt.h; the kernels: ndwt_device_select.h) ----
+// what is decided without a device: the arguments, and the band's size against the 32-bit counters
+static int select_check(const ndwt_plan* p, const void* y, int level, int64_t band, int nk, const int64_t* k, const double* values) {
+    int rc = check_level(p, level);
+    if (rc) return rc;
+    if (!y) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (y_dev)");
+    if (!k) return fail(NDWT_ERR_INVALID_ARG, "null rank array (k)");
+    if (!values) return fail(NDWT_ERR_INVALID_ARG, "null output pointer (values)");
+    const long long nb = ndwt_num_bands(p->ndim, level), N = p->vol / p->comp;
+    if (band < 0 || band >= nb) return fail(NDWT_ERR_INVALID_ARG, "band %lld outside 0..%lld of a level-%d coefficient array", (long long)band, nb - 1, level);
+    if (nk < 1 || nk > kSelectMaxRanks) return fail(NDWT_ERR_INVALID_ARG, "nk = %d: 1..%d ranks per call", nk, kSelectMaxRanks);
+    for (int i = 0; i < nk; ++i)
+        if (k[i] < 0 || k[i] >= N) return fail(NDWT_ERR_INVALID_ARG, "k[%d] = %lld outside [0, %lld), the elements of a band", i, (long long)k[i], N);
+    if (!select_fits(N)) return fail(NDWT_ERR_UNSUPPORTED, "a band of %lld elements: the order statistics count in 32 bits (fewer than 2^32 elements)", N);
+    return NDWT_OK;
+}
+
+// select_passes(T) times: the histogram of one digit over the band, then the pick; the state stays on the device in between.  One copy
+// of the nk keys and one synchronisation of the stream end it.
+extern "C++" template <typename T> static int select_impl(ndwt_plan* p, const T* y, int nk, const int64_t* k, double* values, hipStream_t s) {
+    constexpr bool f64 = sizeof(T) == 8;
+    int rc = p->select_buf.grow(kSelectBufBytes, "for the select state");
+    if (rc) return rc;
+    void* const buf = p->select_buf.ptr;
+    SelectState* const st = (SelectState*)buf;
+    unsigned* const ghist = (unsigned*)((char*)buf + sizeof(SelectState));
+    HIP_TRY(hipMemsetAsync(buf, 0, kSelectBufBytes, s));
+    const bool vec = select_vec((unsigned long long)(uintptr_t)y, p->vol, (int)sizeof(T));
+    const int nblocks = (int)select_grid(p->vol, (int)p->comp, vec, p->num_cus, p->target_blocks);
+    for (int pass = 0; pass < select_passes(f64); ++pass) {
+        const int shift = select_digit_shift(f64, pass), bits = select_digit_bits(f64, pass), top = shift + bits;
+        const unsigned long long himask = top >= select_key_bits(f64) ? 0ULL : ((~0ULL << top) & (f64 ? ~0ULL : 0xffffffffULL));
+        const BandHistArgs<T> a = {y, p->vol, st, ghist, himask, shift, bits, nk, nblocks};
+        rc = launch_band_hist(a, (int)p->comp, vec, select_agg(p->variant_fwd), buf, s);
+        if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: no histogram kernel for this data kind");
+        if (rc != 0) return fail(NDWT_ERR_HIP, "histogram kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        BandPickArgs pa = {st, ghist, {0, 0, 0, 0}, nk, pass, shift};
+        for (int i = 0; i < nk; ++i) pa.k[i] = (unsigned)k[i];
+        rc = launch_band_pick(f64, pa, buf, s);
+        if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: no pick kernel for this data kind");
+        if (rc != 0) return fail(NDWT_ERR_HIP, "pick kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    unsigned long long keys[kSelectMaxRanks] = {};
+    HIP_TRY(hipMemcpyAsync(keys, st->prefix, sizeof(unsigned long long) * (size_t)nk, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int i = 0; i < nk; ++i) {
+        typename SelectKey<T>::type key = (typename SelectKey<T>::type)keys[i];
+        T v;
+        memcpy(&v, &key, sizeof v);
+        values[i] = (double)v;
+    }
+    return NDWT_OK;
+}
+
+int ndwt_band_select(ndwt_plan* p, const void* y, int64_t band_pitch, int level, int64_t band, int nk, const int64_t* k, double* values, void* stream) {
+    int rc = select_check(p, y, level, band, nk, k, values);
+    if (rc) return rc;
+    long long bs = 0;
+    rc = pitch_scalars(p, band_pitch, &bs);
+    if (rc) return rc;
+    return on_device(p, [&](auto t) { return select_impl(p, (const decltype(t)*)y + band * bs, nk, k, values, (hipStream_t)stream); });
+}
+
+// the gain of the last band of a level-1 transform of the plan's filtered axes (what ndwt_band_gains computes, from the same code)
+static double last_band_gain(const ndwt_plan* p) {
+    double g = 1.0;
+    for (int a = 0; a < p->ndim; ++a) {
+        double A[2], D[2];
+        axis_gains(p->filt[a], p->dims[a], p->dilation == NDWT_DILATION_ATROUS, 1, A, D);
+        g *= D[1];
+    }
+    return g;
+}
+
+int ndwt_estimate_sigma_coef(ndwt_plan* p, const void* y, int64_t band_pitch, int level, double* sigma, void* stream) {
+    int rc = check_level(p, level);
+    if (rc) return rc;
+    if (!y) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (y_dev)");
+    if (!sigma) return fail(NDWT_ERR_INVALID_ARG, "null output pointer (sigma)");
+    const long long N = p->vol / p->comp;
+    const int64_t k[2] = {(N - 1) / 2, N / 2};            // the middle, or the two middle order statistics of an even count
+    const int nk = N % 2 ? 1 : 2;
+    double v[2] = {0, 0};
+    rc = ndwt_band_select(p, y, band_pitch, level, ndwt_num_bands(p->ndim, level) - 1, nk, k, v, stream);
+    if (rc) return rc;
+    if (p->sigma_gain == 0.0) p->sigma_gain = last_band_gain(p);
+    const double m = nk == 2 ? 0.5 * (v[0] + v[1]) : v[0];
+    // the median of |N(0, 1)|; complex data: of the Rayleigh distribution with unit parts, sqrt(2 ln 2)
+    *sigma = m / (p->complexity == NDWT_REAL ? 0.6744897501960817 : 1.1774100225154747) / p->sigma_gain;
+    return NDWT_OK;
+}
+
+int ndwt_estimate_sigma(ndwt_plan* p, const void* x, double* sigma, void* stream) {
+    int rc = check_level(p, 1);
+    if (rc) return rc;
+    if (!x) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (x_dev)");
+    if (!sigma) return fail(NDWT_ERR_INVALID_ARG, "null output pointer (sigma)");
+    HIP_TRY(hipSetDevice(p->device));
+    const int64_t pitch = ndwt_band_pitch(p);
+    rc = ensure_coef(p, (size_t)pitch * p->comp * p->esize * (size_t)ndwt_num_bands(p->ndim, 1));
+    if (rc) return rc;
+    rc = ndwt_dec_pitched(p, x, p->coef.ptr, pitch, 1, stream);
+    if (rc) return rc;
+    return ndwt_estimate_sigma_coef(p, p->coef.ptr, pitch, 1, sigma, stream);
 }
 
 int ndwt_denoise_host(ndwt_plan* p, const void* x, void* out, int level, double threshold, int mode) {

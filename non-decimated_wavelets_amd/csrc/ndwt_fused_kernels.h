@@ -101,6 +101,15 @@ template <class K> int launch_cascadem_k(const typename K::Args& a, const double
     return (int)hipGetLastError();
 }
 
+// The order statistics of a band (BandHist / BandPick, ndwt_device_select.h): `nblocks` workgroups; buf_dev is the plan's select buffer,
+// which stands in for the tap table these kernels do not have (a real device pointer: the wrapper forms a reference from it)
+template <class K> int launch_select_k(const typename K::Args& a, int nblocks, const void* buf_dev, hipStream_t s) {
+    if (nblocks < 1 || !buf_dev) return -2;
+    trace_kernel<K>(dim3((unsigned)nblocks), dim3(K::NT));
+    hipLaunchKernelGGL(fused3_kernel<K>, dim3((unsigned)nblocks), dim3(K::NT), 0, s, a, (const typename K::Taps*)buf_dev);
+    return (int)hipGetLastError();
+}
+
 // One entry of an instance list (ndwt_fused_list.h) as an exact-match launch: the pick is this instance, or the next entry is asked.  A
 // launch unit is its list expanded with these and a final "not mine" (-1).
 #define NDWT_FUSED_K(KIND, INV, T, LL, V, VEC, ...)                                                          \

@@ -21,6 +21,7 @@ namespace ndwt {
 //      (a batched 1-D plan, cascade1_levels: fwd 9 = one launch per level in the analysis, inv 9 = in the synthesis; nothing else applies)
 //      (ndwt_denoise_bands of a batched 1-D plan, denoise1_levels: fwd 11 AND inv 11 = the one-launch Den1C wherever it exists, 9 in either slot = off)
 //      (interleaved samples, one axis, cascadem_levels: fwd / inv 9 = one launch per level, 11 = the cascaded march wherever it exists)
+//      (ndwt_band_select, select_agg: fwd 9 = the histogram passes without the wave-wide combining of equal digits)
 //  inv | 3-D synthesis (fused3_select)                                       | 2-D (fused2_select)                | 2-D cascade (cascade2_levels)
 //   0  | default: Inv3Y (gather <= 8 taps, scatter from 10), else Inv3S      | Inv2P depth 4 packed, 1024 waves, where the image fits one round
 //   1  |                                                                     | keeps Inv2S
@@ -313,6 +314,41 @@ inline int cascadem_levels(const SelPlan& p, bool inverse, int left, int* L_out)
         if (cascadem_instantiated({inverse, p.f64, L, n})) { *L_out = L; return n; }
     return 0;
 }
+
+// ---- exact order statistics of a band's |c| (ndwt_band_select; BandHist / BandPick, ndwt_device_select.h): a radix select on the bit
+// pattern of |c|, most significant digit first.  A non-negative IEEE value orders as its unsigned bit pattern, so the key has 32 bits
+// (float, complex64: the magnitude is a float) or 64 (double, complex128).  A pass reads the band once and counts one digit of the keys
+// that carry the digits found so far; digits are kSelectDigitBits wide (2048 counters = 8 KB of LDS per rank), the last one is what is
+// left: float 11 + 11 + 10 bits = 3 passes, double 5 x 11 + 9 = 6.
+constexpr int kSelectDigitBits = 11, kSelectBins = 1 << kSelectDigitBits, kSelectMaxRanks = 4;
+constexpr int select_key_bits(bool f64) { return f64 ? 64 : 32; }
+constexpr int select_passes(bool f64) { return (select_key_bits(f64) + kSelectDigitBits - 1) / kSelectDigitBits; }
+// the digit of pass `pass` (0 = most significant) is bits [shift, shift + bits) of the key
+constexpr int select_digit_shift(bool f64, int pass) {
+    return select_key_bits(f64) - kSelectDigitBits * (pass + 1) > 0 ? select_key_bits(f64) - kSelectDigitBits * (pass + 1) : 0;
+}
+constexpr int select_digit_bits(bool f64, int pass) { return select_key_bits(f64) - kSelectDigitBits * pass - select_digit_shift(f64, pass); }
+// counters are 32-bit: a band of 2^32 elements or more is refused before any launch
+constexpr bool select_fits(long long n_elements) { return n_elements >= 1 && n_elements < (1LL << 32); }
+// 16- / 32-byte loads where the band's address is a multiple of 4 scalars and so is its length, one element at a time otherwise (the
+// rule of shrink_run)
+constexpr bool select_vec(unsigned long long addr, long long n_scalars, int scalar_bytes) {
+    return addr % (4ULL * scalar_bytes) == 0 && n_scalars % 4 == 0;
+}
+// workgroups of 256 threads of a pass: enough for kSelectTurns turns of the grid-stride loop per thread where the band has them (a
+// workgroup zeroes and flushes 2048 counters whatever it read: 8 turns of the 4-scalar form are 8192 keys per 2048 counters), capped
+// as shrink_run caps its grid (num_cus * 16); target_blocks > 0 (ndwt_plan_set_tuning) is an upper bound on top of that
+constexpr int kSelectTurns = 8;
+constexpr long long select_grid(long long n_scalars, int comp, bool vec, int num_cus, int target_blocks) {
+    long long blocks = ((vec ? n_scalars / 4 : n_scalars / comp) + 256 * kSelectTurns - 1) / (256 * kSelectTurns);
+    const long long cap = (long long)num_cus * 16;
+    if (blocks > cap) blocks = cap;
+    if (target_blocks > 0 && blocks > target_blocks) blocks = target_blocks;
+    return blocks < 1 ? 1 : blocks;
+}
+// rounds of the wave-wide combining of equal digits before the LDS atomics (BandHist AGG): 2 by default, kFwdNoCascade = none (A/B runs:
+// tools/bench_select.py; the counts are integers, so every setting gives the same values)
+constexpr int select_agg(int variant_fwd) { return variant_fwd == kFwdNoCascade ? 0 : 2; }
 
 // ---- one fused 3-D launch
 struct Fused3Query {

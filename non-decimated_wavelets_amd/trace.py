@@ -47,6 +47,12 @@ FAMILY_PARAMS_AXIS = {
     "InvMC": [("T", None), ("L", None), ("NLEV", None)],
 }
 
+# the families of csrc/ndwt_device_select.h (order statistics of a band: the histogram pass and the pick step of the radix select), likewise
+FAMILY_PARAMS_SELECT = {
+    "BandHist": [("T", None), ("COMP", None), ("VEC", None), ("AGG", 2)],
+    "BandPick": [("T", None)],
+}
+
 # the plain __global__ templates (csrc/ndwt_api.hip, csrc/ndwt_multi.hip), as their launch sites spell them
 PLAIN_PARAMS = {
     "axis_analysis_kernel": [("T", None)],
@@ -109,7 +115,7 @@ def parse_record(line: str) -> KernelLaunch:
     if not t:
         raise ValueError(f"unparsed kernel type: {text!r}")
     fam = t.group(1)
-    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam) or FAMILY_PARAMS_1D.get(fam) or FAMILY_PARAMS_AXIS.get(fam)
+    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam) or FAMILY_PARAMS_1D.get(fam) or FAMILY_PARAMS_AXIS.get(fam) or FAMILY_PARAMS_SELECT.get(fam)
     if table is None:
         raise ValueError(f"unknown kernel family {fam!r} in {text!r}")
     args = [_value(a) for a in _split_args(t.group(2) or "")]
