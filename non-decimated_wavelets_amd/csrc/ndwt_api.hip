@@ -169,8 +169,6 @@ struct ndwt_plan {
     int fp64_fused = 1;                // fp64: fused 3-D kernels (1) or the per-axis march kernels (0) -- measured: 256^3 fp64 db4 L3 2.5 ms
                                        // fused (LDS analysis + lane-shift synthesis) vs 4.1 ms per-axis
     DevBuf taps_dev[2];                // device tap tables of the fused kernels: [0] analysis (Taps3<T, Lp>), [1] synthesis (Taps3Y<T, Lp>)
-    int shrink_mode = 0;               // ndwt_denoise, during its rec: 0 none, 1 soft, 2 hard -- fused into the synthesis kernels' loads
-    double shrink_thr = 0;
     DevBuf coef;                       // coefficient scratch of ndwt_denoise (all bands of the last level used), lazily allocated
     DevBuf taps_den;                   // device tap table of the fused level-1 denoising kernel (TapsDen<float, L>), built at plan creation where it applies
     DevBuf select_buf;                 // ndwt_band_select: the device-side state and the global histogram (SelectState, then [slot][bin]); lazily allocated
@@ -435,6 +433,11 @@ template <typename T> static int nt_store_ok(long long rs, long long plane, long
 // one fused 3-D launch: what a call site says of it (the rest follows from the plan).  ZMode: the values Fused3Args::z_wrap documents
 enum ZMode { kZHalo = 0, kZPeriodic = 1, kZSplitHalo = 2, kZZeroExt = 3 };   // inputs with their z halo | periodic | halo planes in in[1] / in[2] | zero-extended slab
 constexpr int kShrinkTLowDetails = 0xFE, kShrinkTHighAll = 0xFF;   // bands shrunk on load (ndwt_denoise): the details of a 3-D level / of the t-low half, every band of the t-high half
+// ndwt_denoise's thresholding, done by the synthesis kernels as they load the detail bands: what rec_impl hands down to the launches
+// that can (only asked of plans whose every level runs one: fused_shrink_capable).  Every other synthesis passes kNoShrink.
+struct ShrinkOnLoad { int mode = 0; double thr = 0; };   // mode: 0 none, 1 soft, 2 hard
+constexpr ShrinkOnLoad kNoShrink = {};
+static ShrinkOnLoad shrink_on_load(double thr, int mode) { return {mode == NDWT_SHRINK_HARD ? 2 : 1, thr}; }
 template <typename T> struct Fused3Launch {
     bool inverse;
     int Lp;
@@ -444,7 +447,8 @@ template <typename T> struct Fused3Launch {
     long long nbatch = 1, in_bstride = 0, out_bstride = 0;   // volumes of the launch and the scalars between them
     ZMode z = kZPeriodic;
     long long zlo = 0, zhi = 0, zbs = 0;   // kZZeroExt: input planes outside [zlo, zhi) read as zero, batch item i testing plane + i * zbs
-    int shrink_mask = 0;
+    int shrink_mask = 0;               // synthesis: the bands `shrink` applies to
+    ShrinkOnLoad shrink = {};
     int dil = 1;                       // tap stride of a dilated level on its sub-lattices
     const double* ttaps = nullptr;     // kRouteFused3FoldT: the t taps of this launch's t-band
 };
@@ -462,10 +466,10 @@ template <typename T> static int fused3_run(const ndwt_plan* p, const Fused3Laun
     a.zlo = (int)l.zlo;
     a.zhi = (int)(l.z == kZZeroExt ? l.zhi : l.n3 - (Lp - 1));   // (the other modes never read the window)
     a.zbs = (int)l.zbs;
-    if (inverse && p->shrink_mode && l.shrink_mask) {      // only reached with a lane-shift synthesis kernel (fused_shrink_capable)
-        a.shrink_thr = (T)p->shrink_thr;
+    if (inverse && l.shrink.mode && l.shrink_mask) {      // only reached with a lane-shift synthesis kernel (fused_shrink_capable)
+        a.shrink_thr = (T)l.shrink.thr;
         a.shrink_mask = l.shrink_mask;
-        a.shrink_hard = p->shrink_mode == 2;
+        a.shrink_hard = l.shrink.mode == 2;
     }
     a.n1 = (int)(p->dims[0] * p->comp);                   // scalars along x (interleaved complex: 2 per element)
     a.n2 = (int)(p->dims[1] / dil);                       // dil > 1: one (y, z) sub-lattice per batch item
@@ -528,6 +532,7 @@ template <typename T> struct Fused2Launch {
     bool y_wrap = true;                // false: the inputs carry the y halo (slab mode)
     int dil = 1;                       // tap stride of a dilated level on its row sub-lattices
     long long nbatch = 1;              // images of the launch (a stack: its items, in_bstride / out_bstride apart)
+    ShrinkOnLoad shrink = {};          // synthesis: of the 3 detail bands
 };
 template <typename T> static int fused2_run(const ndwt_plan* p, const Fused2Launch<T>& l, hipStream_t s) {
     const bool inverse = l.inverse;
@@ -543,10 +548,10 @@ template <typename T> static int fused2_run(const ndwt_plan* p, const Fused2Laun
     a.in_bstride = dil > 1 ? p->dims[0] : l.in_bstride;
     a.out_bstride = dil > 1 ? p->dims[0] : out_bstride;
     a.y_wrap = l.y_wrap ? 1 : 0;
-    if (inverse && p->shrink_mode) {                     // ndwt_denoise: threshold the 3 detail bands as they are loaded
-        a.shrink_thr = (T)p->shrink_thr;
+    if (inverse && l.shrink.mode) {                      // ndwt_denoise: threshold the 3 detail bands as they are loaded
+        a.shrink_thr = (T)l.shrink.thr;
         a.shrink_mask = 0xE;
-        a.shrink_hard = p->shrink_mode == 2;
+        a.shrink_hard = l.shrink.mode == 2;
     }
     bool vec4 = (a.n1 % 4 == 0);
     const int nin = inverse ? 4 : 1, nout = inverse ? 1 : 4;
@@ -604,7 +609,7 @@ struct Syn4 {
     long long t_pad = 0;               // zero frames on either side of the t-bands (zero-extended t; these bands lie back to back, without the 256 B)
 };
 template <typename T>
-static int synthesis_4d(ndwt_plan* p, int Lp, const T* const* in, T* out, long long stride, const Syn4& f, hipStream_t s) {
+static int synthesis_4d(ndwt_plan* p, int Lp, const T* const* in, T* out, long long stride, const Syn4& f, const ShrinkOnLoad& shrink, hipStream_t s) {
     const long long plane = p->comp * p->dims[0] * p->dims[1], vol3_out = plane * f.nz_out, pad = f.t_pad * vol3_out;
     const long long band = (f.frames + 2 * f.t_pad) * vol3_out, skew = f.t_pad ? 0 : 256 / (long long)sizeof(T);
     int rc = p->tmp.grow((size_t)(2 * band + skew) * sizeof(T), "for temporaries");
@@ -618,7 +623,7 @@ static int synthesis_4d(ndwt_plan* p, int Lp, const T* const* in, T* out, long l
         T* outs[8] = {bands[h] + pad};
         Fused3Launch<T> l = {true, Lp, in + 8 * h, outs, f.nz_out};
         l.nbatch = f.frames; l.in_bstride = plane * f.nz_in; l.out_bstride = vol3_out; l.z = f.z; l.zhi = f.nz_in;
-        l.shrink_mask = h ? kShrinkTHighAll : kShrinkTLowDetails;
+        l.shrink_mask = h ? kShrinkTHighAll : kShrinkTLowDetails; l.shrink = shrink;
         rc = fused3_run<T>(p, l, s);
         if (rc) return rc;
     }
@@ -685,7 +690,7 @@ static int analysis_level(ndwt_plan* p, const T* in, T* const* out, long long st
 }
 
 template <typename T>
-static int synthesis_level(ndwt_plan* p, const T* const* in, T* out, long long stride, bool slab, hipStream_t s) {
+static int synthesis_level(ndwt_plan* p, const T* const* in, T* out, long long stride, bool slab, const ShrinkOnLoad& shrink, hipStream_t s) {
     const long long n_sh = slab_planes(p, stride, slab), vol_out = p->item_vol(), vol_in = vol_out / p->dims[p->shard] * n_sh;
     const bool on_z = p->shard == 2;
     T* outs[8] = {out};
@@ -698,13 +703,13 @@ static int synthesis_level(ndwt_plan* p, const T* const* in, T* out, long long s
         }
         case kRouteFused3: {
             Fused3Launch<T> l = {true, r.Lp, in, outs, p->dims[2]};
-            l.nbatch = p->items(); l.in_bstride = vol_in; l.out_bstride = vol_out; l.z = slab ? kZHalo : kZPeriodic; l.shrink_mask = kShrinkTLowDetails;
+            l.nbatch = p->items(); l.in_bstride = vol_in; l.out_bstride = vol_out; l.z = slab ? kZHalo : kZPeriodic; l.shrink_mask = kShrinkTLowDetails; l.shrink = shrink;
             return fused3_run<T>(p, l, s);
         }
         case kRouteFused3T: {                              // (a slab on t: the 3-D part runs on the halo frames too)
             Syn4 f = {on_z ? p->dims[3] : n_sh, on_z ? n_sh : p->dims[2], p->dims[2], p->dims[3]};
             f.z = slab && on_z ? kZHalo : kZPeriodic; f.t_wrap = !slab || on_z;
-            return synthesis_4d<T>(p, r.Lp, in, out, stride, f, s);
+            return synthesis_4d<T>(p, r.Lp, in, out, stride, f, shrink, s);
         }
         case kRouteFused2Dilated: {
             Fused2Launch<T> l = {true, r.Lp, in, outs, p->dims[1]};
@@ -713,7 +718,7 @@ static int synthesis_level(ndwt_plan* p, const T* const* in, T* out, long long s
         }
         case kRouteFused2: {
             Fused2Launch<T> l = {true, r.Lp, in, outs, p->dims[1]};
-            l.nbatch = p->items(); l.in_bstride = vol_in; l.out_bstride = vol_out; l.y_wrap = !slab;
+            l.nbatch = p->items(); l.in_bstride = vol_in; l.out_bstride = vol_out; l.y_wrap = !slab; l.shrink = shrink;
             return fused2_run<T>(p, l, s);
         }
         default: return per_axis_level<T>(p, true, in, outs, stride, slab, s);   // kRoutePerAxis
@@ -770,28 +775,39 @@ template <typename T> static int cascade2_run(ndwt_plan* p, int Lp, int nlev, co
     return cascade2_launch(p, a, false, cascade2_tile_width(k), nlev * (Lp - 1), 8, s, [&](const void* td) { return launch_cascade2(k, a, td, s); });
 }
 
-// ---- two to four levels of the signals of a batched 1-D plan in one launch (Fwd1C / Inv1C, ndwt_device_1d.h; when: cascade1_levels).
-// in / out as Fused1CArgs documents them.  Returns 0, or -1: not this data (a pointer off the 16- / 32-byte groups), no instance, or a
-// launch the kernel's tiling cannot express -- the caller takes one launch per level
-template <typename T> static int cascade1_run(ndwt_plan* p, bool inverse, int L, int nlev, const T* const* in, T* const* out, hipStream_t s) {
-    Fused1CArgs<T> a;
-    memset(&a, 0, sizeof a);
+// ---- what the launches of the two 1-D cascades share (Fwd1C / Inv1C and FwdMC / InvMC; the caller has laid out the geometry in `a`): the
+// band pointers into a.in / a.out -- analysis in[0] and out[0 .. nlev], synthesis in[0 .. nlev] and out[0], as Fused1CArgs and MarchCArgs
+// document them -- and their alignment, the device tap table `td` where the family reads one (needs_taps),
+// profiling, the launch and its error mapping.  Returns 0, or -1: not this data (a pointer off the 16- / 32-byte groups) or no instance
+// -- the caller takes one launch per level
+template <typename T, class Args, class Launch>
+static int cascade1d_launch(const ndwt_plan* p, Args& a, bool inverse, int nlev, const T* const* in, T* const* out, const char* what,
+                            bool needs_taps, const void* td, hipStream_t s, Launch&& launch) {
     bool aligned = true;
     for (int b = 0; b < (inverse ? 1 + nlev : 1); ++b) { a.in[b] = in[b]; aligned = aligned && aligned_vec4<T>(in[b]); }
     for (int b = 0; b < (inverse ? 1 : 1 + nlev); ++b) { a.out[b] = out[b]; aligned = aligned && aligned_vec4<T>(out[b]); }
     if (!aligned) return -1;
+    if (needs_taps && !td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
+    prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
+    const int rc = launch();
+    prof_end(p, s, rc);
+    if (rc > 0) return fail(NDWT_ERR_HIP, "cascaded %s %s launch failed: %s", what, inverse ? "synthesis" : "analysis", hipGetErrorString((hipError_t)rc));
+    return rc < 0 ? -1 : 0;
+}
+
+// ---- two to four levels of the signals of a batched 1-D plan in one launch (Fwd1C / Inv1C, ndwt_device_1d.h; when: cascade1_levels).
+// in / out as Fused1CArgs documents them.  Returns 0, or -1 as cascade1d_launch does (no instance: also a launch the kernel's tiling
+// cannot express)
+template <typename T> static int cascade1_run(ndwt_plan* p, bool inverse, int L, int nlev, const T* const* in, T* const* out, hipStream_t s) {
+    Fused1CArgs<T> a;
+    memset(&a, 0, sizeof a);
     const Cascade1Instance k = {inverse, sizeof(T) == 8, (int)p->comp, L, nlev};
     const int WX = cascade1_tile_width(k);
     a.row = p->dims[0] * p->comp;
     a.outer = p->howmany;
     a.nseg = (a.row + WX - 1) / WX;
-    const void* td = p->taps_dev[inverse ? 1 : 0].ptr;
-    if (!td) return fail(NDWT_ERR_UNSUPPORTED, "plan has no device tap table");
-    prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
-    const int rc = launch_cascade1(k, a, td, s);
-    prof_end(p, s, rc);
-    if (rc > 0) return fail(NDWT_ERR_HIP, "cascaded 1-D %s launch failed: %s", inverse ? "synthesis" : "analysis", hipGetErrorString((hipError_t)rc));
-    return rc < 0 ? -1 : 0;
+    const void* const td = p->taps_dev[inverse ? 1 : 0].ptr;
+    return cascade1d_launch(p, a, inverse, nlev, in, out, "1-D", true, td, s, [&] { return launch_cascade1(k, a, td, s); });
 }
 
 // ---- dec, per-band thresholding and rec of the signals of a batched 1-D plan in one launch (Den1C, ndwt_device_1d.h; when:
@@ -828,16 +844,13 @@ template <typename T> static int denoise1_run(ndwt_plan* p, int L, int nlev, con
 // ---- two to four levels of the one strided axis of a plan over interleaved samples in one march (FwdMC / InvMC, ndwt_device_axis.h;
 // when: cascadem_levels).  in / out as MarchCArgs documents them.  The chunking is axis_pass's own rule (about 4096 workgroups, in chunks
 // of the axis), the floor raised to 4 nlev (L - 1) planes -- the march-in is at most a quarter of a thread's planes -- and capped at the
-// axis; force_zchunk / zchunk_dir = planes per chunk.  Returns 0, or -1: not this data (a pointer off the 16- / 32-byte groups), no
-// instance, or a grid beyond 2^31 - 1 workgroups -- the caller takes one launch per level
+// axis; force_zchunk / zchunk_dir = planes per chunk.  Returns 0, or -1 as cascade1d_launch does, or for a grid beyond 2^31 - 1
+// workgroups
 template <typename T> static int cascadem_run(ndwt_plan* p, bool inverse, int L, int nlev, const T* const* in, T* const* out, hipStream_t s) {
     MarchCArgs<T> a;
     memset(&a, 0, sizeof a);
-    bool aligned = true;
-    for (int b = 0; b < (inverse ? 1 + nlev : 1); ++b) { a.in[b] = in[b]; aligned = aligned && aligned_vec4<T>(in[b]); }
-    for (int b = 0; b < (inverse ? 1 : 1 + nlev); ++b) { a.out[b] = out[b]; aligned = aligned && aligned_vec4<T>(out[b]); }
     a.inner = p->comp * p->inner;
-    if (!aligned || a.inner % 4 != 0) return -1;
+    if (a.inner % 4 != 0) return -1;
     a.n = p->dims[0];
     a.outer = p->items();
     a.ngroups = a.inner / 4;
@@ -855,11 +868,8 @@ template <typename T> static int cascadem_run(ndwt_plan* p, bool inverse, int L,
     if (iblocks * a.nchunks > 0x7fffffffLL) return -1;
     const AxisFilter& f = p->filt[0];
     const CascadeMInstance k = {inverse, sizeof(T) == 8, L, nlev};
-    prof_begin(p, inverse ? NDWT_KERNEL_FUSED_SYNTHESIS : NDWT_KERNEL_FUSED_ANALYSIS, s);
-    const int rc = launch_cascadem(k, a, inverse ? f.syn_lo : f.ana_lo, inverse ? f.syn_hi : f.ana_hi, s);
-    prof_end(p, s, rc);
-    if (rc > 0) return fail(NDWT_ERR_HIP, "cascaded march %s launch failed: %s", inverse ? "synthesis" : "analysis", hipGetErrorString((hipError_t)rc));
-    return rc < 0 ? -1 : 0;
+    return cascade1d_launch(p, a, inverse, nlev, in, out, "march", false, nullptr, s,
+                            [&] { return launch_cascadem(k, a, inverse ? f.syn_lo : f.ana_lo, inverse ? f.syn_hi : f.ana_hi, s); });
 }
 
 // detail band b (1 .. 2^d - 1) of level `lev` in the coefficients y of a `level`-level transform (the bookkeeping above)
@@ -867,68 +877,52 @@ template <typename T> static T* detail_band(const ndwt_plan* p, T* y, long long 
     return y + (long long)(1 + ((1 << p->ndim) - 1) * (level - lev) + (b - 1)) * bs;
 }
 
+// the detail bands of `n` levels behind slot 0 of `bands`, the 2^d - 1 of a level together: level `first`, then first + step, .. -- the
+// order the launch's Args document: coarsest level first (Fused2CArgs, Fused2CIArgs, the synthesis of Fused1CArgs and MarchCArgs)
+// everywhere but in the analysis of the two 1-D cascades
+template <typename B> static void level_bands(const ndwt_plan* p, B* y, long long bs, int level, int first, int step, int n, B** bands) {
+    const int nd = (1 << p->ndim) - 1;
+    for (int c = 0; c < n; ++c)
+        for (int b = 1; b <= nd; ++b) bands[1 + nd * c + (b - 1)] = detail_band(p, y, bs, level, first + step * c, b);
+}
+
+// The walk over the levels, finest first: cascade_route names the next launch -- levels lev .. last in one, or level lev alone by
+// level_route.  "None" is final within a call: a cascade that does not take `left` levels takes no fewer either (tests/
+// test_dispatch_select.py checks that of cascade_route), so the walk stops asking, as it does after a cascade that declined its data.
+// The approximations between launches alternate between the plan's two scratch volumes (a launch never writes the one it reads); the
+// last launch writes band 0 of y.
 template <typename T> static int dec_impl(ndwt_plan* p, const T* x, T* y, long long bs, int level, hipStream_t s) {
-    const int nb = 1 << p->ndim;
+    const SelPlan sp = sel(p);
     const T* cur = x;
-    int lev = 1, pp = 0;                                  // pp: the scratch volume the next launch writes (they alternate launch by launch: a
-    {                                                     // launch never writes the approximation it reads)
-        const SelPlan sp = sel(p);
-        int L1 = 0;
-        while (const int n = cascade1_levels(sp, p->howmany, false, level - lev + 1, &L1)) {   // a batched 1-D plan: levels lev .. lev + n - 1
-            const int last = lev + n - 1;
-            const T* in[5] = {cur};
-            T* out[5];
-            out[0] = (last == level) ? y : (T*)p->approx(pp);
-            for (int l = 0; l < n; ++l) out[1 + l] = detail_band(p, y, bs, level, lev + l, 1);
-            const int rc = cascade1_run<T>(p, false, L1, n, in, out, s);
-            if (rc == -1) break;                          // not this data: one launch per level from here on
-            if (rc) return rc;
-            cur = out[0];
-            pp ^= 1;
-            lev = last + 1;
-        }
-        int Lm = 0;
-        while (const int n = cascadem_levels(sp, false, level - lev + 1, &Lm)) {   // interleaved samples, one axis: levels lev .. lev + n - 1
-            const int last = lev + n - 1;
-            const T* in[5] = {cur};
-            T* out[5];
-            out[0] = (last == level) ? y : (T*)p->approx(pp);
-            for (int l = 0; l < n; ++l) out[1 + l] = detail_band(p, y, bs, level, lev + l, 1);
-            const int rc = cascadem_run<T>(p, false, Lm, n, in, out, s);
-            if (rc == -1) break;                          // not this data: one launch per level from here on
-            if (rc) return rc;
-            cur = out[0];
-            pp ^= 1;
-            lev = last + 1;
-        }
-        int Lp = 0;
-        while (const int n = cascade2_levels(sp, false, level - lev + 1, &Lp)) {   // levels lev .. lev + n - 1 in one launch
-            const int last = lev + n - 1;
-            T* out[10];
-            out[0] = (last == level) ? y : (T*)p->approx(pp);
-            for (int l = 0; l < n; ++l)                   // cascade level l (0 = first) is transform level lev + l
-                for (int b = 1; b < nb; ++b) out[1 + 3 * (n - 1 - l) + (b - 1)] = detail_band(p, y, bs, level, lev + l, b);
-            const int rc = cascade2_run<T>(p, Lp, n, cur, out, s);
-            if (rc == -1) break;                          // not this data (alignment): one launch per level from here on
-            if (rc) return rc;
-            cur = out[0];
-            pp ^= 1;
-            lev = last + 1;
-        }
-    }
-    for (; lev <= level; ++lev, pp ^= 1) {
+    int lev = 1, pp = 0;                                  // pp: the scratch volume the next launch writes
+    bool cascades = true;                                 // until none claims the levels left, or one declines
+    while (lev <= level) {
+        const CascadeRoute r = cascades ? cascade_route(sp, false, level - lev + 1) : CascadeRoute{kCascadeNone, 0, 0};
+        if (r.kind == kCascadeNone) cascades = false;
+        const int n = r.kind == kCascadeNone ? 1 : r.nlev, last = lev + n - 1;
+        const T* in[1] = {cur};
         T* out[16];
-        out[0] = (lev == level) ? y : (T*)p->approx(pp);
-        for (int b = 1; b < nb; ++b) out[b] = detail_band(p, y, bs, level, lev, b);
-        int rc = analysis_level<T>(p, cur, out, level_stride(p, lev), false, s);
+        out[0] = (last == level) ? y : (T*)p->approx(pp);
+        if (r.kind == kCascadeImage2) level_bands(p, y, bs, level, last, -1, n, out);
+        else level_bands(p, y, bs, level, lev, +1, n, out);
+        int rc;
+        switch (r.kind) {
+            case kCascadeRows1: rc = cascade1_run<T>(p, false, r.L, n, in, out, s); break;
+            case kCascadeMarch: rc = cascadem_run<T>(p, false, r.L, n, in, out, s); break;
+            case kCascadeImage2: rc = cascade2_run<T>(p, r.L, n, cur, out, s); break;
+            default: rc = analysis_level<T>(p, cur, out, level_stride(p, lev), false, s);
+        }
+        if (rc == -1 && r.kind != kCascadeNone) { cascades = false; continue; }   // not this data: one launch per level from here on
         if (rc) return rc;
         cur = out[0];
+        pp ^= 1;
+        lev = last + 1;
     }
     return NDWT_OK;
 }
 
 // the synthesis side of the cascade (Inv2C): in[0] = approximation of the coarsest level, then the detail bands coarsest level first
-template <typename T> static int cascade2_rec_run(ndwt_plan* p, int Lp, int nlev, const T* const* in, T* out, hipStream_t s) {
+template <typename T> static int cascade2_rec_run(ndwt_plan* p, int Lp, int nlev, const T* const* in, T* out, const ShrinkOnLoad& shrink, hipStream_t s) {
     Fused2CIArgs<T> a;
     memset(&a, 0, sizeof a);
     a.out = out;
@@ -939,73 +933,42 @@ template <typename T> static int cascade2_rec_run(ndwt_plan* p, int Lp, int nlev
     if (!aligned) return -1;
     T* outs[1] = {out};
     a.nt = nt_store_ok<T>(a.rs, a.rs, 0, outs, 1);
-    if (p->shrink_mode) {                                 // ndwt_denoise: threshold the detail bands as their rows are loaded
+    if (shrink.mode) {                                    // ndwt_denoise: threshold the detail bands as their rows are loaded
         a.shrink_on = 1;
-        a.shrink_thr = (T)p->shrink_thr;
-        a.shrink_hard = p->shrink_mode == 2;
+        a.shrink_thr = (T)shrink.thr;
+        a.shrink_hard = shrink.mode == 2;
     }
     const Cascade2Instance k = {true, sizeof(T) == 8, (int)p->comp, Lp, nlev, cascade2_rec_depth(sel(p), Lp, nlev)};
     return cascade2_launch(p, a, true, cascade2_tile_width(k), nlev * (Lp - 1), 4, s, [&](const void* td) { return launch_cascade2(k, a, td, s); });
 }
 
-template <typename T> static int rec_impl(ndwt_plan* p, const T* y, long long bs, T* x, int level, hipStream_t s) {
-    const int nb = 1 << p->ndim;
-    const T* prev = y;   // band 0
+// The walk back, coarsest level first: levels lev .. low in one launch, or level lev alone; the last launch writes x.  shrink: see
+// ShrinkOnLoad.
+template <typename T> static int rec_impl(ndwt_plan* p, const T* y, long long bs, T* x, int level, const ShrinkOnLoad& shrink, hipStream_t s) {
+    const SelPlan sp = sel(p);
+    const T* prev = y;                                    // band 0
     int lev = level, pp = 0;                              // coarsest level still to be synthesised; pp: the scratch volume the next launch writes
-    {
-        const SelPlan sp = sel(p);
-        int L1 = 0;
-        while (const int n = cascade1_levels(sp, p->howmany, true, lev, &L1)) {   // a batched 1-D plan: levels lev, lev - 1, .. lev - n + 1
-            const T* in[5];
-            in[0] = prev;
-            for (int c = 0; c < n; ++c) in[1 + c] = detail_band(p, y, bs, level, lev - c, 1);
-            const int low = lev - n + 1;
-            T* dst[5] = {(low == 1) ? x : (T*)p->approx(pp)};
-            const int rc = cascade1_run<T>(p, true, L1, n, in, dst, s);
-            if (rc == -1) break;
-            if (rc) return rc;
-            prev = dst[0];
-            pp ^= 1;
-            lev = low - 1;
-        }
-        int Lm = 0;
-        while (const int n = cascadem_levels(sp, true, lev, &Lm)) {   // interleaved samples, one axis: levels lev, lev - 1, .. lev - n + 1
-            const T* in[5];
-            in[0] = prev;
-            for (int c = 0; c < n; ++c) in[1 + c] = detail_band(p, y, bs, level, lev - c, 1);
-            const int low = lev - n + 1;
-            T* dst[5] = {(low == 1) ? x : (T*)p->approx(pp)};
-            const int rc = cascadem_run<T>(p, true, Lm, n, in, dst, s);
-            if (rc == -1) break;
-            if (rc) return rc;
-            prev = dst[0];
-            pp ^= 1;
-            lev = low - 1;
-        }
-        int Lp = 0;
-        while (const int n = cascade2_levels(sp, true, lev, &Lp)) {   // levels lev, lev - 1, .. lev - n + 1 in one launch
-            const T* in[10];
-            in[0] = prev;
-            for (int c = 0; c < n; ++c)                   // cascade level c (0 = coarsest) is transform level lev - c
-                for (int b = 1; b < nb; ++b) in[1 + 3 * c + (b - 1)] = detail_band(p, y, bs, level, lev - c, b);
-            const int low = lev - n + 1;
-            T* dst = (low == 1) ? x : (T*)p->approx(pp);
-            const int rc = cascade2_rec_run<T>(p, Lp, n, in, dst, s);
-            if (rc == -1) break;
-            if (rc) return rc;
-            prev = dst;
-            pp ^= 1;
-            lev = low - 1;
-        }
-    }
-    for (; lev >= 1; --lev, pp ^= 1) {
+    bool cascades = true;                                 // until none claims the levels left, or one declines
+    while (lev >= 1) {
+        const CascadeRoute r = cascades ? cascade_route(sp, true, lev) : CascadeRoute{kCascadeNone, 0, 0};
+        if (r.kind == kCascadeNone) cascades = false;
+        const int n = r.kind == kCascadeNone ? 1 : r.nlev, low = lev - n + 1;
         const T* in[16];
         in[0] = prev;
-        for (int b = 1; b < nb; ++b) in[b] = detail_band(p, y, bs, level, lev, b);
-        T* dst = (lev == 1) ? x : (T*)p->approx(pp);
-        int rc = synthesis_level<T>(p, in, dst, level_stride(p, lev), false, s);
+        level_bands(p, y, bs, level, lev, -1, n, in);
+        T* dst[1] = {(low == 1) ? x : (T*)p->approx(pp)};
+        int rc;
+        switch (r.kind) {
+            case kCascadeRows1: rc = cascade1_run<T>(p, true, r.L, n, in, dst, s); break;
+            case kCascadeMarch: rc = cascadem_run<T>(p, true, r.L, n, in, dst, s); break;
+            case kCascadeImage2: rc = cascade2_rec_run<T>(p, r.L, n, in, dst[0], shrink, s); break;
+            default: rc = synthesis_level<T>(p, in, dst[0], level_stride(p, lev), false, shrink, s);
+        }
+        if (rc == -1 && r.kind != kCascadeNone) { cascades = false; continue; }   // not this data: one launch per level from here on
         if (rc) return rc;
-        prev = dst;
+        prev = dst[0];
+        pp ^= 1;
+        lev = low - 1;
     }
     return NDWT_OK;
 }
@@ -1106,7 +1069,7 @@ template <typename T> static int slab_ext4_impl(ndwt_plan* p, int Lp, const void
     const long long n = p->dims[3], h = p->filt[3].len - 1;
     Syn4 f = {n, p->dims[2], p->dims[2], n + h};
     f.t_wrap = false; f.t_pad = h;
-    return synthesis_4d<T>(p, Lp, (const T* const*)in, (T*)out, 1, f, s);
+    return synthesis_4d<T>(p, Lp, (const T* const*)in, (T*)out, 1, f, kNoShrink, s);
 }
 
 // a run of output planes of the slab transform (the caller offsets the pointers): what lets the halo exchange
@@ -1278,7 +1241,7 @@ static int slab_split_z_impl(ndwt_plan* p, const void* in, const void* hb, const
 template <typename T> static int slab_ext_z_impl(ndwt_plan* p, int Lp, const void* const* in, void* out, hipStream_t s) {
     Syn4 f = {p->dims[3], p->dims[2], p->dims[2] + Lp - 1, p->dims[3]};
     f.z = kZZeroExt;
-    return synthesis_4d<T>(p, Lp, (const T* const*)in, (T*)out, 1, f, s);
+    return synthesis_4d<T>(p, Lp, (const T* const*)in, (T*)out, 1, f, kNoShrink, s);
 }
 
 extern "C" {
@@ -1544,7 +1507,7 @@ int ndwt_plan_describe(const ndwt_plan* p, char* buf, int buflen) {
     else if (f3a) s = p->ndim == 3 ? "fused3d analysis, axis synthesis" : "axis+fused3d analysis, axis synthesis";
     else if (ra == kRouteFused2) s = "fused2d";
     int L1 = 0;
-    if (p->howmany > 0) s = cascade1_levels(sel(p), p->howmany, false, 2, &L1) ? "batched1d cascade" : "batched1d axis";
+    if (p->howmany > 0) s = cascade1_levels(sel(p), false, 2, &L1) ? "batched1d cascade" : "batched1d axis";
     if (p->howmany > 0 && p->ndim >= 2) {                 // a stack (ndwt_plan_create_axes): what two levels of it run today
         int Lp = 0;
         s = cascade2_levels(sel(p), false, 2, &Lp) ? "stack2d cascade" : ra == kRouteFused2 ? "stack2d fused" : f3a ? "stack3d fused" : "stack axis";
@@ -1581,7 +1544,7 @@ int ndwt_rec_pitched(ndwt_plan* p, const void* y, int64_t band_pitch, void* x, i
     long long bs = 0;
     rc = pitch_scalars(p, band_pitch, &bs);
     if (rc) return rc;
-    return on_device(p, [&](auto t) { return rec_impl(p, (const decltype(t)*)y, bs, (decltype(t)*)x, level, (hipStream_t)stream); });
+    return on_device(p, [&](auto t) { return rec_impl(p, (const decltype(t)*)y, bs, (decltype(t)*)x, level, kNoShrink, (hipStream_t)stream); });
 }
 
 int ndwt_dec(ndwt_plan* p, const void* x, void* y, int level, void* stream) { return ndwt_dec_pitched(p, x, y, 0, level, stream); }
@@ -1910,8 +1873,8 @@ static int den3_taps(ndwt_plan* p, int Lp) {
     return p->taps_den.upload(h.data(), h.size() * sizeof(float), "the tap table of the fused level-1 kernel");
 }
 
-// kind 0: approximation band of one analysis level (x -> out);  kind 1: Den3 (x, approximation -> out)
-static int den3_launch(ndwt_plan* p, int kind, int Lp, const float* x, const float* apx, float* out, hipStream_t s) {
+// kind 0: approximation band of one analysis level (x -> out);  kind 1: Den3 (x, approximation -> out), thresholding as `shrink` says
+static int den3_launch(ndwt_plan* p, int kind, int Lp, const float* x, const float* apx, float* out, const ShrinkOnLoad& shrink, hipStream_t s) {
     Fused3Args<float> a;
     memset(&a, 0, sizeof a);
     a.n1 = (int)p->dims[0]; a.n2 = (int)p->dims[1]; a.n3 = (int)p->dims[2];
@@ -1921,9 +1884,9 @@ static int den3_launch(ndwt_plan* p, int kind, int Lp, const float* x, const flo
     a.out[0] = out;
     a.in_bstride = a.out_bstride = p->vol;
     if (kind == 1) {
-        a.shrink_thr = (float)p->shrink_thr;
+        a.shrink_thr = (float)shrink.thr;
         a.shrink_mask = 0xFE;
-        a.shrink_hard = p->shrink_mode == 2;
+        a.shrink_hard = shrink.mode == 2;
     }
     // one workgroup per CU (1024 threads); Den3's march starts 2 (L - 1) planes before its first output plane
     const bool small_tile = kind == 0 && p->variant_fwd != kFwdTall && a.n2 > 16;   // the band-0 analysis on 64 x 16 tiles, 3 workgroups per CU (0.36 vs 0.42 ms; kFwdTall: A/B)
@@ -1941,28 +1904,33 @@ static int den3_launch(ndwt_plan* p, int kind, int Lp, const float* x, const flo
     return NDWT_OK;
 }
 
-static int ensure_coef(ndwt_plan* p, size_t need) { return p->coef.grow(need, "for the coefficient scratch"); }
+// The plan's coefficient scratch, grown for `level` levels, and the transform of x in it.  The bands are pitched (ndwt_band_pitch): nobody
+// else reads them.  *bs: the distance between them in scalars
+extern "C++" template <typename T> static int dec_scratch(ndwt_plan* p, const T* x, int level, hipStream_t s, T** coef, long long* bs) {
+    *bs = (long long)ndwt_band_pitch(p) * p->comp;
+    const int rc = p->coef.grow((size_t)*bs * p->esize * (size_t)ndwt_num_bands(p->ndim, level), "for the coefficient scratch");
+    if (rc) return rc;
+    *coef = (T*)p->coef.ptr;
+    return dec_impl<T>(p, x, *coef, *bs, level, s);
+}
 
 // dec -> shrink -> rec with level 1 fused: x -> approximation of level 1 (band 0 only) -> levels 2 .. `level` as a (level - 1)-level
 // transform of that band (the reference applies the same filters at every level, nd_dwt_3D.m:178-186) with the thresholding in the
 // synthesis kernels' loads -> Den3(x, reconstructed approximation).  Volumes moved at level 1: 5 instead of 18.
-static int denoise_fused_level1(ndwt_plan* p, int Lp, const float* x, float* out, int level, double threshold, int mode, hipStream_t s) {
+static int denoise_fused_level1(ndwt_plan* p, int Lp, const float* x, float* out, int level, const ShrinkOnLoad& shrink, hipStream_t s) {
     int rc = den3_taps(p, Lp);
     if (rc) return rc;
     rc = p->den_a1.grow((size_t)p->vol * sizeof(float) + kApproxSkew, "of the level-1 approximation scratch", false);
     if (rc) return rc;
     float* a1 = (float*)((char*)p->den_a1.ptr + kApproxSkew);   // level-1 approximation, then its reconstruction (256 B off the alignment, like the ping-pong scratch)
-    p->shrink_mode = mode == NDWT_SHRINK_HARD ? 2 : 1;
-    p->shrink_thr = threshold;
-    rc = den3_launch(p, 0, Lp, x, nullptr, a1, s);
+    rc = den3_launch(p, 0, Lp, x, nullptr, a1, kNoShrink, s);
     if (rc == NDWT_OK && level > 1) {
-        const int64_t pitch = ndwt_band_pitch(p);
-        rc = ensure_coef(p, (size_t)pitch * p->esize * (size_t)ndwt_num_bands(3, level - 1));
-        if (rc == NDWT_OK) rc = dec_impl<float>(p, a1, (float*)p->coef.ptr, pitch, level - 1, s);
-        if (rc == NDWT_OK) rc = rec_impl<float>(p, (const float*)p->coef.ptr, pitch, a1, level - 1, s);   // (thresholding in the band loads)
+        float* coef = nullptr;                            // (a float 3-D plan: pitch * esize * ndwt_num_bands(3, level - 1) bytes)
+        long long bs = 0;
+        rc = dec_scratch<float>(p, a1, level - 1, s, &coef, &bs);
+        if (rc == NDWT_OK) rc = rec_impl<float>(p, coef, bs, a1, level - 1, shrink, s);   // (thresholding in the band loads)
     }
-    if (rc == NDWT_OK) rc = den3_launch(p, 1, Lp, x, a1, out, s);
-    p->shrink_mode = 0;
+    if (rc == NDWT_OK) rc = den3_launch(p, 1, Lp, x, a1, out, shrink, s);
     return rc;
 }
 
@@ -1970,6 +1938,8 @@ int ndwt_denoise(ndwt_plan* p, const void* x, void* out, int level, double thres
     int rc = shrink_check(p, level, threshold, mode);
     if (rc) return rc;
     if (!x || !out) return fail(NDWT_ERR_INVALID_ARG, "null data pointer");
+    const ShrinkOnLoad shrink = shrink_on_load(threshold, mode);
+    hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipSetDevice(p->device));
     {
         // the finest level without its detail bands in memory, where the fused level-1 kernel applies (it reads x around every
@@ -1979,27 +1949,21 @@ int ndwt_denoise(ndwt_plan* p, const void* x, void* out, int level, double thres
         const size_t nbytes = (size_t)p->vol * p->esize;
         const bool disjoint = xb + nbytes <= ob || ob + nbytes <= xb;
         if (den3_eligible(p, p->fused_level1, &Lp1) && disjoint && aligned_vec4<float>(x) && aligned_vec4<float>(out))
-            return denoise_fused_level1(p, Lp1, (const float*)x, (float*)out, level, threshold, mode, (hipStream_t)stream);
+            return denoise_fused_level1(p, Lp1, (const float*)x, (float*)out, level, shrink, s);
     }
-    // the scratch coefficients are pitched (ndwt_band_pitch): nobody else reads them
-    const int64_t pitch = ndwt_band_pitch(p);
-    rc = ensure_coef(p, (size_t)pitch * p->comp * p->esize * (size_t)ndwt_num_bands(p->ndim, level));
-    if (rc) return rc;
-    void* const coef = p->coef.ptr;
-    rc = ndwt_dec_pitched(p, x, coef, pitch, level, stream);
-    if (rc) return rc;
-    if (fused_shrink_capable(sel(p))) {
+    return with_scalar(p, [&](auto t) {
+        typedef decltype(t) T;
+        T* coef = nullptr;
+        long long bs = 0;
+        int rc = dec_scratch<T>(p, (const T*)x, level, s, &coef, &bs);
+        if (rc) return rc;
         // every level is reconstructed by a lane-shift kernel: the detail bands are thresholded in registers as that
         // kernel loads them, and the separate pass (a read and a write of every detail band) disappears
-        p->shrink_mode = mode == NDWT_SHRINK_HARD ? 2 : 1;
-        p->shrink_thr = threshold;
-        rc = ndwt_rec_pitched(p, coef, pitch, out, level, stream);
-        p->shrink_mode = 0;
+        if (fused_shrink_capable(sel(p))) return rec_impl<T>(p, coef, bs, (T*)out, level, shrink, s);
+        rc = shrink_impl<T>(p, coef, bs, level, threshold, mode, s);
+        if (rc == NDWT_OK) rc = rec_impl<T>(p, coef, bs, (T*)out, level, kNoShrink, s);
         return rc;
-    }
-    rc = ndwt_shrink_pitched(p, coef, pitch, level, threshold, mode, stream);
-    if (rc == NDWT_OK) rc = ndwt_rec_pitched(p, coef, pitch, out, level, stream);
-    return rc;
+    });
 }
 
 int ndwt_denoise_bands(ndwt_plan* p, const void* x, void* out, int level, const double* thresholds, int mode, void* stream) {
@@ -2010,7 +1974,7 @@ int ndwt_denoise_bands(ndwt_plan* p, const void* x, void* out, int level, const 
     {
         // a batched 1-D plan: the whole depth in one launch, where that exists and is wanted (denoise1_levels / denoise1_wanted)
         const SelPlan sp = sel(p);
-        const int n = denoise1_wanted(sp) ? denoise1_levels(sp, p->howmany, level) : 0;
+        const int n = denoise1_wanted(sp) ? denoise1_levels(sp, level) : 0;
         if (n) {
             rc = with_scalar(p, [&](auto t) {
                 return denoise1_run<decltype(t)>(p, p->filt[0].len, n, (const decltype(t)*)x, (decltype(t)*)out, thresholds, mode, (hipStream_t)stream);
@@ -2019,14 +1983,15 @@ int ndwt_denoise_bands(ndwt_plan* p, const void* x, void* out, int level, const 
         }
     }
     // the general route: dec into the plan's pitched scratch, one shrink pass per band, rec (no thresholding in the synthesis loads)
-    const int64_t pitch = ndwt_band_pitch(p);
-    rc = ensure_coef(p, (size_t)pitch * p->comp * p->esize * (size_t)ndwt_num_bands(p->ndim, level));
-    if (rc) return rc;
-    void* const coef = p->coef.ptr;
-    rc = ndwt_dec_pitched(p, x, coef, pitch, level, stream);
-    if (rc == NDWT_OK) rc = ndwt_shrink_bands(p, coef, pitch, level, thresholds, mode, stream);
-    if (rc == NDWT_OK) rc = ndwt_rec_pitched(p, coef, pitch, out, level, stream);
-    return rc;
+    return with_scalar(p, [&](auto t) {
+        typedef decltype(t) T;
+        T* coef = nullptr;
+        long long bs = 0;
+        int rc = dec_scratch<T>(p, (const T*)x, level, (hipStream_t)stream, &coef, &bs);
+        if (rc == NDWT_OK) rc = shrink_bands_impl<T>(p, coef, bs, level, thresholds, mode, (hipStream_t)stream);
+        if (rc == NDWT_OK) rc = rec_impl<T>(p, coef, bs, (T*)out, level, kNoShrink, (hipStream_t)stream);
+        return rc;
+    });
 }
 
 // ---- order statistics of a band's |c|, and the noise estimate on top of them (include/ndwt.h; the kernels: ndwt_device_select.h) ----
@@ -2126,13 +2091,13 @@ int ndwt_estimate_sigma(ndwt_plan* p, const void* x, double* sigma, void* stream
     if (rc) return rc;
     if (!x) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (x_dev)");
     if (!sigma) return fail(NDWT_ERR_INVALID_ARG, "null output pointer (sigma)");
-    HIP_TRY(hipSetDevice(p->device));
-    const int64_t pitch = ndwt_band_pitch(p);
-    rc = ensure_coef(p, (size_t)pitch * p->comp * p->esize * (size_t)ndwt_num_bands(p->ndim, 1));
+    rc = on_device(p, [&](auto t) {
+        decltype(t)* coef = nullptr;
+        long long bs = 0;
+        return dec_scratch(p, (const decltype(t)*)x, 1, (hipStream_t)stream, &coef, &bs);
+    });
     if (rc) return rc;
-    rc = ndwt_dec_pitched(p, x, p->coef.ptr, pitch, 1, stream);
-    if (rc) return rc;
-    return ndwt_estimate_sigma_coef(p, p->coef.ptr, pitch, 1, sigma, stream);
+    return ndwt_estimate_sigma_coef(p, p->coef.ptr, ndwt_band_pitch(p), 1, sigma, stream);
 }
 
 int ndwt_denoise_host(ndwt_plan* p, const void* x, void* out, int level, double threshold, int mode) {
@@ -2204,7 +2169,7 @@ int ndwt_analysis_level_slab(ndwt_plan* p, const void* in, void* const* out, int
 int ndwt_synthesis_level_slab(ndwt_plan* p, const void* const* in, void* out, int stride, void* stream) {
     if (const int rb = refuse_batched(p, "a slab entry point")) return rb;
     if (!p || !in || !out || stride < 1) return fail(NDWT_ERR_INVALID_ARG, "bad arguments");
-    return on_device(p, [&](auto t) { return synthesis_level(p, (const decltype(t)* const*)in, (decltype(t)*)out, stride, true, (hipStream_t)stream); });
+    return on_device(p, [&](auto t) { return synthesis_level(p, (const decltype(t)* const*)in, (decltype(t)*)out, stride, true, kNoShrink, (hipStream_t)stream); });
 }
 
 int ndwt_analysis_level_slab_split(ndwt_plan* p, const void* in_local, const void* halo_before, const void* halo_after,

@@ -242,11 +242,11 @@ inline int cascade2_rec_depth(const SelPlan& p, int Lp, int nlev) {
 
 // ---- two to four levels of the signals of a batched 1-D plan in one launch (Fwd1C / Inv1C, ndwt_device_1d.h) at the reference's
 // dilation: rows of whole groups of 4 scalars, at least 8 L of them (AxisX's own floor: whichever way a level goes, it runs the lane-shift
-// kernel), tap lengths 2 .. 8.  `howmany` = signals of the plan (0: not a batched plan); `left` = levels still to do.  Returns how many
+// kernel), tap lengths 2 .. 8.  p.howmany = signals of the plan (0: not a batched plan); `left` = levels still to do.  Returns how many
 // the next launch takes -- the largest instantiated count <= left -- and the tap length; 0 = one launch per level.  kFwdNoCascade takes
 // the analysis off, kInvCascadeOff the synthesis (A/B runs: tools/bench1d_batch.py).
-inline int cascade1_levels(const SelPlan& p, long long howmany, bool inverse, int left, int* L_out) {
-    if (howmany < 1 || p.ndim != 1 || p.atrous || is_interleaved(p) || !p.path_auto || (p.comp != 1 && p.comp != 2)) return 0;
+inline int cascade1_levels(const SelPlan& p, bool inverse, int left, int* L_out) {
+    if (p.howmany < 1 || p.ndim != 1 || p.atrous || is_interleaved(p) || !p.path_auto || (p.comp != 1 && p.comp != 2)) return 0;
     if (inverse ? p.variant_inv == kInvCascadeOff : p.variant_fwd == kFwdNoCascade) return 0;
     const int L = p.len[0];
     const long long n1 = p.dims[0] * p.comp;              // scalars per row
@@ -256,18 +256,30 @@ inline int cascade1_levels(const SelPlan& p, long long howmany, bool inverse, in
     return 0;
 }
 
+// (the earlier form, the signals as an argument of their own, for callers written against it: the same answer as with p.howmany = howmany)
+inline int cascade1_levels(const SelPlan& p, long long howmany, bool inverse, int left, int* L_out) {
+    SelPlan q = p;
+    q.howmany = howmany;
+    return cascade1_levels(q, inverse, left, L_out);
+}
+
 // ---- ndwt_denoise_bands of a batched 1-D plan in ONE launch (Den1C, ndwt_device_1d.h): dec, the per-band thresholding and rec of all
 // `level` levels with the coefficients in registers, under cascade1_levels' conditions, 1 <= level <= 4 (deeper transforms take the
 // general route: dec, one shrink pass per band, rec).  Returns `level` if the whole depth fits one launch, else 0.  Either A/B switch
 // (kFwdNoCascade, kInvCascadeOff) takes it off.
-inline int denoise1_levels(const SelPlan& p, long long howmany, int level) {
+inline int denoise1_levels(const SelPlan& p, int level) {
     if (level < 1 || level > 4) return 0;
-    if (howmany < 1 || p.ndim != 1 || p.atrous || is_interleaved(p) || !p.path_auto || (p.comp != 1 && p.comp != 2)) return 0;
+    if (p.howmany < 1 || p.ndim != 1 || p.atrous || is_interleaved(p) || !p.path_auto || (p.comp != 1 && p.comp != 2)) return 0;
     if (p.variant_fwd == kFwdNoCascade || p.variant_inv == kInvCascadeOff) return 0;
     const int L = p.len[0];
     const long long n1 = p.dims[0] * p.comp;              // scalars per row
     if (L < 2 || L > 8 || n1 % 4 != 0 || n1 < 8LL * L || n1 >= (1LL << 30)) return 0;
     return den1_instantiated({p.f64, p.comp, L, level}) ? level : 0;
+}
+inline int denoise1_levels(const SelPlan& p, long long howmany, int level) {   // (the earlier form, as cascade1_levels')
+    SelPlan q = p;
+    q.howmany = howmany;
+    return denoise1_levels(q, level);
 }
 // Whether ndwt_denoise_bands takes that launch unasked.  The rule of DESIGN.md 4.3b: a data kind takes it by default only if it was
 // measured to win by more than the 5 % spread between boxes on every measured shape of the kind.  Measured on the MI355X
@@ -313,6 +325,21 @@ inline int cascadem_levels(const SelPlan& p, bool inverse, int left, int* L_out)
     for (int n = left < 4 ? left : 4; n >= 2; --n)
         if (cascadem_instantiated({inverse, p.f64, L, n})) { *L_out = L; return n; }
     return 0;
+}
+
+// ---- the route of the next launch of a multi-level transform with `left` levels still to do: the cascade that takes `nlev` of them in
+// one launch, or kCascadeNone -- one launch for one level, by level_route.  dec_impl / rec_impl (ndwt_api.hip) ask once per launch and
+// switch on the answer; the three predicates above are what the answer is written in.  At most one of them claims a plan: a batched
+// 1-D plan, one axis of interleaved samples, an image (tests/test_dispatch_select.py holds them to that), so the order of the questions
+// decides nothing.  A further cascade family is one more question here and one more case in each walk.
+enum CascadeKind { kCascadeNone, kCascadeRows1, kCascadeMarch, kCascadeImage2 };   // none | Fwd1C / Inv1C | FwdMC / InvMC | Fwd2C / Inv2C
+struct CascadeRoute { CascadeKind kind; int nlev; int L; };   // L: the tap length (padded, for the 2-D family); kCascadeNone: nlev = L = 0
+inline CascadeRoute cascade_route(const SelPlan& p, bool inverse, int left) {
+    int L = 0;
+    if (const int n = cascade1_levels(p, inverse, left, &L)) return {kCascadeRows1, n, L};
+    if (const int n = cascadem_levels(p, inverse, left, &L)) return {kCascadeMarch, n, L};
+    if (const int n = cascade2_levels(p, inverse, left, &L)) return {kCascadeImage2, n, L};
+    return {kCascadeNone, 0, 0};
 }
 
 // ---- exact order statistics of a band's |c| (ndwt_band_select; BandHist / BandPick, ndwt_device_select.h): a radix select on the bit

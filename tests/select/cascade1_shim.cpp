@@ -12,14 +12,25 @@ static SelPlan plan_of(const int* v) {
 // levels the next launch takes (0: one launch per level); *L: the tap length it answered for
 extern "C" int sel_cascade1_levels(const int* plan, long long howmany, int inverse, int left, int* L) {
     *L = 0;
-    return cascade1_levels(plan_of(plan), howmany, inverse != 0, left, L);
+    SelPlan p = plan_of(plan);
+    p.howmany = howmany;
+    return cascade1_levels(p, inverse != 0, left, L);
 }
 // dims[0] as a 64-bit number (rows of 2^30 scalars and beyond)
 extern "C" int sel_cascade1_levels_n(const int* plan, long long n, long long howmany, int inverse, int left) {
     SelPlan p = plan_of(plan);
     p.dims[0] = n;
+    p.howmany = howmany;
     int L = 0;
-    return cascade1_levels(p, howmany, inverse != 0, left, &L);
+    return cascade1_levels(p, inverse != 0, left, &L);
+}
+// the route of the next launch of the level walk (cascade_route): its CascadeKind; *nlev: the levels it takes (0: one launch for one level)
+extern "C" int sel_cascade_route(const int* plan, long long howmany, int inverse, int left, int* nlev) {
+    SelPlan p = plan_of(plan);
+    p.howmany = howmany;
+    const CascadeRoute r = cascade_route(p, inverse != 0, left);
+    *nlev = r.nlev;
+    return (int)r.kind;
 }
 extern "C" int sel_cascade1_listed(int inverse, int f64, int ew, int Lp, int nlev) { return cascade1_instantiated({inverse != 0, f64 != 0, ew, Lp, nlev}); }
 extern "C" int sel_cascade1_tile_width(int inverse, int f64, int ew, int Lp, int nlev) { return cascade1_tile_width({inverse != 0, f64 != 0, ew, Lp, nlev}); }

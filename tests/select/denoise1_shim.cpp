@@ -14,14 +14,14 @@ extern "C" int sel_denoise1_levels(const int* plan, long long howmany, long long
     SelPlan p = plan_of(plan);
     p.howmany = howmany;
     p.inner = inner;
-    return denoise1_levels(p, howmany, level);
+    return denoise1_levels(p, level);
 }
 // dims[0] as a 64-bit number (rows of 2^30 scalars and beyond)
 extern "C" int sel_denoise1_levels_n(const int* plan, long long n, long long howmany, int level) {
     SelPlan p = plan_of(plan);
     p.dims[0] = n;
     p.howmany = howmany;
-    return denoise1_levels(p, howmany, level);
+    return denoise1_levels(p, level);
 }
 // the launch is taken unasked (the data kind's default) or was asked for (variant 11 / 11)
 extern "C" int sel_denoise1_wanted(const int* plan) { return denoise1_wanted(plan_of(plan)); }

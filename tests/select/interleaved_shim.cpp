@@ -25,7 +25,7 @@ extern "C" int il_level_route(const int* plan, long long howmany, long long inne
 }
 extern "C" int il_cascade1_levels(const int* plan, long long howmany, long long inner, int inverse, int left, int* L) {
     *L = 0;
-    return cascade1_levels(plan_of(plan, howmany, inner), howmany, inverse != 0, left, L);
+    return cascade1_levels(plan_of(plan, howmany, inner), inverse != 0, left, L);
 }
 extern "C" int il_cascade2_levels(const int* plan, long long howmany, long long inner, int inverse, int left, int* Lp) {
     *Lp = 0;

@@ -16,6 +16,29 @@ extern "C" int sel_level_path(const int* plan, int stride, int dir, int slab, in
 
 extern "C" int sel_cascade2_levels(const int* plan, int inverse, int left) { int Lp = 0; return cascade2_levels(plan_of(plan), inverse != 0, left, &Lp); }
 
+// The plan with `howmany` items and samples of `inner` elements, under every pair of the `nvar` variants, both directions and
+// left = 1 .. nleft: what the three cascade predicates answer, each asked on its own, and what cascade_route makes of them.  out: 9 ints
+// per case, variant_fwd slowest, then variant_inv, the direction, left -- (n, L) of cascade1_levels, of cascadem_levels, of
+// cascade2_levels (L = 0 where n = 0), then cascade_route's kind, nlev, L
+extern "C" void sel_cascade_routes(const int* plan, long long howmany, long long inner, const int* variants, int nvar, int nleft, int* out) {
+    SelPlan p = plan_of(plan);
+    p.howmany = howmany;
+    p.inner = inner;
+    for (int f = 0; f < nvar; ++f)
+        for (int i = 0; i < nvar; ++i)
+            for (int inverse = 0; inverse < 2; ++inverse)
+                for (int left = 1; left <= nleft; ++left, out += 9) {
+                    p.variant_fwd = variants[f];
+                    p.variant_inv = variants[i];
+                    int L[3] = {0, 0, 0};
+                    const int n[3] = {cascade1_levels(p, inverse != 0, left, &L[0]), cascadem_levels(p, inverse != 0, left, &L[1]),
+                                      cascade2_levels(p, inverse != 0, left, &L[2])};
+                    for (int k = 0; k < 3; ++k) { out[2 * k] = n[k]; out[2 * k + 1] = n[k] ? L[k] : 0; }
+                    const CascadeRoute r = cascade_route(p, inverse != 0, left);
+                    out[6] = (int)r.kind; out[7] = r.nlev; out[8] = r.L;
+                }
+}
+
 // v: f64, inverse, vec4, uniform_yz, tfold, Lp, len[3], ew, dil, n1, n2, nbatch, variant_fwd, variant_inv, num_cus, target_blocks
 // out: the pick in full -- V, TX, TY, NT, RY, WPE, PIN, TPRE, WLDS, DEPTH, ZLDS, UNIYZ, XSC, per_cu, target, VEC4, EW, Lp, f64, and whether
 // the instance lists (ndwt_fused_list.h) hold it;  returns the kernel's name as the launch trace spells it

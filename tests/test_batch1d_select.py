@@ -19,6 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 
 # the table: {float, double} x EW {1, 2} x L {2, 4, 6, 8} x NLEV {2, 3, 4} x {analysis, synthesis}
 TABLE = {(inv, f64, ew, L, nlev) for inv in (0, 1) for f64 in (0, 1) for ew in (1, 2) for L in (2, 4, 6, 8) for nlev in (2, 3, 4)}
+NONE, ROWS1 = 0, 1                                                                # CascadeKind of csrc/ndwt_select.h
 KINDS = {"f32": (False, False), "c64": (False, True), "f64": (True, False), "c128": (True, True)}
 
 
@@ -32,6 +33,7 @@ def shim(tmp_path_factory):
     lib = ctypes.CDLL(out)
     lib.sel_cascade1_levels.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     lib.sel_cascade1_levels_n.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_int]
+    lib.sel_cascade_route.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     return lib
 
 
@@ -48,15 +50,16 @@ def _levels(shim, plan, howmany, inverse, left):
 
 
 def _launches(shim, plan, howmany, inverse, level):
-    """the level loop of dec_impl / rec_impl: cascade launches while the selector says so, then one launch per level"""
+    """the walk of dec_impl / rec_impl: cascade_route (csrc/ndwt_select.h) asked once per launch, for the levels still to do"""
     out, left = [], level
     while left:
-        n, _ = _levels(shim, plan, howmany, inverse, left)
-        if not n:
-            break
-        out.append(n)
-        left -= n
-    return out + [1] * left
+        nlev = ctypes.c_int(-1)
+        kind = shim.sel_cascade_route(plan, howmany, int(inverse), int(left), ctypes.byref(nlev))
+        n = _levels(shim, plan, howmany, inverse, left)[0]
+        assert kind == (ROWS1 if n else NONE) and nlev.value == n
+        out.append(nlev.value if kind != NONE else 1)
+        left -= out[-1]
+    return out
 
 
 @pytest.mark.parametrize("kind", sorted(KINDS))

@@ -410,3 +410,46 @@ def test_short_axis_rows_route_and_pick_what_the_gpu_file_expects(shim):
                     assert not row["trace"] or any(helpers.matches(rec, sp) for sp in specs), (row["id"], kind, stride, "rec" if inverse else "dec", rec, must)
                     fused += 1
     assert checked >= 1000 and fused >= 400, (checked, fused)
+
+
+def test_at_most_one_cascade_claims_a_plan_and_cascade_route_names_it(shim):
+    """What the one walk of dec_impl / rec_impl rests on: over a grid of plans -- 1 to 4 axes, the four data kinds, plain, batched /
+    stack, interleaved and both, both dilations, both paths, 2 .. 12 taps, every pair of the variants the cascades read, both
+    directions, 1 .. 9 levels left, sizes on both sides of every floor the predicates test (rows of 8 L scalars, 3 (L - 1) image rows,
+    24 MiB + 1 of float image, 256 MiB of interleaved samples) and rows that are not whole groups of 4 -- at most one of cascade1_levels,
+    cascadem_levels and cascade2_levels answers a count, and cascade_route answers that family with its count and tap length, or
+    kCascadeNone with zeros.  And kCascadeNone is final: where it is the answer for `left` levels it is the answer for fewer, so a walk
+    that was told "none" need not ask again."""
+    import numpy as np
+    variants, nleft = [0, 9, 10, 11, 12], 9
+    per_plan = len(variants) ** 2 * 2 * nleft
+    out = (ctypes.c_int * (9 * per_plan))()
+    shim.sel_cascade_routes.argtypes = [ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    shim.sel_cascade_routes.restype = None
+    seen, plans = np.zeros(4, dtype=np.int64), 0
+    for ndim in (1, 2, 3, 4):
+        for L in (2, 4, 6, 8, 10, 12):
+            n0s = [8 * L, 8 * L - 4, 4 * L, 4 * L - 2, 63, 66, 512, 2048, 1 << 24, (1 << 24) - 4]
+            n1s = [64] if ndim == 1 else [3 * (L - 1), 3 * (L - 1) - 1, 64, 3072, 3073] if ndim == 2 else [64, 3 * (L - 1)]
+            for n0 in n0s:
+                for n1 in n1s:
+                    dims = ([n0, n1] + [8] * 2)[:ndim]
+                    for f64 in (False, True):
+                        for cplx in (False, True):
+                            for howmany, inner in ((0, 1), (3, 1), (0, 4), (3, 4)):
+                                for atrous in (False, True):
+                                    for generic in (False, True):
+                                        plan = _plan(dims, [L] * ndim, f64, cplx, generic, atrous)
+                                        shim.sel_cascade_routes(plan, howmany, inner, _ints(variants), len(variants), nleft, out)
+                                        a = np.frombuffer(out, dtype=np.int32).reshape(per_plan, 9)
+                                        n, taps = a[:, 0:6:2], a[:, 1:6:2]
+                                        what = (dims, L, f64, cplx, howmany, inner, atrous, generic)
+                                        assert ((n > 0).sum(axis=1) <= 1).all(), what
+                                        kind = (n > 0) @ np.array([1, 2, 3])               # CascadeKind: none, rows1, march, image2
+                                        assert (a[:, 6] == kind).all() and (a[:, 7] == n.sum(axis=1)).all() and (a[:, 8] == taps.sum(axis=1)).all(), what
+                                        assert ((a[:, 6] == 0) == (a[:, 7] == 0)).all() and (a[:, 7] <= np.tile(np.arange(1, nleft + 1), per_plan // nleft)).all(), what
+                                        by_left = a[:, 6].reshape(-1, nleft)                # "none" is final: none at `left` levels, none at fewer
+                                        assert ((by_left[:, 1:] != 0) | (by_left[:, :-1] == 0)).all(), what
+                                        seen += np.bincount(a[:, 6], minlength=4)
+                                        plans += 1
+    assert plans >= 20000 and (seen > 0).all(), (plans, seen)                               # every family, and none, was among the answers

@@ -449,3 +449,40 @@ def test_every_instance_of_the_table_was_launched():
     assert len(INSTANCES) == 61
     ran = set().union(*[cover(kind) for kind in KINDS])
     assert not (INSTANCES - ran), f"never launched: {sorted(INSTANCES - ran)}"
+
+
+@pytest.mark.parametrize("dims,vi,route", [([64, 48], 0, "Inv2"), ([32, 32, 16], 0, "Den3"), ([64, 48], 11, "Inv2C")],
+                         ids=["2d", "3d-den3", "2d-inv2c"])
+def test_rec_is_the_same_before_and_after_a_denoise_on_the_plan(dims, vi, route):
+    """ndwt_denoise's thresholding in the synthesis loads is an argument of its own rec, not state of the plan: rec(y) of the same plan
+    gives the same bits before a denoise, after one (soft and hard), and after one that was refused (a negative threshold).  db2 at 2
+    levels on the smallest shapes that have each shrinking synthesis route: the one-level 2-D kernels, Inv3Y behind Den3, Inv2C
+    (variant inv = 11)."""
+    s, level, nb = stream(), 2, 1 + 2 * (2 ** len(dims) - 1)
+    p = ndwt.Plan(dims, ["db2"] * len(dims), torch.float32, False, True, "reference", max_level=level)
+    if vi:
+        p.set_variant(inv=vi)
+    g = torch.Generator(device="cpu").manual_seed(5)
+    vol = int(np.prod(dims))
+    x = torch.randn(vol, generator=g, dtype=torch.float32).cuda()
+    y, out = torch.empty(vol * nb, dtype=torch.float32, device="cuda"), torch.empty(vol, dtype=torch.float32, device="cuda")
+    p.dec(x.data_ptr(), y.data_ptr(), level, s)
+
+    def rec():
+        r = torch.empty(vol, dtype=torch.float32, device="cuda")
+        p.rec(y.data_ptr(), r.data_ptr(), level, s)
+        torch.cuda.synchronize()
+        return r
+
+    before = rec()
+    assert float((before - x).abs().max()) <= 50 * TOL["single"] * float(x.abs().max())   # (it IS the reconstruction)
+    for hard in (False, True):
+        with ndwt.kernel_trace() as recs:
+            p.denoise(x.data_ptr(), out.data_ptr(), level, 0.5, hard, s)
+        fams = [r.family for r in recs]
+        assert any(f.startswith(route) for f in fams) and "shrink_kernel" not in fams, recs   # the thresholding was in the loads
+        assert float((out - x).abs().max()) > 0.1                                 # ... and it thresholded
+        assert torch.equal(rec(), before), (dims, vi, hard)
+    with pytest.raises(ndwt.NdwtError, match="threshold must be >= 0"):
+        p.denoise(x.data_ptr(), out.data_ptr(), level, -1.0, False, s)
+    assert torch.equal(rec(), before), (dims, vi, "refused")
