@@ -211,7 +211,7 @@ template <class F> static int on_device(const ndwt_plan* p, F&& f) {
 }
 
 // Events come from a pool owned by the plan (get_profile returns them to it), and a launch that did not happen
-// (no instantiation: rc < 0, the caller falls through to another kernel) leaves no record.
+// (rc != 0: a cascade that declined, whose caller takes one launch per level, or an error) leaves no record.
 static bool prof_event(const ndwt_plan* p, hipEvent_t* e) {
     if (!p->ev_pool.empty()) { *e = p->ev_pool.back(); p->ev_pool.pop_back(); return true; }
     return hipEventCreate(e) == hipSuccess;
@@ -239,23 +239,15 @@ static void prof_end(const ndwt_plan* p, hipStream_t s, int rc = 0) {
 static long long level_stride(const ndwt_plan* p, int lev) { return p->dilation == NDWT_DILATION_ATROUS ? (1LL << (lev - 1)) : 1LL; }
 
 template <typename T> static bool aligned_vec4(const void* ptr) { return ((uintptr_t)ptr % (4 * sizeof(T))) == 0; }
-static int launch_march(bool syn, int L, const MarchArgs<float>& a, const double* lo, const double* hi, hipStream_t s) { return launch_march_f32(syn, L, a, lo, hi, s); }
-static int launch_march(bool syn, int L, const MarchArgs<double>& a, const double* lo, const double* hi, hipStream_t s) { return launch_march_f64(syn, L, a, lo, hi, s); }
-static int launch_axisx(bool syn, int L, int ew, const AxisXArgs<float>& a, bool vec4, const double* lo, const double* hi, hipStream_t s) { return launch_axisx_f32(syn, L, ew, a, vec4, lo, hi, s); }
-static int launch_axisx(bool syn, int L, int ew, const AxisXArgs<double>& a, bool vec4, const double* lo, const double* hi, hipStream_t s) { return launch_axisx_f64(syn, L, ew, a, vec4, lo, hi, s); }
 
 // ------------------------------------------------------------------------------ one axis, one pass
+// The view [outer][n][inner] of the pass and whether its pointers lie on groups of 4 scalars go to axis_select (ndwt_select.h), which
+// names the kernel and its launch geometry; this function launches what the pick names.
 template <typename T>
 static int axis_pass(const ndwt_plan* p, bool synthesis, int axis, const long long* dims_cur, long long stride, bool wrap,
                      const T* in0, const T* in1, T* out0, T* out1, hipStream_t s) {
     const AxisFilter& f = p->filt[axis];
-    AxisTaps<T> tp;
-    tp.len = f.len;
-    for (int j = 0; j < kMaxTaps; ++j) { tp.lo[j] = 0; tp.hi[j] = 0; }
-    for (int j = 0; j < f.len; ++j) {
-        tp.lo[j] = (T)(synthesis ? f.syn_lo[j] : f.ana_lo[j]);
-        tp.hi[j] = (T)(synthesis ? f.syn_hi[j] : f.ana_hi[j]);
-    }
+    const double *lo = synthesis ? f.syn_lo : f.ana_lo, *hi = synthesis ? f.syn_hi : f.ana_hi;
     AxisArgs<T> a;
     a.inner = p->comp * p->inner;                         // (interleaved samples: axis 0 is strided too)
     for (int k = 0; k < axis; ++k) a.inner *= dims_cur[k];
@@ -268,64 +260,34 @@ static int axis_pass(const ndwt_plan* p, bool synthesis, int axis, const long lo
     a.n_in = wrap ? a.n : a.n + (long long)(f.len - 1) * stride;
     a.total = a.outer * a.n * a.inner;
     if (a.total == 0) return NDWT_OK;
-    // Register-window march kernel: needs 4-element aligned contiguous runs below the filtered index.  A dilated
-    // (a-trous) periodic axis whose length is a multiple of the tap stride s is s interleaved unit-stride problems:
-    // view [outer][n][inner] as [outer][n/s][s*inner] and march n/s -- this also covers the contiguous axis for s >= 4.
-    long long m_inner = a.inner, m_n = a.n, m_n_in = a.n_in;
-    bool march_ok = p->path == NDWT_PATH_AUTO;
-    if (stride > 1) {
-        if (wrap && a.n % stride == 0 && a.n / stride >= f.len) { m_inner = a.inner * stride; m_n = a.n / stride; m_n_in = m_n; }
-        else march_ok = false;
-    }
-    if (march_ok && m_inner % 4 == 0 && m_inner >= 4 && aligned_vec4<T>(in0) &&
-        (!synthesis || aligned_vec4<T>(in1)) && aligned_vec4<T>(out0) && (synthesis || aligned_vec4<T>(out1))) {
-        MarchArgs<T> m;
-        m.in0 = in0; m.in1 = in1; m.out0 = out0; m.out1 = out1;
-        m.inner = m_inner; m.n = m_n; m.n_in = m_n_in; m.outer = a.outer; m.wrap = a.wrap;
-        m.ngroups = m.inner / 4;
-        const long long iblocks = (m.ngroups * m.outer + 255) / 256;
-        long long want = (4096 + iblocks - 1) / iblocks;
-        if (want < 1) want = 1;
-        long long chunk = (m.n + want - 1) / want;
-        const long long min_chunk = 4LL * (f.len - 1) > 8 ? 4LL * (f.len - 1) : 8;
-        if (chunk < min_chunk) chunk = min_chunk;
-        if (chunk > m.n) chunk = m.n;
-        m.chunk = (int)chunk;
-        m.nchunks = (int)((m.n + chunk - 1) / chunk);
-        prof_begin(p, synthesis ? NDWT_KERNEL_AXIS_SYNTHESIS : NDWT_KERNEL_AXIS_ANALYSIS, s);
-        int rc = launch_march(synthesis, f.len, m, synthesis ? f.syn_lo : f.ana_lo, synthesis ? f.syn_hi : f.ana_hi, s);
-        prof_end(p, s, rc);
-        if (rc == 0) return NDWT_OK;
-        if (rc > 0) return fail(NDWT_ERR_HIP, "march kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-        // rc < 0: no instantiation / grid too large -> fall through to the element-wise kernel
-    }
-    // the contiguous axis (1-D signals, interleaved complex): one wave per row segment, neighbours by lane shifts
-    if (p->path == NDWT_PATH_AUTO && axis == 0 && p->inner == 1 && stride == 1 && wrap && f.len <= 12 && (p->comp == 1 || p->comp == 2) &&
-        a.n * p->comp >= 8 * f.len) {
-        AxisXArgs<T> x;
-        x.in0 = in0; x.in1 = in1; x.out0 = out0; x.out1 = out1;
-        x.row = a.n * p->comp;
-        x.outer = a.outer;
-        x.nseg = 0;
-        const bool v4ok = x.row % 4 == 0 && aligned_vec4<T>(in0) && (!synthesis || aligned_vec4<T>(in1)) && aligned_vec4<T>(out0) &&
-                          (synthesis || aligned_vec4<T>(out1));
-        prof_begin(p, synthesis ? NDWT_KERNEL_AXIS_SYNTHESIS : NDWT_KERNEL_AXIS_ANALYSIS, s);
-        int rc = launch_axisx(synthesis, f.len, (int)p->comp, x, v4ok, synthesis ? f.syn_lo : f.ana_lo, synthesis ? f.syn_hi : f.ana_hi, s);
-        prof_end(p, s, rc);
-        if (rc == 0) return NDWT_OK;
-        if (rc > 0) return fail(NDWT_ERR_HIP, "contiguous-axis kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-    }
-    long long nb = (a.total + 255) / 256;
-    const long long cap = 256LL * 64;   // grid-stride beyond 64 blocks per CU
-    if (nb > cap) nb = cap;
+    const bool aligned = aligned_vec4<T>(in0) && (!synthesis || aligned_vec4<T>(in1)) && aligned_vec4<T>(out0) && (synthesis || aligned_vec4<T>(out1));
+    const AxisQuery q = {sizeof(T) == 8, synthesis, p->path == NDWT_PATH_AUTO, wrap, f.len, stride, (int)p->comp, a.inner, a.n, a.outer,
+                         axis == 0 && p->inner == 1, aligned};
+    const AxisPick k = axis_select(q);
+    int rc;
     prof_begin(p, synthesis ? NDWT_KERNEL_AXIS_SYNTHESIS : NDWT_KERNEL_AXIS_ANALYSIS, s);
-    trace_plain(dim3((unsigned)nb), dim3(256), synthesis ? "axis_synthesis_kernel" : "axis_analysis_kernel", trace_scalar<T>());
-    if (synthesis)
-        hipLaunchKernelGGL(axis_synthesis_kernel<T>, dim3((unsigned)nb), dim3(256), 0, s, in0, in1, out0, tp, a);
-    else
-        hipLaunchKernelGGL(axis_analysis_kernel<T>, dim3((unsigned)nb), dim3(256), 0, s, in0, out0, out1, tp, a);
-    prof_end(p, s);
-    HIP_TRY(hipGetLastError());
+    if (k.kernel == kAxisMarch) {
+        const MarchArgs<T> m = {in0, in1, out0, out1, k.inner, k.n, k.n_in, a.outer, k.chunk, k.nchunks, a.wrap, k.ngroups};
+        rc = launch_axis_march(k.march(), m, lo, hi, s);
+    } else if (k.kernel == kAxisX) {
+        const AxisXArgs<T> x = {in0, in1, out0, out1, k.row, a.outer, k.nseg};
+        rc = launch_axisx(k.axisx(), x, lo, hi, s);
+    } else {
+        AxisTaps<T> tp;
+        tp.len = f.len;
+        for (int j = 0; j < kMaxTaps; ++j) { tp.lo[j] = j < f.len ? (T)lo[j] : 0; tp.hi[j] = j < f.len ? (T)hi[j] : 0; }
+        trace_plain(dim3((unsigned)k.grid), dim3(256), synthesis ? "axis_synthesis_kernel" : "axis_analysis_kernel", trace_scalar<T>());
+        if (synthesis)
+            hipLaunchKernelGGL(axis_synthesis_kernel<T>, dim3((unsigned)k.grid), dim3(256), 0, s, in0, in1, out0, tp, a);
+        else
+            hipLaunchKernelGGL(axis_analysis_kernel<T>, dim3((unsigned)k.grid), dim3(256), 0, s, in0, out0, out1, tp, a);
+        rc = (int)hipGetLastError();
+    }
+    prof_end(p, s, rc);
+    // (-1, -2: after a pick, internal errors -- see fused3_run)
+    if (rc == -1) return fail(NDWT_ERR_UNSUPPORTED, "internal: no per-axis kernel instantiated for the pick (kernel %d, tap length %d)", (int)k.kernel, f.len);
+    if (rc == -2) return fail(NDWT_ERR_UNSUPPORTED, "internal: launch geometry does not match the per-axis kernel's chunks or segments, or its grid is beyond 2^31 - 1");
+    if (rc != 0) return fail(NDWT_ERR_HIP, "per-axis kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     return NDWT_OK;
 }
 
@@ -842,9 +804,8 @@ template <typename T> static int denoise1_run(ndwt_plan* p, int L, int nlev, con
 }
 
 // ---- two to four levels of the one strided axis of a plan over interleaved samples in one march (FwdMC / InvMC, ndwt_device_axis.h;
-// when: cascadem_levels).  in / out as MarchCArgs documents them.  The chunking is axis_pass's own rule (about 4096 workgroups, in chunks
-// of the axis), the floor raised to 4 nlev (L - 1) planes -- the march-in is at most a quarter of a thread's planes -- and capped at the
-// axis; force_zchunk / zchunk_dir = planes per chunk.  Returns 0, or -1 as cascade1d_launch does, or for a grid beyond 2^31 - 1
+// when: cascadem_levels).  in / out as MarchCArgs documents them.  The chunking is march_chunks (ndwt_select.h) with a floor of
+// 4 nlev (L - 1) planes -- the march-in is at most a quarter of a thread's planes; force_zchunk / zchunk_dir = planes per chunk.  Returns 0, or -1 as cascade1d_launch does, or for a grid beyond 2^31 - 1
 // workgroups
 template <typename T> static int cascadem_run(ndwt_plan* p, bool inverse, int L, int nlev, const T* const* in, T* const* out, hipStream_t s) {
     MarchCArgs<T> a;
@@ -855,16 +816,9 @@ template <typename T> static int cascadem_run(ndwt_plan* p, bool inverse, int L,
     a.outer = p->items();
     a.ngroups = a.inner / 4;
     const long long iblocks = (a.ngroups * a.outer + 255) / 256;
-    long long want = (4096 + iblocks - 1) / iblocks;
-    if (want < 1) want = 1;
-    long long chunk = (a.n + want - 1) / want;
-    const long long min_chunk = 4LL * nlev * (L - 1);
-    if (chunk < min_chunk) chunk = min_chunk;
-    const int zc_force = p->zchunk_dir[inverse ? 1 : 0] > 0 ? p->zchunk_dir[inverse ? 1 : 0] : p->force_zchunk;
-    if (zc_force > 0) chunk = zc_force;
-    if (chunk > a.n) chunk = a.n;
-    a.chunk = (int)chunk;
-    a.nchunks = (int)((a.n + chunk - 1) / chunk);
+    const MarchChunks c = march_chunks(a.n, iblocks, 4LL * nlev * (L - 1), p->zchunk_dir[inverse ? 1 : 0] > 0 ? p->zchunk_dir[inverse ? 1 : 0] : p->force_zchunk);
+    a.chunk = c.chunk;
+    a.nchunks = c.nchunks;
     if (iblocks * a.nchunks > 0x7fffffffLL) return -1;
     const AxisFilter& f = p->filt[0];
     const CascadeMInstance k = {inverse, sizeof(T) == 8, L, nlev};

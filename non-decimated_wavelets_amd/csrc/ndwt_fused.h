@@ -55,12 +55,13 @@ int launch_den1(const Den1Instance& k, const Den1CArgs<double>& a, const void* t
 int launch_cascadem(const CascadeMInstance& k, const MarchCArgs<float>& a, const double* lo, const double* hi, hipStream_t s);
 int launch_cascadem(const CascadeMInstance& k, const MarchCArgs<double>& a, const double* lo, const double* hi, hipStream_t s);
 
-// one non-contiguous axis with the window in registers (taps: kernel-form lo/hi of length L)
-int launch_march_f32(bool syn, int L, const MarchArgs<float>& a, const double* lo, const double* hi, hipStream_t s);
-int launch_march_f64(bool syn, int L, const MarchArgs<double>& a, const double* lo, const double* hi, hipStream_t s);
-
-// the contiguous axis with lane shifts (ew = scalars per element: 1 real, 2 interleaved complex)
-int launch_axisx_f32(bool syn, int L, int ew, const AxisXArgs<float>& a, bool vec4, const double* lo, const double* hi, hipStream_t s);
-int launch_axisx_f64(bool syn, int L, int ew, const AxisXArgs<double>& a, bool vec4, const double* lo, const double* hi, hipStream_t s);
+// One pass along one axis, the instance named in full (ndwt_fused_list.h: AxisMarchInstance / AxisXInstance, the tables axis_select
+// reads): a strided axis with the window in registers, or the contiguous axis with lane shifts (its tile: axisx_tile_width).  lo / hi:
+// the kernel-form taps of the direction, length k.L.  -1: not in the lists, -2: the chunks / segments are not the instance's, or the grid
+// is too large -- after a pick, internal errors both.
+int launch_axis_march(const AxisMarchInstance& k, const MarchArgs<float>& a, const double* lo, const double* hi, hipStream_t s);
+int launch_axis_march(const AxisMarchInstance& k, const MarchArgs<double>& a, const double* lo, const double* hi, hipStream_t s);
+int launch_axisx(const AxisXInstance& k, const AxisXArgs<float>& a, const double* lo, const double* hi, hipStream_t s);
+int launch_axisx(const AxisXInstance& k, const AxisXArgs<double>& a, const double* lo, const double* hi, hipStream_t s);
 
 }  // namespace ndwt

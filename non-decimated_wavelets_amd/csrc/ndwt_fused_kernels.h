@@ -65,9 +65,10 @@ template <class K> int launch_cascade2_k(const typename K::Args& a, const void* 
     return launch_wave_tiles<K>(a, a.nbatch > 1 ? a.nbatch : 1, taps_dev, s);   // a stack: its items (a zeroed field: one image)
 }
 
-// The 1-D cascade of a batched plan: one wave per (signal, segment of K::WX scalars), four to the workgroup.  The host's segments
-// (cascade1_tile_width) against the kernel's own, and a grid the launch can express, or -2: the caller takes one launch per level.
-template <class K> int launch_cascade1_k(const typename K::Args& a, const void* taps_dev, hipStream_t s) {
+// The 1-D kernels of a batched plan (Fwd1C / Inv1C; Den1C, whose taps_dev holds Taps1D<T, L>, both directions): one wave per (signal,
+// segment of K::WX scalars), four to the workgroup.  The host's segments (cascade1_tile_width, den1_tile_width) against the kernel's own,
+// and a grid the launch can express, or -2: the caller takes one launch per level / the general route.
+template <class K> int launch_wave_rows_k(const typename K::Args& a, const void* taps_dev, hipStream_t s) {
     if (a.row < 4 || a.row % 4 != 0 || a.row >= (1LL << 30) || a.outer < 1 || a.nseg != (a.row + K::WX - 1) / K::WX) return -2;
     const long long nblocks = (a.outer * a.nseg + K::NT / 64 - 1) / (K::NT / 64);
     if (nblocks > 0x7fffffffLL) return -2;
@@ -76,17 +77,22 @@ template <class K> int launch_cascade1_k(const typename K::Args& a, const void* 
     return (int)hipGetLastError();
 }
 
-// The one-launch denoise of a batched plan (Den1C): the same layout of waves; taps_dev holds Taps1D<T, L> (both directions)
-template <class K> int launch_den1_k(const typename K::Args& a, const void* taps_dev, hipStream_t s) {
-    if (a.row < 4 || a.row % 4 != 0 || a.row >= (1LL << 30) || a.outer < 1 || a.nseg != (a.row + K::WX - 1) / K::WX) return -2;
+// One pass along the contiguous axis (AxisX): the same layout of waves, taps by value, rows of any length below 2^30 scalars.  The host's
+// segments (axis_select: axisx_tile_width) against the kernel's own, and a grid the launch can express, or -2
+template <class K> int launch_axisx_k(const typename K::Args& a, const double* lo, const double* hi, hipStream_t s) {
+    typename K::Taps tp;
+    typedef std::remove_reference_t<decltype(tp.lo[0])> T;
+    for (int j = 0; j < K::L; ++j) { tp.lo[j] = (T)lo[j]; tp.hi[j] = (T)hi[j]; }
+    if (a.row < 1 || a.row >= (1LL << 30) || a.outer < 1 || a.nseg != (a.row + K::WX - 1) / K::WX) return -2;
     const long long nblocks = (a.outer * a.nseg + K::NT / 64 - 1) / (K::NT / 64);
     if (nblocks > 0x7fffffffLL) return -2;
     trace_kernel<K>(dim3((unsigned)nblocks), dim3(K::NT));
-    hipLaunchKernelGGL(fused3_kernel<K>, dim3((unsigned)nblocks), dim3(K::NT), 0, s, a, (const typename K::Taps*)taps_dev);
+    hipLaunchKernelGGL(march_kernel<K>, dim3((unsigned)nblocks), dim3(K::NT), 0, s, a, tp);
     return (int)hipGetLastError();
 }
 
-// The cascaded march of one strided axis: 256 (item, group of 4 scalars) pairs per workgroup, times the chunks of the axis
+// The marches of one strided axis (AxisMarch: one level; FwdMC / InvMC: the cascade): 256 (item, group of 4 scalars) pairs per
+// workgroup, times the chunks of the axis.  The host's chunks (march_chunks) must cover the axis exactly, or -2
 template <class K> int launch_cascadem_k(const typename K::Args& a, const double* lo, const double* hi, hipStream_t s) {
     typename K::Taps tp;
     typedef std::remove_reference_t<decltype(tp.lo[0])> T;
@@ -144,14 +150,21 @@ template <class K> int launch_select_k(const typename K::Args& a, int nblocks, c
 #define NDWT_LAUNCH_C(KIND, T, EWV, LL, NLEV)                                                                \
     if (k == Cascade1Instance{k##KIND == kInv1C, sizeof(T) == 8, EWV, LL, NLEV}) {                            \
         static_assert(KIND<T, LL, NLEV, EWV>::WX == cascade1_tile_width({k##KIND == kInv1C, sizeof(T) == 8, EWV, LL, NLEV}), "tile width"); \
-        return launch_cascade1_k<KIND<T, LL, NLEV, EWV>>(a, taps_dev, s);                                    \
+        return launch_wave_rows_k<KIND<T, LL, NLEV, EWV>>(a, taps_dev, s);                                   \
     }
 #define NDWT_LAUNCH_D(T, EWV, LL, NLEV)                                                                      \
     if (k == Den1Instance{sizeof(T) == 8, EWV, LL, NLEV}) {                                                  \
         static_assert(Den1C<T, LL, NLEV, EWV>::WX == den1_tile_width(LL, EWV, sizeof(T) == 8, NLEV), "tile width"); \
-        return launch_den1_k<Den1C<T, LL, NLEV, EWV>>(a, taps_dev, s);                                       \
+        return launch_wave_rows_k<Den1C<T, LL, NLEV, EWV>>(a, taps_dev, s);                                  \
     }
 #define NDWT_LAUNCH_M(KIND, T, LL, NLEV) \
     if (k == CascadeMInstance{k##KIND == kInvMC, sizeof(T) == 8, LL, NLEV}) return launch_cascadem_k<KIND<T, LL, NLEV>>(a, lo, hi, s);
+#define NDWT_LAUNCH_N(T, LL, SYN) \
+    if (k == AxisMarchInstance{sizeof(T) == 8, SYN, LL}) return launch_cascadem_k<AxisMarch<T, LL, SYN>>(a, lo, hi, s);
+#define NDWT_LAUNCH_X(T, LL, SYN, EWV, VEC)                                                                  \
+    if (k == AxisXInstance{sizeof(T) == 8, SYN, VEC, LL, EWV}) {                                             \
+        static_assert(AxisX<T, LL, SYN, EWV, VEC>::WX == axisx_tile_width({sizeof(T) == 8, SYN, VEC, LL, EWV}), "tile width"); \
+        return launch_axisx_k<AxisX<T, LL, SYN, EWV, VEC>>(a, lo, hi, s);                                    \
+    }
 
 }  // namespace ndwt

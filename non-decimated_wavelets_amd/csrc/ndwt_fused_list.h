@@ -1,7 +1,8 @@
 // ndwt_fused_list.h -- the instances of the fused kernels that kernel selection can name, one list per launch unit (no HIP header: the
 // launch units expand a list into launches, ndwt_select.h and the host tests into questions).  An instance lives in exactly one list: the
 // unit decides how its device code is compiled (csrc/Makefile: NOSLP), and the split over units is what keeps the build parallel.  Every
-// fused family is here: the 3-D kernels, the one-level 2-D ones (Fwd2S / Inv2S, Inv2P) and the 2-D cascade.
+// fused family is here: the 3-D kernels, the one-level 2-D ones (Fwd2S / Inv2S, Inv2P) and the 2-D cascade -- and, since a pass along one
+// axis is picked the same way (ndwt_select.h: axis_select), the two per-axis families AxisMarch and AxisX.
 #pragma once
 #include "ndwt_fused_tile.h"
 
@@ -64,6 +65,14 @@ struct CascadeMInstance { bool inverse, f64; int L, nlev; };
 constexpr bool operator==(const CascadeMInstance& a, const CascadeMInstance& b) {
     return a.inverse == b.inverse && a.f64 == b.f64 && a.L == b.L && a.nlev == b.nlev;
 }
+// AxisMarch<T, L, SYN> (ndwt_device.h): one pass along one strided axis, the filter window in registers
+struct AxisMarchInstance { bool f64, syn; int L; };
+constexpr bool operator==(const AxisMarchInstance& a, const AxisMarchInstance& b) { return a.f64 == b.f64 && a.syn == b.syn && a.L == b.L; }
+// AxisX<T, L, SYN, EW, VEC4> (ndwt_device.h): one pass along the contiguous axis, one wave per row segment
+struct AxisXInstance { bool f64, syn, vec4; int L, ew; };
+constexpr bool operator==(const AxisXInstance& a, const AxisXInstance& b) {
+    return a.f64 == b.f64 && a.syn == b.syn && a.vec4 == b.vec4 && a.L == b.L && a.ew == b.ew;
+}
 
 // ---- the lists.  Entries:  F(T, L, V, VEC4, EW, PIN, TPRE, WLDS)  Fwd3 on tile V
 //                            S(KIND, T, L, V, VEC4, EW)             Inv3 / Inv3S on tile V
@@ -75,6 +84,8 @@ constexpr bool operator==(const CascadeMInstance& a, const CascadeMInstance& b) 
 //                            C(KIND, T, EW, L, NLEV)                Fwd1C / Inv1C
 //                            M(KIND, T, L, NLEV)                    FwdMC / InvMC
 //                            D(T, EW, L, NLEV)                      Den1C
+//                            N(T, L, SYN)                           AxisMarch
+//                            X(T, L, SYN, EW, VEC4)                 AxisX
 // NDWT_F2 / NDWT_S2 / NDWT_Y2 / NDWT_W2: the plain form of an entry for rows of whole groups of 4 scalars and for the rest
 #define NDWT_F2(F, T, L, V, EW) F(T, L, V, true, EW, false, false, 0) F(T, L, V, false, EW, false, false, 0)
 #define NDWT_S2(S, KIND, T, L, V, EW) S(KIND, T, L, V, true, EW) S(KIND, T, L, V, false, EW)
@@ -303,6 +314,22 @@ constexpr bool operator==(const CascadeMInstance& a, const CascadeMInstance& b) 
 #define NDWT_LIST_F64_INVMC(M) NDWT_M234(M, InvMC, double, 2) NDWT_M234(M, InvMC, double, 4) NDWT_M234(M, InvMC, double, 6) M(InvMC, double, 8, 2)
 #define NDWT_LIST_MC(M) NDWT_LIST_F32_FWDMC(M) NDWT_LIST_F32_INVMC(M) NDWT_LIST_F64_FWDMC(M) NDWT_LIST_F64_INVMC(M)
 
+// The per-axis passes (AxisMarch, AxisX: ndwt_device.h): THE table of the instances that exist -- axis_select (ndwt_select.h) answers from
+// it, the launch unit (ndwt_march.hip) expands it.  AxisMarch: {float, double} x 2 .. 20 taps x both directions, 40 instances (interleaved
+// complex: the factor 2 in the inner block).  AxisX: {float, double} x 2 .. 12 taps x both directions x EW {1, 2} x rows in whole groups of
+// 4 scalars or not, 96 instances.  Where neither has an instance a pass runs the element-wise kernels, which take any tap length.
+#define NDWT_N2(N, T, L) N(T, L, false) N(T, L, true)
+#define NDWT_AXIS_MARCH_T(N, T)                                                                                            \
+    NDWT_N2(N, T, 2) NDWT_N2(N, T, 4) NDWT_N2(N, T, 6) NDWT_N2(N, T, 8) NDWT_N2(N, T, 10) NDWT_N2(N, T, 12) NDWT_N2(N, T, 14)   \
+    NDWT_N2(N, T, 16) NDWT_N2(N, T, 18) NDWT_N2(N, T, 20)
+#define NDWT_LIST_F32_AXIS_MARCH(N) NDWT_AXIS_MARCH_T(N, float)
+#define NDWT_LIST_F64_AXIS_MARCH(N) NDWT_AXIS_MARCH_T(N, double)
+#define NDWT_X4(X, T, L, SYN) X(T, L, SYN, 1, true) X(T, L, SYN, 1, false) X(T, L, SYN, 2, true) X(T, L, SYN, 2, false)
+#define NDWT_X8(X, T, L) NDWT_X4(X, T, L, false) NDWT_X4(X, T, L, true)
+#define NDWT_AXISX_T(X, T) NDWT_X8(X, T, 2) NDWT_X8(X, T, 4) NDWT_X8(X, T, 6) NDWT_X8(X, T, 8) NDWT_X8(X, T, 10) NDWT_X8(X, T, 12)
+#define NDWT_LIST_F32_AXISX(X) NDWT_AXISX_T(X, float)
+#define NDWT_LIST_F64_AXISX(X) NDWT_AXISX_T(X, double)
+
 // ---- questions to the lists
 #define NDWT_IS_F(T, L, V, VEC4, EW, PIN, TPRE, WLDS) if (k == fwd3_instance(sizeof(T) == 8, L, V, VEC4, EW, PIN, TPRE, WLDS)) return true;
 #define NDWT_IS_S(KIND, T, L, V, VEC4, EW) if (k == inv3s_instance(k##KIND, sizeof(T) == 8, L, V, VEC4, EW)) return true;
@@ -350,6 +377,18 @@ inline bool cascadem_instantiated(const CascadeMInstance& k) {
     NDWT_LIST_MC(NDWT_IS_M)
     return false;
 }
+#define NDWT_IS_N(T, L, SYN) if (k == AxisMarchInstance{sizeof(T) == 8, SYN, L}) return true;
+inline bool axis_march_instantiated(const AxisMarchInstance& k) {
+    NDWT_LIST_F32_AXIS_MARCH(NDWT_IS_N) NDWT_LIST_F64_AXIS_MARCH(NDWT_IS_N)
+    return false;
+}
+#define NDWT_IS_X(T, L, SYN, EW, VEC4) if (k == AxisXInstance{sizeof(T) == 8, SYN, VEC4, L, EW}) return true;
+inline bool axisx_instantiated(const AxisXInstance& k) {
+    NDWT_LIST_F32_AXISX(NDWT_IS_X) NDWT_LIST_F64_AXISX(NDWT_IS_X)
+    return false;
+}
+// scalars of a row one wave of the instance stores (AxisX::WX)
+constexpr int axisx_tile_width(const AxisXInstance& k) { return wave_row_width(k.syn, k.L, k.ew, k.f64, 1); }
 #define NDWT_IS_W(KIND, T, L, VEC4, WPE, EW) if (k == Fused2SInstance{k##KIND == kInv2S, sizeof(T) == 8, VEC4, L, EW, WPE}) return true;
 inline bool fused2s_instantiated(const Fused2SInstance& k) {
     NDWT_LIST_2S(NDWT_IS_W, Fwd2S) NDWT_LIST_2S(NDWT_IS_W, Inv2S)

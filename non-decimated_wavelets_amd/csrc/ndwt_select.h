@@ -245,22 +245,20 @@ inline int cascade2_rec_depth(const SelPlan& p, int Lp, int nlev) {
 // kernel), tap lengths 2 .. 8.  p.howmany = signals of the plan (0: not a batched plan); `left` = levels still to do.  Returns how many
 // the next launch takes -- the largest instantiated count <= left -- and the tap length; 0 = one launch per level.  kFwdNoCascade takes
 // the analysis off, kInvCascadeOff the synthesis (A/B runs: tools/bench1d_batch.py).
-inline int cascade1_levels(const SelPlan& p, bool inverse, int left, int* L_out) {
-    if (p.howmany < 1 || p.ndim != 1 || p.atrous || is_interleaved(p) || !p.path_auto || (p.comp != 1 && p.comp != 2)) return 0;
-    if (inverse ? p.variant_inv == kInvCascadeOff : p.variant_fwd == kFwdNoCascade) return 0;
+// what Fwd1C / Inv1C and Den1C ask of a plan alike: batched 1-D signals at the reference's dilation, rows as described above
+inline bool rows1_plan_ok(const SelPlan& p) {
+    if (p.howmany < 1 || p.ndim != 1 || p.atrous || is_interleaved(p) || !p.path_auto || (p.comp != 1 && p.comp != 2)) return false;
     const int L = p.len[0];
     const long long n1 = p.dims[0] * p.comp;              // scalars per row
-    if (L < 2 || L > 8 || n1 % 4 != 0 || n1 < 8LL * L || n1 >= (1LL << 30)) return 0;
+    return L >= 2 && L <= 8 && n1 % 4 == 0 && n1 >= 8LL * L && n1 < (1LL << 30);
+}
+inline int cascade1_levels(const SelPlan& p, bool inverse, int left, int* L_out) {
+    if (!rows1_plan_ok(p)) return 0;
+    if (inverse ? p.variant_inv == kInvCascadeOff : p.variant_fwd == kFwdNoCascade) return 0;
+    const int L = p.len[0];
     for (int n = left < 4 ? left : 4; n >= 2; --n)
         if (cascade1_instantiated({inverse, p.f64, p.comp, L, n})) { *L_out = L; return n; }
     return 0;
-}
-
-// (the earlier form, the signals as an argument of their own, for callers written against it: the same answer as with p.howmany = howmany)
-inline int cascade1_levels(const SelPlan& p, long long howmany, bool inverse, int left, int* L_out) {
-    SelPlan q = p;
-    q.howmany = howmany;
-    return cascade1_levels(q, inverse, left, L_out);
 }
 
 // ---- ndwt_denoise_bands of a batched 1-D plan in ONE launch (Den1C, ndwt_device_1d.h): dec, the per-band thresholding and rec of all
@@ -268,18 +266,9 @@ inline int cascade1_levels(const SelPlan& p, long long howmany, bool inverse, in
 // general route: dec, one shrink pass per band, rec).  Returns `level` if the whole depth fits one launch, else 0.  Either A/B switch
 // (kFwdNoCascade, kInvCascadeOff) takes it off.
 inline int denoise1_levels(const SelPlan& p, int level) {
-    if (level < 1 || level > 4) return 0;
-    if (p.howmany < 1 || p.ndim != 1 || p.atrous || is_interleaved(p) || !p.path_auto || (p.comp != 1 && p.comp != 2)) return 0;
+    if (level < 1 || level > 4 || !rows1_plan_ok(p)) return 0;
     if (p.variant_fwd == kFwdNoCascade || p.variant_inv == kInvCascadeOff) return 0;
-    const int L = p.len[0];
-    const long long n1 = p.dims[0] * p.comp;              // scalars per row
-    if (L < 2 || L > 8 || n1 % 4 != 0 || n1 < 8LL * L || n1 >= (1LL << 30)) return 0;
-    return den1_instantiated({p.f64, p.comp, L, level}) ? level : 0;
-}
-inline int denoise1_levels(const SelPlan& p, long long howmany, int level) {   // (the earlier form, as cascade1_levels')
-    SelPlan q = p;
-    q.howmany = howmany;
-    return denoise1_levels(q, level);
+    return den1_instantiated({p.f64, p.comp, p.len[0], level}) ? level : 0;
 }
 // Whether ndwt_denoise_bands takes that launch unasked.  The rule of DESIGN.md 4.3b: a data kind takes it by default only if it was
 // measured to win by more than the 5 % spread between boxes on every measured shape of the kind.  Measured on the MI355X
@@ -340,6 +329,90 @@ inline CascadeRoute cascade_route(const SelPlan& p, bool inverse, int left) {
     if (const int n = cascadem_levels(p, inverse, left, &L)) return {kCascadeMarch, n, L};
     if (const int n = cascade2_levels(p, inverse, left, &L)) return {kCascadeImage2, n, L};
     return {kCascadeNone, 0, 0};
+}
+
+// ---- the chunks of a marched axis (AxisMarch, FwdMC / InvMC): a thread marches `chunk` planes of the n, and a launch has `iblocks`
+// workgroups per chunk.  About 4096 workgroups in all, chunks of at least `floor` planes (the march-in of a chunk re-reads planes of its
+// neighbour), or of `forced` planes where that is set (ndwt_plan_set_tuning: the floor does not apply), and at most the axis.
+struct MarchChunks { int chunk, nchunks; };
+inline MarchChunks march_chunks(long long n, long long iblocks, long long floor, long long forced) {
+    long long want = (4096 + iblocks - 1) / iblocks;
+    if (want < 1) want = 1;
+    long long chunk = (n + want - 1) / want;
+    if (chunk < floor) chunk = floor;
+    if (forced > 0) chunk = forced;
+    if (chunk > n) chunk = n;
+    return {(int)chunk, (int)((n + chunk - 1) / chunk)};
+}
+
+// ---- one pass along one axis (axis_pass, ndwt_api.hip): the route every plan can fall back to -- 1-D signals, interleaved samples, the t
+// axis of 4-D, dilated levels without a sub-lattice form, long double filters, thin slabs, NDWT_PATH_GENERIC.  The array is
+// [outer][n][inner] scalars and the filter runs along n.  Three kernels, asked in this order:
+//   AxisMarch  the filter window in registers, a thread owning 4 consecutive scalars of `inner`: whole groups of 4 below the filtered index
+//              and every pointer on such a group.  A dilated periodic axis whose length is a multiple of the tap stride s, with at least
+//              L samples per sub-lattice, is s interleaved unit-stride problems: [outer][n / s][s * inner] -- the contiguous axis for
+//              s >= 4 included.  Any other dilated pass has no march.
+//   AxisX      the contiguous axis of a plan without interleaved samples, periodic at tap stride 1, up to 12 taps, rows of at least 8 L
+//              scalars: one wave per row segment of wave_row_width scalars, four to the workgroup
+//   the element-wise kernels (axis_analysis_kernel / axis_synthesis_kernel): anything, a grid-stride loop over at most 256 * 64 workgroups
+// A kernel is passed over where it has no instance (ndwt_fused_list.h) or the launch cannot express its grid, so the pick is final:
+// after it, "no instance" and "geometry mismatch" are internal errors of the launch.
+enum AxisKernel { kAxisMarch, kAxisX, kAxisPlain };
+struct AxisQuery {
+    bool f64, syn, path_auto, wrap;    // wrap: periodic; else the input starts `left` planes before output plane 0 and has n + (L - 1) stride planes (a slab)
+    int L;                             // tap length
+    long long stride;                  // tap stride
+    int comp;                          // scalars per element
+    long long inner, n, outer;         // the view, in scalars (inner carries comp and the plan's sample block); all >= 1
+    bool contiguous;                   // the filtered axis is axis 0 of a plan without interleaved samples: inner == comp
+    bool aligned;                      // every pointer the pass reads or writes lies on a group of 4 scalars
+};
+struct AxisPick {
+    AxisKernel kernel;
+    bool f64, syn;
+    int L;
+    long long grid;                    // workgroups of the launch (of 256 threads, whichever the kernel)
+    long long inner, n, n_in, ngroups; // kAxisMarch: the view it marches (a sub-lattice view where the pass is dilated) and inner / 4
+    int chunk, nchunks;                //             march_chunks
+    int ew;                            // kAxisX: scalars per element
+    bool vec4;                         //         rows of whole groups of 4 scalars on aligned pointers
+    long long row, nseg;               //         scalars of a row, wave segments per row
+    constexpr AxisMarchInstance march() const { return {f64, syn, L}; }
+    constexpr AxisXInstance axisx() const { return {f64, syn, vec4, L, ew}; }
+};
+inline AxisPick axis_select(const AxisQuery& q) {
+    AxisPick k = {kAxisPlain, q.f64, q.syn, q.L, 0, 0, 0, 0, 0, 0, 0, q.comp, false, 0, 0};
+    if (q.inner < 1 || q.n < 1 || q.outer < 1) return k;  // (nothing to do: axis_pass does not ask)
+    const long long kMaxGrid = 0x7fffffffLL;
+    long long m_inner = q.inner, m_n = q.n, m_n_in = q.wrap ? q.n : q.n + (long long)(q.L - 1) * q.stride;
+    bool march_ok = q.path_auto;
+    if (q.stride > 1) {
+        if (q.wrap && q.n % q.stride == 0 && q.n / q.stride >= q.L) { m_inner = q.inner * q.stride; m_n = q.n / q.stride; m_n_in = m_n; }
+        else march_ok = false;
+    }
+    if (march_ok && m_inner % 4 == 0 && q.aligned && axis_march_instantiated(k.march())) {
+        const long long ngroups = m_inner / 4, iblocks = (ngroups * q.outer + 255) / 256;
+        const MarchChunks c = march_chunks(m_n, iblocks, 4LL * (q.L - 1) > 8 ? 4LL * (q.L - 1) : 8, 0);
+        if (iblocks * c.nchunks <= kMaxGrid) {
+            k.kernel = kAxisMarch; k.grid = iblocks * c.nchunks;
+            k.inner = m_inner; k.n = m_n; k.n_in = m_n_in; k.ngroups = ngroups; k.chunk = c.chunk; k.nchunks = c.nchunks;
+            return k;
+        }
+    }
+    if (q.path_auto && q.contiguous && q.stride == 1 && q.wrap && q.L <= 12 && q.n * q.comp >= 8LL * q.L) {
+        const long long row = q.n * q.comp;
+        k.vec4 = row % 4 == 0 && q.aligned;
+        if (axisx_instantiated(k.axisx()) && row < (1LL << 30)) {
+            const long long WX = axisx_tile_width(k.axisx()), nseg = (row + WX - 1) / WX, grid = (q.outer * nseg + 3) / 4;
+            if (grid <= kMaxGrid) {
+                k.kernel = kAxisX; k.grid = grid; k.row = row; k.nseg = nseg;
+                return k;
+            }
+        }
+    }
+    const long long nb = (q.outer * q.n * q.inner + 255) / 256;
+    k.grid = nb > 256LL * 64 ? 256LL * 64 : nb;           // grid-stride beyond 64 blocks per CU
+    return k;
 }
 
 // ---- exact order statistics of a band's |c| (ndwt_band_select; BandHist / BandPick, ndwt_device_select.h): a radix select on the bit

@@ -118,6 +118,52 @@ def check_trace(recs, specs, what=""):
         assert any(matches(r, sp) for sp in sps), f"{what}: unexpected launch {r!r}; expected {specs}; launched:\n  {shown}"
 
 
+# ---- kernel selection on the host: csrc/ndwt_select.h behind C entry points (tests/select/select_shim.cpp), compiled with g++
+def build_select_shim(outdir):
+    import ctypes
+    import os
+    import subprocess
+    out = os.path.join(outdir, "libselect_shim.so")
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "select", "select_shim.cpp")
+    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", src, "-o", out], check=True)
+    lib = ctypes.CDLL(out)
+    lib.sel_fused3.restype = ctypes.c_char_p
+    return lib
+
+
+AXIS_MARCH, AXIS_X, AXIS_PLAIN = range(3)                      # AxisKernel of csrc/ndwt_select.h
+AXIS_QUERY = ("f64", "syn", "path_auto", "wrap", "L", "stride", "comp", "inner", "n", "outer", "contiguous", "aligned")
+AXIS_PICK = ("kernel", "grid", "inner", "n", "n_in", "ngroups", "chunk", "nchunks", "ew", "vec4", "row", "nseg", "wx", "listed")
+
+
+def axis_query(n, L=4, f64=False, syn=False, path_auto=True, wrap=True, stride=1, comp=1, inner=None, outer=1, contiguous=None, aligned=True):
+    """an AxisQuery as the 12 integers of sel_axis: one pass of `L` taps along an axis of `n` in the view [outer][n][inner] (inner in
+    scalars; default: the contiguous axis of a plan without interleaved samples, inner = comp)"""
+    inner = comp if inner is None else inner
+    contiguous = inner == comp if contiguous is None else contiguous
+    return [int(v) for v in (f64, syn, path_auto, wrap, L, stride, comp, inner, n, outer, contiguous, aligned)]
+
+
+def axis_picks(shim, queries):
+    """axis_select for every query: a list of dicts over AXIS_PICK (wx: wave_row_width of the query, listed: the instance lists hold the pick)"""
+    import ctypes
+    n = len(queries)
+    flat = (ctypes.c_longlong * (12 * n))(*[v for q in queries for v in q])
+    out = (ctypes.c_longlong * (14 * n))()
+    shim.sel_axis_many(flat, ctypes.c_longlong(n), out)
+    return [dict(zip(AXIS_PICK, out[14 * i:14 * i + 14])) for i in range(n)]
+
+
+def axis_launch(q, k):
+    """the launch record a pick stands for, as the trace spells it: (family, parameters, grid)"""
+    T, syn = ("double" if q[0] else "float"), bool(q[1])
+    if k["kernel"] == AXIS_MARCH:
+        return "AxisMarch", {"T": T, "L": q[4], "SYN": syn}, k["grid"]
+    if k["kernel"] == AXIS_X:
+        return "AxisX", {"T": T, "L": q[4], "SYN": syn, "EW": k["ew"], "VEC4": bool(k["vec4"])}, k["grid"]
+    return ("axis_synthesis_kernel" if syn else "axis_analysis_kernel"), {"T": T}, k["grid"]
+
+
 # Every kernel family of csrc/ndwt_device.h and every plain __global__ kernel of csrc/, with the instances that tell the dispatcher's
 # branches apart.  tests/test_gpu_dispatch.py::test_dispatch_coverage runs a sweep that must launch each entry (and agree with the
 # oracle); tests/test_kernel_trace.py keeps the set of families here equal to the kernels in csrc/.

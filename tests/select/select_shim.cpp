@@ -70,6 +70,24 @@ extern "C" void sel_fused2(const int* v, int* out) {
                        deep ? inv2p_instantiated(k.inv2p()) : fused2s_instantiated(k.fused2s())};
     for (int i = 0; i < 10; ++i) out[i] = r[i];
 }
+// One pass along one axis.  v: f64, syn, path_auto, wrap, L, stride, comp, inner, n, outer, contiguous, aligned
+// out: the pick in full -- kernel (AxisKernel), grid; the march's inner, n, n_in, ngroups, chunk, nchunks; AxisX's ew, vec4, row, nseg;
+// AxisX's segment width by wave_row_width; whether the instance lists (ndwt_fused_list.h) hold the instance (the element-wise kernels: 1)
+extern "C" void sel_axis(const long long* v, long long* out) {
+    const AxisQuery q = {v[0] != 0, v[1] != 0, v[2] != 0, v[3] != 0, (int)v[4], v[5], (int)v[6], v[7], v[8], v[9], v[10] != 0, v[11] != 0};
+    const AxisPick k = axis_select(q);
+    const long long r[14] = {(long long)k.kernel, k.grid, k.inner, k.n, k.n_in, k.ngroups, k.chunk, k.nchunks, k.ew, k.vec4, k.row, k.nseg,
+                             wave_row_width(q.syn, q.L, q.comp, q.f64, 1),
+                             k.kernel == kAxisMarch ? axis_march_instantiated(k.march()) : k.kernel == kAxisX ? axisx_instantiated(k.axisx()) : true};
+    for (int i = 0; i < 14; ++i) out[i] = r[i];
+}
+// the same for `count` queries of 12 values each, 14 answers each
+extern "C" void sel_axis_many(const long long* v, long long count, long long* out) {
+    for (long long i = 0; i < count; ++i) sel_axis(v + 12 * i, out + 14 * i);
+}
+// whether the lists hold AxisMarch<T, L, SYN> / AxisX<T, L, SYN, EW, VEC4>
+extern "C" int sel_axis_march_listed(int f64, int syn, int L) { return axis_march_instantiated({f64 != 0, syn != 0, L}); }
+extern "C" int sel_axisx_listed(int f64, int syn, int vec4, int L, int ew) { return axisx_instantiated({f64 != 0, syn != 0, vec4 != 0, L, ew}); }
 // whether the lists hold the Fwd2S / Inv2S instance v: inverse, f64, vec4, Lp, ew, wpe
 extern "C" int sel_fused2s_listed(const int* v) { return fused2s_instantiated({v[0] != 0, v[1] != 0, v[2] != 0, v[3], v[4], v[5]}); }
 extern "C" int sel_cascade2_rec_depth(int variant_inv) { return cascade2_rec_depth(variant_inv); }

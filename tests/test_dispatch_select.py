@@ -2,18 +2,16 @@
 (csrc/ndwt_select.h), so every row whose level-1 launch is a fused 2-D / 3-D kernel is replayed against that header through a small
 host shim (tests/select/select_shim.cpp, compiled with g++).  The GPU test reads what ran from the launch trace; this one asks the
 same code what it would run.  Every pick -- 3-D, one-level 2-D, Inv2P -- is an instance's full name, so every template parameter a row
-pins (WPE of Fwd2S / Inv2S included) is compared, and every pick is looked up in the instance lists (csrc/ndwt_fused_list.h)."""
+pins (WPE of Fwd2S / Inv2S included) is compared, and every pick is looked up in the instance lists (csrc/ndwt_fused_list.h).  The
+per-axis passes are picked the same way (axis_select): their tests are at the end of this file."""
 import ctypes
-import os
 import shutil
-import subprocess
 
 import pytest
 
 import helpers
 from test_gpu_dispatch import ROWS
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 NUM_CUS = 256
 # template parameters of a pinned kernel that the pick does not name: none -- the pick is the instance's full name
 NOT_IN_PICK = ()
@@ -29,12 +27,7 @@ WHOLE_ARRAY, SLAB_OUTER, SLAB_Z = range(3)                      # SlabMode
 def shim(tmp_path_factory):
     if not shutil.which("g++"):
         pytest.skip("no g++ to compile tests/select/select_shim.cpp")
-    out = str(tmp_path_factory.mktemp("select") / "libselect_shim.so")
-    subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-shared", "-fPIC", os.path.join(HERE, "select", "select_shim.cpp"), "-o", out],
-                   check=True)
-    lib = ctypes.CDLL(out)
-    lib.sel_fused3.restype = ctypes.c_char_p
-    return lib
+    return helpers.build_select_shim(str(tmp_path_factory.mktemp("select")))
 
 
 def _fused3(shim, q):
@@ -453,3 +446,124 @@ def test_at_most_one_cascade_claims_a_plan_and_cascade_route_names_it(shim):
                                         seen += np.bincount(a[:, 6], minlength=4)
                                         plans += 1
     assert plans >= 20000 and (seen > 0).all(), (plans, seen)                               # every family, and none, was among the answers
+
+
+# ---- one pass along one axis: axis_select (csrc/ndwt_select.h), the pick axis_pass launches
+MARCH, AXISX, PLAIN = helpers.AXIS_MARCH, helpers.AXIS_X, helpers.AXIS_PLAIN
+Q = helpers.axis_query
+
+
+def _axis(shim, *a, **kw):
+    return helpers.axis_picks(shim, [Q(*a, **kw)])[0]
+
+
+def test_axis_pick_on_both_sides_of_every_threshold(shim):
+    """written out, one-level passes, both directions: the 1-D signal on both sides of n * comp = 8 L, of rows in whole groups of 4 on
+    aligned pointers and of 12 taps; the per-axis path on request; interleaved samples in whole groups of 4 or not, aligned or not; a
+    dilated pass on both sides of n / stride >= L and of s * inner in groups of 4; a slab pass; and the two grid limits"""
+    for syn in (False, True):
+        k = _axis(shim, 32, 4, syn=syn)                         # float db2: 32 = 8 * 4
+        assert (k["kernel"], k["ew"], k["vec4"], k["row"], k["nseg"], k["grid"]) == (AXISX, 1, 1, 32, 1, 1), k
+        assert _axis(shim, 31, 4, syn=syn)["kernel"] == PLAIN
+        for k in (_axis(shim, 34, 4, syn=syn), _axis(shim, 32, 4, syn=syn, aligned=False)):
+            assert (k["kernel"], k["vec4"], k["grid"]) == (AXISX, 0, 1), k
+        k = _axis(shim, 24, 6, syn=syn, comp=2)                 # complex64 db3: 48 scalars = 8 * 6
+        assert (k["kernel"], k["ew"], k["vec4"], k["row"]) == (AXISX, 2, 1, 48), k
+        assert _axis(shim, 23, 6, syn=syn, comp=2)["kernel"] == PLAIN
+        k = _axis(shim, 96, 12, syn=syn, f64=True)              # double db6
+        assert (k["kernel"], k["row"], k["nseg"]) == (AXISX, 96, 1), k
+        assert _axis(shim, 4096, 14, syn=syn, f64=True)["kernel"] == PLAIN            # db7: no AxisX beyond 12 taps
+        k = _axis(shim, 4096, 4, syn=syn, path_auto=False)
+        assert (k["kernel"], k["grid"]) == (PLAIN, 16), k
+        k = _axis(shim, 40, 4, syn=syn, inner=4)                # interleaved samples of 4 scalars
+        assert (k["kernel"], k["inner"], k["n"], k["n_in"], k["ngroups"], k["chunk"], k["nchunks"], k["grid"]) == (MARCH, 4, 40, 40, 1, 12, 4, 4), k
+        assert _axis(shim, 40, 4, syn=syn, inner=3)["kernel"] == PLAIN
+        assert _axis(shim, 40, 4, syn=syn, inner=4, aligned=False)["kernel"] == PLAIN
+        assert _axis(shim, 32, 4, syn=syn, stride=2)["kernel"] == PLAIN               # 2 interleaved sub-lattices: no group of 4
+        k = _axis(shim, 32, 4, syn=syn, stride=4)
+        assert (k["kernel"], k["inner"], k["n"], k["n_in"], k["chunk"], k["nchunks"], k["grid"]) == (MARCH, 4, 8, 8, 8, 1, 1), k
+        assert _axis(shim, 12, 4, syn=syn, stride=4)["kernel"] == PLAIN               # sub-lattices of 3 < 4 taps
+        assert _axis(shim, 40, 4, syn=syn, inner=4, stride=2, wrap=False)["kernel"] == PLAIN
+        k = _axis(shim, 40, 4, syn=syn, inner=4, wrap=False)
+        assert (k["kernel"], k["n"], k["n_in"]) == (MARCH, 40, 43), k
+        k = _axis(shim, 40, 4, syn=syn, inner=4, outer=(1 << 39) - 256)             # 256 rows to the workgroup, one chunk: 2^31 - 1 workgroups
+        assert (k["kernel"], k["nchunks"], k["grid"]) == (MARCH, 1, (1 << 31) - 1), k
+        k = _axis(shim, 40, 4, syn=syn, inner=4, outer=(1 << 39) - 255)             # ... and one more: the march is passed over
+
+        assert (k["kernel"], k["grid"]) == (PLAIN, 256 * 64), k
+        k = _axis(shim, (1 << 30) - 4, 4, syn=syn)
+        assert (k["kernel"], k["row"]) == (AXISX, (1 << 30) - 4), k
+        assert _axis(shim, 1 << 30, 4, syn=syn)["kernel"] == PLAIN
+
+
+def _parent_axis_pass(f64, syn, path_auto, wrap, L, stride, comp, inner, n, outer, contiguous, aligned):
+    """What axis_pass ran before axis_select existed, written down from its if-chain and from the -1 / -2 answers of the two launchers
+    it tried in turn (launch_march: a switch over 2 .. 20 taps, a grid of 1 .. 2^31 - 1; launch_axisx: ew 1 or 2, a switch over 2 .. 12
+    taps, segments of the kernel's WX, the same grid limit and rows below 2^30).  Returns the launch: kernel, grid and its arguments."""
+    del f64
+    top = (1 << 31) - 1
+    m_inner, m_n, m_n_in = inner, n, (n if wrap else n + (L - 1) * stride)
+    march_ok = bool(path_auto)
+    if stride > 1:
+        if wrap and n % stride == 0 and n // stride >= L:
+            m_inner, m_n, m_n_in = inner * stride, n // stride, n // stride
+        else:
+            march_ok = False
+    if march_ok and m_inner % 4 == 0 and m_inner >= 4 and aligned:
+        ngroups = m_inner // 4
+        iblocks = (ngroups * outer + 255) // 256
+        want = max((4096 + iblocks - 1) // iblocks, 1)
+        chunk = min(max((m_n + want - 1) // want, 4 * (L - 1), 8), m_n)
+        nchunks = (m_n + chunk - 1) // chunk
+        if L in (2, 4, 6, 8, 10, 12, 14, 16, 18, 20) and 0 < iblocks * nchunks <= top:
+            return dict(kernel=MARCH, grid=iblocks * nchunks, inner=m_inner, n=m_n, n_in=m_n_in, ngroups=ngroups, chunk=chunk, nchunks=nchunks)
+    if path_auto and contiguous and stride == 1 and wrap and L <= 12 and comp in (1, 2) and n * comp >= 8 * L:
+        row = n * comp
+        vec4 = row % 4 == 0 and bool(aligned)
+        if L in (2, 4, 6, 8, 10, 12):
+            lh, rh = (L // 2, L // 2 - 1) if syn else (L // 2 - 1, L // 2)
+            wx = 4 * (64 - (lh * comp + 3) // 4 - (rh * comp + 3) // 4)            # AxisX::WX
+            nseg = (row + wx - 1) // wx
+            grid = (outer * nseg + 3) // 4
+            if 0 < grid <= top and row < (1 << 30):
+                return dict(kernel=AXISX, grid=grid, ew=comp, vec4=int(vec4), row=row, nseg=nseg)
+    return dict(kernel=PLAIN, grid=min((outer * n * inner + 255) // 256, 256 * 64))
+
+
+def test_axis_pick_is_the_parents_choice_over_a_sweep(shim):
+    """axis_select over both scalar types, both directions, both paths, periodic or not, 2 .. 20 taps and the odd lengths between, real
+    and interleaved complex, the contiguous axis or not, aligned or not, tap strides 1 .. 8, inner blocks of 1 .. 8 elements, axes on both
+    sides of 8 L / comp, of L * stride and of the multiples of the stride, and three row counts: the pick is what the parent's axis_pass
+    launched, field by field; it is in the instance lists; its chunks cover the axis exactly; its segments are wave_row_width's; and its
+    grid is one the launch can express."""
+    queries = []
+    for L in list(range(2, 21, 2)) + [3, 13, 21, 22]:
+        for comp in (1, 2):
+            for stride in (1, 2, 4, 8):
+                ns = sorted({8 * L // comp - 1, 8 * L // comp, L * stride - stride, L * stride, L * stride + 1, 8 * L * stride + 2 * stride, 4096})
+                for n in ns:
+                    for inner in (1, 2, 3, 4, 8):
+                        for outer in (1, 3, 1 << 33):
+                            for flags in range(64):
+                                f64, syn, path_auto, wrap, contiguous, aligned = [(flags >> b) & 1 for b in range(6)]
+                                queries.append([f64, syn, path_auto, wrap, L, stride, comp, comp * inner, n, outer, contiguous, aligned])
+    assert len(queries) >= 100000
+    seen = [0, 0, 0]
+    for q, k in zip(queries, helpers.axis_picks(shim, queries)):
+        want = _parent_axis_pass(*q)
+        assert all(k[f] == v for f, v in want.items()), (dict(zip(helpers.AXIS_QUERY, q)), k, want)
+        assert k["listed"], (q, k)
+        assert 0 < k["grid"] <= (1 << 31) - 1, (q, k)
+        if k["kernel"] == MARCH:
+            assert (k["nchunks"] - 1) * k["chunk"] < k["n"] <= k["nchunks"] * k["chunk"] and k["ngroups"] * 4 == k["inner"], (q, k)
+        if k["kernel"] == AXISX:
+            assert k["nseg"] == -(-k["row"] // k["wx"]), (q, k)
+        seen[k["kernel"]] += 1
+    assert all(seen), seen                                      # all three kernels were among the answers
+
+
+def test_axis_instance_lists_have_40_and_96_entries(shim):
+    march = sum(shim.sel_axis_march_listed(f64, syn, L) for f64 in (0, 1) for syn in (0, 1) for L in range(1, 25))
+    axisx = sum(shim.sel_axisx_listed(f64, syn, vec4, L, ew) for f64 in (0, 1) for syn in (0, 1) for vec4 in (0, 1) for L in range(1, 25)
+                for ew in range(1, 5))
+    assert (march, axisx) == (40, 96)

@@ -14,6 +14,7 @@ import torch
 
 import ndwt_amd as ndwt
 import ndwt_spatial as orc_c
+import helpers
 from helpers import COVERAGE, check_trace, matches
 
 pytestmark = pytest.mark.gpu
@@ -348,6 +349,153 @@ def test_trace_is_host_side_and_changes_no_result():
     with ndwt.kernel_trace() as recs2:
         pass
     assert recs2 == []                                        # turning it on cleared the log
+
+
+# ---- the per-axis passes: axis_select (csrc/ndwt_select.h) names the kernel of every pass and its grid, and axis_pass launches that.
+# Each case is a plan and the passes its dec and its rec make, in launch order, as the queries axis_pass builds for them
+# (helpers.axis_query: n, taps, then what differs from a periodic pass along the contiguous axis of float data at tap stride 1).  The
+# select shim answers the queries on the host; the trace must show exactly those launches.  The shapes are the written-out cases of
+# tests/test_dispatch_select.py::test_axis_pick_on_both_sides_of_every_threshold that a plan can express.
+def A(aid, kind, n, wn, level=1, dil="reference", inner=1, K=0, generic=False, offset=0, dec=(), rec=()):
+    return pytest.param(dict(kind=kind, n=n, wn=wn, level=level, dil=dil, inner=inner, K=K, generic=generic, offset=offset, dec=list(dec),
+                             rec=list(rec)), id=aid)
+
+
+def _both(n, L, times=1, strides=(1,), **kw):
+    """`times` levels (or the levels of `strides`, finest first) of a 1-D transform: the passes of dec, and those of rec, coarsest first"""
+    q = helpers.axis_query
+    strides = list(strides) * times
+    return dict(dec=[q(n, L, stride=s, **kw) for s in strides], rec=[q(n, L, syn=True, stride=s, **kw) for s in reversed(strides)])
+
+
+AXIS_CASES = [
+    A("1d-f32-n32", "f32", 32, "db2", level=2, **_both(32, 4, 2)),                                       # 32 = 8 L: AxisX VEC4, one segment
+    A("1d-f32-n31", "f32", 31, "db2", level=2, **_both(31, 4, 2)),                                       # element-wise
+    A("1d-f32-n34", "f32", 34, "db2", level=2, **_both(34, 4, 2)),                                       # rows of 34: AxisX VEC4 = false
+    A("1d-f32-n32-offset", "f32", 32, "db2", level=2, offset=1, **_both(32, 4, 2, aligned=False)),       # pointers off the groups: the same
+    A("1d-c64-n24", "c64", 24, "db3", level=2, **_both(24, 6, 2, comp=2)),                               # 48 scalars = 8 L: AxisX EW = 2
+    A("1d-c64-n23", "c64", 23, "db3", level=2, **_both(23, 6, 2, comp=2)),                               # element-wise
+    A("1d-f64-db6-n96", "f64", 96, "db6", level=2, **_both(96, 12, 2, f64=True)),                        # AxisX L = 12
+    A("1d-f64-db7", "f64", 128, "db7", level=2, **_both(128, 14, 2, f64=True)),                          # no AxisX beyond 12 taps
+    A("1d-generic", "f32", 64, "db2", level=2, generic=True, **_both(64, 4, 2, path_auto=False)),
+    A("inter4-n40-k1", "f32", 40, "db2", inner=4, K=1, **_both(40, 4, inner=4, outer=1)),                # AxisMarch: 4 chunks of 12
+    A("inter4-n40-k3", "f32", 40, "db2", inner=4, K=3, **_both(40, 4, inner=4, outer=3)),
+    A("inter3-n40-k1", "f32", 40, "db2", inner=3, K=1, **_both(40, 4, inner=3, outer=1)),                 # samples of 3 scalars: element-wise
+    A("inter3-n40-k3", "f32", 40, "db2", inner=3, K=3, **_both(40, 4, inner=3, outer=3)),
+    A("inter4-n40-k1-offset", "f32", 40, "db2", inner=4, K=1, offset=1, **_both(40, 4, inner=4, outer=1, aligned=False)),
+    A("inter4-n40-k3-offset", "f32", 40, "db2", inner=4, K=3, offset=1, **_both(40, 4, inner=4, outer=3, aligned=False)),
+    A("1d-atrous-n32", "f32", 32, "db2", level=3, dil="atrous", **_both(32, 4, strides=(1, 2, 4))),      # AxisX; 2 sub-lattices: element-wise; 4: AxisMarch on [8][4]
+    A("1d-atrous-n12", "f32", 12, "db2", level=3, dil="atrous", **_both(12, 4, strides=(1, 2, 4))),      # 12 < 8 L; inner 2; 3 < L samples
+    A("slab-f64-db9", "slab", 20, "db9"),                                                                # _axis_slab_case: its passes are written there
+]
+_AXIS_KINDS = {"f32": ("single", False), "c64": ("single", True), "f64": ("double", False)}
+
+
+@pytest.fixture(scope="module")
+def select_shim(tmp_path_factory):
+    return helpers.build_select_shim(str(tmp_path_factory.mktemp("select")))
+
+
+def _check_axis_launches(shim, recs, queries, what):
+    picks = helpers.axis_picks(shim, queries)
+    want = [helpers.axis_launch(q, k) for q, k in zip(queries, picks)]
+    shown = "\n  ".join(map(repr, recs))
+    assert len(recs) == len(want), f"{what}: {len(want)} passes expected; launched:\n  {shown}"
+    for r, (fam, params, grid) in zip(recs, want):
+        assert matches(r, (fam, params)) and r.grid == (grid, 1, 1) and r.block == (256, 1, 1), f"{what}: the pick is {fam} {params} grid {grid}; launched:\n  {shown}"
+
+
+def _oracle_1d(a, fn):
+    """fn on every (item, inner index) column of a [K, n, inner] array, real and imaginary part on their own: [K, n, inner, bands..]"""
+    out = None
+    for k in range(a.shape[0]):
+        for c in range(a.shape[2]):
+            v = a[k, :, c]
+            r = fn(v.real) + 1j * fn(v.imag) if np.iscomplexobj(v) else fn(v)
+            if out is None:
+                out = np.zeros(a.shape[:1] + r.shape[:1] + a.shape[2:3] + r.shape[1:], dtype=r.dtype)
+            out[k, :, c] = r
+    return out
+
+
+@pytest.mark.parametrize("case", AXIS_CASES)
+def test_axis_pass_launches_the_pick(select_shim, case):
+    """every traced launch of dec and of rec is axis_select's pick for that pass -- family, T, L, SYN, EW, VEC4 and grid -- and the values
+    hold the bounds of tests/test_gpu_parity.py against the numpy oracle: dec <= TOL, rec(dec(x)) <= 20 TOL"""
+    import ndwt_oracle as orc
+    if case["kind"] == "slab":
+        return _axis_slab_case(select_shim, case["n"])
+    prec, cplx = _AXIS_KINDS[case["kind"]]
+    ndt, tdt = _dtypes(prec, cplx)
+    n, wn, level, dil, inner, K, off = case["n"], case["wn"], case["level"], case["dil"], case["inner"], max(case["K"], 1), case["offset"]
+    kw = dict(inner=inner, howmany=case["K"]) if case["K"] else {}
+    plan = ndwt.Plan([n], [wn], torch.float32 if prec == "single" else torch.float64, cplx, True, dil, max_level=level, **kw)
+    if case["generic"]:
+        plan.set_path(True)
+    rng = np.random.default_rng(zlib.crc32(repr((case["kind"], n, wn, level, dil, inner, K)).encode()))
+    x = rng.standard_normal((K, n, inner)) + (1j * rng.standard_normal((K, n, inner)) if cplx else 0)
+    x = x.astype(ndt).astype(np.complex128 if cplx else np.float64)
+    nb, vol = ndwt.num_bands(1, level), K * n * inner
+    want = _oracle_1d(x, lambda v: orc.spatial_dec(v, [wn], level, 1, dil))          # [K, n, inner, nb]
+    xb, yb, rb = _Buf(vol, tdt, off), _Buf(nb * vol, tdt, off), _Buf(vol, tdt, off)
+    xb.view.copy_(torch.from_numpy(x.astype(ndt).reshape(-1)).cuda())
+    stream = torch.cuda.current_stream().cuda_stream
+    what = f"{case['kind']} n={n} {wn} L{level} {dil} inner={inner} K={case['K']} offset={off}"
+    with ndwt.kernel_trace() as recs:
+        plan.dec(xb.ptr(), yb.ptr(), level, stream)
+    torch.cuda.synchronize()
+    _check_axis_launches(select_shim, recs, case["dec"], f"dec {what}")
+    y = np.moveaxis(yb.view.cpu().numpy().reshape(nb, K, n, inner), 0, -1)
+    err = np.abs(y - want).max() / np.abs(want).max()
+    print(f"[axis-pick] {what}: dec {err:.3g} (bound {TOL[prec]:.3g})")
+    assert err <= TOL[prec], (what, "dec", err)
+    with ndwt.kernel_trace() as recs:
+        plan.rec(yb.ptr(), rb.ptr(), level, stream)
+    torch.cuda.synchronize()
+    _check_axis_launches(select_shim, recs, case["rec"], f"rec {what}")
+    back = rb.view.cpu().numpy().reshape(K, n, inner)
+    err = np.abs(back - x).max() / np.abs(x).max()
+    print(f"[axis-pick] {what}: rec(dec(x)) {err:.3g} (bound {20 * TOL[prec]:.3g})")
+    assert err <= 20 * TOL[prec], (what, "round trip", err)
+    for b in (yb, rb):
+        assert float(b.t[:off].abs().sum()) == 0 and float(b.t[off + b.n:].abs().sum()) == 0, (what, "stored outside the output")
+
+
+def _axis_slab_case(select_shim, N):
+    """one level of a double db9 plan (18 taps: no fused form) on a 20 x 20 x 20 slab of the outermost axis with its 17 halo planes: the
+    pass along the sharded axis is not periodic -- AxisMarch with n_in = n + L - 1 --, y marches, x runs the element-wise kernels; the
+    same checks as above.  The slab is the whole periodic volume, so its halo planes are its own planes from the other end."""
+    import ndwt_oracle as orc
+    q, L, tol = helpers.axis_query, 18, TOL["double"]
+    plan = ndwt.Plan([N, N, N], ["db9"] * 3, torch.float64, False, True, "reference", max_level=1, global_outer=N)
+    ab, aa, sb, sa = plan.slab_halo(1)
+    assert (ab, aa, sb, sa) == (8, 9, 9, 8)
+    x = np.random.default_rng(20).standard_normal((N, N, N))
+    xk = torch.from_numpy(np.ascontiguousarray(x.T)).cuda()                         # (z, y, x)
+    stream = torch.cuda.current_stream().cuda_stream
+    z, yy, xx = (dict(f64=True, inner=N * N, outer=1, wrap=False, contiguous=False), dict(f64=True, inner=N, contiguous=False), dict(f64=True))
+    xin = xk[torch.arange(-ab, N + aa) % N].contiguous()
+    bands = torch.zeros(8, N, N, N, dtype=torch.float64, device="cuda")
+    with ndwt.kernel_trace() as recs:
+        plan.analysis_level_slab(xin.data_ptr(), [bands[b].data_ptr() for b in range(8)], 1, stream)
+    torch.cuda.synchronize()
+    half = [q(N, L, outer=N, **yy), q(N, L, outer=N * N, **xx), q(N, L, outer=N * N, **xx)]
+    _check_axis_launches(select_shim, recs, [q(N, L, **z)] + half + half, "slab analysis")
+    want = orc.spatial_dec(x, ["db9"] * 3, 1, 1)
+    err = np.abs(np.transpose(bands.cpu().numpy()) - want).max() / np.abs(want).max()
+    print(f"[axis-pick] slab double db9: dec {err:.3g} (bound {tol:.3g})")
+    assert err <= tol, ("slab analysis", err)
+    cin = bands[:, torch.arange(-sb, N + sa) % N].contiguous()                      # (band, 37 planes, y, x)
+    out = torch.zeros(N, N, N, dtype=torch.float64, device="cuda")
+    with ndwt.kernel_trace() as recs:
+        plan.synthesis_level_slab([cin[b].data_ptr() for b in range(8)], out.data_ptr(), 1, stream)
+    torch.cuda.synchronize()
+    nh = N + L - 1
+    half = [q(N, L, syn=True, outer=N * nh, **xx), q(N, L, syn=True, outer=N * nh, **xx), q(N, L, syn=True, outer=nh, **yy)]
+    _check_axis_launches(select_shim, recs, half + half + [q(N, L, syn=True, **z)], "slab synthesis")
+    err = float((out - xk).abs().max()) / np.abs(x).max()
+    print(f"[axis-pick] slab double db9: rec(dec(x)) {err:.3g} (bound {20 * tol:.3g})")
+    assert err <= 20 * tol, ("slab round trip", err)
 
 
 # ---- coverage: one compact sweep of small shapes that must launch every entry of helpers.COVERAGE, every call checked against the oracle

@@ -94,8 +94,9 @@ def axis_specs(T, inverse):
 def expected(row, kind, inverse):
     """(must, may): every `must` spec is launched, and every launch is a `must` or a `may` spec.  A fused level names its kernel by
     family, scalar type, padded tap length and x step (EW = the tap stride of a dilated level, else the scalars per element); a level on
-    the per-axis passes may run any of the three per-axis kernels of its direction -- which one is axis_pass's choice (csrc/ndwt_api.hip),
-    not the selector's -- unless the row pins them (`axis`)."""
+    the per-axis passes may run any of the three per-axis kernels of its direction -- which one is the selector's answer per pass
+    (axis_select, csrc/ndwt_select.h; tests/test_dispatch_select.py checks it on the host, tests/test_gpu_dispatch.py against the
+    trace), which this restatement does not repeat -- unless the row pins them (`axis`)."""
     prec, cplx = KINDS[kind]
     T, f64, comp = ("float" if prec == "single" else "double"), prec == "double", 2 if cplx else 1
     must, per_axis = [], False
@@ -201,7 +202,7 @@ ROWS = [
     R("d-2x20x4-db1.10.2", "d", [2, 20, 4], ["db1", "db10", "db2"], 3, dil="reference"),       # an axis of 2 under 20 padded taps wraps ten times
     R("d-2d-20x2-db10.1", "d", [20, 2], ["db10", "db1"], 3, dil="reference"),
     R("d-4x2x12-db2.1.6", "d", [4, 2, 12], ["db2", "db1", "db6"], 3, dil="reference"),
-    # AxisX takes rows of n * comp >= 8 L scalars (axis_pass): one side, the threshold, the other side -- for real and complex data
+    # AxisX takes rows of n * comp >= 8 L scalars (axis_select): one side, the threshold, the other side -- for real and complex data
     *[R(f"d-1d-n{n}-db{o}", "d", [n], f"db{o}", 3, dil="reference", kinds=kinds)
       for o in (2, 6) for m, kinds in ((16 * o, REAL), (8 * o, ("c64", "c128"))) for n in (m - 1, m, m + 1)],
     # variant 11 / 11 (the cascades wherever they exist): whatever runs, the values hold
