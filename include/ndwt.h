@@ -280,7 +280,7 @@ int ndwt_denoise_bands(ndwt_plan* plan, const void* x_dev, void* out_dev, int le
  *   (band_pitch 0 = packed), for nk = 1 .. 4 ranks in one call; a rank may be given twice.  Real data: |c| exactly (the value's own
  *   bits, widened to double).  Interleaved complex data: the magnitude sqrt(re^2 + im^2) in the plan's scalar type, as the shrink
  *   computes and compares it.  A NaN orders after every number, -0 and +0 are equal.  A band is the plan's WHOLE array: all signals of
- *   a batch and all items of a stack pooled (as ndwt_shrink_bands sees it); a statistic per item is not offered.  Every plan kind
+ *   a batch and all items of a stack pooled (as ndwt_shrink_bands sees it); per item: ndwt_band_select_items, below.  Every plan kind
  *   ndwt_shrink_bands serves.  The band is read 3 times (float, complex64) or 6 times (double, complex128), whatever nk -- a radix
  *   select on the bit pattern, no sort, no copy -- and never written; the plan keeps 32 KB of device scratch for it.  Bands of 2^32
  *   elements or more: NDWT_ERR_UNSUPPORTED.
@@ -301,6 +301,45 @@ int ndwt_band_select(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int
                      double* values, void* stream);
 int ndwt_estimate_sigma_coef(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double* sigma, void* stream);
 int ndwt_estimate_sigma(ndwt_plan* plan, const void* x_dev, double* sigma, void* stream);
+/* ---- the same per ITEM: channels, coils, traces and slices do not share one noise level ----
+ * An item is one signal of ndwt_plan_create_many, one image or volume of a stack (ndwt_plan_create_axes), one of the `howmany` blocks of
+ * ndwt_plan_create_interleaved: its part of a band is one contiguous run of scalars, item j behind item j - 1.  `items` below is their
+ * number; an unbatched plan is one item, and every call here then equals its band-wide form.
+ * ndwt_band_select_items: values[j * nk + i] = the k[i]-th smallest |c| of item j's part of band `band`; key, NaN ordering, -0 / +0 and
+ *   the complex magnitude exactly as ndwt_band_select, k[i] in [0, elements of ONE item).  Synchronous like it, never writes the band,
+ *   every plan kind ndwt_shrink_bands serves; the refusals are those of ndwt_band_select and name the argument; items of 2^32 elements
+ *   or more (or 2^31 items): NDWT_ERR_UNSUPPORTED.  With at least as many items as the device has compute units, of up to 2^22 scalars
+ *   each, the whole call is ONE launch (ItemSelect: one workgroup runs the radix select of one item with its histogram in LDS; 4096 float
+ *   signals of 4096 samples: 0.25 ms), and so it is where that was measured to win: from 8 items on for items of up to
+ *   2^14 scalars, from 64 on up to 2^18.  Otherwise the band-wide passes run once per item on that item's part, with one copy back at the end.
+ *   ndwt_plan_set_variant(plan, *, 11, ...) forces the one launch, 9 the loop; real values are the same bit for bit.  The plan keeps
+ *   64 bytes of device scratch per item on top of ndwt_band_select's.
+ * ndwt_estimate_sigma_coef_items / ndwt_estimate_sigma_items: sigma[j] = the formula of ndwt_estimate_sigma_coef on item j (the same
+ *   gain, the same constants, an even count takes the mean of the two middle order statistics).  sigma: HOST, `items` doubles.
+ * thresholds (ndwt_shrink_bands_items / ndwt_denoise_bands_items): a HOST table, thresholds[j * nb + b] for item j and band b, nb =
+ *   ndwt_num_bands(filtered axes, level), the bands in the order of the coefficient array; read before the call returns.  An entry of 0
+ *   leaves that item's part of that band alone; an all-zero table launches no shrink.  A null table, a negative or NaN entry:
+ *   NDWT_ERR_INVALID_ARG, the message names the item and the band.  The arithmetic is that of ndwt_shrink_bands; every (band, item)
+ *   block is shrunk in ONE launch (ShrinkItems), with the values ndwt_shrink_bands gives on a plan of that one item.  The table reaches
+ *   the device through a pinned host buffer and a device buffer that the plan owns and only grows (nothing is allocated per call after
+ *   the first); the copy is enqueued on `stream`, and a later call waits for it before it overwrites the pinned buffer, so calls back to
+ *   back on one stream each use their own table.  That wait blocks the HOST (hipEventSynchronize) until the previous call's copy has
+ *   run, so a call is at most one call ahead of the device, and the two calls cannot be captured into a graph.  (Calls of one plan on
+ *   different streams are not ordered with each other, as for every call that uses the plan's scratch.)
+ * ndwt_shrink_bands_items: every plan kind ndwt_shrink_bands serves.  ndwt_denoise_bands_items: every plan kind ndwt_denoise_bands
+ *   serves -- dec into the plan's pitched scratch, the one shrink launch, rec.  A batched 1-D plan runs the whole call in ONE launch
+ *   under exactly the conditions of ndwt_denoise_bands (Den1C with a threshold row per signal, read from a device table of 5 scalars per
+ *   signal: unasked for float, complex64 and double, ndwt_plan_set_variant(plan, 11, 11, ...) for complex128, 9 in either slot off; x and
+ *   out 16- / 32-byte aligned and not overlapping, else the route above, silently); signal j's values are those of ndwt_denoise_bands
+ *   with row j, bit for bit.
+ * Not built: a device-pointer form of the table; thresholds per item inside the fused synthesis kernels' loads.  The band-wide calls,
+ *   the host-pointer forms, the handles, the slab entry points and the MATLAB gateway are unchanged. */
+int ndwt_band_select_items(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, int64_t band, int nk, const int64_t* k,
+                           double* values, void* stream);
+int ndwt_estimate_sigma_coef_items(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double* sigma, void* stream);
+int ndwt_estimate_sigma_items(ndwt_plan* plan, const void* x_dev, double* sigma, void* stream);
+int ndwt_shrink_bands_items(ndwt_plan* plan, void* y_dev, int64_t band_pitch, int level, const double* thresholds, int mode, void* stream);
+int ndwt_denoise_bands_items(ndwt_plan* plan, const void* x_dev, void* out_dev, int level, const double* thresholds, int mode, void* stream);
 
 /* Split complex: separate real / imaginary arrays, the layout the reference's gateway receives from MATLAB
  * (mxGetPr / mxGetPi, nd_dwt_mex.c:55-58,90-93) and hands to nd_dwt_dec / nd_dwt_rec (outR/outI, imageR/imageI,

@@ -33,7 +33,8 @@ EXPORTS = [
     "ndwt_coef_shrink", "ndwt_coef_get_host", "ndwt_coef_put_host", "ndwt_plan_create_slab_axis", "ndwt_slab_segments_strided",
     "ndwt_mplan_create_axis", "ndwt_trace_enable", "ndwt_trace_get", "ndwt_plan_create_many", "ndwt_plan_create_axes",
     "ndwt_plan_create_interleaved", "ndwt_band_gains", "ndwt_shrink_bands", "ndwt_denoise_bands", "ndwt_band_select",
-    "ndwt_estimate_sigma_coef", "ndwt_estimate_sigma",
+    "ndwt_estimate_sigma_coef", "ndwt_estimate_sigma", "ndwt_band_select_items", "ndwt_estimate_sigma_coef_items", "ndwt_estimate_sigma_items",
+    "ndwt_shrink_bands_items", "ndwt_denoise_bands_items",
 ]
 
 
@@ -119,6 +120,12 @@ def lib() -> ctypes.CDLL:
     L.ndwt_estimate_sigma_coef.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                            ctypes.c_void_p]
     L.ndwt_estimate_sigma.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
+    # the per-item forms: the signatures of their band-wide namesakes (the host arrays are longer)
+    L.ndwt_band_select_items.argtypes = L.ndwt_band_select.argtypes
+    L.ndwt_estimate_sigma_coef_items.argtypes = L.ndwt_estimate_sigma_coef.argtypes
+    L.ndwt_estimate_sigma_items.argtypes = L.ndwt_estimate_sigma.argtypes
+    L.ndwt_shrink_bands_items.argtypes = L.ndwt_shrink_bands.argtypes
+    L.ndwt_denoise_bands_items.argtypes = L.ndwt_denoise_bands.argtypes
     L.ndwt_denoise_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int]
     for f in (L.ndwt_dec_split, L.ndwt_rec_split):
         f.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p]

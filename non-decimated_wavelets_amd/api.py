@@ -225,6 +225,56 @@ class Plan:
         L.check(L.lib().ndwt_estimate_sigma(self._h, x_ptr, ctypes.byref(s), ctypes.c_void_p(stream)))
         return float(s.value)
 
+    # -- the per-item forms (include/ndwt.h): an item is one signal of a batch, one image / volume of a stack, one block of interleaved samples --
+    @property
+    def items(self):
+        """items of the plan: the signals of a batch, the images / volumes of a stack (the axes of `dims` that are not filtered), the
+        blocks of interleaved samples; 1 for one array"""
+        if self.howmany:
+            return int(self.howmany)
+        if self.axes is not None:
+            return int(np.prod([d for a, d in enumerate(self.dims) if a not in self.axes], dtype=np.int64))
+        return 1
+
+    def _item_table(self, thresholds, level):
+        nb = num_bands(self.ndim if self.axes is None else len(self.axes), level)   # (the filtered axes)
+        t = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float64))
+        if t.shape != (self.items, nb):
+            raise ValueError(f"a [{self.items}, {nb}] array of thresholds expected (items x bands of a {level}-level transform), got {list(t.shape)}")
+        return t, t.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+    def band_select_items(self, y_ptr, level, band, ks, stream=0, band_pitch=0):
+        """band_select for every item: an [items, len(ks)] array, row j the ks[i]-th smallest |c| of item j's part of the band; the ranks
+        count inside ONE item (include/ndwt.h: ndwt_band_select_items).  Synchronous."""
+        k = np.ascontiguousarray(np.asarray(ks, dtype=np.int64).reshape(-1))
+        out = np.zeros((self.items, max(k.size, 1)))
+        L.check(L.lib().ndwt_band_select_items(self._h, y_ptr, int(band_pitch), int(level), int(band), int(k.size), k.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                               out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.c_void_p(stream)))
+        return out.reshape(-1)[:self.items * k.size].reshape(self.items, k.size)
+
+    def estimate_sigma_coef_items(self, y_ptr, level, stream=0, band_pitch=0):
+        """estimate_sigma_coef for every item: a length-`items` array"""
+        s = np.zeros(self.items)
+        L.check(L.lib().ndwt_estimate_sigma_coef_items(self._h, y_ptr, int(band_pitch), int(level), s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                       ctypes.c_void_p(stream)))
+        return s
+
+    def estimate_sigma_items(self, x_ptr, stream=0):
+        """estimate_sigma for every item: a length-`items` array"""
+        s = np.zeros(self.items)
+        L.check(L.lib().ndwt_estimate_sigma_items(self._h, x_ptr, s.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.c_void_p(stream)))
+        return s
+
+    def shrink_bands_items(self, y_ptr, level, thresholds, hard=False, stream=0, band_pitch=0):
+        """in-place thresholding with an [items, num_bands] array: entry [j, b] for item j's part of band b (0 = leave it alone), all in one launch"""
+        t, tp = self._item_table(thresholds, level)
+        L.check(L.lib().ndwt_shrink_bands_items(self._h, y_ptr, int(band_pitch), int(level), tp, int(bool(hard)), ctypes.c_void_p(stream)))
+
+    def denoise_bands_items(self, x_ptr, out_ptr, level, thresholds, hard=False, stream=0):
+        """dec -> shrink_bands_items -> rec with the coefficients in the plan's scratch"""
+        t, tp = self._item_table(thresholds, level)
+        L.check(L.lib().ndwt_denoise_bands_items(self._h, x_ptr, out_ptr, int(level), tp, int(bool(hard)), ctypes.c_void_p(stream)))
+
     def denoise_host(self, x_ptr, out_ptr, level, threshold, hard=False):
         L.check(L.lib().ndwt_denoise_host(self._h, x_ptr, out_ptr, int(level), float(threshold), int(bool(hard))))
 
@@ -767,6 +817,8 @@ class _NdDwtBase:
         with torch.cuda.device(dev):
             if thr is None:
                 plan.shrink(yk.data_ptr(), level, threshold, mode == "hard", _current_stream(dev), band_pitch=pitch)
+            elif thr.ndim == 2:
+                plan.shrink_bands_items(yk.data_ptr(), level, thr, mode == "hard", _current_stream(dev), band_pitch=pitch)
             else:
                 plan.shrink_bands(yk.data_ptr(), level, thr, mode == "hard", _current_stream(dev), band_pitch=pitch)
         return self._from_device(yk, like_numpy, dev)
@@ -790,30 +842,43 @@ class _NdDwtBase:
         with torch.cuda.device(dev):
             if thr is None:
                 plan.denoise(xk.data_ptr(), out.data_ptr(), level, threshold, mode == "hard", _current_stream(dev))
+            elif thr.ndim == 2:
+                plan.denoise_bands_items(xk.data_ptr(), out.data_ptr(), level, thr, mode == "hard", _current_stream(dev))
             else:
                 plan.denoise_bands(xk.data_ptr(), out.data_ptr(), level, thr, mode == "hard", _current_stream(dev))
         return self._from_device(out, like_numpy, dev)
 
     def _band_thresholds(self, threshold, level):
-        """None for a scalar threshold (today's call), else the sequence as an array of one threshold per band"""
+        """None for a scalar threshold (today's call), else the sequence as an array of one threshold per band; a [K, bands] array of a
+        batch or stack of K > 1 items stays 2-D: a row of thresholds per item (Plan.shrink_bands_items / denoise_bands_items)"""
         if np.ndim(threshold) == 0:
             return None
         if isinstance(threshold, torch.Tensor):
             threshold = threshold.detach().cpu().numpy()
-        thr = np.asarray(threshold, dtype=np.float64).reshape(-1)
-        if thr.size != num_bands(self.NDIM, level):
-            raise ValueError(f"threshold must be a scalar or {num_bands(self.NDIM, level)} values, one per band of a {level}-level transform (got {thr.size})")
-        return thr
+        thr = np.asarray(threshold, dtype=np.float64)
+        nb = num_bands(self.NDIM, level)
+        if thr.ndim == 2 and self._items > 1 and thr.shape == (self._items, nb):
+            return np.ascontiguousarray(thr)
+        if thr.size != nb:
+            per_item = f", or a [{self._items}, {nb}] array, one row per item" if self._items > 1 else ""
+            raise ValueError(f"threshold must be a scalar or {nb} values, one per band of a {level}-level transform{per_item} (got shape {list(thr.shape)})")
+        return thr.reshape(-1)
+
+    @property
+    def _items(self):
+        """K: the signals of a batch or the items of a stack (1 without either)"""
+        return int(self.batch or self.stack or 1)
 
     def band_gains(self, level):
         """standard deviation of every band for unit-variance white input (ndwt_band_gains): thresholds = k * sigma * band_gains(level)"""
         return L.band_gains(self.sizes, self.wname[: self.NDIM], int(level), self.pres_l2_norm, self.dilation)
 
     # -- the sigma of thresholds = k * sigma * band_gains(level), estimated on the device (extension; not in the reference) --
-    def estimate_sigma(self, x):
+    def estimate_sigma(self, x, per_item=False):
         """Standard deviation of white noise in the signal `x` (Donoho and Johnstone): the median of |c| over the finest all-high-pass
         band of a level-1 dec, / 0.6745 and / that band's gain; complex x: / 1.1774, the sigma of each of the real and imaginary parts.
-        The band is the whole array (all signals of a batch, all items of a stack).  A float; the call waits for the result."""
+        The band is the whole array (all signals of a batch, all items of a stack).  A float; the call waits for the result.
+        per_item=True: one estimate per signal of the batch / item of the stack, a length-K array."""
         x = self._prep_dec_input(x)
         if list(x.shape) != self._shape:
             raise ValueError(f"input size {list(x.shape)} does not match the object's sizes {self._shape}")
@@ -821,6 +886,8 @@ class _NdDwtBase:
         xk = self._to_device_kernel_order(x, dev, self.NDIM)
         plan = self._plan(xk.is_complex(), 1, dev)
         with torch.cuda.device(dev):
+            if per_item:
+                return plan.estimate_sigma_items(xk.data_ptr(), _current_stream(dev))
             return plan.estimate_sigma(xk.data_ptr(), _current_stream(dev))
 
     def _coef_for_stats(self, y):
@@ -831,27 +898,39 @@ class _NdDwtBase:
         yk, pitch = self._coef_kernel_order(y, dev)
         return yk, pitch, level, dev, self._plan(yk.is_complex(), level, dev)
 
-    def estimate_sigma_coef(self, y):
+    def estimate_sigma_coef(self, y, per_item=False):
         """estimate_sigma from a coefficient array (what dec returns, any level): its last band is the one the estimate reads"""
         yk, pitch, level, dev, plan = self._coef_for_stats(y)
         with torch.cuda.device(dev):
+            if per_item:
+                return plan.estimate_sigma_coef_items(yk.data_ptr(), level, _current_stream(dev), band_pitch=pitch)
             return plan.estimate_sigma_coef(yk.data_ptr(), level, _current_stream(dev), band_pitch=pitch)
 
-    def band_median(self, y, band):
+    def band_median(self, y, band, per_item=False):
         """The median of |c| over band `band` of a coefficient array, exactly (an even count: the mean of the two middle order
-        statistics, as numpy.median); complex data: of the magnitude the shrink compares.  Computed on the device without a sort."""
+        statistics, as numpy.median); complex data: of the magnitude the shrink compares.  Computed on the device without a sort.
+        per_item=True: the median of every signal of the batch / item of the stack on its own, a length-K array."""
         yk, pitch, level, dev, plan = self._coef_for_stats(y)
         n = int(np.prod(yk.shape[1:]))
+        if per_item:
+            n //= plan.items
+            with torch.cuda.device(dev):
+                v = plan.band_select_items(yk.data_ptr(), level, int(band), [(n - 1) // 2] if n % 2 else [n // 2 - 1, n // 2], _current_stream(dev), band_pitch=pitch)
+            return v[:, 0].copy() if n % 2 else 0.5 * (v[:, 0] + v[:, 1])
         with torch.cuda.device(dev):
             v = plan.band_select(yk.data_ptr(), level, int(band), [(n - 1) // 2] if n % 2 else [n // 2 - 1, n // 2], _current_stream(dev), band_pitch=pitch)
         return float(v[0]) if n % 2 else 0.5 * float(v[0] + v[1])
 
-    def universal_thresholds(self, x, level, k=None):
+    def universal_thresholds(self, x, level, k=None, per_item=False):
         """k * estimate_sigma(x) * band_gains(level) with entry 0 (the approximation) set to 0: one threshold per band, as denoise(x, level,
         thresholds) and shrink(y, thresholds) take them.  k defaults to the universal sqrt(2 ln N), N = the samples of one item's
-        filtered axes."""
+        filtered axes.  per_item=True: a [K, bands] array, row j from the estimate of item j alone (column 0 zero)."""
         if k is None:
             k = float(np.sqrt(2.0 * np.log(float(np.prod(self.sizes, dtype=np.float64)))))
+        if per_item:
+            thr = float(k) * np.outer(self.estimate_sigma(x, per_item=True), self.band_gains(level))
+            thr[:, 0] = 0.0
+            return thr
         thr = float(k) * self.estimate_sigma(x) * self.band_gains(level)
         thr[0] = 0.0
         return thr

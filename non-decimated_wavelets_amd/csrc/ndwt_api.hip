@@ -18,6 +18,7 @@
 
 #include "../../include/ndwt.h"
 #include "ndwt_device.h"
+#include "ndwt_device_items.h"
 #include "ndwt_device_select.h"
 #include "ndwt_filters.h"
 #include "ndwt_fused.h"
@@ -173,6 +174,14 @@ struct ndwt_plan {
     DevBuf taps_den;                   // device tap table of the fused level-1 denoising kernel (TapsDen<float, L>), built at plan creation where it applies
     DevBuf select_buf;                 // ndwt_band_select: the device-side state and the global histogram (SelectState, then [slot][bin]); lazily allocated
     double sigma_gain = 0.0;           // ndwt_estimate_sigma*: the gain of the last level-1 band (last_band_gain), computed at the first call
+    // the threshold table of the *_items calls ([item][band], in the plan's scalar type): written into a pinned host buffer, copied to a
+    // device buffer on the call's stream; both only grow.  thr_event is recorded behind the copy: the next call waits for it before it
+    // overwrites the pinned buffer (the copy may still be reading it)
+    DevBuf thr_dev;
+    void* thr_host = nullptr;
+    size_t thr_host_bytes = 0;
+    hipEvent_t thr_event = nullptr;
+    bool thr_copy_pending = false;
     DevBuf taps_den1;                  // a batched 1-D plan whose levels can cascade: Taps1D<T, L>, the tables of both directions for Den1C
     DevBuf den_a1;                     // ndwt_denoise, fused level 1: the level-1 approximation / its reconstruction -- a scratch of its own (lazily
                                        // allocated), not `tmp`: dec_impl / rec_impl run in between and may re-allocate that one
@@ -199,6 +208,8 @@ struct ndwt_plan {
     ~ndwt_plan() {                     // (the buffers free themselves; the caller has made the plan's device current)
         for (auto& r : prof) { (void)hipEventDestroy(r.start); (void)hipEventDestroy(r.stop); }
         for (auto e : ev_pool) (void)hipEventDestroy(e);
+        if (thr_event) (void)hipEventDestroy(thr_event);
+        if (thr_host) (void)hipHostFree(thr_host);
     }
 };
 
@@ -777,7 +788,9 @@ template <typename T> static int cascade1_run(ndwt_plan* p, bool inverse, int L,
 // level first), converted as shrink_run converts them.  Returns 0, or -1: not this data -- x or out off the 16- / 32-byte groups, x and
 // out overlapping (a wave reads halo scalars that another wave's store may already have replaced), no instance, no tap table, or a grid
 // beyond 2^31 - 1 workgroups -- and the caller takes the general route
-template <typename T> static int denoise1_run(ndwt_plan* p, int L, int nlev, const T* x, T* out, const double* thr, int mode, hipStream_t s) {
+// thr_rows: null, or the device table [signals][5] of ndwt_denoise_bands_items, every row in the order of a.thr -- Den1C<.., ROWTHR>
+template <typename T> static int denoise1_run(ndwt_plan* p, int L, int nlev, const T* x, T* out, const double* thr, int mode, hipStream_t s,
+                                              const T* thr_rows = nullptr) {
     const char *xb = (const char*)x, *ob = (const char*)out;
     const size_t nbytes = (size_t)p->vol * sizeof(T);
     if (!aligned_vec4<T>(x) || !aligned_vec4<T>(out) || !(xb + nbytes <= ob || ob + nbytes <= xb)) return -1;
@@ -787,8 +800,11 @@ template <typename T> static int denoise1_run(ndwt_plan* p, int L, int nlev, con
     memset(&a, 0, sizeof a);
     a.in[0] = x;
     a.out[0] = out;
-    a.thr[0] = (T)thr[0];
-    for (int l = 0; l < nlev; ++l) a.thr[1 + l] = (T)thr[1 + (nlev - 1 - l)];   // cascade level l (0 = finest) is transform level l + 1: band 1 + (nlev - (l + 1))
+    if (thr) {
+        a.thr[0] = (T)thr[0];
+        for (int l = 0; l < nlev; ++l) a.thr[1 + l] = (T)thr[1 + (nlev - 1 - l)];   // cascade level l (0 = finest) is transform level l + 1: band 1 + (nlev - (l + 1))
+    }
+    a.thr_rows = thr_rows;
     a.hard = mode == NDWT_SHRINK_HARD;
     const Den1Instance k = {sizeof(T) == 8, (int)p->comp, L, nlev};
     const int WX = den1_tile_width(k);
@@ -797,7 +813,7 @@ template <typename T> static int denoise1_run(ndwt_plan* p, int L, int nlev, con
     a.nseg = (a.row + WX - 1) / WX;
     if ((a.outer * a.nseg + 3) / 4 > 0x7fffffffLL) return -1;
     prof_begin(p, NDWT_KERNEL_FUSED_SYNTHESIS, s);
-    const int rc = launch_den1(k, a, td, s);
+    const int rc = thr_rows ? launch_den1r(k, a, td, s) : launch_den1(k, a, td, s);
     prof_end(p, s, rc);
     if (rc > 0) return fail(NDWT_ERR_HIP, "one-launch denoise failed: %s", hipGetErrorString((hipError_t)rc));
     return rc < 0 ? -1 : 0;
@@ -1965,22 +1981,18 @@ static int select_check(const ndwt_plan* p, const void* y, int level, int64_t ba
     return NDWT_OK;
 }
 
-// select_passes(T) times: the histogram of one digit over the band, then the pick; the state stays on the device in between.  One copy
-// of the nk keys and one synchronisation of the stream end it.
-extern "C++" template <typename T> static int select_impl(ndwt_plan* p, const T* y, int nk, const int64_t* k, double* values, hipStream_t s) {
+// select_passes(T) times: the histogram of one digit over the n scalars at y, then the pick; the state `st` and the histogram `ghist`
+// (in the plan's select buffer, zero before the first pass) stay on the device in between.  Enqueued only.
+extern "C++" template <typename T> static int select_passes_run(ndwt_plan* p, const T* y, long long n, SelectState* st, unsigned* ghist, int nk, const int64_t* k, hipStream_t s) {
     constexpr bool f64 = sizeof(T) == 8;
-    int rc = p->select_buf.grow(kSelectBufBytes, "for the select state");
-    if (rc) return rc;
     void* const buf = p->select_buf.ptr;
-    SelectState* const st = (SelectState*)buf;
-    unsigned* const ghist = (unsigned*)((char*)buf + sizeof(SelectState));
-    HIP_TRY(hipMemsetAsync(buf, 0, kSelectBufBytes, s));
-    const bool vec = select_vec((unsigned long long)(uintptr_t)y, p->vol, (int)sizeof(T));
-    const int nblocks = (int)select_grid(p->vol, (int)p->comp, vec, p->num_cus, p->target_blocks);
+    int rc = 0;
+    const bool vec = select_vec((unsigned long long)(uintptr_t)y, n, (int)sizeof(T));
+    const int nblocks = (int)select_grid(n, (int)p->comp, vec, p->num_cus, p->target_blocks);
     for (int pass = 0; pass < select_passes(f64); ++pass) {
         const int shift = select_digit_shift(f64, pass), bits = select_digit_bits(f64, pass), top = shift + bits;
         const unsigned long long himask = top >= select_key_bits(f64) ? 0ULL : ((~0ULL << top) & (f64 ? ~0ULL : 0xffffffffULL));
-        const BandHistArgs<T> a = {y, p->vol, st, ghist, himask, shift, bits, nk, nblocks};
+        const BandHistArgs<T> a = {y, n, st, ghist, himask, shift, bits, nk, nblocks};
         rc = launch_band_hist(a, (int)p->comp, vec, select_agg(p->variant_fwd), buf, s);
         if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: no histogram kernel for this data kind");
         if (rc != 0) return fail(NDWT_ERR_HIP, "histogram kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
@@ -1990,6 +2002,17 @@ extern "C++" template <typename T> static int select_impl(ndwt_plan* p, const T*
         if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: no pick kernel for this data kind");
         if (rc != 0) return fail(NDWT_ERR_HIP, "pick kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     }
+    return NDWT_OK;
+}
+// the passes over the whole band; one copy of the nk keys and one synchronisation of the stream end it
+extern "C++" template <typename T> static int select_impl(ndwt_plan* p, const T* y, int nk, const int64_t* k, double* values, hipStream_t s) {
+    int rc = p->select_buf.grow(kSelectBufBytes, "for the select state");
+    if (rc) return rc;
+    void* const buf = p->select_buf.ptr;
+    SelectState* const st = (SelectState*)buf;
+    HIP_TRY(hipMemsetAsync(buf, 0, kSelectBufBytes, s));
+    rc = select_passes_run<T>(p, y, p->vol, st, (unsigned*)((char*)buf + sizeof(SelectState)), nk, k, s);
+    if (rc) return rc;
     unsigned long long keys[kSelectMaxRanks] = {};
     HIP_TRY(hipMemcpyAsync(keys, st->prefix, sizeof(unsigned long long) * (size_t)nk, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
@@ -2052,6 +2075,226 @@ int ndwt_estimate_sigma(ndwt_plan* p, const void* x, double* sigma, void* stream
     });
     if (rc) return rc;
     return ndwt_estimate_sigma_coef(p, p->coef.ptr, ndwt_band_pitch(p), 1, sigma, stream);
+}
+
+// ---- the per-item forms: a statistic and a threshold row for every item of a batched plan (include/ndwt.h; the kernels:
+// ndwt_device_items.h).  An item's part of a band is the item_vol() scalars at item * item_vol(); an unbatched plan is one item. ----
+// select_check with the ranks inside ONE item, and the item's size against the 32-bit counters
+static int select_items_check(const ndwt_plan* p, const void* y, int level, int64_t band, int nk, const int64_t* k, const double* values) {
+    int rc = check_level(p, level);
+    if (rc) return rc;
+    if (!y) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (y_dev)");
+    if (!k) return fail(NDWT_ERR_INVALID_ARG, "null rank array (k)");
+    if (!values) return fail(NDWT_ERR_INVALID_ARG, "null output pointer (values)");
+    const long long nb = ndwt_num_bands(p->ndim, level), N = p->item_vol() / p->comp;
+    if (band < 0 || band >= nb) return fail(NDWT_ERR_INVALID_ARG, "band %lld outside 0..%lld of a level-%d coefficient array", (long long)band, nb - 1, level);
+    if (nk < 1 || nk > kSelectMaxRanks) return fail(NDWT_ERR_INVALID_ARG, "nk = %d: 1..%d ranks per call", nk, kSelectMaxRanks);
+    for (int i = 0; i < nk; ++i)
+        if (k[i] < 0 || k[i] >= N) return fail(NDWT_ERR_INVALID_ARG, "k[%d] = %lld outside [0, %lld), the elements of one item of a band", i, (long long)k[i], N);
+    if (!select_fits(N)) return fail(NDWT_ERR_UNSUPPORTED, "items of %lld elements: the order statistics count in 32 bits (fewer than 2^32 elements)", N);
+    if (p->items() > 0x7fffffffLL) return fail(NDWT_ERR_UNSUPPORTED, "%lld items: the per-item order statistics serve fewer than 2^31", p->items());
+    return NDWT_OK;
+}
+
+// By select_items_route: ItemSelect on `items` workgroups, or the passes of select_impl once per item.  Either way the keys of every
+// item stay in the plan's select buffer behind the band-wide state and histogram; one copy and one synchronisation of the stream end it.
+extern "C++" template <typename T> static int select_items_impl(ndwt_plan* p, const T* y, int nk, const int64_t* k, double* values, hipStream_t s) {
+    const long long items = p->items(), n = p->item_vol();
+    static_assert(sizeof(SelectState) >= sizeof(unsigned long long) * kSelectMaxRanks, "a state per item holds the keys of either route");
+    int rc = p->select_buf.grow(kSelectBufBytes + (size_t)items * sizeof(SelectState), "for the select state");
+    if (rc) return rc;
+    char* const buf = (char*)p->select_buf.ptr;
+    char* const per_item = buf + kSelectBufBytes;
+    const bool one = select_items_route(n, items, p->num_cus, p->variant_inv) == kItemsOneLaunch;
+    const size_t stride = one ? sizeof(unsigned long long) * kSelectMaxRanks : sizeof(SelectState);
+    if (one) {
+        ItemSelectArgs<T> a = {y, n, (unsigned long long*)per_item, {0, 0, 0, 0}, nk};
+        for (int i = 0; i < nk; ++i) a.k[i] = (unsigned)k[i];
+        rc = launch_item_select(a, (int)p->comp, select_vec((unsigned long long)(uintptr_t)y, n, (int)sizeof(T)), (int)items, buf, s);
+        if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: no per-item select kernel for this data kind");
+        if (rc != 0) return fail(NDWT_ERR_HIP, "per-item select kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    } else {
+        HIP_TRY(hipMemsetAsync(buf, 0, kSelectBufBytes + (size_t)items * sizeof(SelectState), s));
+        for (long long j = 0; j < items; ++j) {
+            rc = select_passes_run<T>(p, y + j * n, n, (SelectState*)per_item + j, (unsigned*)(buf + sizeof(SelectState)), nk, k, s);
+            if (rc) return rc;
+        }
+    }
+    std::vector<unsigned long long> keys((size_t)items * stride / sizeof(unsigned long long));
+    HIP_TRY(hipMemcpyAsync(keys.data(), per_item, (size_t)items * stride, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (long long j = 0; j < items; ++j)
+        for (int i = 0; i < nk; ++i) {
+            typename SelectKey<T>::type key = (typename SelectKey<T>::type)keys[(size_t)j * (stride / sizeof(unsigned long long)) + i];
+            T v;
+            memcpy(&v, &key, sizeof v);
+            values[j * nk + i] = (double)v;
+        }
+    return NDWT_OK;
+}
+
+int ndwt_band_select_items(ndwt_plan* p, const void* y, int64_t band_pitch, int level, int64_t band, int nk, const int64_t* k, double* values, void* stream) {
+    int rc = select_items_check(p, y, level, band, nk, k, values);
+    if (rc) return rc;
+    long long bs = 0;
+    rc = pitch_scalars(p, band_pitch, &bs);
+    if (rc) return rc;
+    return on_device(p, [&](auto t) { return select_items_impl(p, (const decltype(t)*)y + band * bs, nk, k, values, (hipStream_t)stream); });
+}
+
+int ndwt_estimate_sigma_coef_items(ndwt_plan* p, const void* y, int64_t band_pitch, int level, double* sigma, void* stream) {
+    int rc = check_level(p, level);
+    if (rc) return rc;
+    if (!y) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (y_dev)");
+    if (!sigma) return fail(NDWT_ERR_INVALID_ARG, "null output pointer (sigma)");
+    const long long N = p->item_vol() / p->comp, items = p->items();
+    const int64_t k[2] = {(N - 1) / 2, N / 2};            // the middle, or the two middle order statistics of an even count
+    const int nk = N % 2 ? 1 : 2;
+    std::vector<double> v((size_t)items * nk);
+    rc = ndwt_band_select_items(p, y, band_pitch, level, ndwt_num_bands(p->ndim, level) - 1, nk, k, v.data(), stream);
+    if (rc) return rc;
+    if (p->sigma_gain == 0.0) p->sigma_gain = last_band_gain(p);
+    for (long long j = 0; j < items; ++j) {
+        const double m = nk == 2 ? 0.5 * (v[2 * j] + v[2 * j + 1]) : v[j];
+        sigma[j] = m / (p->complexity == NDWT_REAL ? 0.6744897501960817 : 1.1774100225154747) / p->sigma_gain;
+    }
+    return NDWT_OK;
+}
+
+int ndwt_estimate_sigma_items(ndwt_plan* p, const void* x, double* sigma, void* stream) {
+    int rc = check_level(p, 1);
+    if (rc) return rc;
+    if (!x) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (x_dev)");
+    if (!sigma) return fail(NDWT_ERR_INVALID_ARG, "null output pointer (sigma)");
+    rc = on_device(p, [&](auto t) {
+        decltype(t)* coef = nullptr;
+        long long bs = 0;
+        return dec_scratch(p, (const decltype(t)*)x, 1, (hipStream_t)stream, &coef, &bs);
+    });
+    if (rc) return rc;
+    return ndwt_estimate_sigma_coef_items(p, p->coef.ptr, ndwt_band_pitch(p), 1, sigma, stream);
+}
+
+// bands_check for a table [items][nb]
+static int items_table_check(const ndwt_plan* p, int level, const double* thr, int mode) {
+    int rc = check_level(p, level);
+    if (rc) return rc;
+    if (!thr) return fail(NDWT_ERR_INVALID_ARG, "null thresholds");
+    const long long nb = ndwt_num_bands(p->ndim, level), items = p->items();
+    for (long long j = 0; j < items; ++j)
+        for (long long b = 0; b < nb; ++b)
+            if (!(thr[j * nb + b] >= 0.0)) return fail(NDWT_ERR_INVALID_ARG, "threshold of item %lld, band %lld must be >= 0", j, b);
+    if (mode != NDWT_SHRINK_SOFT && mode != NDWT_SHRINK_HARD) return fail(NDWT_ERR_INVALID_ARG, "mode must be NDWT_SHRINK_SOFT or NDWT_SHRINK_HARD");
+    if (items > 0x7fffffffLL) return fail(NDWT_ERR_UNSUPPORTED, "%lld items: the per-item thresholds serve fewer than 2^31", items);
+    return NDWT_OK;
+}
+
+// The table in the plan's scalar type (converted as shrink_run converts its threshold) on the device, by way of the plan's pinned buffer:
+// the copy is enqueued on `s`, in order with the kernels of this and of earlier calls on that stream that read the device buffer.
+extern "C++" template <typename T> static int items_table_upload(ndwt_plan* p, const double* thr, size_t count, hipStream_t s, const T** table) {
+    const size_t bytes = count * sizeof(T);
+    if (p->thr_copy_pending) {                            // the previous call's copy has left the pinned buffer before it is overwritten
+        HIP_TRY(hipEventSynchronize(p->thr_event));
+        p->thr_copy_pending = false;
+    }
+    if (bytes > p->thr_host_bytes) {
+        if (p->thr_host) HIP_TRY(hipHostFree(p->thr_host));
+        p->thr_host = nullptr;
+        p->thr_host_bytes = 0;
+        const size_t want = bytes < 4096 ? 4096 : bytes;
+        const hipError_t e = hipHostMalloc(&p->thr_host, want, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            p->thr_host = nullptr;
+            return fail(NDWT_ERR_ALLOC, "hipHostMalloc(%zu bytes) for the threshold table failed: %s", want, hipGetErrorString(e));
+        }
+        p->thr_host_bytes = want;
+    }
+    if (!p->thr_event) HIP_TRY(hipEventCreateWithFlags(&p->thr_event, hipEventDisableTiming));
+    const int rc = p->thr_dev.grow(p->thr_host_bytes, "for the threshold table");
+    if (rc) return rc;
+    T* const h = (T*)p->thr_host;
+    for (size_t i = 0; i < count; ++i) h[i] = (T)thr[i];
+    HIP_TRY(hipMemcpyAsync(p->thr_dev.ptr, h, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(p->thr_event, s));
+    p->thr_copy_pending = true;
+    *table = (const T*)p->thr_dev.ptr;
+    return NDWT_OK;
+}
+
+// ShrinkItems on every (band, item) block in one launch; an all-zero table launches (and uploads) nothing.  Past 2^31 - 1 workgroups:
+// one launch per band
+extern "C++" template <typename T> static int shrink_items_impl(ndwt_plan* p, T* y, long long bs, int level, const double* thr, int mode, hipStream_t s) {
+    const long long nb = ndwt_num_bands(p->ndim, level), items = p->items(), n = p->item_vol();
+    bool any = false;
+    for (long long i = 0; i < nb * items && !any; ++i) any = thr[i] != 0.0;
+    if (!any) return NDWT_OK;
+    const T* table = nullptr;
+    int rc = items_table_upload<T>(p, thr, (size_t)(nb * items), s, &table);
+    if (rc) return rc;
+    const bool vec = aligned_vec4<T>(y) && bs % 4 == 0 && n % 4 == 0;
+    const bool per_band = nb * items > 0x7fffffffLL;      // (items < 2^31: a band alone always fits)
+    const long long chunks = shrink_items_chunks(n, (int)p->comp, vec, per_band ? 1 : nb, items, p->num_cus);
+    ShrinkItemsArgs<T> a = {y, bs, n, table, items, (int)nb, 0, (int)nb, (int)chunks, mode};
+    for (int b = 0; b < (per_band ? (int)nb : 1); ++b) {
+        if (per_band) { a.band0 = b; a.nbands = 1; }
+        rc = launch_shrink_items(a, (int)p->comp, vec, table, s);
+        if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: no per-item shrink kernel for this data kind or grid");
+        if (rc != 0) return fail(NDWT_ERR_HIP, "per-item shrink kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    return NDWT_OK;
+}
+
+int ndwt_shrink_bands_items(ndwt_plan* p, void* y, int64_t band_pitch, int level, const double* thresholds, int mode, void* stream) {
+    int rc = items_table_check(p, level, thresholds, mode);
+    if (rc) return rc;
+    if (!y) return fail(NDWT_ERR_INVALID_ARG, "null data pointer");
+    long long bs = 0;
+    rc = pitch_scalars(p, band_pitch, &bs);
+    if (rc) return rc;
+    return on_device(p, [&](auto t) { return shrink_items_impl(p, (decltype(t)*)y, bs, level, thresholds, mode, (hipStream_t)stream); });
+}
+
+// A batched 1-D plan: the whole depth in one launch with a threshold row per signal, under the conditions of ndwt_denoise_bands
+// (denoise1_wanted / denoise1_levels, the pointers as denoise1_run asks) where the ROWTHR instance exists.  Else, and on every other plan
+// kind: dec into the plan's pitched scratch, ShrinkItems, rec (no thresholding in the synthesis loads)
+int ndwt_denoise_bands_items(ndwt_plan* p, const void* x, void* out, int level, const double* thresholds, int mode, void* stream) {
+    int rc = items_table_check(p, level, thresholds, mode);
+    if (rc) return rc;
+    if (!x || !out) return fail(NDWT_ERR_INVALID_ARG, "null data pointer");
+    HIP_TRY(hipSetDevice(p->device));
+    {
+        const SelPlan sp = sel(p);
+        const int n = denoise1_wanted(sp) ? denoise1_levels(sp, level) : 0;
+        if (n && den1r_instantiated({sp.f64, sp.comp, sp.len[0], n})) {
+            rc = with_scalar(p, [&](auto t) {
+                typedef decltype(t) T;
+                const T *xt = (const T*)x, *ot = (const T*)out;
+                const size_t vol = (size_t)p->vol;
+                if (!aligned_vec4<T>(x) || !aligned_vec4<T>(out) || !(xt + vol <= ot || ot + vol <= xt)) return -1;   // (before the table is uploaded)
+                // the rows in the order of Den1CArgs::thr: the approximation, then the detail bands finest cascade level first
+                const long long items = p->items(), nb = n + 1;
+                std::vector<double> rows((size_t)items * 5, 0.0);
+                for (long long j = 0; j < items; ++j) {
+                    rows[5 * j] = thresholds[j * nb];
+                    for (int l = 0; l < n; ++l) rows[5 * j + 1 + l] = thresholds[j * nb + 1 + (n - 1 - l)];
+                }
+                const T* table = nullptr;
+                const int rc = items_table_upload<T>(p, rows.data(), rows.size(), (hipStream_t)stream, &table);
+                if (rc) return rc;
+                return denoise1_run<T>(p, p->filt[0].len, n, xt, (T*)out, nullptr, mode, (hipStream_t)stream, table);
+            });
+            if (rc != -1) return rc;                      // -1: not this data -- the general route, silently
+        }
+    }
+    return on_device(p, [&](auto t) {
+        typedef decltype(t) T;
+        T* coef = nullptr;
+        long long bs = 0;
+        int rc = dec_scratch<T>(p, (const T*)x, level, (hipStream_t)stream, &coef, &bs);
+        if (rc == NDWT_OK) rc = shrink_items_impl<T>(p, coef, bs, level, thresholds, mode, (hipStream_t)stream);
+        if (rc == NDWT_OK) rc = rec_impl<T>(p, coef, bs, (T*)out, level, kNoShrink, (hipStream_t)stream);
+        return rc;
+    });
 }
 
 int ndwt_denoise_host(ndwt_plan* p, const void* x, void* out, int level, double threshold, int mode) {

@@ -142,15 +142,19 @@ template <typename T, int L_, int NLEV_, int EW_ = 1, int WPE_ = 4> struct Inv1C
 template <typename T> struct Den1CArgs : Fused1CArgs<T> {   // in[0]: the signals; out[0]: the result
     T thr[5];              // [0] the approximation of the last level, [1 + l] the detail band of cascade level l (0 = finest); 0: the band is left alone
     int hard;
+    const T* thr_rows = nullptr;   // Den1C<.., ROWTHR = true>: a device table [outer][5], row j the thr[] of signal j (ndwt_denoise_bands_items)
 };
 template <typename T, int L> struct Taps1D {              // both directions of a 1-D plan, as the host appends them (axis 0 is used)
     Taps3<T, L> ana, syn;
 };
 
-template <typename T, int L_, int NLEV_, int EW_ = 1, int WPE_ = 4> struct Den1C {
+// ROWTHR: the thresholds of a wave are those of its signal, read from a.thr_rows (five loads per wave, the row number is the wave's);
+// false: a.thr for every signal
+template <typename T, int L_, int NLEV_, int EW_ = 1, int WPE_ = 4, bool ROWTHR_ = false> struct Den1C {
     typedef WaveRowGeom<T, L_, EW_, false> WA;
     typedef WaveRowGeom<T, L_, EW_, true> WS;
     static constexpr int L = L_, NLEV = NLEV_, EW = EW_, NT = 256, WPE = WPE_;
+    static constexpr bool ROWTHR = ROWTHR_;
     static constexpr int HL = NLEV * (WA::GL + WS::GL), HR = NLEV * (WA::GR + WS::GR);
     static constexpr int WX = 4 * ((64 - HL - HR) / WA::LPL * WA::LPL);   // output scalars per wave segment
     static_assert(NLEV >= 1 && NLEV <= 4, "one to four levels per launch");
@@ -177,6 +181,16 @@ template <typename T, int L_, int NLEV_, int EW_ = 1, int WPE_ = 4> struct Den1C
         st.base = o * a.row;
         st.xg = (int)(sg * WX) + 4 * (tid % 64 - HL);
         return st.base + modn64(st.xg, a.row);            // (rows are whole groups of 4: a group never straddles the wrap)
+    }
+    // a value every lane of the wave holds alike: in scalar registers on the device, so that what is loaded through it is a scalar load
+    static NDWT_DEV long long wave_uniform(long long v) {
+#ifndef NDWT_HOST_EMU
+        const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(unsigned long long)v);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)((unsigned long long)v >> 32));
+        return (long long)(((unsigned long long)hi << 32) | lo);
+#else
+        return v;
+#endif
     }
     // this lane stores: inside the window valid after the last synthesis level, and inside the row
     static NDWT_DEV bool stores(const State& st, const Args& a, int tid) {
@@ -215,11 +229,21 @@ template <typename T, int L_, int NLEV_, int EW_ = 1, int WPE_ = 4> struct Den1C
             ex.each([&](int tid, State& st) __attribute__((always_inline)) { ana_level<lev>(ex, st, tp, tid); });
             ex.each([&](int, State& st) __attribute__((always_inline)) { st.cur = st.nxt; });
         NDWT_SEND
-        ex.each([&](int, State& st) __attribute__((always_inline)) {
-            if (a.thr[0] > T(0)) shrink4(st.cur, a.thr[0], a.hard);
-            NDWT_SFOR(lev, NLEV)
-                if (a.thr[1 + lev] > T(0)) shrink4(st.det[lev], a.thr[1 + lev], a.hard);
-            NDWT_SEND
+        ex.each([&](int tid, State& st) __attribute__((always_inline)) {
+            if constexpr (ROWTHR) {
+                // the row of place(): the wave's (row, segment) item, the waves past the last item clamped onto it -- inside the table
+                const long long item = (long long)bid * (NT / 64) + tid / 64, nitems = a.outer * a.nseg;
+                const T* const thr = a.thr_rows + 5 * wave_uniform((item < nitems ? item : nitems - 1) / a.nseg);
+                if (thr[0] > T(0)) shrink4(st.cur, thr[0], a.hard);
+                NDWT_SFOR(lev, NLEV)
+                    if (thr[1 + lev] > T(0)) shrink4(st.det[lev], thr[1 + lev], a.hard);
+                NDWT_SEND
+            } else {
+                if (a.thr[0] > T(0)) shrink4(st.cur, a.thr[0], a.hard);
+                NDWT_SFOR(lev, NLEV)
+                    if (a.thr[1 + lev] > T(0)) shrink4(st.det[lev], a.thr[1 + lev], a.hard);
+                NDWT_SEND
+            }
         });
         NDWT_SFOR(c, NLEV)
             ex.each([&](int tid, State& st) __attribute__((always_inline)) { syn_level<NLEV - 1 - c>(ex, st, a, tp, tid); });

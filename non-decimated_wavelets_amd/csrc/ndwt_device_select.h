@@ -205,60 +205,76 @@ struct BandPickArgs {
     int nk, pass, shift;
 };
 
-// one workgroup: per slot, the digit at which the cumulative count of its owner's histogram passes the slot's rank
+// The pick of one pass, once: BandPick runs it on the plan's global histogram and state, ItemSelect (ndwt_device_items.h) on its
+// workgroup's own in LDS.  Per slot, the digit at which the cumulative count of its owner's histogram passes the slot's rank; the
+// extended prefix, the rank that remains inside that digit and the new owner go to `state`.  kPickThreads threads, three phases with
+// the executor's barrier between them; the caller's State carries own[kSelectMaxRanks] across them.  rank_of(r): the rank slot r looks
+// for in this pass (the first pass: the one asked for; afterwards the state's).  ZERO: the histogram of every slot that was counted is
+// zero again for the next pass.
+constexpr int kPickThreads = 256, kPickPer = kSelectBins / kPickThreads;
+struct PickScratch {
+    unsigned part[kSelectMaxRanks][kPickThreads];
+    unsigned long long newp[kSelectMaxRanks];
+    unsigned newr[kSelectMaxRanks];
+};
+template <bool ZERO, class State, class Exec, class RankOf>
+NDWT_DEV void pick_scan(Exec& ex, PickScratch& sh, unsigned* hist, SelectState* state, RankOf&& rank_of, int nk, int shift) {
+    constexpr int NT = kPickThreads, PER = kPickPer;
+    ex.each([&](int tid, State& st) __attribute__((always_inline)) {
+        for (int r = 0; r < kSelectMaxRanks; ++r) {
+            st.own[r] = r < nk ? state->owner[r] : -1;
+            if (r >= nk) continue;
+            unsigned sum = 0;
+            for (int j = 0; j < PER; ++j) sum += hist[st.own[r] * kSelectBins + tid * PER + j];
+            sh.part[r][tid] = sum;
+        }
+    });
+    ex.barrier();
+    ex.each([&](int tid, State& st) __attribute__((always_inline)) {
+        if (tid >= nk) return;
+        const int r = tid;
+        const unsigned want = rank_of(r);
+        unsigned cum = 0;
+        int c = 0;
+        for (; c < NT - 1; ++c) {                         // (the rank lies below the total by construction: the last chunk takes what is left)
+            if (cum + sh.part[r][c] > want) break;
+            cum += sh.part[r][c];
+        }
+        int bin = c * PER;
+        for (int j = 0; j < PER - 1; ++j, ++bin) {
+            const unsigned v = hist[st.own[r] * kSelectBins + bin];
+            if (cum + v > want) break;
+            cum += v;
+        }
+        sh.newp[r] = state->prefix[r] | ((unsigned long long)bin << shift);
+        sh.newr[r] = want - cum;
+    });
+    ex.barrier();
+    ex.each([&](int tid, State& st) __attribute__((always_inline)) {
+        if (ZERO)
+            for (int r = 0; r < kSelectMaxRanks; ++r)
+                if (r < nk && st.own[r] == r)
+                    for (int j = 0; j < PER; ++j) hist[r * kSelectBins + tid * PER + j] = 0;
+        if (tid >= nk) return;
+        int o = tid;
+        for (int r = tid - 1; r >= 0; --r)
+            if (sh.newp[r] == sh.newp[tid]) o = r;
+        state->prefix[tid] = sh.newp[tid];
+        state->rank[tid] = sh.newr[tid];
+        state->owner[tid] = o;
+    });
+}
+
+// one workgroup: pick_scan on the plan's select buffer
 template <typename T> struct BandPick {
-    static constexpr int NT = 256, WPE = 1, PER = kSelectBins / NT;
+    static constexpr int NT = kPickThreads, WPE = 1, PER = kPickPer;
     typedef BandPickArgs Args;
     typedef SelectTaps Taps;
-    struct Shared {
-        unsigned part[kSelectMaxRanks][NT];
-        unsigned long long newp[kSelectMaxRanks];
-        unsigned newr[kSelectMaxRanks];
-    };
+    typedef PickScratch Shared;
     struct State { int own[kSelectMaxRanks]; };
     template <class Exec> static NDWT_DEV void block(Exec& ex, Shared& sh, const Args& a, const Taps&, int) {
-        ex.each([&](int tid, State& st) __attribute__((always_inline)) {
-            for (int r = 0; r < kSelectMaxRanks; ++r) {
-                st.own[r] = r < a.nk ? a.st->owner[r] : -1;
-                if (r >= a.nk) continue;
-                unsigned sum = 0;
-                for (int j = 0; j < PER; ++j) sum += a.ghist[st.own[r] * kSelectBins + tid * PER + j];
-                sh.part[r][tid] = sum;
-            }
-        });
-        ex.barrier();
-        ex.each([&](int tid, State& st) __attribute__((always_inline)) {
-            if (tid >= a.nk) return;
-            const int r = tid;
-            const unsigned rank = a.pass == 0 ? a.k[r] : a.st->rank[r];
-            unsigned cum = 0;
-            int c = 0;
-            for (; c < NT - 1; ++c) {                     // (the rank lies below the total by construction: the last chunk takes what is left)
-                if (cum + sh.part[r][c] > rank) break;
-                cum += sh.part[r][c];
-            }
-            int bin = c * PER;
-            for (int j = 0; j < PER - 1; ++j, ++bin) {
-                const unsigned v = a.ghist[st.own[r] * kSelectBins + bin];
-                if (cum + v > rank) break;
-                cum += v;
-            }
-            sh.newp[r] = a.st->prefix[r] | ((unsigned long long)bin << a.shift);
-            sh.newr[r] = rank - cum;
-        });
-        ex.barrier();
-        ex.each([&](int tid, State& st) __attribute__((always_inline)) {
-            for (int r = 0; r < kSelectMaxRanks; ++r)     // the histogram of every slot that was counted is zero again for the next pass
-                if (r < a.nk && st.own[r] == r)
-                    for (int j = 0; j < PER; ++j) a.ghist[r * kSelectBins + tid * PER + j] = 0;
-            if (tid >= a.nk) return;
-            int o = tid;
-            for (int r = tid - 1; r >= 0; --r)
-                if (sh.newp[r] == sh.newp[tid]) o = r;
-            a.st->prefix[tid] = sh.newp[tid];
-            a.st->rank[tid] = sh.newr[tid];
-            a.st->owner[tid] = o;
-        });
+        pick_scan<true, State>(ex, sh, a.ghist, a.st,
+                               [&](int r) __attribute__((always_inline)) { return a.pass == 0 ? a.k[r] : a.st->rank[r]; }, a.nk, a.shift);
     }
 };
 

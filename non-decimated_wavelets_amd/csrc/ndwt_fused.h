@@ -48,6 +48,9 @@ int launch_cascade1(const Cascade1Instance& k, const Fused1CArgs<double>& a, con
 // unit has the instance, -2: the launch geometry is not the instance's tile, or the grid is too large.
 int launch_den1(const Den1Instance& k, const Den1CArgs<float>& a, const void* taps_dev, hipStream_t s);
 int launch_den1(const Den1Instance& k, const Den1CArgs<double>& a, const void* taps_dev, hipStream_t s);
+// ... with a threshold row per signal, a.thr_rows (ndwt_denoise1r_*.hip: NDWT_LIST_*_DEN1R)
+int launch_den1r(const Den1Instance& k, const Den1CArgs<float>& a, const void* taps_dev, hipStream_t s);
+int launch_den1r(const Den1Instance& k, const Den1CArgs<double>& a, const void* taps_dev, hipStream_t s);
 
 // Two to four levels of one strided axis inside one march (FwdMC / InvMC), the instance named in full (ndwt_fused_list.h:
 // CascadeMInstance, the table cascadem_levels reads); lo / hi: the kernel-form taps of the direction, length k.L.  -1: no unit has the

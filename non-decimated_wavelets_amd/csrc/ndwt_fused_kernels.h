@@ -157,6 +157,11 @@ template <class K> int launch_select_k(const typename K::Args& a, int nblocks, c
         static_assert(Den1C<T, LL, NLEV, EWV>::WX == den1_tile_width(LL, EWV, sizeof(T) == 8, NLEV), "tile width"); \
         return launch_wave_rows_k<Den1C<T, LL, NLEV, EWV>>(a, taps_dev, s);                                  \
     }
+#define NDWT_LAUNCH_DR(T, EWV, LL, NLEV)                                                                 \
+    if (k == Den1Instance{sizeof(T) == 8, EWV, LL, NLEV}) {                                                  \
+        static_assert(Den1C<T, LL, NLEV, EWV, 4, true>::WX == den1_tile_width(LL, EWV, sizeof(T) == 8, NLEV), "tile width"); \
+        return launch_wave_rows_k<Den1C<T, LL, NLEV, EWV, 4, true>>(a, taps_dev, s);                         \
+    }
 #define NDWT_LAUNCH_M(KIND, T, LL, NLEV) \
     if (k == CascadeMInstance{k##KIND == kInvMC, sizeof(T) == 8, LL, NLEV}) return launch_cascadem_k<KIND<T, LL, NLEV>>(a, lo, hi, s);
 #define NDWT_LAUNCH_N(T, LL, SYN) \

@@ -300,6 +300,17 @@ constexpr bool operator==(const AxisXInstance& a, const AxisXInstance& b) {
     NDWT_D1234(D, double, 2, 2) NDWT_D1234(D, double, 2, 4) D(double, 2, 6, 1) D(double, 2, 6, 2) D(double, 2, 6, 3)      \
     D(double, 2, 8, 1) D(double, 2, 8, 2)
 #define NDWT_LIST_DEN1(D) NDWT_LIST_F32_DEN1(D) NDWT_LIST_C64_DEN1(D) NDWT_LIST_F64_DEN1(D) NDWT_LIST_C128_DEN1(D)
+// ... and with a threshold row per signal (Den1C<.., ROWTHR = true>; ndwt_denoise_bands_items, launch units ndwt_denoise1r_*.hip): a table
+// of its own, the same (T, EW, L, NLEV) less the same three complex128 instances -- the row's thresholds live in scalar registers, and
+// every listed instance builds with the VGPRs of its uniform twin and no scratch.  An instance that spilled where its
+// twin does not would leave THIS table only.
+#define NDWT_LIST_F32_DEN1R(D) NDWT_D1_KIND(D, float, 1)
+#define NDWT_LIST_C64_DEN1R(D) NDWT_D1_KIND(D, float, 2)
+#define NDWT_LIST_F64_DEN1R(D) NDWT_D1_KIND(D, double, 1)
+#define NDWT_LIST_C128_DEN1R(D)                                                                                           \
+    NDWT_D1234(D, double, 2, 2) NDWT_D1234(D, double, 2, 4) D(double, 2, 6, 1) D(double, 2, 6, 2) D(double, 2, 6, 3)      \
+    D(double, 2, 8, 1) D(double, 2, 8, 2)
+#define NDWT_LIST_DEN1R(D) NDWT_LIST_F32_DEN1R(D) NDWT_LIST_C64_DEN1R(D) NDWT_LIST_F64_DEN1R(D) NDWT_LIST_C128_DEN1R(D)
 
 // The cascaded march of one strided axis (FwdMC / InvMC, ndwt_device_axis.h): THE table of the instances that exist -- cascadem_levels
 // (ndwt_select.h) answers from it, the launch units (ndwt_marchc_{f32,f64}.hip) expand it.  {float, double} x 2 .. 8 taps x 2 .. 4 levels
@@ -365,6 +376,10 @@ inline bool cascade1_instantiated(const Cascade1Instance& k) {
 // scalars of a row one wave of the instance stores (Fwd1C::WX, Inv1C::WX: the same rule as the 2-D cascade's)
 constexpr int cascade1_tile_width(const Cascade1Instance& k) { return wave_row_width(k.inverse, k.Lp, k.ew, k.f64, k.nlev); }
 #define NDWT_IS_D(T, EW, L, NLEV) if (k == Den1Instance{sizeof(T) == 8, EW, L, NLEV}) return true;
+inline bool den1r_instantiated(const Den1Instance& k) {
+    NDWT_LIST_DEN1R(NDWT_IS_D)
+    return false;
+}
 inline bool den1_instantiated(const Den1Instance& k) {
     NDWT_LIST_DEN1(NDWT_IS_D)
     return false;

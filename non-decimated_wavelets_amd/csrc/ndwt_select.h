@@ -19,9 +19,10 @@ namespace ndwt {
 //  10  |                                                                     | cascade whatever the image size, kernel mode 1 (no take-in-only steps)
 //  11  |                                                                     | cascade whatever the image size
 //      (a batched 1-D plan, cascade1_levels: fwd 9 = one launch per level in the analysis, inv 9 = in the synthesis; nothing else applies)
-//      (ndwt_denoise_bands of a batched 1-D plan, denoise1_levels: fwd 11 AND inv 11 = the one-launch Den1C wherever it exists, 9 in either slot = off)
+//      (ndwt_denoise_bands / ndwt_denoise_bands_items of a batched 1-D plan, denoise1_levels: fwd 11 AND inv 11 = the one-launch Den1C wherever it exists, 9 in either slot = off)
 //      (interleaved samples, one axis, cascadem_levels: fwd / inv 9 = one launch per level, 11 = the cascaded march wherever it exists)
 //      (ndwt_band_select, select_agg: fwd 9 = the histogram passes without the wave-wide combining of equal digits)
+//      (ndwt_band_select_items, select_items_route: inv 11 = every item in one launch (ItemSelect), inv 9 = the BandHist / BandPick passes once per item)
 //  inv | 3-D synthesis (fused3_select)                                       | 2-D (fused2_select)                | 2-D cascade (cascade2_levels)
 //   0  | default: Inv3Y (gather <= 8 taps, scatter from 10), else Inv3S      | Inv2P depth 4 packed, 1024 waves, where the image fits one round
 //   1  |                                                                     | keeps Inv2S
@@ -449,6 +450,44 @@ constexpr long long select_grid(long long n_scalars, int comp, bool vec, int num
 // rounds of the wave-wide combining of equal digits before the LDS atomics (BandHist AGG): 2 by default, kFwdNoCascade = none (A/B runs:
 // tools/bench_select.py; the counts are integers, so every setting gives the same values)
 constexpr int select_agg(int variant_fwd) { return variant_fwd == kFwdNoCascade ? 0 : 2; }
+
+// ---- the order statistics of every ITEM of a band (ndwt_band_select_items): two routes to the same keys
+//   kItemsOneLaunch  ItemSelect (ndwt_device_items.h): one workgroup runs all passes of one item, every item in one launch
+//   kItemsLoop       the BandHist / BandPick passes above once per item, on that item's sub-range; one copy back at the end
+// With at least as many items as CUs the one launch fills the chip and moves the same bytes with 2 * passes * items - 1 fewer launches:
+// taken unasked (derived, not measured; 4096 x 4096 float: 251 us against 198 ms for the loop).  With fewer items one workgroup per item
+// leaves CUs idle while the loop spreads every item over the chip: the one launch takes about as long as ONE item takes one workgroup,
+// the loop about items x passes x 21 us of launches.  Measured on the MI355X (tools/bench_select_items.py, real data, us per call, one
+// launch / loop; the table is in DESIGN.md 4.3f):
+//   items   2^14 scalars            2^18 scalars             2^22 scalars
+//   8       float 124 / 534  (0.23) float  681 /  511 (1.33) float  9981 /  650 (15.3)
+//           double 171 / 1021 (0.17) double 1234 / 1047 (1.18) double 18333 / 1224 (15.0)
+//   64      float 125 / 3797 (0.03) float  758 / 3777 (0.20) float 10469 / 5062 (2.07)
+//           double 182 / 8041 (0.02) double 1299 / 8176 (0.16) double 19017 / 9644 (1.97)
+// By the rule of DESIGN.md 4.3b -- a size takes the one launch unasked only where it was measured to beat the loop by more than the 5 %
+// spread between boxes, and what was not shown to win keeps the loop -- items of up to 2^14 scalars take it from 8 items on, items of
+// up to 2^18 scalars from 64 items on; fewer than 8 items, 2^18 scalars on fewer than 64 items (it lost at 8; 16 and 32 were not
+// measured) and anything larger keep the loop.  Complex data were not measured: the sizes count scalars.
+// items >= num_cus is bounded too: one workgroup needs about 10 ms for 2^22 float scalars (above) and grows with the item, while the loop
+// costs about 0.08 ms per item of that size, so at 256 items the one launch wins by 2 at 2^22 scalars and ties near 2^24.  Items beyond
+// 2^22 scalars, the largest size measured, keep the loop whatever their number.
+// variant_inv 11 forces the one launch, 9 the loop (A/B runs and the tests).
+enum ItemsRoute { kItemsOneLaunch, kItemsLoop };
+constexpr long long kItemsFewFrom = 8, kItemsOneLaunchMaxScalars = 1LL << 14;          // from 8 items on: items of up to 2^14 scalars
+constexpr long long kItemsManyFrom = 64, kItemsOneLaunchMaxScalarsMany = 1LL << 18;    // from 64 items on: items of up to 2^18 scalars
+constexpr long long kItemsOneLaunchMaxScalarsFull = 1LL << 22;                         // from num_cus items on: items of up to 2^22 scalars
+constexpr ItemsRoute select_items_route(long long item_scalars, long long items, int num_cus, int variant_inv) {
+    return variant_inv == kInvCascadeAlways ? kItemsOneLaunch : variant_inv == kInvCascadeOff ? kItemsLoop
+         : ((items >= num_cus && item_scalars <= kItemsOneLaunchMaxScalarsFull) || (items >= kItemsFewFrom && item_scalars <= kItemsOneLaunchMaxScalars) ||
+            (items >= kItemsManyFrom && item_scalars <= kItemsOneLaunchMaxScalarsMany)) ? kItemsOneLaunch : kItemsLoop;
+}
+// ... and the workgroups per (band, item) block of ShrinkItems: at least one, as many as the block has steps of 256 threads for, all
+// blocks together capped as shrink_run caps its grid (num_cus * 16) wherever bands * items is below that cap
+constexpr long long shrink_items_chunks(long long item_scalars, int comp, bool vec, long long bands, long long items, int num_cus) {
+    const long long steps = ((vec ? item_scalars / 4 : item_scalars / comp) + 255) / 256, room = (long long)num_cus * 16 / (bands * items);
+    const long long c = steps < room ? steps : room;
+    return c < 1 ? 1 : c;
+}
 
 // ---- one fused 3-D launch
 struct Fused3Query {

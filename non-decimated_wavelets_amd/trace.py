@@ -38,7 +38,7 @@ FAMILY_PARAMS = {
 FAMILY_PARAMS_1D = {
     "Fwd1C": [("T", None), ("L", None), ("NLEV", None), ("EW", 1), ("WPE", 4)],
     "Inv1C": [("T", None), ("L", None), ("NLEV", None), ("EW", 1), ("WPE", 4)],
-    "Den1C": [("T", None), ("L", None), ("NLEV", None), ("EW", 1), ("WPE", 4)],
+    "Den1C": [("T", None), ("L", None), ("NLEV", None), ("EW", 1), ("WPE", 4), ("ROWTHR", False)],
 }
 
 # the families of csrc/ndwt_device_axis.h (all levels of one strided axis inside one march: plans over interleaved samples), likewise
@@ -51,6 +51,13 @@ FAMILY_PARAMS_AXIS = {
 FAMILY_PARAMS_SELECT = {
     "BandHist": [("T", None), ("COMP", None), ("VEC", None), ("AGG", 2)],
     "BandPick": [("T", None)],
+}
+
+# the families of csrc/ndwt_device_items.h (the per-item calls: the radix select of one item in one workgroup, the shrink of every (band, item) block
+# with its own threshold), likewise
+FAMILY_PARAMS_ITEMS = {
+    "ItemSelect": [("T", None), ("COMP", None), ("VEC", None), ("AGG", 2)],
+    "ShrinkItems": [("T", None), ("COMP", None), ("VEC", None)],
 }
 
 # the plain __global__ templates (csrc/ndwt_api.hip, csrc/ndwt_multi.hip), as their launch sites spell them
@@ -115,7 +122,7 @@ def parse_record(line: str) -> KernelLaunch:
     if not t:
         raise ValueError(f"unparsed kernel type: {text!r}")
     fam = t.group(1)
-    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam) or FAMILY_PARAMS_1D.get(fam) or FAMILY_PARAMS_AXIS.get(fam) or FAMILY_PARAMS_SELECT.get(fam)
+    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam) or FAMILY_PARAMS_1D.get(fam) or FAMILY_PARAMS_AXIS.get(fam) or FAMILY_PARAMS_SELECT.get(fam) or FAMILY_PARAMS_ITEMS.get(fam)
     if table is None:
         raise ValueError(f"unknown kernel family {fam!r} in {text!r}")
     args = [_value(a) for a in _split_args(t.group(2) or "")]
