@@ -340,6 +340,43 @@ int ndwt_estimate_sigma_coef_items(ndwt_plan* plan, const void* y_dev, int64_t b
 int ndwt_estimate_sigma_items(ndwt_plan* plan, const void* x_dev, double* sigma, void* stream);
 int ndwt_shrink_bands_items(ndwt_plan* plan, void* y_dev, int64_t band_pitch, int level, const double* thresholds, int mode, void* stream);
 int ndwt_denoise_bands_items(ndwt_plan* plan, const void* x_dev, void* out_dev, int level, const double* thresholds, int mode, void* stream);
+/* ---- sums of a band: what an iterative solver evaluates every iteration (its objective, its stopping rule) and what a data-driven
+ * threshold needs next to sigma -- the l1 norm, the energy, the largest magnitude and the count of non-zeros, in ONE read of the array ----
+ * For every (band, item) block of a level-`level` coefficient array on the device (band_pitch 0 = packed), four doubles in this order:
+ *   NDWT_NORM_L1    real data: the sum of |c|.  Interleaved complex data: the sum of the magnitude sqrt(re^2 + im^2) computed in the plan's
+ *                   scalar type, exactly as the shrink compares it and ndwt_band_select orders it, then widened
+ *   NDWT_NORM_L2SQ  the sum of c^2; complex data: of re^2 + im^2, from the widened parts
+ *   NDWT_NORM_MAX   the largest |c|; complex data: the largest of that magnitude (bit for bit ndwt_band_select's last order statistic)
+ *   NDWT_NORM_NNZ   the count of elements with c != 0; complex data: with re != 0 or im != 0
+ *   All four are accumulated in double whatever the data kind, the squares with a fused multiply-add, the count in a 64-bit integer that
+ *   is converted to double at the end.  A NaN in a block makes that block's l1, l2sq and max NaN and counts as non-zero; -0 is zero.
+ *   There are no floating-point atomics and no hand-off between workgroups inside a launch: the order of every sum is a fixed function
+ *   of the shape and the launch geometry (the device's compute units, ndwt_plan_set_tuning's target_blocks), so two calls on one device
+ *   return the same bits.
+ * nb = ndwt_num_bands(filtered axes, level); band 0 is a band like any other.
+ * ndwt_band_norms: a band is the plan's WHOLE array, all signals of a batch and all items of a stack pooled, as ndwt_shrink_bands and
+ *   ndwt_band_select see it.  norms: HOST, [nb][4] doubles.
+ * ndwt_band_norms_items: the items of ndwt_band_select_items, above; norms: HOST, [items][nb][4] doubles, norms[(j * nb + b) * 4 + s].
+ *   An unbatched plan is one item, and the call then equals ndwt_band_norms.
+ *   Both are synchronous like the other forms with host pointers: they enqueue on `stream`, copy the results back once, synchronise the
+ *   stream once and return.
+ * ndwt_band_norms_dev: the same values (per_item != 0: the layout of ndwt_band_norms_items, else of ndwt_band_norms) into DEVICE memory
+ *   at norms_dev, 8-byte aligned.  It only enqueues -- no copy, no synchronisation; the results are there in stream order: the form a
+ *   solver uses to keep its objective on the device.
+ * Every plan kind ndwt_shrink_bands serves.  All blocks are read in ONE launch (BandNorms, workgroups of 256 threads, each block split
+ *   into chunks while every thread keeps 8 turns of its loop and the grid stays within 16 workgroups per compute unit); where a block has
+ *   more than one chunk a second, small launch (NormsFinish) adds the chunks' partial results in a fixed order.  The partials, and the
+ *   results of the host forms, live in a device buffer the plan owns and only grows: nothing is allocated per call after the first.  The
+ *   coefficient array is never written.  plan, y_dev, norms or norms_dev null, a level outside the plan's, a band pitch smaller than a
+ *   band, norms_dev not 8-byte aligned: NDWT_ERR_INVALID_ARG, the message names the argument, and nothing is launched; 2^31 items or
+ *   more: NDWT_ERR_UNSUPPORTED.  (Calls of one plan on different streams are not ordered with each other, as for every call that uses
+ *   the plan's scratch.)
+ * Not built: a statistic fused into the shrink or the synthesis loads; weighted norms on the device.  The existing calls, the
+ *   host-pointer forms, the handles, the slab entry points and the MATLAB gateway are unchanged. */
+enum { NDWT_NORM_L1 = 0, NDWT_NORM_L2SQ = 1, NDWT_NORM_MAX = 2, NDWT_NORM_NNZ = 3, NDWT_NORM_COUNT = 4 };
+int ndwt_band_norms(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double* norms, void* stream);
+int ndwt_band_norms_items(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double* norms, void* stream);
+int ndwt_band_norms_dev(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, int per_item, double* norms_dev, void* stream);
 
 /* Split complex: separate real / imaginary arrays, the layout the reference's gateway receives from MATLAB
  * (mxGetPr / mxGetPi, nd_dwt_mex.c:55-58,90-93) and hands to nd_dwt_dec / nd_dwt_rec (outR/outI, imageR/imageI,

@@ -19,6 +19,7 @@ NDWT_F32, NDWT_F64 = 0, 1
 NDWT_REAL, NDWT_COMPLEX_INTERLEAVED = 0, 1
 NDWT_DILATION_REFERENCE, NDWT_DILATION_ATROUS = 0, 1
 NDWT_PATH_AUTO, NDWT_PATH_GENERIC = 0, 1
+NDWT_NORM_L1, NDWT_NORM_L2SQ, NDWT_NORM_MAX, NDWT_NORM_NNZ, NDWT_NORM_COUNT = 0, 1, 2, 3, 4
 
 EXPORTS = [
     "ndwt_wave_filters", "ndwt_num_bands", "ndwt_level_from_bands", "ndwt_plan_create", "ndwt_plan_create_slab", "ndwt_plan_destroy",
@@ -34,7 +35,7 @@ EXPORTS = [
     "ndwt_mplan_create_axis", "ndwt_trace_enable", "ndwt_trace_get", "ndwt_plan_create_many", "ndwt_plan_create_axes",
     "ndwt_plan_create_interleaved", "ndwt_band_gains", "ndwt_shrink_bands", "ndwt_denoise_bands", "ndwt_band_select",
     "ndwt_estimate_sigma_coef", "ndwt_estimate_sigma", "ndwt_band_select_items", "ndwt_estimate_sigma_coef_items", "ndwt_estimate_sigma_items",
-    "ndwt_shrink_bands_items", "ndwt_denoise_bands_items",
+    "ndwt_shrink_bands_items", "ndwt_denoise_bands_items", "ndwt_band_norms", "ndwt_band_norms_items", "ndwt_band_norms_dev",
 ]
 
 
@@ -126,6 +127,10 @@ def lib() -> ctypes.CDLL:
     L.ndwt_estimate_sigma_items.argtypes = L.ndwt_estimate_sigma.argtypes
     L.ndwt_shrink_bands_items.argtypes = L.ndwt_shrink_bands.argtypes
     L.ndwt_denoise_bands_items.argtypes = L.ndwt_denoise_bands.argtypes
+    # the band norms: host results [nb][4] / [items][nb][4], or the same on the device (per_item chooses the layout)
+    L.ndwt_band_norms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
+    L.ndwt_band_norms_items.argtypes = L.ndwt_band_norms.argtypes
+    L.ndwt_band_norms_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L.ndwt_denoise_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int]
     for f in (L.ndwt_dec_split, L.ndwt_rec_split):
         f.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p]

@@ -275,6 +275,29 @@ class Plan:
         t, tp = self._item_table(thresholds, level)
         L.check(L.lib().ndwt_denoise_bands_items(self._h, x_ptr, out_ptr, int(level), tp, int(bool(hard)), ctypes.c_void_p(stream)))
 
+    # -- the band norms (include/ndwt.h: ndwt_band_norms): column NDWT_NORM_L1 / _L2SQ / _MAX / _NNZ of every band, in one read --
+    def _num_bands(self, level):
+        return num_bands(self.ndim if self.axes is None else len(self.axes), level)   # (the filtered axes)
+
+    def band_norms(self, y_ptr, level, stream=0, band_pitch=0):
+        """an [nb, 4] array: sum |c|, sum |c|^2, max |c| and the count of non-zeros of every band of a level-`level` coefficient array on the
+        device, the band being the plan's whole array (all items pooled); complex data: the magnitude the shrink compares.  Synchronous."""
+        out = np.zeros((self._num_bands(level), L.NDWT_NORM_COUNT))
+        L.check(L.lib().ndwt_band_norms(self._h, y_ptr, int(band_pitch), int(level), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.c_void_p(stream)))
+        return out
+
+    def band_norms_items(self, y_ptr, level, stream=0, band_pitch=0):
+        """band_norms for every item: an [items, nb, 4] array, [j, b] from item j's part of band b alone.  Synchronous."""
+        out = np.zeros((self.items, self._num_bands(level), L.NDWT_NORM_COUNT))
+        L.check(L.lib().ndwt_band_norms_items(self._h, y_ptr, int(band_pitch), int(level), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                              ctypes.c_void_p(stream)))
+        return out
+
+    def band_norms_dev(self, y_ptr, level, out_ptr, per_item=False, stream=0, band_pitch=0):
+        """the same into DEVICE memory at out_ptr ([nb, 4] doubles, per_item: [items, nb, 4]; 8-byte aligned): enqueued on `stream` only, no
+        copy and no synchronisation -- the results are there in stream order"""
+        L.check(L.lib().ndwt_band_norms_dev(self._h, y_ptr, int(band_pitch), int(level), int(bool(per_item)), out_ptr, ctypes.c_void_p(stream)))
+
     def denoise_host(self, x_ptr, out_ptr, level, threshold, hard=False):
         L.check(L.lib().ndwt_denoise_host(self._h, x_ptr, out_ptr, int(level), float(threshold), int(bool(hard))))
 
@@ -933,6 +956,61 @@ class _NdDwtBase:
             return thr
         thr = float(k) * self.estimate_sigma(x) * self.band_gains(level)
         thr[0] = 0.0
+        return thr
+
+    # -- sums over the bands, in one read of the coefficient array on the device (extension; not in the reference) --
+    def _band_norms(self, y, per_item):
+        """(the [bands, 4] or [K, bands, 4] array of Plan.band_norms / band_norms_items, elements of one block, scalars per element)"""
+        yk, pitch, level, dev, plan = self._coef_for_stats(y)
+        n = int(np.prod(yk.shape[1:]))
+        with torch.cuda.device(dev):
+            if per_item:
+                return plan.band_norms_items(yk.data_ptr(), level, _current_stream(dev), band_pitch=pitch), n // plan.items, 2 if yk.is_complex() else 1
+            return plan.band_norms(yk.data_ptr(), level, _current_stream(dev), band_pitch=pitch), n, 2 if yk.is_complex() else 1
+
+    def band_norms(self, y, per_item=False):
+        """The sums of every band of a coefficient array (what dec returns), computed on the device in one read of it: a dict of arrays
+        `l1` (sum of |c|), `l2sq` (sum of |c|^2), `max` (the largest |c|) and `nnz` (the count of c != 0), one entry per band, band 0
+        included; complex data: |c| is the magnitude the shrink compares.  A band is the whole array (all signals of a batch, all items of
+        a stack); per_item=True: [K, bands] arrays, row j from signal / item j alone.  The call waits for the result."""
+        v, _, _ = self._band_norms(y, per_item)
+        return {"l1": v[..., L.NDWT_NORM_L1].copy(), "l2sq": v[..., L.NDWT_NORM_L2SQ].copy(), "max": v[..., L.NDWT_NORM_MAX].copy(),
+                "nnz": v[..., L.NDWT_NORM_NNZ].copy()}
+
+    def l1_norm(self, y, weights=None, per_item=False):
+        """sum over the bands of weights[b] * (the sum of |c| over band b): the penalty of an l1-regularised solver.  weights: one per band;
+        by default 0 for band 0 and 1 for every other band, the bands `shrink` touches.  A float, or a length-K array with per_item=True."""
+        if y.ndim != len(self._shape) + 1 or list(y.shape[:-1]) != self._shape:
+            raise ValueError(f"coefficient array must have shape {self._shape + ['bands']}")
+        nb = int(y.shape[-1])
+        if weights is None:
+            w = np.ones(nb)
+            w[0] = 0.0
+        else:
+            w = np.asarray(weights, dtype=np.float64).reshape(-1)
+            if w.size != nb:
+                raise ValueError(f"{nb} weights expected, one per band of the coefficient array, got {w.size}")
+        r = self.band_norms(y, per_item)["l1"] @ w
+        return r if per_item else float(r)
+
+    def sparsity(self, y, per_item=False):
+        """the fraction of coefficients that are not zero, over all bands: a float, or a length-K array with per_item=True"""
+        v, n, _ = self._band_norms(y, per_item)
+        r = v[..., L.NDWT_NORM_NNZ].sum(axis=-1) / (float(n) * v.shape[-2])
+        return r if per_item else float(r)
+
+    def bayes_thresholds(self, x, level, per_item=False):
+        """BayesShrink thresholds for this frame (Chang, Yu and Vetterli), one per band, as denoise(x, level, thresholds) and shrink(y,
+        thresholds) take them.  With s_b = estimate_sigma(x) * band_gains(level)[b], the noise in band b, and v_b = max(l2sq_b / (elements *
+        parts) - s_b^2, 0), the signal variance of each part (1 for real, 2 for complex data) of a coefficient of dec(x, level):
+        t_b = s_b^2 / sqrt(v_b), and where v_b = 0 -- a band of noise alone -- t_b = the band's largest magnitude, so the band goes to zero.
+        Entry 0 (the approximation) is 0.  per_item=True: a [K, bands] array, row j from signal / item j alone."""
+        level = int(level)
+        s = np.multiply.outer(np.asarray(self.estimate_sigma(x, per_item=per_item), dtype=np.float64), self.band_gains(level))
+        v, n, comp = self._band_norms(self.dec(x, level), per_item)
+        var = np.maximum(v[..., L.NDWT_NORM_L2SQ] / (float(n) * comp) - s * s, 0.0)
+        thr = np.where(var > 0.0, s * s / np.sqrt(np.where(var > 0.0, var, 1.0)), v[..., L.NDWT_NORM_MAX])
+        thr[..., 0] = 0.0
         return thr
 
     def _prep_dec_input(self, x):

@@ -19,6 +19,7 @@
 #include "../../include/ndwt.h"
 #include "ndwt_device.h"
 #include "ndwt_device_items.h"
+#include "ndwt_device_norms.h"
 #include "ndwt_device_select.h"
 #include "ndwt_filters.h"
 #include "ndwt_fused.h"
@@ -173,6 +174,8 @@ struct ndwt_plan {
     DevBuf coef;                       // coefficient scratch of ndwt_denoise (all bands of the last level used), lazily allocated
     DevBuf taps_den;                   // device tap table of the fused level-1 denoising kernel (TapsDen<float, L>), built at plan creation where it applies
     DevBuf select_buf;                 // ndwt_band_select: the device-side state and the global histogram (SelectState, then [slot][bin]); lazily allocated
+    DevBuf norms_buf;                  // ndwt_band_norms*: the results of the host forms ([item][band][4] doubles), then the partials of the chunks
+                                       // ([band][item][chunk][4]); lazily allocated, only ever grown
     double sigma_gain = 0.0;           // ndwt_estimate_sigma*: the gain of the last level-1 band (last_band_gain), computed at the first call
     // the threshold table of the *_items calls ([item][band], in the plan's scalar type): written into a pinned host buffer, copied to a
     // device buffer on the call's stream; both only grow.  thr_event is recorded behind the copy: the next call waits for it before it
@@ -2295,6 +2298,85 @@ int ndwt_denoise_bands_items(ndwt_plan* p, const void* x, void* out, int level, 
         if (rc == NDWT_OK) rc = rec_impl<T>(p, coef, bs, (T*)out, level, kNoShrink, (hipStream_t)stream);
         return rc;
     });
+}
+
+// ---- the band norms: l1, energy, max and non-zeros of every (band, item) block in one read (include/ndwt.h; the kernels:
+// ndwt_device_norms.h) ----
+// select_items_check without the band and the ranks
+static int norms_check(const ndwt_plan* p, const void* y, int level, const double* norms, const char* norms_name) {
+    int rc = check_level(p, level);
+    if (rc) return rc;
+    if (!y) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (y_dev)");
+    if (!norms) return fail(NDWT_ERR_INVALID_ARG, "null output pointer (%s)", norms_name);
+    if (p->items() > 0x7fffffffLL) return fail(NDWT_ERR_UNSUPPORTED, "%lld items: the band norms serve fewer than 2^31", p->items());
+    return NDWT_OK;
+}
+
+// BandNorms on every (band, item) block of `items` items of n scalars in one launch, by norms_chunks; with more than one chunk the
+// partials go to the plan's buffer and NormsFinish combines them.  out_dev: [items][nb][4] doubles, or null: the results' place in the
+// plan's buffer (returned in *res).  Past 2^31 - 1 workgroups: one launch per band.  Enqueued only.
+extern "C++" template <typename T> static int norms_run(ndwt_plan* p, const T* y, long long bs, int level, long long items, long long n, double* out_dev, double** res,
+                                                        hipStream_t s) {
+    const long long nb = ndwt_num_bands(p->ndim, level);
+    const bool vec = aligned_vec4<T>(y) && bs % 4 == 0 && n % 4 == 0;
+    const bool per_band = norms_per_band(nb, items);
+    const long long chunks = norms_chunks(n, (int)p->comp, vec, per_band ? 1 : nb, items, p->num_cus, p->target_blocks);
+    const size_t res_bytes = (size_t)(nb * items) * 4 * sizeof(double);
+    int rc = p->norms_buf.grow(res_bytes * (chunks > 1 ? 1 + (size_t)chunks : 1), "for the band norms");
+    if (rc) return rc;
+    double* const results = out_dev ? out_dev : (double*)p->norms_buf.ptr;
+    double* const partials = (double*)((char*)p->norms_buf.ptr + res_bytes);
+    BandNormsArgs<T> a = {y, bs, n, chunks > 1 ? partials : results, items, (int)nb, 0, (int)nb, (int)chunks};
+    NormsFinishArgs f = {partials, results, items, (int)nb, 0, (int)nb, (int)chunks};
+    for (int b = 0; b < (per_band ? (int)nb : 1); ++b) {
+        if (per_band) { a.band0 = f.band0 = b; a.nbands = f.nbands = 1; }
+        rc = launch_band_norms(a, (int)p->comp, vec, p->norms_buf.ptr, s);
+        if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: no band-norms kernel for this data kind or grid");
+        if (rc != 0) return fail(NDWT_ERR_HIP, "band-norms kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (chunks == 1) continue;
+        rc = launch_norms_finish(f, p->norms_buf.ptr, s);
+        if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: a grid the band-norms combine cannot express");
+        if (rc != 0) return fail(NDWT_ERR_HIP, "band-norms combine launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    if (res) *res = results;
+    return NDWT_OK;
+}
+
+// the host forms: the launches, then one copy of the results and one synchronisation of the stream
+static int norms_host(ndwt_plan* p, const void* y, int64_t band_pitch, int level, bool per_item, double* norms, void* stream) {
+    int rc = norms_check(p, y, level, norms, "norms");
+    if (rc) return rc;
+    long long bs = 0;
+    rc = pitch_scalars(p, band_pitch, &bs);
+    if (rc) return rc;
+    const long long items = per_item ? p->items() : 1, n = per_item ? p->item_vol() : p->vol;
+    return on_device(p, [&](auto t) {
+        double* res = nullptr;
+        const int rc = norms_run(p, (const decltype(t)*)y, bs, level, items, n, nullptr, &res, (hipStream_t)stream);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(norms, res, (size_t)(ndwt_num_bands(p->ndim, level) * items) * 4 * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        return (int)NDWT_OK;
+    });
+}
+
+int ndwt_band_norms(ndwt_plan* p, const void* y, int64_t band_pitch, int level, double* norms, void* stream) {
+    return norms_host(p, y, band_pitch, level, false, norms, stream);
+}
+
+int ndwt_band_norms_items(ndwt_plan* p, const void* y, int64_t band_pitch, int level, double* norms, void* stream) {
+    return norms_host(p, y, band_pitch, level, true, norms, stream);
+}
+
+int ndwt_band_norms_dev(ndwt_plan* p, const void* y, int64_t band_pitch, int level, int per_item, double* norms_dev, void* stream) {
+    int rc = norms_check(p, y, level, norms_dev, "norms_dev");
+    if (rc) return rc;
+    if ((uintptr_t)norms_dev % sizeof(double) != 0) return fail(NDWT_ERR_INVALID_ARG, "norms_dev must be 8-byte aligned");
+    long long bs = 0;
+    rc = pitch_scalars(p, band_pitch, &bs);
+    if (rc) return rc;
+    const long long items = per_item ? p->items() : 1, n = per_item ? p->item_vol() : p->vol;
+    return on_device(p, [&](auto t) { return norms_run(p, (const decltype(t)*)y, bs, level, items, n, norms_dev, nullptr, (hipStream_t)stream); });
 }
 
 int ndwt_denoise_host(ndwt_plan* p, const void* x, void* out, int level, double threshold, int mode) {

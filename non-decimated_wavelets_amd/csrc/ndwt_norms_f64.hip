@@ -1,0 +1,16 @@
+// the band norms (BandNorms, ndwt_device_norms.h): double and complex128 data; NormsFinish, which reads doubles whatever the data
+#include "ndwt_device_norms.h"
+#include "ndwt_fused_kernels.h"
+namespace ndwt {
+#define NDWT_LAUNCH_H(T, COMP, VEC) \
+    if (comp == COMP && vec == VEC) return launch_select_k<BandNorms<T, COMP, VEC>>(a, (int)(a.nbands * a.items * a.chunks), buf_dev, s);
+int launch_band_norms(const BandNormsArgs<double>& a, int comp, bool vec, const void* buf_dev, hipStream_t s) {
+    if (a.nbands < 1 || a.items < 1 || a.chunks < 1 || (long long)a.nbands * a.items * a.chunks > 0x7fffffffLL) return -2;
+    NDWT_LAUNCH_H(double, 1, true) NDWT_LAUNCH_H(double, 1, false) NDWT_LAUNCH_H(double, 2, true) NDWT_LAUNCH_H(double, 2, false)
+    return -1;
+}
+int launch_norms_finish(const NormsFinishArgs& a, const void* buf_dev, hipStream_t s) {
+    if (a.nbands < 1 || a.items < 1 || a.chunks < 2 || (long long)a.nbands * a.items > 0x7fffffffLL) return -2;
+    return launch_select_k<NormsFinish<>>(a, (int)(a.nbands * a.items), buf_dev, s);
+}
+}  // namespace ndwt

@@ -488,6 +488,21 @@ constexpr long long shrink_items_chunks(long long item_scalars, int comp, bool v
     const long long c = steps < room ? steps : room;
     return c < 1 ? 1 : c;
 }
+// ... and the workgroups per (band, item) block of BandNorms (ndwt_device_norms.h): at least one; a further chunk only while every
+// thread of 256 still has kSelectTurns turns of its loop (a workgroup that reads too little is all prologue, LDS combine and flush:
+// DESIGN.md 4.3e); all blocks together capped at num_cus * 16 wherever bands * items is below that cap; target_blocks > 0
+// (ndwt_plan_set_tuning) is an upper bound on all blocks on top of that.  More than one chunk means a second launch (NormsFinish).
+constexpr long long norms_chunks(long long item_scalars, int comp, bool vec, long long bands, long long items, int num_cus, int target_blocks) {
+    const long long steps = vec ? item_scalars / 4 : item_scalars / comp, blocks = bands * items;
+    long long c = steps / (256 * kSelectTurns);
+    const long long room = (long long)num_cus * 16 / blocks;
+    if (c > room) c = room;
+    if (target_blocks > 0 && c > target_blocks / blocks) c = target_blocks / blocks;
+    return c < 1 ? 1 : c;
+}
+// past 2^31 - 1 (band, item) blocks a launch cannot number its workgroups: one launch per band (items < 2^31: a band alone always fits,
+// and has one chunk)
+constexpr bool norms_per_band(long long bands, long long items) { return bands * items > 0x7fffffffLL; }
 
 // ---- one fused 3-D launch
 struct Fused3Query {

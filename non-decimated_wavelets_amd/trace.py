@@ -60,6 +60,13 @@ FAMILY_PARAMS_ITEMS = {
     "ShrinkItems": [("T", None), ("COMP", None), ("VEC", None)],
 }
 
+# the families of csrc/ndwt_device_norms.h (the band norms: l1, energy, max and non-zeros of every (band, item) block in one read, and the combine of
+# the chunks of a block at the launch boundary), likewise
+FAMILY_PARAMS_NORMS = {
+    "BandNorms": [("T", None), ("COMP", None), ("VEC", None)],
+    "NormsFinish": [("NT", 64)],
+}
+
 # the plain __global__ templates (csrc/ndwt_api.hip, csrc/ndwt_multi.hip), as their launch sites spell them
 PLAIN_PARAMS = {
     "axis_analysis_kernel": [("T", None)],
@@ -122,7 +129,7 @@ def parse_record(line: str) -> KernelLaunch:
     if not t:
         raise ValueError(f"unparsed kernel type: {text!r}")
     fam = t.group(1)
-    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam) or FAMILY_PARAMS_1D.get(fam) or FAMILY_PARAMS_AXIS.get(fam) or FAMILY_PARAMS_SELECT.get(fam) or FAMILY_PARAMS_ITEMS.get(fam)
+    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam) or FAMILY_PARAMS_1D.get(fam) or FAMILY_PARAMS_AXIS.get(fam) or FAMILY_PARAMS_SELECT.get(fam) or FAMILY_PARAMS_ITEMS.get(fam) or FAMILY_PARAMS_NORMS.get(fam)
     if table is None:
         raise ValueError(f"unknown kernel family {fam!r} in {text!r}")
     args = [_value(a) for a in _split_args(t.group(2) or "")]
