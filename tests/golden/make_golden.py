@@ -2,8 +2,11 @@
 """Generates tests/golden/*.npz from the CPU oracle (oracle/ndwt_oracle.py, FFT-domain 'mat' restatement
 of Functions/nd_dwt_{1,2,3,4}D.m; the a-trous vectors come from the signal-domain restatement).
 
-The reference stores no vectors and cannot run here, so these fixtures pin OUR oracle's
-outputs: inputs x, coefficients y = dec(x, level), arbitrary coefficients c and r = rec(c).
+The reference stores no vectors, so these fixtures are OUR oracle's outputs: inputs x,
+coefficients y = dec(x, level), arbitrary coefficients c and r = rec(c).  They are pinned to the reference
+all the same: tests/test_reference_c.py has the reference's own mex/nddwt.c, compiled unchanged over a plain
+DFT, reproduce every y_*_l2* and rec_*_l2* array to 1e-12 of max|c| (not the *_atrous keys: the reference has
+no such mode).  Fixtures written BY the reference are in refc/ (make_golden_refc.py).
 Run from the repository root:  python tests/golden/make_golden.py
 """
 import os

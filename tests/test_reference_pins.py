@@ -6,7 +6,10 @@
   * the db1 closed forms the reference ships as signal-domain code: harr_nddwt_2D.m (tests/test_oracle.py) and the
     4-D one, harr_nddwt_4D.m:262-281,555-579 (multi-level band bookkeeping of :173,:228), against all three oracle
     restatements.  tests/test_gpu_parity.py compares the HIP path with the same closed form.
-Parity with MATLAB output stays "unpinned" by the rules (no fixtures exist); these are the pins that do exist.
+The reference's C control flow (mex/nddwt.c: band slots, level order, the conjugate, the normalisations) is pinned elsewhere, by running
+that file itself: tests/test_reference_c.py (the oracle) and tests/test_gpu_reference_c.py (the HIP kernels).  What stays restated is the
+MATLAB side -- get_filters, the fftn around the mex call, the 'mat' path --, nd_dwt_mex.c and the prebuilt mex binaries; for those, the
+pins in this file are the ones that exist.
 """
 import json
 import os
