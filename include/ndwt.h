@@ -377,6 +377,48 @@ enum { NDWT_NORM_L1 = 0, NDWT_NORM_L2SQ = 1, NDWT_NORM_MAX = 2, NDWT_NORM_NNZ = 
 int ndwt_band_norms(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double* norms, void* stream);
 int ndwt_band_norms_items(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double* norms, void* stream);
 int ndwt_band_norms_dev(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, int per_item, double* norms_dev, void* stream);
+/* ---- joint shrinkage across the items of a plan: the prox of the l2,1 norm (group soft thresholding), and that norm ----
+ * The items of a batched, stack or interleaved plan are often coils, echoes, channels, colour planes or traces of ONE object, and the
+ * regulariser is joint sparsity: a coefficient survives if the GROUP of coefficients at its position across all items is large.
+ * With K = the plan's items and N = the elements of one item of a band, the group at (band b, position p in [0, N)) is c_j = y[b][j][p],
+ * j = 0 .. K - 1, every c_j a scalar or an interleaved complex element.  T = the plan's scalar type.  Per group:
+ *   s = the sum over j in ascending order of re_j^2 (+ im_j^2, re before im), accumulated in double with a fused multiply-add on the
+ *       widened parts, from 0 (the way NDWT_NORM_L2SQ is accumulated);
+ *   m = sqrt((T)s): one rounding of s to T, then T's square root;   t = (T)thresholds[b];
+ *   m > t: every part of every c_j is multiplied in T by g = 1 (NDWT_SHRINK_HARD) or g = (m - t) / m (NDWT_SHRINK_SOFT, computed in T);
+ *   else every part of the group is stored as +0 -- an explicit zero, not c * 0: a group that holds a NaN (m > t is then false) becomes
+ *       zeros, as a NaN does in ndwt_shrink of real data.
+ * thresholds: HOST, nb = ndwt_num_bands(filtered axes, level) doubles, each >= 0, band 0 a band like any other; thresholds[b] == 0 leaves
+ *   band b untouched (no workgroup of that band writes anything); an all-zero array launches and uploads nothing.
+ * ndwt_shrink_joint: in place on a level-`level` coefficient array on the device (band_pitch 0 = packed), all bands in ONE launch
+ *   (JointShrink) that reads the array once and writes it once where K <= 8 (the group of a step stays in registers); with more items a
+ *   workgroup sweeps the items twice, the second sweep reads them again.  The thresholds reach the device as ndwt_shrink_bands_items'
+ *   table does, through the plan's pinned host buffer and a copy enqueued on `stream` (items_table_upload, nb entries): a later call
+ *   of any of the table forms waits for that copy before it overwrites the pinned buffer.  That wait blocks the HOST
+ *   (hipEventSynchronize) until the previous call's copy has run, so a call is at most one call ahead of the device, and two such calls
+ *   cannot be captured into a graph.
+ * ndwt_denoise_joint: dec into the plan's scratch, the joint shrink, rec -- always this general route.
+ * ndwt_group_norms: for every band four doubles in the slots of NDWT_NORM_*, norms: HOST, [nb][4]:
+ *   NDWT_NORM_L1    the sum over p of m, every m widened and summed in double: the l2,1 norm of the band
+ *   NDWT_NORM_L2SQ  the sum over p of s
+ *   NDWT_NORM_MAX   the largest m; a NaN sticks
+ *   NDWT_NORM_NNZ   the count of groups with s != 0; a NaN counts
+ *   No floating-point atomics; the order of every sum is a fixed function of the shape and the launch geometry, as for ndwt_band_norms.
+ *   Synchronous like ndwt_band_norms: enqueues on `stream`, copies the results back once, synchronises the stream once.
+ * ndwt_group_norms_dev: the same values into DEVICE memory at norms_dev ([nb][4] doubles, 8-byte aligned); it only enqueues.
+ * Every plan kind ndwt_shrink_bands serves; an unbatched plan is one item, and the group is the element.  One launch (GroupNorms),
+ *   plus NormsFinish where a band has more than one workgroup; the grid of both kernels: workgroups of 256 threads, a band split into
+ *   chunks while every thread keeps max(1, 8 / K) steps -- one step moves a load of every item -- within 16 workgroups per compute unit
+ *   and ndwt_plan_set_tuning's target_blocks.  Refusals are those of ndwt_shrink_bands and ndwt_band_norms: plan, y_dev, x_dev, out_dev,
+ *   thresholds, norms or norms_dev null, a threshold below 0 or NaN, a mode that is neither, a level outside the plan's, a band pitch
+ *   smaller than a band, norms_dev not 8-byte aligned: NDWT_ERR_INVALID_ARG, the message names the argument, nothing is launched.
+ * Not built: a joint form inside the one-launch denoise of a batched 1-D plan (Den1C: a signal lives in one wave there, its neighbours
+ *   in other waves); groups over the `inner` axis of an interleaved plan (the samples of one element: they belong to one item); per-item
+ *   weights inside the group; a norm fused into the shrink.  The handles, the slab entry points and the MATLAB gateway are unchanged. */
+int ndwt_shrink_joint(ndwt_plan* plan, void* y_dev, int64_t band_pitch, int level, const double* thresholds, int mode, void* stream);
+int ndwt_denoise_joint(ndwt_plan* plan, const void* x_dev, void* out_dev, int level, const double* thresholds, int mode, void* stream);
+int ndwt_group_norms(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double* norms, void* stream);
+int ndwt_group_norms_dev(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double* norms_dev, void* stream);
 
 /* Split complex: separate real / imaginary arrays, the layout the reference's gateway receives from MATLAB
  * (mxGetPr / mxGetPi, nd_dwt_mex.c:55-58,90-93) and hands to nd_dwt_dec / nd_dwt_rec (outR/outI, imageR/imageI,

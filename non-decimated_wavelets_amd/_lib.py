@@ -36,6 +36,7 @@ EXPORTS = [
     "ndwt_plan_create_interleaved", "ndwt_band_gains", "ndwt_shrink_bands", "ndwt_denoise_bands", "ndwt_band_select",
     "ndwt_estimate_sigma_coef", "ndwt_estimate_sigma", "ndwt_band_select_items", "ndwt_estimate_sigma_coef_items", "ndwt_estimate_sigma_items",
     "ndwt_shrink_bands_items", "ndwt_denoise_bands_items", "ndwt_band_norms", "ndwt_band_norms_items", "ndwt_band_norms_dev",
+    "ndwt_shrink_joint", "ndwt_denoise_joint", "ndwt_group_norms", "ndwt_group_norms_dev",
 ]
 
 
@@ -131,6 +132,11 @@ def lib() -> ctypes.CDLL:
     L.ndwt_band_norms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
     L.ndwt_band_norms_items.argtypes = L.ndwt_band_norms.argtypes
     L.ndwt_band_norms_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    # joint shrinkage across the items and the group norms: thresholds [nb] on the host; results [nb][4] on the host or on the device
+    L.ndwt_shrink_joint.argtypes = L.ndwt_shrink_bands.argtypes
+    L.ndwt_denoise_joint.argtypes = L.ndwt_denoise_bands.argtypes
+    L.ndwt_group_norms.argtypes = L.ndwt_band_norms.argtypes
+    L.ndwt_group_norms_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     L.ndwt_denoise_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int]
     for f in (L.ndwt_dec_split, L.ndwt_rec_split):
         f.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p]

@@ -298,6 +298,31 @@ class Plan:
         copy and no synchronisation -- the results are there in stream order"""
         L.check(L.lib().ndwt_band_norms_dev(self._h, y_ptr, int(band_pitch), int(level), int(bool(per_item)), out_ptr, ctypes.c_void_p(stream)))
 
+    # -- joint shrinkage across the items and the norms of the groups (include/ndwt.h: ndwt_shrink_joint) --
+    def shrink_joint(self, y_ptr, level, thresholds, hard=False, stream=0, band_pitch=0):
+        """in-place group thresholding: the group is the coefficients at one position of a band across all items of the plan; one threshold
+        per band (num_bands of them, band 0 included; 0 = leave the band alone), all bands in one launch"""
+        t, tp = self._thresholds(thresholds)
+        self._check_band_count(t, level)
+        L.check(L.lib().ndwt_shrink_joint(self._h, y_ptr, int(band_pitch), int(level), tp, int(bool(hard)), ctypes.c_void_p(stream)))
+
+    def denoise_joint(self, x_ptr, out_ptr, level, thresholds, hard=False, stream=0):
+        """dec -> shrink_joint -> rec, the coefficients in the plan's scratch"""
+        t, tp = self._thresholds(thresholds)
+        self._check_band_count(t, level)
+        L.check(L.lib().ndwt_denoise_joint(self._h, x_ptr, out_ptr, int(level), tp, int(bool(hard)), ctypes.c_void_p(stream)))
+
+    def group_norms(self, y_ptr, level, stream=0, band_pitch=0):
+        """an [nb, 4] array in the columns of band_norms, over the groups of every band: the sum of the groups' magnitudes (the l2,1 norm), the
+        sum of their squares, the largest and the count of groups that are not all zero.  Synchronous."""
+        out = np.zeros((self._num_bands(level), L.NDWT_NORM_COUNT))
+        L.check(L.lib().ndwt_group_norms(self._h, y_ptr, int(band_pitch), int(level), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.c_void_p(stream)))
+        return out
+
+    def group_norms_dev(self, y_ptr, level, out_ptr, stream=0, band_pitch=0):
+        """the same into DEVICE memory at out_ptr ([nb, 4] doubles, 8-byte aligned): enqueued on `stream` only"""
+        L.check(L.lib().ndwt_group_norms_dev(self._h, y_ptr, int(band_pitch), int(level), out_ptr, ctypes.c_void_p(stream)))
+
     def denoise_host(self, x_ptr, out_ptr, level, threshold, hard=False):
         L.check(L.lib().ndwt_denoise_host(self._h, x_ptr, out_ptr, int(level), float(threshold), int(bool(hard))))
 
@@ -816,16 +841,19 @@ class _NdDwtBase:
         return self._from_device(xk, like_numpy, dev)
 
     # -- consumers for iterative solvers (extension; not in the reference) --
-    def shrink(self, y, threshold, mode="soft"):
+    def shrink(self, y, threshold, mode="soft", joint=False):
         """Soft / hard thresholding of every detail band of a coefficient array (band 0, the coarsest approximation,
-        is kept); complex data: the magnitude is shrunk.  Returns a new array of the same kind as `y`."""
+        is kept); complex data: the magnitude is shrunk.  Returns a new array of the same kind as `y`.
+        joint=True: the K signals of a batch / items of a stack are thresholded together -- the magnitude compared and shrunk is that of
+        the group of K coefficients at one position (group soft thresholding, the prox of the l2,1 norm); a scalar threshold: every
+        detail band, band 0 kept; a sequence: one threshold per band."""
         if mode not in ("soft", "hard"):
             raise ValueError("mode must be 'soft' or 'hard'")
         like_numpy = isinstance(y, np.ndarray)
         if y.ndim != len(self._shape) + 1 or list(y.shape[:-1]) != self._shape:
             raise ValueError(f"coefficient array must have shape {self._shape + ['bands']}")
         level = self._level_from_bands(int(y.shape[-1]))
-        thr = self._band_thresholds(threshold, level)
+        thr = self._joint_thresholds(threshold, level) if joint else self._band_thresholds(threshold, level)
         dev = self._dev(y if isinstance(y, torch.Tensor) else None)
         yk, pitch = self._coef_kernel_order(y, dev)
         if isinstance(y, torch.Tensor) and yk.data_ptr() == y.data_ptr():
@@ -838,7 +866,9 @@ class _NdDwtBase:
                 yk = yk.clone()
         plan = self._plan(yk.is_complex(), level, dev)
         with torch.cuda.device(dev):
-            if thr is None:
+            if joint:
+                plan.shrink_joint(yk.data_ptr(), level, thr, mode == "hard", _current_stream(dev), band_pitch=pitch)
+            elif thr is None:
                 plan.shrink(yk.data_ptr(), level, threshold, mode == "hard", _current_stream(dev), band_pitch=pitch)
             elif thr.ndim == 2:
                 plan.shrink_bands_items(yk.data_ptr(), level, thr, mode == "hard", _current_stream(dev), band_pitch=pitch)
@@ -846,14 +876,14 @@ class _NdDwtBase:
                 plan.shrink_bands(yk.data_ptr(), level, thr, mode == "hard", _current_stream(dev), band_pitch=pitch)
         return self._from_device(yk, like_numpy, dev)
 
-    def denoise(self, x, level, threshold, mode="soft"):
-        """rec(shrink(dec(x, level), threshold)) in one call: the coefficients stay in a scratch array of the plan."""
+    def denoise(self, x, level, threshold, mode="soft", joint=False):
+        """rec(shrink(dec(x, level), threshold)) in one call: the coefficients stay in a scratch array of the plan.  joint: as shrink's."""
         if mode not in ("soft", "hard"):
             raise ValueError("mode must be 'soft' or 'hard'")
         level = int(level)
         if level < 1:
             raise ValueError("level must be >= 1")
-        thr = self._band_thresholds(threshold, level)
+        thr = self._joint_thresholds(threshold, level) if joint else self._band_thresholds(threshold, level)
         like_numpy = isinstance(x, np.ndarray)
         x = self._prep_dec_input(x)
         if list(x.shape) != self._shape:
@@ -863,7 +893,9 @@ class _NdDwtBase:
         plan = self._plan(xk.is_complex(), level, dev)
         out = torch.empty_like(xk)
         with torch.cuda.device(dev):
-            if thr is None:
+            if joint:
+                plan.denoise_joint(xk.data_ptr(), out.data_ptr(), level, thr, mode == "hard", _current_stream(dev))
+            elif thr is None:
                 plan.denoise(xk.data_ptr(), out.data_ptr(), level, threshold, mode == "hard", _current_stream(dev))
             elif thr.ndim == 2:
                 plan.denoise_bands_items(xk.data_ptr(), out.data_ptr(), level, thr, mode == "hard", _current_stream(dev))
@@ -886,6 +918,19 @@ class _NdDwtBase:
             per_item = f", or a [{self._items}, {nb}] array, one row per item" if self._items > 1 else ""
             raise ValueError(f"threshold must be a scalar or {nb} values, one per band of a {level}-level transform{per_item} (got shape {list(thr.shape)})")
         return thr.reshape(-1)
+
+    def _joint_thresholds(self, threshold, level):
+        """the thresholds of a joint call, one per band: a scalar for every detail band with band 0 kept, or the sequence; a row per item
+        has no meaning there"""
+        nb = num_bands(self.NDIM, level)
+        if np.ndim(threshold) == 0:
+            thr = np.full(nb, float(threshold))
+            thr[0] = 0.0
+            return thr
+        thr = self._band_thresholds(threshold, level)
+        if thr.ndim == 2:
+            raise ValueError(f"joint=True takes a scalar or {nb} thresholds, one per band: the items of a group share one (got shape {list(thr.shape)})")
+        return thr
 
     @property
     def _items(self):
@@ -992,6 +1037,32 @@ class _NdDwtBase:
                 raise ValueError(f"{nb} weights expected, one per band of the coefficient array, got {w.size}")
         r = self.band_norms(y, per_item)["l1"] @ w
         return r if per_item else float(r)
+
+    def group_norms(self, y):
+        """The sums over the groups of every band of a coefficient array -- a group is the K coefficients at one position across the
+        signals of a batch / items of a stack -- in one read of it: a dict of arrays `l1` (the sum of the groups' magnitudes: the l2,1
+        norm of the band), `l2sq` (the sum of their squares), `max` (the largest) and `nnz` (the count of groups that are not all zero),
+        one entry per band, band 0 included.  Without a batch or stack the group is the element.  The call waits for the result."""
+        yk, pitch, level, dev, plan = self._coef_for_stats(y)
+        with torch.cuda.device(dev):
+            v = plan.group_norms(yk.data_ptr(), level, _current_stream(dev), band_pitch=pitch)
+        return {"l1": v[:, L.NDWT_NORM_L1].copy(), "l2sq": v[:, L.NDWT_NORM_L2SQ].copy(), "max": v[:, L.NDWT_NORM_MAX].copy(),
+                "nnz": v[:, L.NDWT_NORM_NNZ].copy()}
+
+    def l21_norm(self, y, weights=None):
+        """sum over the bands of weights[b] * (the l2,1 norm of band b): the penalty whose prox shrink(.., joint=True) is.  weights: one per
+        band; by default 0 for band 0 and 1 for every other band.  A float."""
+        if y.ndim != len(self._shape) + 1 or list(y.shape[:-1]) != self._shape:
+            raise ValueError(f"coefficient array must have shape {self._shape + ['bands']}")
+        nb = int(y.shape[-1])
+        if weights is None:
+            w = np.ones(nb)
+            w[0] = 0.0
+        else:
+            w = np.asarray(weights, dtype=np.float64).reshape(-1)
+            if w.size != nb:
+                raise ValueError(f"{nb} weights expected, one per band of the coefficient array, got {w.size}")
+        return float(self.group_norms(y)["l1"] @ w)
 
     def sparsity(self, y, per_item=False):
         """the fraction of coefficients that are not zero, over all bands: a float, or a length-K array with per_item=True"""

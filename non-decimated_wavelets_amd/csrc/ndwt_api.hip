@@ -19,6 +19,7 @@
 #include "../../include/ndwt.h"
 #include "ndwt_device.h"
 #include "ndwt_device_items.h"
+#include "ndwt_device_joint.h"
 #include "ndwt_device_norms.h"
 #include "ndwt_device_select.h"
 #include "ndwt_filters.h"
@@ -2377,6 +2378,103 @@ int ndwt_band_norms_dev(ndwt_plan* p, const void* y, int64_t band_pitch, int lev
     if (rc) return rc;
     const long long items = per_item ? p->items() : 1, n = per_item ? p->item_vol() : p->vol;
     return on_device(p, [&](auto t) { return norms_run(p, (const decltype(t)*)y, bs, level, items, n, norms_dev, nullptr, (hipStream_t)stream); });
+}
+
+// ---- joint shrinkage across the items of a plan and the norms of the groups (include/ndwt.h; the kernels: ndwt_device_joint.h) ----
+// JointShrink on every band in one launch, by joint_chunks; the thresholds [nb] go up as a table of one row.  An all-zero array
+// launches (and uploads) nothing.
+extern "C++" template <typename T> static int joint_shrink_impl(ndwt_plan* p, T* y, long long bs, int level, const double* thr, int mode, hipStream_t s) {
+    const long long nb = ndwt_num_bands(p->ndim, level), items = p->items(), n = p->item_vol();
+    bool any = false;
+    for (long long b = 0; b < nb && !any; ++b) any = thr[b] != 0.0;
+    if (!any) return NDWT_OK;
+    const T* table = nullptr;
+    int rc = items_table_upload<T>(p, thr, (size_t)nb, s, &table);
+    if (rc) return rc;
+    const bool vec = aligned_vec4<T>(y) && bs % 4 == 0 && n % 4 == 0;
+    const long long chunks = joint_chunks(n, (int)p->comp, vec, nb, items, p->num_cus, p->target_blocks);
+    const JointShrinkArgs<T> a = {y, bs, n, table, items, (int)nb, (int)chunks, mode};
+    rc = launch_joint_shrink(a, (int)p->comp, vec, items <= kJointReg, table, s);
+    if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: no joint shrink kernel for this data kind or grid");
+    if (rc != 0) return fail(NDWT_ERR_HIP, "joint shrink kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    return NDWT_OK;
+}
+
+int ndwt_shrink_joint(ndwt_plan* p, void* y, int64_t band_pitch, int level, const double* thresholds, int mode, void* stream) {
+    int rc = bands_check(p, level, thresholds, mode);
+    if (rc) return rc;
+    if (!y) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (y_dev)");
+    long long bs = 0;
+    rc = pitch_scalars(p, band_pitch, &bs);
+    if (rc) return rc;
+    return on_device(p, [&](auto t) { return joint_shrink_impl(p, (decltype(t)*)y, bs, level, thresholds, mode, (hipStream_t)stream); });
+}
+
+// the general route only: dec into the plan's pitched scratch, JointShrink, rec (no thresholding in the synthesis loads)
+int ndwt_denoise_joint(ndwt_plan* p, const void* x, void* out, int level, const double* thresholds, int mode, void* stream) {
+    int rc = bands_check(p, level, thresholds, mode);
+    if (rc) return rc;
+    if (!x || !out) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (x_dev or out_dev)");
+    return on_device(p, [&](auto t) {
+        typedef decltype(t) T;
+        T* coef = nullptr;
+        long long bs = 0;
+        int rc = dec_scratch<T>(p, (const T*)x, level, (hipStream_t)stream, &coef, &bs);
+        if (rc == NDWT_OK) rc = joint_shrink_impl<T>(p, coef, bs, level, thresholds, mode, (hipStream_t)stream);
+        if (rc == NDWT_OK) rc = rec_impl<T>(p, coef, bs, (T*)out, level, kNoShrink, (hipStream_t)stream);
+        return rc;
+    });
+}
+
+// GroupNorms on every band in one launch, by joint_chunks; with more than one chunk the partials go to the plan's buffer and NormsFinish
+// (one item) combines them.  out_dev: [nb][4] doubles, or null: the results' place in the plan's buffer (returned in *res).  Enqueued only.
+extern "C++" template <typename T> static int group_norms_run(ndwt_plan* p, const T* y, long long bs, int level, double* out_dev, double** res, hipStream_t s) {
+    const long long nb = ndwt_num_bands(p->ndim, level), items = p->items(), n = p->item_vol();
+    const bool vec = aligned_vec4<T>(y) && bs % 4 == 0 && n % 4 == 0;
+    const long long chunks = joint_chunks(n, (int)p->comp, vec, nb, items, p->num_cus, p->target_blocks);
+    const size_t res_bytes = (size_t)nb * 4 * sizeof(double);
+    int rc = p->norms_buf.grow(res_bytes * (chunks > 1 ? 1 + (size_t)chunks : 1), "for the group norms");
+    if (rc) return rc;
+    double* const results = out_dev ? out_dev : (double*)p->norms_buf.ptr;
+    double* const partials = (double*)((char*)p->norms_buf.ptr + res_bytes);
+    const GroupNormsArgs<T> a = {y, bs, n, chunks > 1 ? partials : results, items, (int)nb, (int)chunks};
+    rc = launch_group_norms(a, (int)p->comp, vec, p->norms_buf.ptr, s);
+    if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: no group-norms kernel for this data kind or grid");
+    if (rc != 0) return fail(NDWT_ERR_HIP, "group-norms kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    if (chunks > 1) {
+        const NormsFinishArgs f = {partials, results, 1, (int)nb, 0, (int)nb, (int)chunks};
+        rc = launch_norms_finish(f, p->norms_buf.ptr, s);
+        if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: a grid the group-norms combine cannot express");
+        if (rc != 0) return fail(NDWT_ERR_HIP, "group-norms combine launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    if (res) *res = results;
+    return NDWT_OK;
+}
+
+int ndwt_group_norms(ndwt_plan* p, const void* y, int64_t band_pitch, int level, double* norms, void* stream) {
+    int rc = norms_check(p, y, level, norms, "norms");
+    if (rc) return rc;
+    long long bs = 0;
+    rc = pitch_scalars(p, band_pitch, &bs);
+    if (rc) return rc;
+    return on_device(p, [&](auto t) {
+        double* res = nullptr;
+        const int rc = group_norms_run(p, (const decltype(t)*)y, bs, level, nullptr, &res, (hipStream_t)stream);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(norms, res, (size_t)ndwt_num_bands(p->ndim, level) * 4 * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        return (int)NDWT_OK;
+    });
+}
+
+int ndwt_group_norms_dev(ndwt_plan* p, const void* y, int64_t band_pitch, int level, double* norms_dev, void* stream) {
+    int rc = norms_check(p, y, level, norms_dev, "norms_dev");
+    if (rc) return rc;
+    if ((uintptr_t)norms_dev % sizeof(double) != 0) return fail(NDWT_ERR_INVALID_ARG, "norms_dev must be 8-byte aligned");
+    long long bs = 0;
+    rc = pitch_scalars(p, band_pitch, &bs);
+    if (rc) return rc;
+    return on_device(p, [&](auto t) { return group_norms_run(p, (const decltype(t)*)y, bs, level, norms_dev, nullptr, (hipStream_t)stream); });
 }
 
 int ndwt_denoise_host(ndwt_plan* p, const void* x, void* out, int level, double threshold, int mode) {

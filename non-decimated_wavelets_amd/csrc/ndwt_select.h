@@ -503,6 +503,20 @@ constexpr long long norms_chunks(long long item_scalars, int comp, bool vec, lon
 // past 2^31 - 1 (band, item) blocks a launch cannot number its workgroups: one launch per band (items < 2^31: a band alone always fits,
 // and has one chunk)
 constexpr bool norms_per_band(long long bands, long long items) { return bands * items > 0x7fffffffLL; }
+// ... and the workgroups per band of JointShrink / GroupNorms (ndwt_device_joint.h), whose step moves one load of every item: at least
+// one; a further chunk only while every thread of 256 keeps max(1, kSelectTurns / items) steps; all bands together within num_cus * 16;
+// target_blocks > 0 is an upper bound on all workgroups on top of that, as for norms_chunks.
+constexpr long long joint_chunks(long long item_scalars, int comp, bool vec, long long bands, long long items, int num_cus, int target_blocks) {
+    const long long steps = vec ? item_scalars / 4 : item_scalars / comp, turns = kSelectTurns / items < 1 ? 1 : kSelectTurns / items;
+    long long c = steps / (256 * turns);
+    const long long room = (long long)num_cus * 16 / bands;
+    if (c > room) c = room;
+    if (target_blocks > 0 && c > target_blocks / bands) c = target_blocks / bands;
+    return c < 1 ? 1 : c;
+}
+// JointShrink keeps the group of a step in registers up to this many items (the instance is compiled for exactly this many: the
+// largest of 4, 8 and 16 that leaves complex128 in the 4-scalar form without scratch and without spills -- 16 spills scalar registers, one address per item)
+constexpr int kJointReg = 8;
 
 // ---- one fused 3-D launch
 struct Fused3Query {
