@@ -137,6 +137,20 @@ int dispatch(int Lp, int vec4, ndwt::Fused3Args<T>& a, const double* lo, const d
 #undef CASE
 }
 
+// 14 and 16 taps on the small test tile: the kernels whose lists go that far (Fwd3, Inv3S; the LDS kernel Inv3 stops at 12)
+template <typename T, template <typename, int, int, int, int, int, bool, int, int> class KIND, int TX, int TY, int NT, int RY>
+int dispatch_long(int Lp, int vec4, ndwt::Fused3Args<T>& a, const double* lo, const double* hi) {
+#define CASE(LL)                                                              \
+    case LL:                                                                  \
+        return vec4 ? run<KIND<T, LL, TX, TY, NT, RY, true, 2, 1>, T>(a, lo, hi)     \
+                    : run<KIND<T, LL, TX, TY, NT, RY, false, 2, 1>, T>(a, lo, hi);
+    switch (Lp) {
+        CASE(14) CASE(16)
+        default: return -1;
+    }
+#undef CASE
+}
+
 // INV is a compile-time parameter so that the analysis and synthesis kernels land in separate translation units
 // (tests/emu/Makefile compiles this file once per EMU_PART, in parallel)
 template <typename T, bool INV>
@@ -257,10 +271,11 @@ int emu3(int Lp, int vec4, const T* in, T* out, int n1, int n2, int n3, int nbat
         geometry(16, 8);
         if constexpr (INV) {
             if (variant == 2)   // lane-shift synthesis on the small tile, every tap length
-                return dispatch<T, ndwt::Inv3S, 16, 8, 128, 2, true>(Lp, vec4, a, lo, hi);
+                return Lp > 12 ? dispatch_long<T, ndwt::Inv3S, 16, 8, 128, 2>(Lp, vec4, a, lo, hi)
+                               : dispatch<T, ndwt::Inv3S, 16, 8, 128, 2, true>(Lp, vec4, a, lo, hi);
             return dispatch<T, ndwt::Inv3, 16, 8, 64, 2, true>(Lp, vec4, a, lo, hi);
         } else {
-            return dispatch<T, ndwt::Fwd3, 16, 8, 64, 2, true>(Lp, vec4, a, lo, hi);
+            return Lp > 12 ? dispatch_long<T, ndwt::Fwd3, 16, 8, 64, 2>(Lp, vec4, a, lo, hi) : dispatch<T, ndwt::Fwd3, 16, 8, 64, 2, true>(Lp, vec4, a, lo, hi);
         }
     }
     if constexpr (INV) {
@@ -332,7 +347,7 @@ int emu2(int inverse, int Lp, int vec4, const T* in, T* out, int n1, int n2, int
         }
     if (ew == 2) {
         switch (Lp) {
-            CASE2C(2) CASE2C(4) CASE2C(8)
+            CASE2C(2) CASE2C(4) CASE2C(8) CASE2C(10) CASE2C(12) CASE2C(14) CASE2C(16)
             default: return -1;
         }
     }
@@ -347,7 +362,7 @@ int emu2(int inverse, int Lp, int vec4, const T* in, T* out, int n1, int n2, int
             return vec4 ? run2<ndwt::Fwd2S<T, LL, true>, T>(a, lo, hi) : run2<ndwt::Fwd2S<T, LL, false>, T>(a, lo, hi); \
         }
     switch (Lp) {
-        CASE2(2) CASE2(4) CASE2(6) CASE2(8) CASE2(10) CASE2(12)
+        CASE2(2) CASE2(4) CASE2(6) CASE2(8) CASE2(10) CASE2(12) CASE2(14) CASE2(16) CASE2(18) CASE2(20)
         default: return -1;
     }
 #undef CASE2
@@ -380,7 +395,7 @@ int emu_march(int syn, int L, const T* in0, const T* in1, T* out0, T* out1, long
     a.nchunks = (int)((n + a.chunk - 1) / a.chunk);
 #define CASEM(LL) case LL: return syn ? run_march<T, LL, true>(a, lo, hi) : run_march<T, LL, false>(a, lo, hi);
     switch (L) {
-        CASEM(2) CASEM(4) CASEM(8) CASEM(12) CASEM(20)
+        CASEM(2) CASEM(4) CASEM(8) CASEM(10) CASEM(12) CASEM(14) CASEM(16) CASEM(18) CASEM(20)
         default: return -1;
     }
 #undef CASEM
@@ -419,7 +434,7 @@ int emu_axisx(int syn, int L, int ew, int vec4, const T* in0, const T* in1, T* o
         if (ew == 1) return syn ? run_axisx<T, LL, true, 1>(a, vec4, lo, hi) : run_axisx<T, LL, false, 1>(a, vec4, lo, hi); \
         return syn ? run_axisx<T, LL, true, 2>(a, vec4, lo, hi) : run_axisx<T, LL, false, 2>(a, vec4, lo, hi);
     switch (L) {
-        CASEX(2) CASEX(8) CASEX(12)
+        CASEX(2) CASEX(8) CASEX(10) CASEX(12)
         default: return -1;
     }
 #undef CASEX
@@ -681,6 +696,11 @@ extern "C" int ndwt_emu_pin3_f32(int Lp, const float* x, float* out, int n1, int
         case 16: {   // 16 taps: plain taps, 2 of the 16 z-window slots in LDS (Fwd3 WLDS)
             typedef ndwt::Fused3Tile<float, false, 6> TL;
             return run<ndwt::Fwd3<float, 16, TL::TX, TL::TY, TL::NT, TL::RY, true, 2, 1, false, false, false, 2>, float>(a, alo, ahi);
+        }
+        case 18: {   // 18 taps on rows of whole groups of 4: the 512-thread 64x16 tile, the whole window in registers
+            typedef ndwt::Fused3Tile<float, false, 1> TL;
+            ndwt::fused3_geometry(a, TL::TX, TL::TY, Lp, 4, zchunk);
+            return run<ndwt::Fwd3<float, 18, TL::TX, TL::TY, TL::NT, TL::RY, true, 2, 1, false, false, false, 0>, float>(a, alo, ahi);
         }
         case 20: {   // 20 taps: the 512-thread 64x16 tile, two columns per thread, 4 of the 20 window slots of each in LDS
             typedef ndwt::Fused3Tile<float, false, 1> TL;
