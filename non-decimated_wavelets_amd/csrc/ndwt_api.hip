@@ -20,6 +20,7 @@
 #include "ndwt_device.h"
 #include "ndwt_device_items.h"
 #include "ndwt_device_joint.h"
+#include "ndwt_device_joint_tile.h"
 #include "ndwt_device_norms.h"
 #include "ndwt_device_select.h"
 #include "ndwt_filters.h"
@@ -2381,8 +2382,8 @@ int ndwt_band_norms_dev(ndwt_plan* p, const void* y, int64_t band_pitch, int lev
 }
 
 // ---- joint shrinkage across the items of a plan and the norms of the groups (include/ndwt.h; the kernels: ndwt_device_joint.h) ----
-// JointShrink on every band in one launch, by joint_chunks; the thresholds [nb] go up as a table of one row.  An all-zero array
-// launches (and uploads) nothing.
+// JointShrink on every band in one launch, by joint_chunks -- or JointTile, by joint_tile_strips, where joint_route names it; the
+// thresholds [nb] go up as a table of one row.  An all-zero array launches (and uploads) nothing.
 extern "C++" template <typename T> static int joint_shrink_impl(ndwt_plan* p, T* y, long long bs, int level, const double* thr, int mode, hipStream_t s) {
     const long long nb = ndwt_num_bands(p->ndim, level), items = p->items(), n = p->item_vol();
     bool any = false;
@@ -2392,9 +2393,10 @@ extern "C++" template <typename T> static int joint_shrink_impl(ndwt_plan* p, T*
     int rc = items_table_upload<T>(p, thr, (size_t)nb, s, &table);
     if (rc) return rc;
     const bool vec = aligned_vec4<T>(y) && bs % 4 == 0 && n % 4 == 0;
-    const long long chunks = joint_chunks(n, (int)p->comp, vec, nb, items, p->num_cus, p->target_blocks);
+    const bool tile = joint_route(n, (int)p->comp, vec, nb, items, p->num_cus, p->variant_inv) == kJointTile;
+    const long long chunks = tile ? joint_tile_strips(n, (int)p->comp, vec) : joint_chunks(n, (int)p->comp, vec, nb, items, p->num_cus, p->target_blocks);
     const JointShrinkArgs<T> a = {y, bs, n, table, items, (int)nb, (int)chunks, mode};
-    rc = launch_joint_shrink(a, (int)p->comp, vec, items <= kJointReg, table, s);
+    rc = tile ? launch_joint_tile(a, (int)p->comp, vec, table, s) : launch_joint_shrink(a, (int)p->comp, vec, items <= kJointReg, table, s);
     if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: no joint shrink kernel for this data kind or grid");
     if (rc != 0) return fail(NDWT_ERR_HIP, "joint shrink kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     return NDWT_OK;
@@ -2426,19 +2428,21 @@ int ndwt_denoise_joint(ndwt_plan* p, const void* x, void* out, int level, const 
     });
 }
 
-// GroupNorms on every band in one launch, by joint_chunks; with more than one chunk the partials go to the plan's buffer and NormsFinish
-// (one item) combines them.  out_dev: [nb][4] doubles, or null: the results' place in the plan's buffer (returned in *res).  Enqueued only.
+// GroupNorms on every band in one launch, by joint_chunks -- or GroupNormsTile, by joint_tile_strips, where joint_route names it; with
+// more than one chunk (strip) the partials go to the plan's buffer and NormsFinish (one item) combines them.  out_dev: [nb][4] doubles, or null: the results' place in the plan's
+// buffer (returned in *res).  Enqueued only.
 extern "C++" template <typename T> static int group_norms_run(ndwt_plan* p, const T* y, long long bs, int level, double* out_dev, double** res, hipStream_t s) {
     const long long nb = ndwt_num_bands(p->ndim, level), items = p->items(), n = p->item_vol();
     const bool vec = aligned_vec4<T>(y) && bs % 4 == 0 && n % 4 == 0;
-    const long long chunks = joint_chunks(n, (int)p->comp, vec, nb, items, p->num_cus, p->target_blocks);
+    const bool tile = joint_route(n, (int)p->comp, vec, nb, items, p->num_cus, p->variant_inv) == kJointTile;
+    const long long chunks = tile ? joint_tile_strips(n, (int)p->comp, vec) : joint_chunks(n, (int)p->comp, vec, nb, items, p->num_cus, p->target_blocks);
     const size_t res_bytes = (size_t)nb * 4 * sizeof(double);
     int rc = p->norms_buf.grow(res_bytes * (chunks > 1 ? 1 + (size_t)chunks : 1), "for the group norms");
     if (rc) return rc;
     double* const results = out_dev ? out_dev : (double*)p->norms_buf.ptr;
     double* const partials = (double*)((char*)p->norms_buf.ptr + res_bytes);
     const GroupNormsArgs<T> a = {y, bs, n, chunks > 1 ? partials : results, items, (int)nb, (int)chunks};
-    rc = launch_group_norms(a, (int)p->comp, vec, p->norms_buf.ptr, s);
+    rc = tile ? launch_group_norms_tile(a, (int)p->comp, vec, p->norms_buf.ptr, s) : launch_group_norms(a, (int)p->comp, vec, p->norms_buf.ptr, s);
     if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: no group-norms kernel for this data kind or grid");
     if (rc != 0) return fail(NDWT_ERR_HIP, "group-norms kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
     if (chunks > 1) {

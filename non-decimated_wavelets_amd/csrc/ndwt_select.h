@@ -517,6 +517,50 @@ constexpr long long joint_chunks(long long item_scalars, int comp, bool vec, lon
 // JointShrink keeps the group of a step in registers up to this many items (the instance is compiled for exactly this many: the
 // largest of 4, 8 and 16 that leaves complex128 in the 4-scalar form without scratch and without spills -- 16 spills scalar registers, one address per item)
 constexpr int kJointReg = 8;
+// ---- the tile form of the same two calls (JointTile / GroupNormsTile, ndwt_device_joint_tile.h): a workgroup takes a STRIP of
+// kJointTileSW consecutive steps of one band and walks all items, kJointTileJ of them at a time through an LDS tile, so that a band of
+// short items gets steps / kJointTileSW workgroups whose 256 threads all load, where joint_chunks gives it steps / 256 whose threads each
+// chase the items one behind the other.  The values are the same bits (the sum of a group still runs over the items in ascending order).
+constexpr int kJointTileSW = 8, kJointTileJ = 128;
+// the strips (workgroups) per band
+constexpr long long joint_tile_strips(long long item_scalars, int comp, bool vec) {
+    return ((vec ? item_scalars / 4 : item_scalars / comp) + kJointTileSW - 1) / kJointTileSW;
+}
+// Which form a launch takes.  variant_inv 11 forces the tile form wherever a launch can number its workgroups, 9 never takes it (A/B
+// runs and the tests), anything else is the measured default.  With fewer than kJointTileFrom items the tile form is never taken
+// unasked: up to kJointReg items the register form runs at the copy rate, and a pass of the tile form loads 256 / kJointTileSW items.
+// Measured on the MI355X (tools/bench_joint_tile.py, batches of real signals in the 4-scalar form, us per call, tile form / chunk form,
+// ONE rule for the shrink and for the norms; the full table is in DESIGN.md 4.3h and profiles/bench_joint_tile.txt).  Float, level 1:
+//   items   1024 scalars               4096 scalars               16384 scalars              65536 scalars
+//   16      shrink 16.5 / 21.4 (0.77)  16.3 / 22.2 (0.73)         16.2 / 22.4 (0.73)         22.6 / 22.2 (1.02)
+//           norms   9.9 /  8.2 (1.20)   9.7 / 11.6 (0.84)         11.5 / 11.6 (0.99)         26.3 / 11.6 (2.27)
+//   64      shrink 16.4 / 41.9 (0.39)  16.4 / 45.0 (0.36)         18.3 / 42.0 (0.43)         26.6 / 40.8 (0.65)
+//           norms  10.5 / 17.9 (0.58)   9.7 / 21.0 (0.46)         12.1 / 21.2 (0.57)         29.3 / 22.2 (1.32)
+//   256     shrink 18.9 / 125.1 (0.15) 19.8 / 120.9 (0.16)        22.7 / 121.1 (0.19)        62.5 / 167.6 (0.37)
+//           norms  11.6 / 54.9 (0.21)  11.8 / 58.6 (0.20)         14.6 / 62.4 (0.23)         42.8 / 91.8 (0.47)
+//   4096    shrink 78.4 / 2386.6 (0.03) 95.3 / 2209.1 (0.04)      (1024 items: 71.6 / 583.5 (0.12); norms 35.7 / 336.5 (0.11))
+//           norms  59.2 / 1315.2 (0.05) 55.0 / 1342.0 (0.04)
+// Double and level 4 (5 bands) give the same picture; the worst ratios of the cells the rule takes are the norms of 64 items of 16384
+// scalars at level 4, 0.86 (float) and 0.68 (double), and of 256 items of 65536, 0.56 (double).  By the rule of DESIGN.md 4.3b -- a
+// form is taken unasked only where it was measured at least 10 % below the other, twice the 5 % spread between boxes -- the tile form
+// takes bands of up to kJointTileMaxSteps steps from kJointTileFrom items on and bands of up to kJointTileMaxStepsMany steps from
+// kJointTileManyFrom items on.  At 64 items of 65536 scalars the shrink wins (0.63 .. 0.74) but the norms lose (1.03 .. 1.47: thousands
+// of strips of 64 items each end in a tree and a partial), and the rule is one for both.  With 16 items only the 4096-scalar cells
+// qualify (0.72 .. 0.88); fewer than kJointTileFrom items keep the chunk form whatever was measured.  Longer items than 65536 scalars were not measured and keep the
+// chunk form; more items than measured at a length take the tile form (the chunk form's chain of loads grows with the items, a
+// strip's work does not change shape).  The element-wise form was not measured and is on request only; complex data were not
+// measured: their steps are counted like those of real data.
+enum JointRoute { kJointChunks, kJointTile };
+constexpr long long kJointTileFrom = 64, kJointTileMaxSteps = 4096;                    // from 64 items on: bands of up to 4096 steps
+constexpr long long kJointTileManyFrom = 256, kJointTileMaxStepsMany = 16384;          // from 256 items on: bands of up to 16384 steps
+constexpr JointRoute joint_route(long long item_scalars, int comp, bool vec, long long bands, long long items, int num_cus, int variant_inv) {
+    if (variant_inv == kInvCascadeOff || bands < 1 || bands * joint_tile_strips(item_scalars, comp, vec) > 0x7fffffffLL) return kJointChunks;
+    if (variant_inv == kInvCascadeAlways) return kJointTile;
+    (void)num_cus;                                            // (the table holds for the one device it was measured on)
+    const long long steps = vec ? item_scalars / 4 : item_scalars / comp;
+    return vec && ((items >= kJointTileFrom && steps <= kJointTileMaxSteps) || (items >= kJointTileManyFrom && steps <= kJointTileMaxStepsMany)) ? kJointTile
+                                                                                                                                                  : kJointChunks;
+}
 
 // ---- one fused 3-D launch
 struct Fused3Query {
