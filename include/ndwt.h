@@ -377,6 +377,59 @@ enum { NDWT_NORM_L1 = 0, NDWT_NORM_L2SQ = 1, NDWT_NORM_MAX = 2, NDWT_NORM_NNZ = 
 int ndwt_band_norms(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double* norms, void* stream);
 int ndwt_band_norms_items(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double* norms, void* stream);
 int ndwt_band_norms_dev(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, int per_item, double* norms_dev, void* stream);
+/* ---- SURE thresholds (SureShrink): what Stein's unbiased estimate of the risk of a soft threshold needs of a band, at up to
+ * NDWT_RISK_MAX_CAND candidate thresholds in ONE read of the array; the estimate; and the search for the threshold that minimises it ----
+ * ndwt_band_risk, ndwt_band_risk_items: for every (band, item) block of a level-`level` coefficient array on the device (band_pitch 0 =
+ *   packed) and every candidate i < nc of that block, three doubles in this order.  t = the candidate rounded once to the plan's scalar
+ *   type, as the shrink rounds its threshold; m = the magnitude of an element: |c|, of interleaved complex data sqrt(re^2 + im^2) computed
+ *   in the plan's scalar type -- the bits the shrink compares, ndwt_band_select orders and NDWT_NORM_MAX returns.
+ *   NDWT_RISK_COUNT   the count of elements with !(m > t): those a shrink at t sets to zero.  A NaN counts.  An integer, written as a double
+ *   NDWT_RISK_ENERGY  the sum of c^2 (complex: re^2 + im^2) over those elements, accumulated in double from the widened parts with a fused
+ *                     multiply-add, as NDWT_NORM_L2SQ is.  A NaN in the block makes it NaN for every candidate
+ *   NDWT_RISK_INVSUM  complex data: the sum of 1.0 / (double)m over the elements with m > t.  Real data: 0, nothing is computed for it
+ *   nc: 1 .. NDWT_RISK_MAX_CAND.  nb = ndwt_num_bands(filtered axes, level).
+ *   cand: HOST, [nb][nc] doubles (ndwt_band_risk: a band is the plan's whole array, as ndwt_band_norms sees it) or [items][nb][nc]
+ *   (ndwt_band_risk_items: the items of ndwt_band_norms_items), cand[((j * nb + b) * nc + i)].  A candidate is >= 0; +inf is allowed (it
+ *   counts every element).  A row whose FIRST entry is negative skips its block: no workgroup reads that block and its nc * 3 results are
+ *   0 -- how the approximation band is left out.  A NaN, or a negative entry elsewhere in a row: NDWT_ERR_INVALID_ARG, the message names
+ *   the band, (the item,) and the position, and nothing is launched.
+ *   risk: HOST, [nb][nc][3] or [items][nb][nc][3] doubles, risk[((j * nb + b) * nc + i) * 3 + s].
+ *   Blocks, items, pooling, band_pitch, the grid (one launch, BandRisk, over all blocks; a second small one, RiskFinish, where a block
+ *   has more than one chunk), the plan-owned buffer and the fixed order of every sum -- no floating-point atomics, two calls on one device
+ *   return the same bits -- are those of ndwt_band_norms, and so are the plan kinds served and the refusals (plan, y_dev, cand or risk
+ *   null, level, pitch: NDWT_ERR_INVALID_ARG; 2^31 items: NDWT_ERR_UNSUPPORTED).  The candidates go to the device as the threshold table
+ *   of ndwt_shrink_bands_items does, with its host wait for the previous table's copy.  Synchronous like ndwt_band_norms: enqueue on
+ *   `stream`, one copy back, one synchronisation.  The coefficient array is never written.
+ * ndwt_sure_from_risk: HOST only, no device and no plan.  With d = comp (1 real, 2 complex), n the elements of the block, s the standard
+ *   deviation of the noise in each real part of a coefficient of the band (sigma * the band's gain, ndwt_band_gains) and t = cand[i],
+ *   C, E, I = the three statistics risk[3 * i ..] of candidate i:
+ *     sure[i] = n d s^2 + E + t^2 (n - C) - 2 s^2 (d C + (d - 1) t I)
+ *   Stein's unbiased estimate of the risk of soft thresholding at t; for d = 2 of the magnitude shrink the library performs.  (Where
+ *   nothing lies above t -- t = +inf -- the terms in n - C and I are 0.)  comp not 1 or 2, n or s negative, NaN or infinite, nc < 1, a
+ *   null pointer: NDWT_ERR_INVALID_ARG.
+ * ndwt_sure_thresholds, ndwt_sure_thresholds_items: the soft threshold of every block that minimises that estimate, searched on the
+ *   device's statistics.  sigma: the noise level of the data (the items form: HOST, [items]), finite and >= 0; thresholds: HOST, [nb] or
+ *   [items][nb] -- a row ndwt_shrink_bands(_items) and ndwt_denoise_bands(_items) take as it is; sure: HOST, the estimate at the
+ *   threshold returned, same shape, or null.  rounds: 1 .. 8; 0 means 3.
+ *   Band 0 gets the threshold 0 (and the estimate 0) and is never read.  For every other block, with s = sigma * the plan's own gain of
+ *   the band, N the elements of ONE item's filtered axes and n the elements of the block (n = N but for a pooled batch or interleaved
+ *   samples): t_max = s sqrt(2 ln N), the universal threshold; the search starts from lo = 0, hi = t_max and best = (t = 0, n d s^2: the
+ *   estimate at 0).  Every round forms the 8 candidates lo + (hi - lo) (i + 1) / 8 in double, rounds each to the plan's scalar type -- the
+ *   statistics are then those of exactly the threshold a later shrink applies --, runs ONE ndwt_band_risk(_items) over all blocks, takes
+ *   the first candidate with the smallest estimate, makes it `best` if it is below, and with step = (hi - lo) / 8 continues on
+ *   lo = max(best.t - step, 0), hi = min(best.t + step, t_max).  Three rounds resolve t_max / 128.  A block with s = 0, with one element,
+ *   or with a NaN keeps the threshold 0.  The detail bands are read `rounds` times.  Refusals: those of ndwt_band_risk; sigma or
+ *   thresholds null, sigma negative, NaN or infinite, rounds outside 0 .. 8: NDWT_ERR_INVALID_ARG, nothing is launched.
+ * Not built: a device-pointer form of either table; more than 8 candidates in a call; groups across items (the joint form of the
+ *   estimate); the MATLAB gateway. */
+enum { NDWT_RISK_COUNT = 0, NDWT_RISK_ENERGY = 1, NDWT_RISK_INVSUM = 2, NDWT_RISK_STATS = 3 };
+#define NDWT_RISK_MAX_CAND 8
+int ndwt_band_risk(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, int nc, const double* cand, double* risk, void* stream);
+int ndwt_band_risk_items(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, int nc, const double* cand, double* risk, void* stream);
+int ndwt_sure_from_risk(int comp, double n, double s, int nc, const double* cand, const double* risk, double* sure);
+int ndwt_sure_thresholds(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double sigma, int rounds, double* thresholds, double* sure, void* stream);
+int ndwt_sure_thresholds_items(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, const double* sigma, int rounds, double* thresholds, double* sure,
+                               void* stream);
 /* ---- joint shrinkage across the items of a plan: the prox of the l2,1 norm (group soft thresholding), and that norm ----
  * The items of a batched, stack or interleaved plan are often coils, echoes, channels, colour planes or traces of ONE object, and the
  * regulariser is joint sparsity: a coefficient survives if the GROUP of coefficients at its position across all items is large.

@@ -3,10 +3,10 @@
 Import with `importlib.import_module("non-decimated_wavelets_amd")` (the directory name is not a
 Python identifier) or through the `ndwt_amd` alias module at the repository root.
 """
-from ._lib import LIB_PATH, NdwtError, band_gains, build, lib, wave_filters  # noqa: F401
+from ._lib import LIB_PATH, NdwtError, band_gains, build, lib, sure_from_risk, wave_filters  # noqa: F401
 from .trace import KernelLaunch, kernel_trace  # noqa: F401
 
-__all__ = ["LIB_PATH", "NdwtError", "build", "lib", "wave_filters", "band_gains", "kernel_trace", "KernelLaunch", "Plan", "num_bands", "nd_dwt_1D", "nd_dwt_2D",
+__all__ = ["LIB_PATH", "NdwtError", "build", "lib", "wave_filters", "band_gains", "sure_from_risk", "kernel_trace", "KernelLaunch", "Plan", "num_bands", "nd_dwt_1D", "nd_dwt_2D",
            "nd_dwt_3D", "nd_dwt_4D", "ShardedNdDwt", "MultiPlan", "Coefficients"]
 
 

@@ -20,6 +20,8 @@ NDWT_REAL, NDWT_COMPLEX_INTERLEAVED = 0, 1
 NDWT_DILATION_REFERENCE, NDWT_DILATION_ATROUS = 0, 1
 NDWT_PATH_AUTO, NDWT_PATH_GENERIC = 0, 1
 NDWT_NORM_L1, NDWT_NORM_L2SQ, NDWT_NORM_MAX, NDWT_NORM_NNZ, NDWT_NORM_COUNT = 0, 1, 2, 3, 4
+NDWT_RISK_COUNT, NDWT_RISK_ENERGY, NDWT_RISK_INVSUM, NDWT_RISK_STATS = 0, 1, 2, 3
+NDWT_RISK_MAX_CAND = 8
 
 EXPORTS = [
     "ndwt_wave_filters", "ndwt_num_bands", "ndwt_level_from_bands", "ndwt_plan_create", "ndwt_plan_create_slab", "ndwt_plan_destroy",
@@ -36,6 +38,7 @@ EXPORTS = [
     "ndwt_plan_create_interleaved", "ndwt_band_gains", "ndwt_shrink_bands", "ndwt_denoise_bands", "ndwt_band_select",
     "ndwt_estimate_sigma_coef", "ndwt_estimate_sigma", "ndwt_band_select_items", "ndwt_estimate_sigma_coef_items", "ndwt_estimate_sigma_items",
     "ndwt_shrink_bands_items", "ndwt_denoise_bands_items", "ndwt_band_norms", "ndwt_band_norms_items", "ndwt_band_norms_dev",
+    "ndwt_band_risk", "ndwt_band_risk_items", "ndwt_sure_from_risk", "ndwt_sure_thresholds", "ndwt_sure_thresholds_items",
     "ndwt_shrink_joint", "ndwt_denoise_joint", "ndwt_group_norms", "ndwt_group_norms_dev",
 ]
 
@@ -132,6 +135,15 @@ def lib() -> ctypes.CDLL:
     L.ndwt_band_norms.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
     L.ndwt_band_norms_items.argtypes = L.ndwt_band_norms.argtypes
     L.ndwt_band_norms_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    # the SURE statistics: candidates [nb][nc] / [items][nb][nc] and results [..][nc][3] on the host; the estimate (host only); the search
+    c_double_p = ctypes.POINTER(ctypes.c_double)
+    L.ndwt_band_risk.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_double_p, c_double_p, ctypes.c_void_p]
+    L.ndwt_band_risk_items.argtypes = L.ndwt_band_risk.argtypes
+    L.ndwt_sure_from_risk.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_int, c_double_p, c_double_p, c_double_p]
+    L.ndwt_sure_thresholds.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_double, ctypes.c_int, c_double_p, c_double_p,
+                                       ctypes.c_void_p]
+    L.ndwt_sure_thresholds_items.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, c_double_p, ctypes.c_int, c_double_p, c_double_p,
+                                             ctypes.c_void_p]
     # joint shrinkage across the items and the group norms: thresholds [nb] on the host; results [nb][4] on the host or on the device
     L.ndwt_shrink_joint.argtypes = L.ndwt_shrink_bands.argtypes
     L.ndwt_denoise_joint.argtypes = L.ndwt_denoise_bands.argtypes
@@ -239,3 +251,19 @@ def band_gains(dims, wnames, level, pres_l2_norm=0, dilation="reference"):
     check(lib().ndwt_band_gains(len(dims), c_dims, c_names, int(bool(pres_l2_norm)), NDWT_DILATION_ATROUS if dilation == "atrous" else NDWT_DILATION_REFERENCE,
                                 int(level), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
     return out[:nb]
+
+
+def sure_from_risk(comp, n, s, cand, risk):
+    """Stein's unbiased estimate of the risk of a soft threshold at every candidate of ONE block, from the statistics of band_risk --
+    include/ndwt.h: ndwt_sure_from_risk.  comp: 1 real, 2 complex data; n: the elements of the block; s: the standard deviation of the
+    noise in each real part of a coefficient of the band; cand: nc thresholds; risk: [nc, 3] (count, energy, invsum).  A length-nc
+    numpy array.  Host only: no device is needed."""
+    import numpy as np
+    c = np.ascontiguousarray(np.asarray(cand, dtype=np.float64).reshape(-1))
+    r = np.ascontiguousarray(np.asarray(risk, dtype=np.float64))
+    if r.shape != (c.size, NDWT_RISK_STATS):
+        raise ValueError(f"risk must be a [{c.size}, {NDWT_RISK_STATS}] array, one row per candidate, got {list(r.shape)}")
+    out = np.zeros(max(c.size, 1))
+    dp = ctypes.POINTER(ctypes.c_double)
+    check(lib().ndwt_sure_from_risk(int(comp), float(n), float(s), int(c.size), c.ctypes.data_as(dp), r.ctypes.data_as(dp), out.ctypes.data_as(dp)))
+    return out[:c.size]

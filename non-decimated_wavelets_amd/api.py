@@ -298,6 +298,57 @@ class Plan:
         copy and no synchronisation -- the results are there in stream order"""
         L.check(L.lib().ndwt_band_norms_dev(self._h, y_ptr, int(band_pitch), int(level), int(bool(per_item)), out_ptr, ctypes.c_void_p(stream)))
 
+    # -- the SURE statistics and the threshold search (include/ndwt.h: ndwt_band_risk, ndwt_sure_thresholds) --
+    def _risk_table(self, cand, level, items):
+        nb = self._num_bands(level)
+        c = np.ascontiguousarray(np.asarray(cand, dtype=np.float64))
+        lead = (nb,) if items is None else (items, nb)
+        if c.shape[:-1] != lead or c.ndim != len(lead) + 1:
+            raise ValueError(f"a {list(lead) + ['nc']} array of candidate thresholds expected, got {list(c.shape)}")
+        if not 1 <= c.shape[-1] <= L.NDWT_RISK_MAX_CAND:
+            raise ValueError(f"1 to {L.NDWT_RISK_MAX_CAND} candidates per block, got {c.shape[-1]}")
+        return c, np.zeros(c.shape + (L.NDWT_RISK_STATS,))
+
+    def band_risk(self, y_ptr, level, cand, stream=0, band_pitch=0):
+        """an [nb, nc, 3] array: for every band of a level-`level` coefficient array on the device (the plan's whole array, all items
+        pooled) and every candidate threshold cand[b, i] the count of |c| <= t, the energy of those elements and (complex data) the sum
+        of 1 / |c| over the others, in one read of the array.  cand: [nb, nc], nc <= 8; a row that begins with a negative entry skips
+        its band (zeros).  Synchronous."""
+        c, out = self._risk_table(cand, level, None)
+        dp = ctypes.POINTER(ctypes.c_double)
+        L.check(L.lib().ndwt_band_risk(self._h, y_ptr, int(band_pitch), int(level), int(c.shape[-1]), c.ctypes.data_as(dp), out.ctypes.data_as(dp), ctypes.c_void_p(stream)))
+        return out
+
+    def band_risk_items(self, y_ptr, level, cand, stream=0, band_pitch=0):
+        """band_risk for every item: cand [items, nb, nc], an [items, nb, nc, 3] array.  Synchronous."""
+        c, out = self._risk_table(cand, level, self.items)
+        dp = ctypes.POINTER(ctypes.c_double)
+        L.check(L.lib().ndwt_band_risk_items(self._h, y_ptr, int(band_pitch), int(level), int(c.shape[-1]), c.ctypes.data_as(dp), out.ctypes.data_as(dp),
+                                             ctypes.c_void_p(stream)))
+        return out
+
+    def sure_thresholds(self, y_ptr, level, sigma, rounds=3, stream=0, band_pitch=0):
+        """(thresholds, sure): for every band the soft threshold that minimises Stein's unbiased risk estimate on [0, sigma * gain *
+        sqrt(2 ln N)], searched in `rounds` reads of the detail bands, and the estimate there; band 0 gets 0.  Two length-nb arrays."""
+        nb = self._num_bands(level)
+        thr, sure = np.zeros(nb), np.zeros(nb)
+        dp = ctypes.POINTER(ctypes.c_double)
+        L.check(L.lib().ndwt_sure_thresholds(self._h, y_ptr, int(band_pitch), int(level), float(sigma), int(rounds), thr.ctypes.data_as(dp), sure.ctypes.data_as(dp),
+                                             ctypes.c_void_p(stream)))
+        return thr, sure
+
+    def sure_thresholds_items(self, y_ptr, level, sigma, rounds=3, stream=0, band_pitch=0):
+        """sure_thresholds for every item with its own sigma (a length-`items` sequence): two [items, nb] arrays"""
+        s = np.ascontiguousarray(np.asarray(sigma, dtype=np.float64).reshape(-1))
+        if s.size != self.items:
+            raise ValueError(f"{self.items} values of sigma expected, one per item, got {s.size}")
+        nb = self._num_bands(level)
+        thr, sure = np.zeros((self.items, nb)), np.zeros((self.items, nb))
+        dp = ctypes.POINTER(ctypes.c_double)
+        L.check(L.lib().ndwt_sure_thresholds_items(self._h, y_ptr, int(band_pitch), int(level), s.ctypes.data_as(dp), int(rounds), thr.ctypes.data_as(dp),
+                                                   sure.ctypes.data_as(dp), ctypes.c_void_p(stream)))
+        return thr, sure
+
     # -- joint shrinkage across the items and the norms of the groups (include/ndwt.h: ndwt_shrink_joint) --
     def shrink_joint(self, y_ptr, level, thresholds, hard=False, stream=0, band_pitch=0):
         """in-place group thresholding: the group is the coefficients at one position of a band across all items of the plan; one threshold
@@ -1081,6 +1132,49 @@ class _NdDwtBase:
         v, n, comp = self._band_norms(self.dec(x, level), per_item)
         var = np.maximum(v[..., L.NDWT_NORM_L2SQ] / (float(n) * comp) - s * s, 0.0)
         thr = np.where(var > 0.0, s * s / np.sqrt(np.where(var > 0.0, var, 1.0)), v[..., L.NDWT_NORM_MAX])
+        thr[..., 0] = 0.0
+        return thr
+
+    def band_risk(self, y, thresholds, per_item=False):
+        """What Stein's unbiased risk estimate of a soft threshold needs of every band of a coefficient array (what dec returns), at up
+        to 8 candidate thresholds per band in one read of the array: a dict of arrays `count` (the elements with |c| <= t, those a shrink at
+        t sets to zero), `energy` (the sum of |c|^2 over them) and `invsum` (complex data: the sum of 1 / |c| over the others; real data:
+        0), shaped like `thresholds`: [bands, nc], or with per_item=True [K, bands, nc], row j from signal / item j alone.  A row of
+        thresholds that begins with a negative entry skips its band: zeros.  The call waits for the result."""
+        yk, pitch, level, dev, plan = self._coef_for_stats(y)
+        if isinstance(thresholds, torch.Tensor):
+            thresholds = thresholds.detach().cpu().numpy()
+        with torch.cuda.device(dev):
+            if per_item:
+                v = plan.band_risk_items(yk.data_ptr(), level, thresholds, _current_stream(dev), band_pitch=pitch)
+            else:
+                v = plan.band_risk(yk.data_ptr(), level, thresholds, _current_stream(dev), band_pitch=pitch)
+        return {"count": v[..., L.NDWT_RISK_COUNT].copy(), "energy": v[..., L.NDWT_RISK_ENERGY].copy(), "invsum": v[..., L.NDWT_RISK_INVSUM].copy()}
+
+    def sure_thresholds(self, x, level, per_item=False, hybrid=True, rounds=3):
+        """SureShrink thresholds for this frame (Donoho and Johnstone), one per band, as denoise(x, level, thresholds) and shrink(y,
+        thresholds) take them: with s_b = estimate_sigma(x) * band_gains(level)[b], the soft threshold in [0, s_b sqrt(2 ln N)] that
+        minimises Stein's unbiased estimate of the risk over band b of dec(x, level), searched on the device in `rounds` reads of the
+        detail bands (3: to 1/128 of the interval).  hybrid=True: a band too sparse for the estimate -- (l2sq_b / s_b^2 - d N) / (d N) <=
+        log2(N)^1.5 / sqrt(N), d = 1 for real and 2 for complex data, N = the samples of one item's filtered axes -- gets the universal
+        s_b sqrt(2 ln N).  Entry 0 (the approximation) is 0.  per_item=True: a [K, bands] array, row j from signal / item j alone."""
+        level = int(level)
+        sigma = self.estimate_sigma(x, per_item=per_item)
+        y = self.dec(x, level)
+        yk, pitch, _, dev, plan = self._coef_for_stats(y)
+        with torch.cuda.device(dev):
+            if per_item:
+                thr, _ = plan.sure_thresholds_items(yk.data_ptr(), level, sigma, rounds, _current_stream(dev), band_pitch=pitch)
+            else:
+                thr, _ = plan.sure_thresholds(yk.data_ptr(), level, sigma, rounds, _current_stream(dev), band_pitch=pitch)
+        if hybrid:
+            N = float(np.prod(self.sizes, dtype=np.float64))
+            s = np.multiply.outer(np.asarray(sigma, dtype=np.float64), self.band_gains(level))
+            v, n, comp = self._band_norms(y, per_item)
+            dn = float(n) * comp
+            with np.errstate(divide="ignore", invalid="ignore"):
+                sparse = (v[..., L.NDWT_NORM_L2SQ] / (s * s) - dn) / dn <= np.log2(N) ** 1.5 / np.sqrt(N)
+            thr = np.where(sparse, s * np.sqrt(2.0 * np.log(N)), thr)
         thr[..., 0] = 0.0
         return thr
 

@@ -22,6 +22,7 @@
 #include "ndwt_device_joint.h"
 #include "ndwt_device_joint_tile.h"
 #include "ndwt_device_norms.h"
+#include "ndwt_device_risk.h"
 #include "ndwt_device_select.h"
 #include "ndwt_filters.h"
 #include "ndwt_fused.h"
@@ -2379,6 +2380,208 @@ int ndwt_band_norms_dev(ndwt_plan* p, const void* y, int64_t band_pitch, int lev
     if (rc) return rc;
     const long long items = per_item ? p->items() : 1, n = per_item ? p->item_vol() : p->vol;
     return on_device(p, [&](auto t) { return norms_run(p, (const decltype(t)*)y, bs, level, items, n, norms_dev, nullptr, (hipStream_t)stream); });
+}
+
+// ---- the SURE statistics: count, energy and reciprocal sum of every (band, item) block at up to NDWT_RISK_MAX_CAND thresholds in one
+// read (include/ndwt.h; the kernels: ndwt_device_risk.h) ----
+// norms_check, and the candidate table [items][nb][nc]: every entry >= 0 (+inf included), but a row may begin with a negative one
+static int risk_check(const ndwt_plan* p, const void* y, int level, bool per_item, int nc, const double* cand, const double* risk) {
+    int rc = check_level(p, level);
+    if (rc) return rc;
+    if (!y) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (y_dev)");
+    if (!cand) return fail(NDWT_ERR_INVALID_ARG, "null candidate thresholds (cand)");
+    if (!risk) return fail(NDWT_ERR_INVALID_ARG, "null output pointer (risk)");
+    if (nc < 1 || nc > NDWT_RISK_MAX_CAND) return fail(NDWT_ERR_INVALID_ARG, "nc = %d outside 1..%d candidates", nc, NDWT_RISK_MAX_CAND);
+    if (p->items() > 0x7fffffffLL) return fail(NDWT_ERR_UNSUPPORTED, "%lld items: the band risk serves fewer than 2^31", p->items());
+    const long long nb = ndwt_num_bands(p->ndim, level), items = per_item ? p->items() : 1;
+    for (long long j = 0; j < items; ++j)
+        for (long long b = 0; b < nb; ++b)
+            for (int i = 0; i < nc; ++i) {
+                const double t = cand[(j * nb + b) * nc + i];
+                if (t >= 0.0 || (i == 0 && t < 0.0)) continue;
+                if (per_item) return fail(NDWT_ERR_INVALID_ARG, "cand of item %lld, band %lld, position %d must be >= 0 (a negative first entry skips the block)", j, b, i);
+                return fail(NDWT_ERR_INVALID_ARG, "cand of band %lld, position %d must be >= 0 (a negative first entry skips the block)", b, i);
+            }
+    return NDWT_OK;
+}
+
+// BandRisk on every (band, item) block of `items` items of n scalars in one launch, on the grid of norms_run; with more than one chunk
+// the partials go behind the results in the plan's buffer and RiskFinish combines them.  The results' place is returned in *res.
+// Enqueued only (but for the wait of items_table_upload).
+extern "C++" template <typename T> static int risk_run(ndwt_plan* p, const T* y, long long bs, int level, long long items, long long n, int nc, const double* cand,
+                                                       double** res, hipStream_t s) {
+    const long long nb = ndwt_num_bands(p->ndim, level);
+    const bool vec = aligned_vec4<T>(y) && bs % 4 == 0 && n % 4 == 0;
+    const bool per_band = norms_per_band(nb, items);
+    const long long chunks = norms_chunks(n, (int)p->comp, vec, per_band ? 1 : nb, items, p->num_cus, p->target_blocks);
+    if (risk_thread_elements(n, (int)p->comp, vec, chunks) > 0xffffffffLL)
+        return fail(NDWT_ERR_UNSUPPORTED, "a block of %lld elements on %lld workgroups: a thread of the band risk counts fewer than 2^32", n / p->comp, chunks);
+    const T* table = nullptr;
+    int rc = items_table_upload<T>(p, cand, (size_t)(nb * items) * nc, s, &table);
+    if (rc) return rc;
+    const size_t res_bytes = (size_t)(nb * items) * nc * 3 * sizeof(double);
+    rc = p->norms_buf.grow(res_bytes * (chunks > 1 ? 1 + (size_t)chunks : 1), "for the band risk");
+    if (rc) return rc;
+    double* const results = (double*)p->norms_buf.ptr;
+    double* const partials = (double*)((char*)p->norms_buf.ptr + res_bytes);
+    BandRiskArgs<T> a = {y, bs, n, table, chunks > 1 ? partials : results, items, (int)nb, 0, (int)nb, (int)chunks, nc};
+    RiskFinishArgs f = {partials, results, items, (int)nb, 0, (int)nb, (int)chunks, nc};
+    for (int b = 0; b < (per_band ? (int)nb : 1); ++b) {
+        if (per_band) { a.band0 = f.band0 = b; a.nbands = f.nbands = 1; }
+        rc = launch_band_risk(a, (int)p->comp, vec, p->norms_buf.ptr, s);
+        if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: no band-risk kernel for this data kind or grid");
+        if (rc != 0) return fail(NDWT_ERR_HIP, "band-risk kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+        if (chunks == 1) continue;
+        rc = launch_risk_finish(f, p->norms_buf.ptr, s);
+        if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: a grid the band-risk combine cannot express");
+        if (rc != 0) return fail(NDWT_ERR_HIP, "band-risk combine launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    *res = results;
+    return NDWT_OK;
+}
+
+// the launches, then one copy of the results and one synchronisation of the stream
+static int risk_host(ndwt_plan* p, const void* y, int64_t band_pitch, int level, bool per_item, int nc, const double* cand, double* risk, void* stream) {
+    int rc = risk_check(p, y, level, per_item, nc, cand, risk);
+    if (rc) return rc;
+    long long bs = 0;
+    rc = pitch_scalars(p, band_pitch, &bs);
+    if (rc) return rc;
+    const long long items = per_item ? p->items() : 1, n = per_item ? p->item_vol() : p->vol;
+    return on_device(p, [&](auto t) {
+        double* res = nullptr;
+        const int rc = risk_run(p, (const decltype(t)*)y, bs, level, items, n, nc, cand, &res, (hipStream_t)stream);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(risk, res, (size_t)(ndwt_num_bands(p->ndim, level) * items) * nc * 3 * sizeof(double), hipMemcpyDeviceToHost, (hipStream_t)stream));
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        return (int)NDWT_OK;
+    });
+}
+
+int ndwt_band_risk(ndwt_plan* p, const void* y, int64_t band_pitch, int level, int nc, const double* cand, double* risk, void* stream) {
+    return risk_host(p, y, band_pitch, level, false, nc, cand, risk, stream);
+}
+
+int ndwt_band_risk_items(ndwt_plan* p, const void* y, int64_t band_pitch, int level, int nc, const double* cand, double* risk, void* stream) {
+    return risk_host(p, y, band_pitch, level, true, nc, cand, risk, stream);
+}
+
+int ndwt_sure_from_risk(int comp, double n, double s, int nc, const double* cand, const double* risk, double* sure) {
+    if (comp != 1 && comp != 2) return fail(NDWT_ERR_INVALID_ARG, "comp must be 1 (real) or 2 (complex)");
+    if (!(n >= 0.0) || std::isinf(n)) return fail(NDWT_ERR_INVALID_ARG, "n must be finite and >= 0");
+    if (!(s >= 0.0) || std::isinf(s)) return fail(NDWT_ERR_INVALID_ARG, "s must be finite and >= 0");
+    if (nc < 1) return fail(NDWT_ERR_INVALID_ARG, "nc must be >= 1");
+    if (!cand) return fail(NDWT_ERR_INVALID_ARG, "null candidate thresholds (cand)");
+    if (!risk) return fail(NDWT_ERR_INVALID_ARG, "null statistics (risk)");
+    if (!sure) return fail(NDWT_ERR_INVALID_ARG, "null output pointer (sure)");
+    const double d = comp, s2 = s * s;
+    for (int i = 0; i < nc; ++i) {
+        const double t = cand[i], C = risk[3 * i + NDWT_RISK_COUNT], E = risk[3 * i + NDWT_RISK_ENERGY], I = risk[3 * i + NDWT_RISK_INVSUM];
+        // (t = +inf leaves nothing above it: n - C and I are 0, and their terms are dropped, not inf * 0)
+        const double above = n - C == 0.0 ? 0.0 : t * t * (n - C), curl = comp == 1 || I == 0.0 ? 0.0 : (d - 1.0) * t * I;
+        sure[i] = n * d * s2 + E + above - 2.0 * s2 * (d * C + curl);
+    }
+    return NDWT_OK;
+}
+
+// the gains of the bands of a transform of the plan's filtered axes (what ndwt_band_gains computes, from the same code)
+static void plan_band_gains(const ndwt_plan* p, int level, double* gains) {
+    std::vector<double> A[NDWT_MAX_DIMS], D[NDWT_MAX_DIMS];
+    for (int a = 0; a < p->ndim; ++a) {
+        A[a].resize((size_t)level + 1);
+        D[a].resize((size_t)level + 1);
+        axis_gains(p->filt[a], p->dims[a], p->dilation == NDWT_DILATION_ATROUS, level, A[a].data(), D[a].data());
+    }
+    const int nb = 1 << p->ndim;
+    const long long bands = ndwt_num_bands(p->ndim, level);
+    for (long long b = 0; b < bands; ++b) {
+        const int lev = b == 0 ? level : level - (int)((b - 1) / (nb - 1));
+        const int bits = b == 0 ? 0 : 1 + (int)((b - 1) % (nb - 1));
+        double g = 1.0;
+        for (int a = 0; a < p->ndim; ++a) g *= ((bits >> a) & 1) ? D[a][(size_t)lev] : A[a][(size_t)lev];
+        gains[b] = g;
+    }
+}
+
+// The search of ndwt_sure_thresholds(_items) (include/ndwt.h): every round is ONE ndwt_band_risk(_items) call over all blocks, 8
+// candidates a block on its own interval; band 0 and the blocks with nothing to search (s = 0, one element) are skipped rows.
+static int sure_search(ndwt_plan* p, const void* y, int64_t band_pitch, int level, bool per_item, const double* sigma, int rounds, double* thresholds, double* sure,
+                       void* stream) {
+    int rc = check_level(p, level);
+    if (rc) return rc;
+    if (!y) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (y_dev)");
+    if (!sigma) return fail(NDWT_ERR_INVALID_ARG, "null sigma");
+    if (!thresholds) return fail(NDWT_ERR_INVALID_ARG, "null output pointer (thresholds)");
+    if (rounds < 0 || rounds > 8) return fail(NDWT_ERR_INVALID_ARG, "rounds = %d outside 1..8 (0: the default, 3)", rounds);
+    if (p->items() > 0x7fffffffLL) return fail(NDWT_ERR_UNSUPPORTED, "%lld items: the band risk serves fewer than 2^31", p->items());
+    long long bs = 0;
+    rc = pitch_scalars(p, band_pitch, &bs);               // (before anything is written: a refused call leaves its outputs alone)
+    if (rc) return rc;
+    const long long nb = ndwt_num_bands(p->ndim, level), items = per_item ? p->items() : 1, blocks = nb * items;
+    for (long long j = 0; j < items; ++j)
+        if (!(sigma[j] >= 0.0) || std::isinf(sigma[j])) {
+            if (per_item) return fail(NDWT_ERR_INVALID_ARG, "sigma of item %lld must be finite and >= 0", j);
+            return fail(NDWT_ERR_INVALID_ARG, "sigma must be finite and >= 0");
+        }
+    if (rounds == 0) rounds = 3;
+    constexpr int NC = NDWT_RISK_MAX_CAND;
+    const bool f32 = p->dtype == NDWT_F32;
+    const double d = (double)p->comp;
+    double N = 1.0;                                       // elements of ONE item's filtered axes
+    for (int a = 0; a < p->ndim; ++a) N *= (double)p->dims[a];
+    const double n = (double)((per_item ? p->item_vol() : p->vol) / p->comp);   // elements of a block
+    std::vector<double> gains((size_t)nb), s((size_t)blocks), tmax((size_t)blocks), lo((size_t)blocks, 0.0), hi((size_t)blocks), best_r((size_t)blocks);
+    std::vector<double> cand((size_t)blocks * NC), risk((size_t)blocks * NC * 3);
+    plan_band_gains(p, level, gains.data());
+    for (long long k = 0; k < blocks; ++k) {
+        s[k] = sigma[k / nb] * gains[k % nb];
+        tmax[k] = hi[k] = k % nb == 0 ? 0.0 : s[k] * std::sqrt(2.0 * std::log(N));
+        thresholds[k] = 0.0;
+        best_r[k] = k % nb == 0 ? 0.0 : n * d * s[k] * s[k];
+    }
+    for (int r = 0; r < rounds; ++r) {
+        bool any = false;
+        for (long long k = 0; k < blocks; ++k) {
+            double* const c = &cand[(size_t)k * NC];
+            if (!(tmax[k] > 0.0)) {                       // band 0, s = 0, one element: a skipped row
+                c[0] = -1.0;
+                for (int i = 1; i < NC; ++i) c[i] = 0.0;
+                continue;
+            }
+            any = true;
+            for (int i = 0; i < NC; ++i) {                // rounded as the shrink rounds its threshold: the statistics are those of what it applies
+                const double t = lo[k] + (hi[k] - lo[k]) * (double)(i + 1) / 8.0;
+                c[i] = f32 ? (double)(float)t : t;
+            }
+        }
+        if (!any) break;
+        rc = risk_host(p, y, band_pitch, level, per_item, NC, cand.data(), risk.data(), stream);
+        if (rc) return rc;
+        for (long long k = 0; k < blocks; ++k) {
+            if (!(tmax[k] > 0.0)) continue;
+            double v[NC];
+            (void)ndwt_sure_from_risk((int)p->comp, n, s[k], NC, &cand[(size_t)k * NC], &risk[(size_t)k * NC * 3], v);
+            int at = 0;
+            for (int i = 1; i < NC; ++i)
+                if (v[i] < v[at] || (v[at] != v[at] && v[i] == v[i])) at = i;   // the first of the smallest (a NaN is never smaller)
+            if (v[at] < best_r[k]) { best_r[k] = v[at]; thresholds[k] = cand[(size_t)k * NC + at]; }
+            const double step = (hi[k] - lo[k]) / 8.0;
+            lo[k] = std::max(thresholds[k] - step, 0.0);
+            hi[k] = std::min(thresholds[k] + step, tmax[k]);
+        }
+    }
+    if (sure)
+        for (long long k = 0; k < blocks; ++k) sure[k] = best_r[k];
+    return NDWT_OK;
+}
+
+int ndwt_sure_thresholds(ndwt_plan* p, const void* y, int64_t band_pitch, int level, double sigma, int rounds, double* thresholds, double* sure, void* stream) {
+    return sure_search(p, y, band_pitch, level, false, &sigma, rounds, thresholds, sure, stream);
+}
+
+int ndwt_sure_thresholds_items(ndwt_plan* p, const void* y, int64_t band_pitch, int level, const double* sigma, int rounds, double* thresholds, double* sure,
+                               void* stream) {
+    return sure_search(p, y, band_pitch, level, true, sigma, rounds, thresholds, sure, stream);
 }
 
 // ---- joint shrinkage across the items of a plan and the norms of the groups (include/ndwt.h; the kernels: ndwt_device_joint.h) ----

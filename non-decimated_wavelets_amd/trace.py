@@ -67,6 +67,13 @@ FAMILY_PARAMS_NORMS = {
     "NormsFinish": [("NT", 64)],
 }
 
+# the families of csrc/ndwt_device_risk.h (the SURE statistics of every (band, item) block at up to 8 thresholds in one read, and the combine of the
+# chunks of a block), likewise
+FAMILY_PARAMS_RISK = {
+    "BandRisk": [("T", None), ("COMP", None), ("VEC", None)],
+    "RiskFinish": [("NT", 64)],
+}
+
 # the families of csrc/ndwt_device_joint.h (joint shrinkage across the items of a plan and the norms of the groups), likewise
 FAMILY_PARAMS_JOINT = {
     "JointShrink": [("T", None), ("COMP", None), ("VEC", None), ("REG", None)],
@@ -141,7 +148,7 @@ def parse_record(line: str) -> KernelLaunch:
     if not t:
         raise ValueError(f"unparsed kernel type: {text!r}")
     fam = t.group(1)
-    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam) or FAMILY_PARAMS_1D.get(fam) or FAMILY_PARAMS_AXIS.get(fam) or FAMILY_PARAMS_SELECT.get(fam) or FAMILY_PARAMS_ITEMS.get(fam) or FAMILY_PARAMS_NORMS.get(fam) or FAMILY_PARAMS_JOINT.get(fam) or FAMILY_PARAMS_JOINT_TILE.get(fam)
+    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam) or FAMILY_PARAMS_1D.get(fam) or FAMILY_PARAMS_AXIS.get(fam) or FAMILY_PARAMS_SELECT.get(fam) or FAMILY_PARAMS_ITEMS.get(fam) or FAMILY_PARAMS_NORMS.get(fam) or FAMILY_PARAMS_RISK.get(fam) or FAMILY_PARAMS_JOINT.get(fam) or FAMILY_PARAMS_JOINT_TILE.get(fam)
     if table is None:
         raise ValueError(f"unknown kernel family {fam!r} in {text!r}")
     args = [_value(a) for a in _split_args(t.group(2) or "")]
