@@ -483,6 +483,61 @@ int ndwt_shrink_joint(ndwt_plan* plan, void* y_dev, int64_t band_pitch, int leve
 int ndwt_denoise_joint(ndwt_plan* plan, const void* x_dev, void* out_dev, int level, const double* thresholds, int mode, void* stream);
 int ndwt_group_norms(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double* norms, void* stream);
 int ndwt_group_norms_dev(ndwt_plan* plan, const void* y_dev, int64_t band_pitch, int level, double* norms_dev, void* stream);
+/* ---- neighbourhood shrinkage: the energy of a small window inside a coefficient's own band decides that coefficient ----
+ * In an undecimated frame an edge or a spike is a cluster of large coefficients at adjacent positions; noise does not cluster.  The rules
+ * that use this -- NeighShrink (Chen, Bui and Krzyzak), NeighBlock and NeighCoeff (Cai and Silverman), the locally adaptive Wiener rule
+ * (Mihcak et al.) -- share one primitive, built here.  T = the plan's scalar type; d = the filtered axes of one item, 1, 2 or 3, of
+ * lengths n_a, axis 0 the fastest; r = radius, 1, 2 or 3; M = (2r + 1)^d.  Positions are those of one item's part of one band, and
+ * every index wraps periodically within that item -- the transform's own boundary rule -- never into the next item or band.
+ * The window sum at position p, all of it in double:
+ *   A(p) = over dx = -r .. r in ascending order along axis 0, for each neighbour re before im, a = fma((double)e, (double)e, a) from
+ *          a = 0.0: every square added with a fused multiply-add on the widened part (the way the joint shrink accumulates s);
+ *   B(p) = the sum over dy = -r .. r in ascending order along axis 1 of A, plain double additions, the first term first;
+ *   C(p) = the same sum over dz along axis 2 of B;
+ *   S(p) = A for d = 1, B for d = 2, C for d = 3.  The sum along the last axis is formed anew from its 2r + 1 terms at every position:
+ *          no running sum that adds a term and takes one away, so no value depends on where a workgroup's march began.
+ * t = (T)thresholds[b]; tt = (double)t * (double)t, formed on the host.
+ *   S > tt, compared in double: NDWT_SHRINK_SOFT g = (T)((S - tt) / S) -- a double subtraction, a double division, one rounding to T --
+ *       and every part of the coefficient is multiplied by g in T; NDWT_SHRINK_HARD the coefficient is copied;
+ *   else every part is stored as +0 -- an explicit zero: a window that holds a NaN turns its centre into zero, as in the joint shrink.
+ *   A band with thresholds[b] == 0 is copied to the output bit for bit: NaN, -0 and everything else pass unchanged.
+ * The soft rule is c * max(1 - t^2 / S, 0).  With s = sigma * the band's gain (ndwt_band_gains) and N the elements of an item:
+ *   t = s * sqrt(2 ln N) is NeighShrink; t^2 = M s^2 the local Wiener estimate c * max(S / M - s^2, 0) / (S / M);
+ *   t^2 = 4.50524 M s^2 Cai and Silverman's constant, the root of lambda - ln(lambda) = 3.
+ * thresholds: HOST, nb = ndwt_num_bands(filtered axes, level) doubles, each >= 0, band 0 a band like any other -- the rules and the
+ *   messages of ndwt_shrink_bands.  The squared thresholds reach the device as the joint shrink's table does, through the plan's
+ *   pinned host buffer and a copy enqueued on `stream` (items_table_upload, nb doubles): a later call of any of the table forms waits
+ *   on the HOST (hipEventSynchronize) for that copy before it overwrites the pinned buffer, so a call is at most one call ahead of the
+ *   device, and two such calls cannot be captured into a graph.
+ * ndwt_shrink_neigh is OUT OF PLACE: a neighbour's original value is needed after the neighbour's owner has been processed, so no
+ *   in-place form exists across workgroups.  out_dev has the layout and the pitch of y_dev (band_pitch 0 = packed); the call never
+ *   writes y_dev and never writes the scalars between the bands of out_dev.  The two arrays may overlap in exactly ONE form,
+ *   out_dev == y_dev - band_pitch (in scalars of the pitch: the output is the input moved one band slot down); any other overlap is
+ *   refused with NDWT_ERR_INVALID_ARG, "out_dev overlaps y_dev".  In that form band b is written where band b - 1 was read, so the
+ *   bands run in ascending order, one launch per band in stream order, and a zero-threshold band is one device-to-device copy.  In
+ *   every other case all (band, item) blocks run in ONE launch (NeighShrink), a zero-threshold band is copied inside the kernel, and
+ *   an all-zero array uploads and launches nothing: the bands are copied.
+ *   The grid: workgroups of 256 threads, nb x items x chunks x tiles of them in the one launch (items x chunks x tiles in a launch
+ *   of the shifted form).  A tile is 256 positions of axis 0 for d <= 2, and 64 x 16 positions of axes 0 and 1 for d = 3 (64 x 8 for
+ *   complex128, and for double and complex64 at radius 3); the last axis of d >= 2 is marched, split into chunks of at least 2r + 1
+ *   planes only while the launch has fewer workgroups than 8 per compute unit (ndwt_plan_set_tuning's target_blocks > 0 stands in for
+ *   that count).  No atomics, no hand-off between workgroups: two calls give the same bits whatever the grid.
+ * ndwt_denoise_neigh: dec, the shrink, rec without a second coefficient array: the plan's coefficient scratch grows to nb + 1 band
+ *   slots (on the first such call only; no other call sees a different scratch), dec writes slots 1 .. nb, the shrink runs one slot
+ *   down, rec reads from slot 0.
+ * Served: unbatched plans of 1, 2 and 3 dimensions, batched 1-D plans (ndwt_plan_create_many), stacks of images and volumes
+ *   (ndwt_plan_create_axes), float, complex64, double and complex128, any band pitch >= a band.
+ * Refused with NDWT_ERR_UNSUPPORTED, the message naming the reason: interleaved plans (ndwt_plan_create_interleaved with inner > 1:
+ *   the neighbours lie `inner` elements apart); four filtered axes; a filtered axis shorter than 2r + 1 (the window would count an
+ *   element twice); an item whose line (plane, for d = 3) reaches 2^31 scalars.
+ * Refused with NDWT_ERR_INVALID_ARG, the message naming the argument, nothing launched: plan, y_dev, x_dev, out_dev or thresholds
+ *   null, a radius outside 1 .. 3, a mode that is neither, a level outside the plan's, a band pitch smaller than a band, a threshold
+ *   below 0 or NaN.
+ * Not built: interleaved plans and four filtered axes (refused above); a threshold row per item; a window across levels (parent and
+ *   child); the window sum as an output of its own; a statistic fused in; the handles, the slab entry points and the MATLAB gateway. */
+int ndwt_shrink_neigh(ndwt_plan* plan, const void* y_dev, void* out_dev, int64_t band_pitch, int level, int radius, const double* thresholds, int mode,
+                      void* stream);
+int ndwt_denoise_neigh(ndwt_plan* plan, const void* x_dev, void* out_dev, int level, int radius, const double* thresholds, int mode, void* stream);
 
 /* Split complex: separate real / imaginary arrays, the layout the reference's gateway receives from MATLAB
  * (mxGetPr / mxGetPi, nd_dwt_mex.c:55-58,90-93) and hands to nd_dwt_dec / nd_dwt_rec (outR/outI, imageR/imageI,

@@ -40,6 +40,7 @@ EXPORTS = [
     "ndwt_shrink_bands_items", "ndwt_denoise_bands_items", "ndwt_band_norms", "ndwt_band_norms_items", "ndwt_band_norms_dev",
     "ndwt_band_risk", "ndwt_band_risk_items", "ndwt_sure_from_risk", "ndwt_sure_thresholds", "ndwt_sure_thresholds_items",
     "ndwt_shrink_joint", "ndwt_denoise_joint", "ndwt_group_norms", "ndwt_group_norms_dev",
+    "ndwt_shrink_neigh", "ndwt_denoise_neigh",
 ]
 
 
@@ -149,6 +150,10 @@ def lib() -> ctypes.CDLL:
     L.ndwt_denoise_joint.argtypes = L.ndwt_denoise_bands.argtypes
     L.ndwt_group_norms.argtypes = L.ndwt_band_norms.argtypes
     L.ndwt_group_norms_dev.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    # neighbourhood shrinkage: out of place, a radius, thresholds [nb] on the host
+    L.ndwt_shrink_neigh.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int,
+                                    ctypes.c_void_p]
+    L.ndwt_denoise_neigh.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, c_double_p, ctypes.c_int, ctypes.c_void_p]
     L.ndwt_denoise_host.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_int]
     for f in (L.ndwt_dec_split, L.ndwt_rec_split):
         f.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p]

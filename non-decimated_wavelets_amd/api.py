@@ -374,6 +374,22 @@ class Plan:
         """the same into DEVICE memory at out_ptr ([nb, 4] doubles, 8-byte aligned): enqueued on `stream` only"""
         L.check(L.lib().ndwt_group_norms_dev(self._h, y_ptr, int(band_pitch), int(level), out_ptr, ctypes.c_void_p(stream)))
 
+    # -- neighbourhood shrinkage: the energy of a window inside a coefficient's own band decides it (include/ndwt.h: ndwt_shrink_neigh) --
+    def shrink_neigh(self, y_ptr, out_ptr, level, thresholds, radius=1, hard=False, stream=0, band_pitch=0):
+        """out of place, from y_ptr into out_ptr (the same layout and pitch): a coefficient is scaled by max(1 - t^2 / S, 0), S the sum of
+        squares over the periodic window of (2 radius + 1) positions per filtered axis around it, inside its own item of its own band; one
+        threshold per band (num_bands of them, band 0 included; 0 = copy the band), all bands in one launch.  out_ptr may be y_ptr one
+        band slot down (y_ptr - band pitch) and nothing else that overlaps y_ptr."""
+        t, tp = self._thresholds(thresholds)
+        self._check_band_count(t, level)
+        L.check(L.lib().ndwt_shrink_neigh(self._h, y_ptr, out_ptr, int(band_pitch), int(level), int(radius), tp, int(bool(hard)), ctypes.c_void_p(stream)))
+
+    def denoise_neigh(self, x_ptr, out_ptr, level, thresholds, radius=1, hard=False, stream=0):
+        """dec -> shrink_neigh -> rec, the coefficients in the plan's scratch (one band slot more than a transform fills)"""
+        t, tp = self._thresholds(thresholds)
+        self._check_band_count(t, level)
+        L.check(L.lib().ndwt_denoise_neigh(self._h, x_ptr, out_ptr, int(level), int(radius), tp, int(bool(hard)), ctypes.c_void_p(stream)))
+
     def denoise_host(self, x_ptr, out_ptr, level, threshold, hard=False):
         L.check(L.lib().ndwt_denoise_host(self._h, x_ptr, out_ptr, int(level), float(threshold), int(bool(hard))))
 
@@ -448,6 +464,22 @@ class Plan:
     def synthesis_level_slab(self, in_ptrs, out_ptr, stride=1, stream=0):
         arr = (ctypes.c_void_p * len(in_ptrs))(*in_ptrs)
         L.check(L.lib().ndwt_synthesis_level_slab(self._h, arr, out_ptr, int(stride), ctypes.c_void_p(stream)))
+
+
+def neigh_threshold_row(sigma, gains, sizes, radius=1, rule="universal"):
+    """Host arithmetic of _NdDwtBase.neigh_thresholds: sigma the noise of the signal, gains the band gains, sizes the filtered axes of one
+    item.  A row of len(gains) thresholds, entry 0 zero."""
+    if rule not in ("universal", "wiener", "block"):
+        raise ValueError("rule must be 'universal', 'wiener' or 'block'")
+    if int(radius) not in (1, 2, 3):
+        raise ValueError("radius must be 1, 2 or 3")
+    s = float(sigma) * np.asarray(gains, dtype=np.float64)
+    N = float(np.prod(np.atleast_1d(sizes), dtype=np.float64))
+    M = float((2 * int(radius) + 1) ** len(np.atleast_1d(sizes)))
+    k = np.sqrt(2.0 * np.log(N)) if rule == "universal" else np.sqrt(M) if rule == "wiener" else np.sqrt(4.50524 * M)
+    thr = k * s
+    thr[0] = 0.0
+    return thr
 
 
 class Coefficients:
@@ -953,6 +985,60 @@ class _NdDwtBase:
             else:
                 plan.denoise_bands(xk.data_ptr(), out.data_ptr(), level, thr, mode == "hard", _current_stream(dev))
         return self._from_device(out, like_numpy, dev)
+
+    # -- neighbourhood shrinkage (extension; not in the reference): NeighShrink, NeighBlock / NeighCoeff, the local Wiener rule --
+    def shrink_neigh(self, y, threshold, radius=1, mode="soft"):
+        """Thresholding by the energy of a coefficient's neighbourhood: with S the sum of |c|^2 over the periodic window of 2 radius + 1
+        positions per filtered axis around a coefficient -- inside its own band, and its own signal of a batch / item of a stack -- the
+        coefficient becomes c * max(1 - t^2 / S, 0) (mode 'hard': c where S > t^2, else 0).  threshold: a scalar for every detail band
+        (band 0 kept), or one value per band (0 = the band is kept); neigh_thresholds gives the usual rules.  radius: 1, 2 or 3.
+        Returns a new array of the same kind as `y`; `y` is only read."""
+        if mode not in ("soft", "hard"):
+            raise ValueError("mode must be 'soft' or 'hard'")
+        like_numpy = isinstance(y, np.ndarray)
+        if y.ndim != len(self._shape) + 1 or list(y.shape[:-1]) != self._shape:
+            raise ValueError(f"coefficient array must have shape {self._shape + ['bands']}")
+        level = self._level_from_bands(int(y.shape[-1]))
+        thr = self._joint_thresholds(threshold, level)
+        dev = self._dev(y if isinstance(y, torch.Tensor) else None)
+        yk, pitch = self._coef_kernel_order(y, dev)
+        if pitch:                                              # the result keeps the pitch of the array it came from
+            flat = torch.empty(yk.shape[0] * pitch, dtype=yk.dtype, device=dev)
+            out = flat.as_strided(tuple(yk.shape), tuple(yk.stride()))
+        else:
+            out = torch.empty_like(yk)
+        plan = self._plan(yk.is_complex(), level, dev)
+        with torch.cuda.device(dev):
+            plan.shrink_neigh(yk.data_ptr(), out.data_ptr(), level, thr, int(radius), mode == "hard", _current_stream(dev), band_pitch=pitch)
+        return self._from_device(out, like_numpy, dev)
+
+    def denoise_neigh(self, x, level, threshold, radius=1, mode="soft"):
+        """rec(shrink_neigh(dec(x, level), threshold, radius)) in one call: the coefficients stay in a scratch array of the plan"""
+        if mode not in ("soft", "hard"):
+            raise ValueError("mode must be 'soft' or 'hard'")
+        level = int(level)
+        if level < 1:
+            raise ValueError("level must be >= 1")
+        thr = self._joint_thresholds(threshold, level)
+        like_numpy = isinstance(x, np.ndarray)
+        x = self._prep_dec_input(x)
+        if list(x.shape) != self._shape:
+            raise ValueError(f"input size {list(x.shape)} does not match the object's sizes {self._shape}")
+        dev = self._dev(x if isinstance(x, torch.Tensor) else None)
+        xk = self._to_device_kernel_order(x, dev, self.NDIM)
+        plan = self._plan(xk.is_complex(), level, dev)
+        out = torch.empty_like(xk)
+        with torch.cuda.device(dev):
+            plan.denoise_neigh(xk.data_ptr(), out.data_ptr(), level, thr, int(radius), mode == "hard", _current_stream(dev))
+        return self._from_device(out, like_numpy, dev)
+
+    def neigh_thresholds(self, x, level, radius=1, rule="universal"):
+        """The thresholds of shrink_neigh / denoise_neigh for the usual rules, one per band, entry 0 (the approximation) 0.  With s_b =
+        estimate_sigma(x) * band_gains(level)[b], N = the samples of one item's filtered axes and M = (2 radius + 1)^dimensions:
+          'universal'  t_b = s_b sqrt(2 ln N): NeighShrink (Chen, Bui and Krzyzak)
+          'wiener'     t_b^2 = M s_b^2: the locally adaptive Wiener estimate c * max(S / M - s_b^2, 0) / (S / M) (Mihcak et al.)
+          'block'      t_b^2 = 4.50524 M s_b^2: Cai and Silverman's constant for NeighBlock / NeighCoeff, the root of l - ln l = 3"""
+        return neigh_threshold_row(self.estimate_sigma(x), self.band_gains(int(level)), self.sizes, radius, rule)
 
     def _band_thresholds(self, threshold, level):
         """None for a scalar threshold (today's call), else the sequence as an array of one threshold per band; a [K, bands] array of a

@@ -21,6 +21,7 @@
 #include "ndwt_device_items.h"
 #include "ndwt_device_joint.h"
 #include "ndwt_device_joint_tile.h"
+#include "ndwt_device_neigh.h"
 #include "ndwt_device_norms.h"
 #include "ndwt_device_risk.h"
 #include "ndwt_device_select.h"
@@ -2682,6 +2683,101 @@ int ndwt_group_norms_dev(ndwt_plan* p, const void* y, int64_t band_pitch, int le
     rc = pitch_scalars(p, band_pitch, &bs);
     if (rc) return rc;
     return on_device(p, [&](auto t) { return group_norms_run(p, (const decltype(t)*)y, bs, level, norms_dev, nullptr, (hipStream_t)stream); });
+}
+
+// ---- neighbourhood shrinkage: the energy of a window inside a coefficient's own band decides it (include/ndwt.h; the kernel:
+// ndwt_device_neigh.h) ----
+// what both entry points check, before any device call
+static int neigh_check(const ndwt_plan* p, int level, int radius, const double* thr, int mode) {
+    int rc = bands_check(p, level, thr, mode);
+    if (rc) return rc;
+    if (radius < 1 || radius > 3) return fail(NDWT_ERR_INVALID_ARG, "radius %d outside 1..3", radius);
+    if (p->inner > 1)
+        return fail(NDWT_ERR_UNSUPPORTED, "neighbourhood shrinkage does not serve interleaved plans: the neighbours of an element lie inner = %lld elements apart", p->inner);
+    if (p->ndim > 3) return fail(NDWT_ERR_UNSUPPORTED, "neighbourhood shrinkage serves 1 to 3 filtered axes, this plan has %d", p->ndim);
+    for (int k = 0; k < p->ndim; ++k)
+        if (p->dims[k] < 2 * radius + 1)
+            return fail(NDWT_ERR_UNSUPPORTED, "filtered axis %d has %lld elements, fewer than the window of 2 * radius + 1 = %d: the window would count an element twice", k,
+                        p->dims[k], 2 * radius + 1);
+    for (int k = 0; k < p->ndim; ++k)
+        if (p->dims[k] > 0x7fffffffLL || p->dims[0] * (p->ndim == 3 ? p->dims[1] : 1) * p->comp > 0x7fffffffLL)
+            return fail(NDWT_ERR_UNSUPPORTED, "neighbourhood shrinkage serves items whose lines (planes, with 3 filtered axes) stay below 2^31 scalars");
+    return NDWT_OK;
+}
+
+// NeighShrink from y into out, both at the pitch bs.  The squared thresholds go up in double as a table of one row (items_table_upload);
+// a band whose threshold is 0 has -1 there: copied.  out apart from y: every (band, item) block in ONE launch, by neigh_geometry; an
+// all-zero array uploads nothing and launches nothing, the bands are copied.  out == y - bs: band b is written where band b - 1 was
+// read, so the bands run in ascending order, one launch each in stream order, a zero-threshold band as one copy.
+extern "C++" template <typename T> static int neigh_shrink_impl(ndwt_plan* p, const T* y, T* out, long long bs, int level, int radius, const double* thr, int mode,
+                                                                hipStream_t s) {
+    const long long nb = ndwt_num_bands(p->ndim, level), items = p->items(), n = p->item_vol();
+    const uintptr_t yb = (uintptr_t)y, ob = (uintptr_t)out, span = (uintptr_t)((nb - 1) * bs + p->vol) * sizeof(T);
+    const bool shifted = ob + (uintptr_t)bs * sizeof(T) == yb;
+    if (!shifted && !(yb + span <= ob || ob + span <= yb))
+        return fail(NDWT_ERR_INVALID_ARG, "out_dev overlaps y_dev (the one form allowed: out_dev == y_dev - band_pitch, the output one band slot down)");
+    std::vector<double> tt((size_t)nb);
+    bool any = false;
+    for (long long b = 0; b < nb; ++b) {
+        const T t = (T)thr[b];
+        tt[b] = thr[b] == 0.0 ? -1.0 : (double)t * (double)t;
+        any = any || thr[b] != 0.0;
+    }
+    const auto copy_band = [&](long long b) { return hipMemcpyAsync(out + b * bs, y + b * bs, (size_t)p->vol * sizeof(T), hipMemcpyDeviceToDevice, s); };
+    if (!any) {
+        for (long long b = 0; b < nb; ++b) HIP_TRY(copy_band(b));
+        return NDWT_OK;
+    }
+    const double* table = nullptr;
+    int rc = items_table_upload<double>(p, tt.data(), (size_t)nb, s, &table);
+    if (rc) return rc;
+    const int nd = p->ndim;
+    const NeighGeom g = neigh_geometry(nd, p->dims[0], nd >= 2 ? p->dims[1] : 1, nd == 3 ? p->dims[2] : 1, (int)(sizeof(T) * p->comp), radius,
+                                       (shifted ? 1 : nb) * items, p->num_cus, p->target_blocks);
+    NeighArgs<T> a = {y, out, bs, n, table, items, (int)p->dims[0], nd >= 2 ? (int)p->dims[1] : 1, nd == 3 ? (int)p->dims[2] : 1, 0, (int)nb,
+                      (int)g.ntx, (int)g.nty, (int)g.chunk, (int)g.nchunks, mode};
+    for (long long b = 0; b < (shifted ? nb : 1); ++b) {
+        if (shifted) {
+            if (thr[b] == 0.0) { HIP_TRY(copy_band(b)); continue; }
+            a.band0 = (int)b;
+            a.nbands = 1;
+        }
+        rc = launch_neigh_shrink(a, (int)p->comp, nd, radius, table, s);
+        if (rc < 0) return fail(NDWT_ERR_UNSUPPORTED, "internal: no neighbourhood shrink kernel for this data kind or grid");
+        if (rc != 0) return fail(NDWT_ERR_HIP, "neighbourhood shrink kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+    }
+    return NDWT_OK;
+}
+
+int ndwt_shrink_neigh(ndwt_plan* p, const void* y, void* out, int64_t band_pitch, int level, int radius, const double* thresholds, int mode, void* stream) {
+    int rc = neigh_check(p, level, radius, thresholds, mode);
+    if (rc) return rc;
+    if (!y) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (y_dev)");
+    if (!out) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (out_dev)");
+    long long bs = 0;
+    rc = pitch_scalars(p, band_pitch, &bs);
+    if (rc) return rc;
+    return on_device(p, [&](auto t) {
+        return neigh_shrink_impl(p, (const decltype(t)*)y, (decltype(t)*)out, bs, level, radius, thresholds, mode, (hipStream_t)stream);
+    });
+}
+
+// dec into slots 1 .. nb of the plan's pitched scratch (grown by one slot, once), the shrink one slot down, rec from slot 0
+int ndwt_denoise_neigh(ndwt_plan* p, const void* x, void* out, int level, int radius, const double* thresholds, int mode, void* stream) {
+    int rc = neigh_check(p, level, radius, thresholds, mode);
+    if (rc) return rc;
+    if (!x || !out) return fail(NDWT_ERR_INVALID_ARG, "null data pointer (x_dev or out_dev)");
+    return on_device(p, [&](auto t) {
+        typedef decltype(t) T;
+        const long long bs = (long long)ndwt_band_pitch(p) * p->comp;
+        int rc = p->coef.grow((size_t)bs * p->esize * (size_t)(ndwt_num_bands(p->ndim, level) + 1), "for the coefficient scratch");
+        if (rc) return rc;
+        T* const slot0 = (T*)p->coef.ptr;
+        rc = dec_impl<T>(p, (const T*)x, slot0 + bs, bs, level, (hipStream_t)stream);
+        if (rc == NDWT_OK) rc = neigh_shrink_impl<T>(p, slot0 + bs, slot0, bs, level, radius, thresholds, mode, (hipStream_t)stream);
+        if (rc == NDWT_OK) rc = rec_impl<T>(p, slot0, bs, (T*)out, level, kNoShrink, (hipStream_t)stream);
+        return rc;
+    });
 }
 
 int ndwt_denoise_host(ndwt_plan* p, const void* x, void* out, int level, double threshold, int mode) {

@@ -561,6 +561,28 @@ constexpr JointRoute joint_route(long long item_scalars, int comp, bool vec, lon
     return vec && ((items >= kJointTileFrom && steps <= kJointTileMaxSteps) || (items >= kJointTileManyFrom && steps <= kJointTileMaxStepsMany)) ? kJointTile
                                                                                                                                                   : kJointChunks;
 }
+// ---- neighbourhood shrinkage (NeighShrink, ndwt_device_neigh.h): a workgroup of 256 threads owns a tile of the leading filtered axes of
+// one item of one band and marches along the last one.  The tile: a row of a wave along axis 0; for 3 filtered axes 64 x 16 positions,
+// 4 a thread -- 64 x 8 for elements of 16 bytes (complex128), and for elements of 8 bytes at radius 3, whose ring and waiting centres
+// would not fit the 128 registers of 4 waves per SIMD otherwise (they spill 16); below 3 axes a line of 256 positions, one a thread.  What the halo costs is in DESIGN.md 4.3j.
+constexpr int neigh_tx(int nd) { return nd == 3 ? 64 : 256; }
+constexpr int neigh_ty(int nd, int elem_bytes, int r) { return nd != 3 ? 1 : elem_bytes <= 4 || (elem_bytes <= 8 && r < 3) ? 16 : 8; }
+// The grid: the tiles of an item, and the chunks of the march.  A chunk reads 2r planes more than it writes, so the march is split only
+// while the launch has fewer workgroups than kNeighRounds per compute unit -- ndwt_plan_set_tuning's target_blocks > 0 stands in for
+// that count -- and never into chunks of fewer than 2r + 1 planes.  One filtered axis: no march, one chunk.  blocks: bands * items of
+// the launch.
+struct NeighGeom { long long ntx, nty, chunk, nchunks; };
+constexpr int kNeighRounds = 8;
+constexpr NeighGeom neigh_geometry(int nd, long long n0, long long n1, long long n2, int elem_bytes, int r, long long blocks, int num_cus, int target_blocks) {
+    const long long tx = neigh_tx(nd), ty = neigh_ty(nd, elem_bytes, r);
+    const long long ntx = (n0 + tx - 1) / tx, nty = nd == 3 ? (n1 + ty - 1) / ty : 1, nm = nd == 1 ? 1 : nd == 2 ? n1 : n2;
+    const long long tiles = ntx * nty * blocks, want = target_blocks > 0 ? target_blocks : (long long)num_cus * kNeighRounds;
+    long long c = (want + tiles - 1) / tiles;
+    if (c > nm / (2 * r + 1)) c = nm / (2 * r + 1);
+    if (c < 1) c = 1;
+    const long long chunk = (nm + c - 1) / c;
+    return {ntx, nty, chunk, (nm + chunk - 1) / chunk};
+}
 
 // ---- one fused 3-D launch
 struct Fused3Query {

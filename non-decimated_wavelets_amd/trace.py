@@ -86,6 +86,11 @@ FAMILY_PARAMS_JOINT_TILE = {
     "GroupNormsTile": [("T", None), ("COMP", None), ("VEC", None)],
 }
 
+# the family of csrc/ndwt_device_neigh.h (neighbourhood shrinkage: a window's energy inside a coefficient's own band decides it), likewise
+FAMILY_PARAMS_NEIGH = {
+    "NeighShrink": [("T", None), ("COMP", None), ("ND", None), ("R", None)],
+}
+
 # the plain __global__ templates (csrc/ndwt_api.hip, csrc/ndwt_multi.hip), as their launch sites spell them
 PLAIN_PARAMS = {
     "axis_analysis_kernel": [("T", None)],
@@ -148,7 +153,7 @@ def parse_record(line: str) -> KernelLaunch:
     if not t:
         raise ValueError(f"unparsed kernel type: {text!r}")
     fam = t.group(1)
-    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam) or FAMILY_PARAMS_1D.get(fam) or FAMILY_PARAMS_AXIS.get(fam) or FAMILY_PARAMS_SELECT.get(fam) or FAMILY_PARAMS_ITEMS.get(fam) or FAMILY_PARAMS_NORMS.get(fam) or FAMILY_PARAMS_RISK.get(fam) or FAMILY_PARAMS_JOINT.get(fam) or FAMILY_PARAMS_JOINT_TILE.get(fam)
+    table = FAMILY_PARAMS.get(fam) or PLAIN_PARAMS.get(fam) or FAMILY_PARAMS_1D.get(fam) or FAMILY_PARAMS_AXIS.get(fam) or FAMILY_PARAMS_SELECT.get(fam) or FAMILY_PARAMS_ITEMS.get(fam) or FAMILY_PARAMS_NORMS.get(fam) or FAMILY_PARAMS_RISK.get(fam) or FAMILY_PARAMS_JOINT.get(fam) or FAMILY_PARAMS_JOINT_TILE.get(fam) or FAMILY_PARAMS_NEIGH.get(fam)
     if table is None:
         raise ValueError(f"unknown kernel family {fam!r} in {text!r}")
     args = [_value(a) for a in _split_args(t.group(2) or "")]
